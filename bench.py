@@ -11,7 +11,13 @@ N ranks share the FIXED frame (tiles dealt round-robin) -> strong scaling.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, warm-up, the K timed steps and
+the line (the run-time instance of the scene comes from the catalog build() compiled, when it is there).  --full adds
+everything else below: the `jit`, `tolerance`, `configs`, `frame` and `cpu_baseline` blocks at N = 1 and the untiled
+check of the gathered frame at N > 1.  --dump-outputs DIR writes the image_buffer of the last timed step (rank 0's
+gathered frame at N > 1) to DIR/image_buffer.npy, float32 (W, H, 4); a frame above 64 MB is written as a fixed, seeded
+sample of its pixels (DIR/image_buffer_sample.npy, (n, 4) float32, and DIR/image_buffer_sample_pixel.npy, the pixels'
+flat indices i * H + j as float64).
 
   --workload c2 (default)  Cornell Box 1920x1080, 256 spp, 8 bounces          (configs[1], the metric)
   --workload c1            Cornell Box 256x256, 16 spp, 4 bounces             (configs[0])
@@ -22,7 +28,7 @@ Prints ONE JSON line on rank 0.
 
 `roofline` is the bound that applies — FP32 vector (VALU) issue: algorithmic FLOPs of SURVEY.md 8(d) per launch / the
 kernels' HIP-event time vs the 157.3 TFLOP/s FP32 vector peak — and carries `traffic`, the HBM bytes per launch of the
-dominant kernel from the committed PMC passes.  `hbm` is the view the metric's name asks for.  At N = 1 the default
+dominant kernel from the committed PMC passes.  `hbm` is the view the metric's name asks for.  At N = 1 the --full
 line also carries `configs`: every other BASELINE config (multi-GPU ones as rank 0's share) and the src/ form, each at
 a bounded sample count with its own FLOP model and roofline fraction; `jit`: what the run-time compiled kernels cost
 at first use and what the same step reaches without them; `cpu_baseline`: the CPU restatement timed on this host.
@@ -60,7 +66,7 @@ def parse():
     ap.add_argument("--scheduler", type=int, default=-1, help="0 = in-register refill, 1 = LDS ray pool (library default)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="rtpbr_set_option knob (A/B runs), repeatable")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the per-config block of the default line")
+    ap.add_argument("--no-configs", action="store_true", help="skip the per-config block of the --full line")
     ap.add_argument("--no-jit", action="store_true", help="use the ahead-of-time kernels instead of the run-time compiled, scene-specialised ones")
     ap.add_argument("--keep-jit-cache", action="store_true", help="use the user's code-object cache (default: a fresh one, so that first-use compile time is measured)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "torch", "host"],
@@ -69,9 +75,12 @@ def parse():
     ap.add_argument("--collective-at-1", action="store_true", help="with --gpus 1: still set up a (1-rank) RCCL communicator and run the gather every step")
     ap.add_argument("--same-device", action="store_true", help="functional test: all ranks share GPU 0 (--transport host, or --transport rccl with RTPBR_RCCL_LIB "
                                                                 "pointing at tests/stubs/libfake_rccl.so: RCCL itself refuses two ranks on one device)")
-    ap.add_argument("--check-gather", action="store_true", help="(the default for N > 1) rank 0 also renders the frame untiled, OUTSIDE the timed region, and reports whether the gathered frame equals it bit for bit")
+    ap.add_argument("--check-gather", action="store_true", help="(the default for N > 1 with --full) rank 0 also renders the frame untiled, OUTSIDE the timed region, and reports whether the gathered frame equals it bit for bit")
     ap.add_argument("--no-check-gather", action="store_true", help="N > 1: skip the untiled reference render")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline (jit, tolerance, configs, frame, "
+                                                        "cpu_baseline; at N > 1 the untiled check of the gathered frame)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the image_buffer of the last timed step as .npy files into DIR")
     a = ap.parse_args()
     if a.backend == "gloo":
         a.transport = "host"
@@ -439,6 +448,25 @@ def frame_latency(a, device, W=768, H=432, frames=200):
             "note": "the bounce-step of a one-step launch runs as the wavefront split (gen / march / shade kernels, rt_split.hpp)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(r, out_dir):
+    """--dump-outputs: what the caller of the timed path receives after its last step, image_buffer (W, H, 4) float32 —
+    whole when it fits in DUMP_MAX_BYTES, else a fixed, seeded sample of its pixels together with their flat indices"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(r.image_buffer, dtype=np.float32)
+    if img.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image_buffer.npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    n = DUMP_MAX_BYTES // 2 // flat.itemsize // flat.shape[1]       # half the budget for the sampled pixels, a quarter for their indices
+    pix = np.sort(np.random.default_rng(0).choice(flat.shape[0], n, replace=False))
+    np.save(os.path.join(out_dir, "image_buffer_sample.npy"), flat[pix])
+    np.save(os.path.join(out_dir, "image_buffer_sample_pixel.npy"), pix.astype(np.float64))
+
+
 def main():
     a = parse()
     import torch
@@ -459,21 +487,22 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
         else:
             dist.init_process_group("gloo", rank=rank, world_size=world)       # control plane only
-    # The catalog of code objects compiled at BUILD time for the BASELINE scenes (raytracingpbr_amd/prebuild.py) would serve this
-    # run without any compilation.  The main flow keeps measuring the real first use (hipcc --genco into a fresh cache), so it
-    # looks past the catalog — unless there is no compiler on this machine, in which case the catalog is exactly what a target
-    # without hipcc runs on; `jit.no_compiler_value` below is that configuration, measured in every default run.
+    # The catalog of code objects compiled at BUILD time for the BASELINE scenes (raytracingpbr_amd/prebuild.py) serves a plain
+    # run without any compilation (the same instance a compile would produce).  --full measures the real first use (hipcc
+    # --genco into a fresh cache), so it looks past the catalog — unless there is no compiler on this machine, in which case the
+    # catalog is exactly what a target without hipcc runs on; `jit.no_compiler_value` below is that configuration.
     import shutil as _sh
     # (the compiler rt_jit.hip would fork: $HIPCC if set — taken literally —, else /opt/rocm/bin/hipcc, else hipcc on PATH)
     _cc = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.access("/opt/rocm/bin/hipcc", os.X_OK) else "hipcc")
     have_compiler = bool(_sh.which(_cc))
-    if have_compiler and "RTPBR_JIT_CATALOG" not in os.environ and not a.keep_jit_cache:
+    if a.full and have_compiler and "RTPBR_JIT_CATALOG" not in os.environ and not a.keep_jit_cache:
         os.environ["RTPBR_JIT_CATALOG"] = "/nonexistent-rtpbr-catalog"
         catalog_hidden = True
     else:
         catalog_hidden = False
     if not a.keep_jit_cache and "RTPBR_JIT_CACHE" not in os.environ:
-        # a fresh private code-object cache: the first use below then measures the real compile; ranks share it
+        # a fresh private code-object cache (the user's is left alone): with the catalog hidden the first use below then measures
+        # the real compile; ranks share it
         d = [tempfile.mkdtemp(prefix="rtpbr-bench-jit-")] if rank == 0 else [None]
         if dist is not None:
             dist.broadcast_object_list(d, src=0)
@@ -543,6 +572,8 @@ def main():
         gather_ms.append((time.perf_counter() - t) * 1e3)
 
     m = measure(wl, r, a.steps, a.warmup, fence, timed_gather if gather is not None else None)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(r, a.dump_outputs)
     dt = m["dt"]
     render_ms = m["trace_ms"] + m["primary_ms"]
     if dist is not None:
@@ -553,7 +584,7 @@ def main():
         dist.all_gather_object(per_rank, {"rank": rank, "kernel_ms_per_step": round(render_ms / a.steps, 3),
                                           "gather_ms_per_step": round(sum(gather_ms[-a.steps:]) / a.steps, 3), "wall_s": round(m["dt"], 4)})
         multi["per_rank"] = per_rank
-        if not a.no_check_gather and rank == 0:
+        if (a.check_gather or a.full) and not a.no_check_gather and rank == 0:
             import numpy as np
             # the same sequence of steps, untiled (sample indices advance from step to step; the src/ form also keeps ray state)
             full = make_renderer(wl, local_rank, a, jit=not a.no_jit)
@@ -660,7 +691,7 @@ def main():
         if multi:
             out["multi_gpu"] = multi
         r.close()
-        if world == 1:
+        if world == 1 and a.full:
             # ---- what the run-time compiled kernels cost and buy (same workload, one step each)
             jit = {"first_use_s": round(first_use_s, 3), "first_use_minus_one_step_s": round(first_use_s - dt / a.steps, 3),
                    "first_use_note": "first rtpbr_sample() of a whole step: hipcc --genco of the scene's kernels into a fresh cache + module load "

@@ -887,7 +887,7 @@ def test_bench_multirank_path_functional(workload):
 def test_bench_every_workload_single_gpu_contract(workload):
     """bench.py --workload X at N = 1 (small frame): the line keeps the driver's contract and carries its own FLOP model"""
     j = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", workload, "--width", "320", "--height", "180", "--spp", "8",
-                    "--no-cpu-baseline", "--no-configs"])
+                    "--full", "--no-cpu-baseline", "--no-configs"])
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["higher_is_better"] is True
     assert j["unit"] == ("Mbounce-steps/s" if workload == "src" else "Msamples/s") and j["dtype"] == "f32" and j["data"] == "synthetic"
     r = j["roofline"]
@@ -929,12 +929,12 @@ def test_bench_scale_command_with_one_process_per_rank(workload, nproc):
 def test_real_rccl_two_ranks_when_two_devices():
     """First contact with a multi-GPU node checks itself: when this box has >= 2 devices, the SCALE command with N = 2 runs on
     REAL RCCL (no stub) — ncclCommInitRank with two ranks, ncclGather over the fabric, the abort path armed — and the line must
-    say so: two ranks, and the gathered frame equal to the untiled one bit for bit (bench.py checks that by default for N > 1).
+    say so: two ranks, and the gathered frame equal to the untiled one bit for bit (bench.py --full checks that for N > 1).
     Skipped on a one-GPU box (there the stub-backed test above covers everything but RCCL itself)."""
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
-    j = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "480", "--height", "270", "--spp", "16", "--no-cpu-baseline"], nproc=2)
+    j = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "480", "--height", "270", "--spp", "16", "--full", "--no-cpu-baseline"], nproc=2)
     mg = j["multi_gpu"]
     assert j["n_gpus"] == 2 and mg["rccl_nranks"] == 2 and mg["rccl_version"] > 20000
     assert mg["gathered_equals_untiled"] is True
@@ -945,11 +945,33 @@ def test_bench_default_transport_is_the_c_abi_rccl_gather():
     behind the C ABI — driven by bench.py itself on this box's one GPU (a 1-rank communicator): RCCL reports the rank
     count, the set-up time is in the line and it is seconds, not minutes."""
     j = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "480", "--height", "270", "--spp", "16",
-                    "--collective-at-1", "--no-cpu-baseline", "--no-configs"])
+                    "--collective-at-1", "--full", "--no-cpu-baseline", "--no-configs"])
     mg = j["multi_gpu"]
     assert mg["rccl_nranks"] == 1 and mg["rccl_rank"] == 0 and mg["rccl_version"] > 20000
     assert mg["comm_init_s"] < 60 and "ncclGather" in mg["transport"]
     assert j["jit"]["first_use_s"] > 0 and j["roofline"]["frac"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run carries the headline only (no --full blocks), and --dump-outputs writes the image_buffer of its
+    last timed step: the frame a renderer holds after the same sequence of calls (first use, warm-up, timed steps)."""
+    from raytracingpbr_amd import workloads
+    W, H, SPP, warmup, steps = 320, 180, 8, 1, 3
+    j = _run_bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--width", str(W), "--height", str(H), "--spp", str(SPP),
+                    "--dump-outputs", str(tmp_path)])
+    assert j["steps"] == steps and j["ms_per_step"] > 0 and j["value"] > 0
+    assert not {"jit", "tolerance", "configs", "frame", "cpu_baseline"} & set(j)
+    got = np.load(tmp_path / "image_buffer.npy")
+    assert got.dtype == np.float32 and got.shape == (W, H, 4) and np.all(got[..., 3] == SPP)
+    wl = workloads.get("c2", W, H, SPP)
+    r = Renderer(wl.scene, wl.cfg)
+    wl.setup(r)
+    r.sample(SPP)
+    for _ in range(warmup + steps):
+        r.refresh()
+        r.sample(SPP)
+    assert np.array_equal(bits(got), bits(r.image_buffer))
+    r.close()
 
 
 def test_gathered_frame_equals_single_gpu_frame():

@@ -369,3 +369,30 @@ def test_catalog_serves_the_baseline_scenes_without_a_compiler(tmp_path, monkeyp
     monkeypatch.setenv("RTPBR_JIT_CATALOG", str(tmp_path / "nowhere"))
     with pytest.raises(RuntimeError):
         prebuild.prebuild_one(lib, "c2", (0, 0), 1, "jit=1 jit_bake=2")
+
+
+def test_bench_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a frame within the size cap is written whole; a larger one as a fixed, seeded sample of its
+    pixels with their flat indices — the same pixels in every run, so that two builds compare output for output."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    img = np.random.default_rng(1).random((64, 48, 4), dtype=np.float32)
+    r = types.SimpleNamespace(image_buffer=img)
+    bench.dump_outputs(r, str(tmp_path / "whole"))
+    assert np.array_equal(np.load(tmp_path / "whole" / "image_buffer.npy"), img)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", img.nbytes // 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(r, str(tmp_path / d))
+        assert not os.path.exists(tmp_path / d / "image_buffer.npy")
+    sizes = 0
+    for name in ("image_buffer_sample.npy", "image_buffer_sample_pixel.npy"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        sizes += a.nbytes
+    assert sizes <= img.nbytes // 4
+    vals = np.load(tmp_path / "a" / "image_buffer_sample.npy")
+    pix = np.load(tmp_path / "a" / "image_buffer_sample_pixel.npy").astype(np.int64)
+    assert len(np.unique(pix)) == len(pix) > 0 and np.array_equal(vals, img.reshape(-1, 4)[pix])

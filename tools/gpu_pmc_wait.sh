@@ -8,7 +8,7 @@ i=0
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC" "SQ_INSTS_SMEM SQ_INSTS_VALU SQ_INSTS_SALU SQ_INST_CYCLES_SALU SQ_INST_CYCLES_SMEM SQ_WAIT_INST_LDS SQ_INSTS_BRANCH SQ_INSTS_SENDMSG"; do
   i=$((i+1))
   rm -rf $OUT/pmcw_$i
-  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pmcw_$i -o pmc -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline $BENCH_OPTS > /dev/null 2> $OUT/pmcw_$i.err
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pmcw_$i -o pmc -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline $BENCH_OPTS > /dev/null 2> $OUT/pmcw_$i.err
   python - <<PY
 import csv, glob, collections
 fs = glob.glob("$OUT/pmcw_$i/**/*counter_collection.csv", recursive=True)

@@ -11,7 +11,7 @@ cd $R
 echo "nproc $(nproc); $(grep -m1 'model name' /proc/cpuinfo); cgroup cpu.max $(cat /sys/fs/cgroup/cpu.max 2>/dev/null)" | tee $OUT/host_$TAG.txt
 python -m pytest tests -x -q -m gpu 2>&1 | tail -8 | tee $OUT/pytest_gpu_$TAG.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee $OUT/smoke_$TAG.log
-python bench.py --steps 3 --warmup 1 2>$OUT/bench_$TAG.err | tee $OUT/bench_$TAG.json
+python bench.py --full --steps 3 --warmup 1 2>$OUT/bench_$TAG.err | tee $OUT/bench_$TAG.json
 export TMPDIR=/tmp
 cd /tmp
 BENCH="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-configs --keep-jit-cache"

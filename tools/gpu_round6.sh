@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   grep -h "^\[fast\]\|^\[refpin\]" $OUT/${TAG}_pytest.log | head -40
 fi
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1; tail -1 $OUT/${TAG}_smoke.log
-timeout 1500 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full --steps ${STEPS:-20} --warmup ${WARMUP:-5} > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 j = json.load(open("$OUT/${TAG}_bench.json"))

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rt_ctx.hpp"
+#include "rt_features.hpp"
 
 using namespace rt;
 
@@ -99,6 +100,21 @@ extern "C" int rtpbr_create(int device, rtpbr_ctx** out) {
     return RTPBR_OK;
 }
 
+// buffers of rtpbr_render_features / rtpbr_denoise (allocated on first use)
+static void free_features(rtpbr_ctx* c) {
+    (void)hipFree(c->feat_albedo);
+    (void)hipFree(c->feat_normal);
+    (void)hipFree(c->feat_depth);
+    (void)hipFree(c->feat_object);
+    (void)hipFree(c->feat_guides);
+    (void)hipFree(c->denoised);
+    (void)hipFree(c->denoise_scratch);
+    c->feat_albedo = c->feat_normal = c->feat_depth = c->denoised = nullptr;
+    c->feat_object = nullptr;
+    c->feat_guides = c->denoise_scratch = nullptr;
+    c->feat_valid = false;
+}
+
 extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     if (!c) return RTPBR_OK;
     (void)hipSetDevice(c->device);
@@ -118,6 +134,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->primary);
     (void)hipFree(c->cost_buffer);
     (void)hipFree(c->march_out);
+    free_features(c);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
     rt_rccl_release(c);
@@ -198,6 +215,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
     c->cfg = *cfg;
     c->P.cfg = *cfg;
     c->have_cfg = true;
+    c->feat_valid = false;
     if (realloc_buf) {
         size_t n = (size_t)cfg->width * cfg->height;
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -213,6 +231,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
         c->ray_buffer = nullptr;
         c->diff_buffer = nullptr;
         c->diff_pixels = nullptr;
+        free_features(c);
         HIP_TRY(hipMalloc(&c->image_buffer, n * sizeof(float4)));
         HIP_TRY(hipMalloc(&c->image_pixels, n * 3 * sizeof(float)));
         HIP_TRY(hipMalloc(&c->ray_buffer, n * sizeof(rtpbr_ray)));
@@ -319,6 +338,7 @@ extern "C" int rtpbr_set_scene(rtpbr_ctx* c, const rtpbr_object* objs, int n, in
         if (objs[i].type < RTPBR_SHAPE_NONE || objs[i].type > RTPBR_SHAPE_BUNNY) return fail(RTPBR_EINVAL, "unknown shape type");
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
+    c->feat_valid = false;
     ObjFull full[MAX_OBJ];
     memset(full, 0, sizeof full);
     bool all_box = true, all_bunny = true, any_bunny = false;
@@ -526,6 +546,7 @@ extern "C" int rtpbr_get_scene(rtpbr_ctx* c, rtpbr_object* objs, int n) {
 extern "C" int rtpbr_set_camera(rtpbr_ctx* c, const rtpbr_camera* cam) {
     if (!c || !cam) return fail(RTPBR_EINVAL, "null argument");
     if (int r = flush_shade(c)) return r;
+    c->feat_valid = false;
     c->cam = *cam;
     vec3 lf = mk(cam->lookfrom[0], cam->lookfrom[1], cam->lookfrom[2]);
     vec3 la = mk(cam->lookat[0], cam->lookat[1], cam->lookat[2]);
@@ -611,6 +632,7 @@ extern "C" int rtpbr_set_shape_data(rtpbr_ctx* c, int shape, const float* data, 
                 for (int i = 0; i < 4; i++)
                     for (int j = 0; j < 4; j++)
                         dev[64 + layer * 272 + k * 68 + i * 16 + m * 4 + j] = data[64 + layer * 272 + k * 68 + m * 16 + i * 4 + j];
+    c->feat_valid = false;
     if (!c->bunny) HIP_TRY(hipMalloc(&c->bunny, 625 * sizeof(float)));
     HIP_TRY(hipMemcpy(c->bunny, dev, 625 * sizeof(float), hipMemcpyHostToDevice));
     c->P.bunny = c->bunny;
@@ -636,7 +658,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b < 5; b++)
+    for (int b = 0; b < 10; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -1296,6 +1318,118 @@ extern "C" int rtpbr_post_process(rtpbr_ctx* c) {
     return RTPBR_OK;
 }
 
+// ---- first-hit features and the a-trous denoise (rt_features.hip): the filter the reference's post_process() leaves as a TODO
+// (src/postprocessor.py:30 "# ToDo: Post Denoise").  Whole-frame only: a rank of a tiled render holds part of the frame.
+static int features_alloc(rtpbr_ctx* c) {
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->feat_albedo) HIP_TRY(hipMalloc(&c->feat_albedo, n * 3 * sizeof(float)));
+    if (!c->feat_normal) HIP_TRY(hipMalloc(&c->feat_normal, n * 3 * sizeof(float)));
+    if (!c->feat_depth) HIP_TRY(hipMalloc(&c->feat_depth, n * sizeof(float)));
+    if (!c->feat_object) HIP_TRY(hipMalloc(&c->feat_object, n * sizeof(int32_t)));
+    if (!c->feat_guides) HIP_TRY(hipMalloc(&c->feat_guides, n * sizeof(float4)));
+    return RTPBR_OK;
+}
+
+enum : unsigned { W_FEATURES = (1u << RTPBR_BUF_FEAT_ALBEDO) | (1u << RTPBR_BUF_FEAT_NORMAL) | (1u << RTPBR_BUF_FEAT_DEPTH) | (1u << RTPBR_BUF_FEAT_OBJECT),
+                  W_DENOISED = 1u << RTPBR_BUF_DENOISED_PIXELS };
+
+extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, "rtpbr_render_features / rtpbr_denoise work on the whole frame: not with tiles of world > 1");
+    for (int i = 0; i < c->n_obj; i++)
+        if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
+    if (int r = set_dev(c)) return r;
+    if (int r = features_alloc(c)) return r;
+    if (int r = rt_order_after_reads(c, W_FEATURES)) return r;
+    // the context's Params with the general march table (signature 0, no lazy box keys): what the run-time object-count instances read
+    Params P = c->P;
+    P.cfg = c->cfg;
+    P.cam.inv_w = 1.0f / (float)c->cfg.width;
+    P.cam.inv_h = 1.0f / (float)c->cfg.height;
+    P.n_obj = c->n_obj;
+    P.box_sig = 0;
+    P.box_lazy = 0;
+    pack_table(c->objm, c->n_obj, 0, P.objm);
+    P.objfull = c->objfull;
+    P.bunny = c->bunny;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    FeatArgs A;
+    A.albedo = c->feat_albedo;
+    A.normal = c->feat_normal;
+    A.depth = c->feat_depth;
+    A.object = c->feat_object;
+    A.guide_nz = c->feat_guides;
+    launch_features(P, A, c->kind, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->feat_valid = true;
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_params d;
+    if (p) {
+        d = *p;
+    } else {
+        d.iterations = RTPBR_DENOISE_DEFAULT_ITERATIONS;
+        d.demodulate = RTPBR_DENOISE_DEFAULT_DEMODULATE;
+        d.sigma_color = RTPBR_DENOISE_DEFAULT_SIGMA_COLOR;
+        d.sigma_normal = RTPBR_DENOISE_DEFAULT_SIGMA_NORMAL;
+        d.sigma_depth = RTPBR_DENOISE_DEFAULT_SIGMA_DEPTH;
+        d.sigma_albedo = RTPBR_DENOISE_DEFAULT_SIGMA_ALBEDO;
+    }
+    if (d.iterations < 0 || d.iterations > 8) return fail(RTPBR_EINVAL, "denoise iterations must be 0..8");
+    if (d.demodulate != 0 && d.demodulate != 1) return fail(RTPBR_EINVAL, "denoise demodulate must be 0 or 1");
+    const float sig[4] = {d.sigma_color, d.sigma_normal, d.sigma_depth, d.sigma_albedo};
+    float inv[4];
+    for (int k = 0; k < 4; k++) {
+        inv[k] = 1.0f / (sig[k] * sig[k]);
+        if (!(sig[k] > 0.0f) || !std::isfinite(sig[k]) || !std::isfinite(inv[k]))
+            return fail(RTPBR_EINVAL, "denoise sigmas must be finite and > 0 (and not so small that 1/sigma^2 overflows)");
+    }
+    // the colour weight alone grows, by 4 per level: it must stay finite up to the last level, 4^(iterations-1)
+    if (d.iterations > 1 && !std::isfinite(inv[0] * (float)(1u << (2 * (d.iterations - 1)))))
+        return fail(RTPBR_EINVAL, "denoise sigma_color too small for this many levels: 1/sigma^2 * 4^(iterations-1) overflows");
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, "rtpbr_render_features / rtpbr_denoise work on the whole frame: not with tiles of world > 1");
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;
+    if (int r = set_dev(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->denoised) HIP_TRY(hipMalloc(&c->denoised, n * 3 * sizeof(float)));
+    if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
+    if (int r = rt_order_after_reads(c, W_DENOISED)) return r;
+    DenoiseArgs A;
+    A.cfg = c->cfg;
+    A.image_buffer = c->image_buffer;
+    A.guide_nz = c->feat_guides;
+    A.albedo = c->feat_albedo;
+    A.object = c->feat_object;
+    A.out = c->denoised;
+    A.in = inv[1];
+    A.iz = inv[2];
+    A.demodulate = d.demodulate;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    if (d.iterations == 0) {
+        A.src = nullptr;
+        A.dst = nullptr;
+        A.ic = inv[0];
+        A.step = 0;
+        launch_atrous_level(A, true, true, c->stream);
+    }
+    for (int k = 0; k < d.iterations; k++) {
+        A.src = k == 0 ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
+        A.dst = k + 1 == d.iterations ? nullptr : c->denoise_scratch + (size_t)(k & 1) * n;
+        A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
+        A.step = 1 << k;
+        launch_atrous_level(A, k == 0, k + 1 == d.iterations, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_sync(rtpbr_ctx* c) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (int r = set_dev(c)) return r;
@@ -1314,8 +1448,16 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_RAY_BUFFER: *p = c->ray_buffer; *n = np * sizeof(rtpbr_ray); return 0;
         case RTPBR_BUF_DIFF_BUFFER: *p = c->diff_buffer; *n = np * 8; return 0;
         case RTPBR_BUF_DIFF_PIXELS: *p = c->diff_pixels; *n = np * 4; return 0;
+        case RTPBR_BUF_FEAT_ALBEDO: *p = c->feat_albedo; *n = np * 12; break;
+        case RTPBR_BUF_FEAT_NORMAL: *p = c->feat_normal; *n = np * 12; break;
+        case RTPBR_BUF_FEAT_DEPTH: *p = c->feat_depth; *n = np * 4; break;
+        case RTPBR_BUF_FEAT_OBJECT: *p = c->feat_object; *n = np * 4; break;
+        case RTPBR_BUF_DENOISED_PIXELS: *p = c->denoised; *n = np * 12; break;
+        default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
-    return fail(RTPBR_EINVAL, "unknown buffer id");
+    // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise first");
+    return 0;
 }
 
 extern "C" int rtpbr_read_buffer(rtpbr_ctx* c, int which, void* dst, size_t nbytes) {
@@ -1415,6 +1557,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_DENOISED_PIXELS)
+        return fail(RTPBR_EINVAL, "the feature and denoise buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

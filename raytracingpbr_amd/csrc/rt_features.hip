@@ -1,0 +1,230 @@
+// rt_features.hip — kernels of rtpbr_render_features / rtpbr_denoise (see rt_features.hpp).
+#include <hip/hip_runtime.h>
+
+#include "rt_features.hpp"
+#include "rt_trace.hpp"
+
+namespace rt {
+
+// Primary ray through the centre of pixel i = x * H + y (lanes along y: the buffers' contiguous index).  Modelled on
+// primary_rays_impl (rt_trace.hpp) without its claim counter: one lane per pixel, P.counters untouched.
+template <int KIND>
+__global__ void __launch_bounds__(256) feature_rays(const Params P, const FeatArgs A) {
+    __shared__ ObjFull lds_obj[MAX_OBJ];
+    stage_objects(P, lds_obj);
+    const int H = P.cfg.height;
+    const uint32_t n = (uint32_t)P.cfg.width * (uint32_t)H;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in_frame = i < n;
+    const int px = (int)(i / (uint32_t)H), py = (int)(i - (uint32_t)px * (uint32_t)H);
+    const CamFrame& f = P.cam;
+    const vec3 lf = mk(f.lf[0], f.lf[1], f.lf[2]);
+    const bool src = P.cfg.march_kind == RTPBR_MARCH_SRC;
+    Lane L;
+    L.state = ST_IDLE;
+    L.n_steps = L.n_raycasts = L.n_hits = L.n_sky = 0;
+    L.o = L.d = mk(0, 0, 0);
+    L.t = L.w = L.s = L.dist = L.t_eval = 0.0f;
+    L.idx = 0;
+    L.steps_left = 0;
+    if (in_frame) {
+        // gen_ray (rt_device.hpp) with j1 = j2 = 0.5 and no lens draws: the origin is lookfrom for both camera kinds
+        float u, v;
+        if (P.cfg.camera_kind == RTPBR_CAMERA_PINHOLE) {
+            u = ((float)px + 0.5f) / (float)P.cfg.width;
+            v = ((float)py + 0.5f) / (float)P.cfg.height;
+        } else {
+            u = ((float)px + 0.5f) * f.inv_w;
+            v = ((float)py + 0.5f) * f.inv_h;
+        }
+        vec3 po = fma3(v, mk(f.ver[0], f.ver[1], f.ver[2]), fma3(u, mk(f.hor[0], f.hor[1], f.hor[2]), mk(f.llc[0], f.llc[1], f.llc[2])));
+        L.o = lf;
+        L.d = normalize(po - lf);
+        if (src) {      // raycast() src/scene.py:59-84: t = 0, d = MAX_DIS
+            L.w = P.cfg.omega0;
+            L.dist = P.cfg.max_dis;
+            L.steps_left = P.cfg.max_raymarch;
+            L.state = ST_MARCH;
+        } else {
+            march_init(P, L);
+        }
+    }
+    if (src) {
+        while (__any(L.state == ST_MARCH))
+            if (L.state == ST_MARCH) march_step_src<KIND>(P, L);
+    } else {
+        while (__any(L.state == ST_MARCH))
+            if (L.state == ST_MARCH) march_step<KIND, 0>(P, L);
+    }
+    if (!in_frame) return;
+    vec3 alb = mk(0, 0, 0), nrm = mk(0, 0, 0);
+    float depth = P.cfg.max_dis;
+    int obj = -1;
+    if (L.state == ST_HIT) {
+        // the hit position the sample path shades at: src moves the origin, the examples evaluate at o + t_eval d
+        const vec3 hp = src ? L.o : fma3(L.t_eval, L.d, L.o);
+        const ObjFull& o = lds_obj[L.idx];
+        alb = mk(o.albedo[0], o.albedo[1], o.albedo[2]);
+        nrm = calc_normal<KIND>(P, o, hp);
+        depth = length(hp - lf);
+        obj = L.idx;
+    }
+    A.albedo[(size_t)i * 3 + 0] = alb.x;
+    A.albedo[(size_t)i * 3 + 1] = alb.y;
+    A.albedo[(size_t)i * 3 + 2] = alb.z;
+    A.normal[(size_t)i * 3 + 0] = nrm.x;
+    A.normal[(size_t)i * 3 + 1] = nrm.y;
+    A.normal[(size_t)i * 3 + 2] = nrm.z;
+    A.depth[i] = depth;
+    A.object[i] = obj;
+    A.guide_nz[i] = make_float4(nrm.x, nrm.y, nrm.z, depth);
+}
+
+RT_D vec3 xyz(float4 v) { return mk(v.x, v.y, v.z); }
+RT_D float sq3(vec3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }      // |v|^2 in this order, no fma
+RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), c.z / (1.0f + c.z)); }
+RT_D vec3 albedo_clamped(const DenoiseArgs& A, uint32_t i) {
+    return mk(fmax_(A.albedo[(size_t)i * 3 + 0], 1e-3f), fmax_(A.albedo[(size_t)i * 3 + 1], 1e-3f), fmax_(A.albedo[(size_t)i * 3 + 2], 1e-3f));
+}
+// The filter's start colour of a pixel from T7 (level 0): the average, divided by max(albedo, 1e-3) when demodulating
+RT_D vec3 start_colour(float4 b, vec3 ac, int demod) {
+    vec3 c = mk(b.x / b.w, b.y / b.w, b.z / b.w);
+    return demod ? mk(c.x / ac.x, c.y / ac.y, c.z / ac.z) : c;
+}
+constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pixel without samples: matches no object index (>= -1)
+
+// One a-trous level.  Taps: dy outer, dx inner, -2..2, at p + step (dx, dy); h = H[|dx|] H[|dy|], H = {3/8, 1/4, 1/16};
+// e = |r(c_p) - r(c_q)|^2 ic + |n_p - n_q|^2 in + ((z_p - z_q) / max(z_p, 1e-6))^2 iz + |a_p - a_q|^2 ia (left to right),
+// r(c) = c / (1 + c); w = h exp_(-min(e, 80)).  Taps outside the frame, without samples or on another object are skipped.
+// A tap is only taken on the centre's own object index and the albedo is a per-object constant (0 on a miss), so a_q = a_p on
+// every tap taken: the albedo term is exactly +0 (e + 0 = e) and the neighbour's demodulation divides by the centre's albedo.
+// Neither is loaded per tap: a tap reads the 4-byte object index (level 0) or the object word carried in the previous level's
+// record (colour, object), then — on the centre's object only — the 16-byte (normal, depth) record.
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
+    const int H = A.height, W = A.width;
+    const uint32_t n = (uint32_t)W * (uint32_t)H;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
+    int op;
+    float4 cp4;
+    bool valid;
+    if constexpr (FIRST) {
+        cp4 = A.image_buffer[i];
+        op = A.object[i];
+        valid = cp4.w > 0.0f;
+    } else {
+        cp4 = A.src[i];
+        op = __float_as_int(cp4.w);
+        valid = op != NO_SAMPLES;
+    }
+    if (!valid) {       // no samples: exactly what post_process shows, and nobody's neighbour
+        if constexpr (LAST) {
+            const vec3 t = tone_map(A.cfg, A.image_buffer[i]);
+            A.out[(size_t)i * 3 + 0] = t.x;
+            A.out[(size_t)i * 3 + 1] = t.y;
+            A.out[(size_t)i * 3 + 2] = t.z;
+        } else {
+            A.dst[i] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(NO_SAMPLES));
+        }
+        return;
+    }
+    const bool need_albedo = (FIRST || LAST) && A.demodulate;
+    const vec3 ac = need_albedo ? albedo_clamped(A, i) : mk(1.0f, 1.0f, 1.0f);
+    const vec3 cp = FIRST ? start_colour(cp4, ac, A.demodulate) : xyz(cp4);
+    const float4 gp_nz = A.guide_nz[i];
+    const vec3 np = xyz(gp_nz);
+    const float zp = gp_nz.w;
+    const float izp = fmax_(zp, 1e-6f);
+    const vec3 rp = tonemap_r(cp);
+    const int s = A.step;
+    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    constexpr float HK[3] = {0.375f, 0.25f, 0.0625f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int yq = y + s * dy;
+        if (yq < 0 || yq >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int xq = x + s * dx;
+            if (xq < 0 || xq >= W) continue;
+            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+            vec3 cq;
+            if constexpr (FIRST) {
+                if (A.object[q] != op) continue;
+                const float4 b = A.image_buffer[q];
+                if (!(b.w > 0.0f)) continue;
+                cq = start_colour(b, ac, A.demodulate);
+            } else {
+                const float4 c4 = A.src[q];
+                if (__float_as_int(c4.w) != op) continue;
+                cq = xyz(c4);
+            }
+            const float4 gq_nz = A.guide_nz[q];
+            const float h = HK[dx < 0 ? -dx : dx] * HK[dy < 0 ? -dy : dy];
+            const float dz = (zp - gq_nz.w) / izp;
+            float e = sq3(rp - tonemap_r(cq)) * A.ic;
+            e = e + sq3(np - xyz(gq_nz)) * A.in;
+            e = e + (dz * dz) * A.iz;
+            // (+ |a_p - a_q|^2 ia = + 0: see above)
+            // (e is clamped where exp no longer matters: a weight under 2e-35 against the centre's 9/64; far past it the Cephes
+            // reduction of exp_ loses its argument and could overflow)
+            const float w = h * exp_(-fmin_(e, 80.0f));
+            sw = sw + w;
+            sx = sx + w * cq.x;
+            sy = sy + w * cq.y;
+            sz = sz + w * cq.z;
+        }
+    }
+    vec3 c = mk(sx / sw, sy / sw, sz / sw);
+    if constexpr (LAST) {
+        if (A.demodulate) c = mk(c.x * ac.x, c.y * ac.y, c.z * ac.z);
+        const vec3 t = tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
+        A.out[(size_t)i * 3 + 0] = t.x;
+        A.out[(size_t)i * 3 + 1] = t.y;
+        A.out[(size_t)i * 3 + 2] = t.z;
+    } else {
+        A.dst[i] = make_float4(c.x, c.y, c.z, __int_as_float(op));
+    }
+}
+
+// iterations = 0: the average, demodulated and remodulated, tone-mapped (with demodulate = 0 bit for bit post_process's image_pixels)
+__global__ void __launch_bounds__(256) atrous_none(const DenoiseArgs A) {
+    const uint32_t n = (uint32_t)A.width * (uint32_t)A.height;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 b = A.image_buffer[i];
+    vec3 t;
+    if (b.w > 0.0f) {
+        const vec3 ac = A.demodulate ? albedo_clamped(A, i) : mk(1.0f, 1.0f, 1.0f);
+        vec3 c = start_colour(b, ac, A.demodulate);
+        if (A.demodulate) c = mk(c.x * ac.x, c.y * ac.y, c.z * ac.z);
+        t = tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
+    } else {
+        t = tone_map(A.cfg, b);
+    }
+    A.out[(size_t)i * 3 + 0] = t.x;
+    A.out[(size_t)i * 3 + 1] = t.y;
+    A.out[(size_t)i * 3 + 2] = t.z;
+}
+
+void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st) {
+    const unsigned grid = (unsigned)(((size_t)P.cfg.width * P.cfg.height + 255) / 256);
+    if (kind == KIND_BOXES) hipLaunchKernelGGL((feature_rays<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, A);
+    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((feature_rays<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P, A);
+    else if (kind == KIND_MIXED) hipLaunchKernelGGL((feature_rays<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P, A);
+    else hipLaunchKernelGGL((feature_rays<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P, A);
+}
+
+// first && last with step 0 (no level) is the iterations = 0 pass
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, hipStream_t st) {
+    const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
+    if (A.step == 0) hipLaunchKernelGGL(atrous_none, dim3(grid), dim3(256), 0, st, A);
+    else if (first && last) hipLaunchKernelGGL((atrous_level<true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (first) hipLaunchKernelGGL((atrous_level<true, false>), dim3(grid), dim3(256), 0, st, A);
+    else if (last) hipLaunchKernelGGL((atrous_level<false, true>), dim3(grid), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((atrous_level<false, false>), dim3(grid), dim3(256), 0, st, A);
+}
+
+}  // namespace rt

@@ -1,0 +1,48 @@
+// rt_features.hpp — first-hit feature buffers and the edge-aware a-trous denoise (rtpbr_render_features, rtpbr_denoise).
+//
+// The reference's post_process() (src/postprocessor.py:24-43) tone-maps the raw Monte Carlo average and leaves a
+// "# ToDo: Post Denoise" where a filter would go.  These kernels fill that gap without touching the sample path:
+//   feature_rays<KIND>   one lane per pixel: the primary ray through the pixel centre (gen_ray with both jitters 0.5, no
+//                        lens offset), marched with the configured march kind; writes albedo / shading normal / depth /
+//                        object index of the first hit (RTPBR_BUF_FEAT_*) and the packed (normal, depth) record the filter reads;
+//   atrous_level<F,L>    one a-trous level (Dammertz et al. 2010, "Edge-avoiding A-Trous wavelet transform for fast global
+//                        illumination filtering"): 5x5 B3-spline taps at stride 2^k, weighted by colour, normal, depth and
+//                        albedo distance (the last is 0 on every tap taken: see atrous_level), skipping other objects and empty
+//                        pixels.  A level's output record is (colour, object index).  The average / demodulation is fused into
+//                        the first level, remodulation and the tone map into the last.
+// The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_denoise) so that a CPU restatement matches bit for bit.
+#pragma once
+#include "rt_types.hpp"
+
+namespace rt {
+
+// feature_rays arguments (beside a copy of the context's Params, which stays the first kernel argument: the march table is
+// read from the kernarg segment at offsetof(Params, objm))
+struct FeatArgs {
+    float* albedo;        // (W,H,3)
+    float* normal;        // (W,H,3)
+    float* depth;         // (W,H)
+    int32_t* object;      // (W,H)
+    float4* guide_nz;     // (W,H): (normal.xyz, depth)
+};
+
+// atrous_level arguments: one level
+struct DenoiseArgs {
+    rtpbr_config cfg;             // tone map
+    const float4* image_buffer;   // T7: read by the first level (average) and by the last (empty pixels, as post_process)
+    const float4* guide_nz;
+    const float* albedo;          // (W,H,3): the centre's, for (de)modulation
+    const int32_t* object;        // (W,H): level 0's taps
+    const float4* src;            // levels > 0: the previous level's (colour, object index as bits; -2 = pixel without samples)
+    float4* dst;                  // every level but the last
+    float* out;                   // the last level: denoised display colour (W,H,3)
+    float ic, in, iz;             // 1/sigma^2 of colour (already x 4^k), normal, depth (the albedo term is 0 on every tap taken)
+    int32_t step;                 // 2^k
+    int32_t demodulate;
+    int32_t width, height;
+};
+
+void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, hipStream_t st);
+
+}  // namespace rt

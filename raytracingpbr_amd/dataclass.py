@@ -94,3 +94,13 @@ class Counters(_Pod):
 
 assert C.sizeof(Ray) == 40 and C.sizeof(Material) == 40 and C.sizeof(Transform) == 72
 assert C.sizeof(SDFObject) == 116 and C.sizeof(Camera) == 52
+
+
+class DenoiseParams(_Pod):
+    """rtpbr_denoise_params (include/rtpbr.h): a-trous levels, albedo demodulation and the four edge-stopping sigmas."""
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
+
+    # include/rtpbr.h RTPBR_DENOISE_DEFAULT_*, what rtpbr_denoise(ctx, NULL) uses; Renderer.denoise() fills the parameters not
+    # given from here (tests/test_feature_ref.py::test_python_denoise_defaults_match_the_header keeps the two equal)
+    DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 2.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "sigma_albedo": 0.1}

@@ -14,10 +14,12 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, Ray, SDFObject
+from .dataclass import Camera, Counters, DenoiseParams, Ray, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
+# first-hit features (render_features) and the denoised display image (denoise); they exist from the first of those calls on
+BUF_FEAT_ALBEDO, BUF_FEAT_NORMAL, BUF_FEAT_DEPTH, BUF_FEAT_OBJECT, BUF_DENOISED_PIXELS = 5, 6, 7, 8, 9
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -105,12 +107,32 @@ class Renderer:
     def sync(self):
         self.api.call("sync", self._ctx)
 
+    # ------------------------------------------------------------ first-hit features and the denoise (include/rtpbr.h)
+    def render_features(self):
+        """One primary ray through every pixel centre: albedo, shading normal, depth and object index of the first hit."""
+        self.api.call("render_features", self._ctx)
+
+    def denoise(self, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
+        """Edge-aware a-trous filter of image_buffer into ``denoised_pixels`` (the features are rendered first when stale).
+        ``None`` = the library's default for that parameter."""
+        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
+                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
+        if all(v is None for v in given.values()):
+            self.api.call("denoise", self._ctx, None)
+            return
+        v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+        p = DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                          float(v["sigma_depth"]), float(v["sigma_albedo"]))
+        self.api.call("denoise", self._ctx, C.byref(p))
+
     # ------------------------------------------------------------ buffers (field.to_numpy())
     def _shape(self, which):
         W, H = self.config.width, self.config.height
         return {BUF_IMAGE_BUFFER: ((W, H, 4), np.float32), BUF_IMAGE_PIXELS: ((W, H, 3), np.float32),
                 BUF_RAY_BUFFER: ((W, H, 10), np.float32), BUF_DIFF_BUFFER: ((W, H, 2), np.float32),
-                BUF_DIFF_PIXELS: ((W, H), np.float32)}[which]
+                BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),
+                BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
+                BUF_DENOISED_PIXELS: ((W, H, 3), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -216,6 +238,26 @@ class Renderer:
     @property
     def diff_pixels(self):
         return self._read(BUF_DIFF_PIXELS)
+
+    @property
+    def feature_albedo(self):
+        return self._read(BUF_FEAT_ALBEDO)
+
+    @property
+    def feature_normal(self):
+        return self._read(BUF_FEAT_NORMAL)
+
+    @property
+    def feature_depth(self):
+        return self._read(BUF_FEAT_DEPTH)
+
+    @property
+    def feature_object(self):
+        return self._read(BUF_FEAT_OBJECT)
+
+    @property
+    def denoised_pixels(self):
+        return self._read(BUF_DENOISED_PIXELS)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

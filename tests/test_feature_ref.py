@@ -1,0 +1,65 @@
+"""CPU tier: the reference of the first-hit features and the a-trous denoise (tests/feature_ref/feature_ref.c) that the GPU
+tests hold rtpbr_render_features / rtpbr_denoise to."""
+import os
+import re
+
+import numpy as np
+
+import feature_ref_lib as fr
+from oracle_backend import OracleRenderer
+from raytracingpbr_amd import Config, cornell_box
+from raytracingpbr_amd.dataclass import DenoiseParams
+
+
+def test_reference_builds():
+    assert os.path.exists(fr.build())
+    assert hasattr(fr.lib(), "fr_features") and hasattr(fr.lib(), "fr_denoise")
+
+
+def test_zero_levels_reproduce_post_process_bitwise():
+    """iterations = 0, demodulate = 0 is the oracle's post_process, pixels without samples included"""
+    cfg = Config.cornell_v3(37, 29, seed=3, max_raytrace=3)
+    sc = cornell_box("v3")
+    o = OracleRenderer(sc, cfg)
+    o.sample(2)
+    ib = o.image_buffer
+    ib[5:9, 3:6] = 0.0                     # no samples there: post_process shows NaN, and so must the filter
+    o.image_buffer = ib
+    o.post_process()
+    feats = fr.features(sc, cfg)
+    out = fr.denoise(cfg, ib, feats, iterations=0, demodulate=0)
+    assert np.array_equal(out.view(np.uint32), o.image_pixels.view(np.uint32))
+
+
+def test_constant_image_stays_constant():
+    cfg = Config.cornell_v3(41, 33, seed=0, max_raytrace=3)
+    sc = cornell_box("v3")
+    feats = fr.features(sc, cfg)
+    ib = np.empty((41, 33, 4), np.float32)
+    ib[..., :3] = (0.3 * 4, 0.5 * 4, 0.2 * 4)
+    ib[..., 3] = 4.0
+    flat = fr.denoise(cfg, ib, feats, iterations=0, demodulate=0)
+    for demod in (0, 1):
+        out = fr.denoise(cfg, ib, feats, iterations=4, demodulate=demod)
+        np.testing.assert_allclose(out, flat, rtol=2e-6, atol=0)
+
+
+def test_cornell_v3_centre_hits_the_back_wall():
+    """The centre column above the two blocks looks at the back wall (object 0): its albedo, its axis-aligned normal
+    facing the camera, its distance."""
+    cfg = Config.cornell_v3(64, 64, seed=0, max_raytrace=3)
+    sc = cornell_box("v3")
+    f = fr.features(sc, cfg)
+    assert f["object"][32, 40] == 0
+    assert np.array_equal(f["albedo"][32, 40], np.array(sc.objects[0].material.albedo, np.float32))
+    assert np.array_equal(f["normal"][32, 40], np.array([0, 0, 1], np.float32))
+    assert 35.0 < f["depth"][32, 40] < 46.0          # camera at z = 35 (scale10 room), wall face near z = -9
+    assert f["object"][32, 32] == 5                  # the frame's centre itself: the tall block in front of the wall
+    assert np.all(f["object"] >= -1) and np.all(f["object"] < len(sc.objects))
+
+
+def test_python_denoise_defaults_match_the_header():
+    """Renderer.denoise() with some parameters given takes the others from DenoiseParams.DEFAULTS: the header's values"""
+    hdr = open(os.path.join(os.path.dirname(fr.DIR), "..", "include", "rtpbr.h")).read()
+    found = {m.group(1).lower(): float(m.group(2)) for m in re.finditer(r"#define RTPBR_DENOISE_DEFAULT_([A-Z_]+)\s+([0-9.]+)f?", hdr)}
+    assert found == {k: float(v) for k, v in DenoiseParams.DEFAULTS.items()}

@@ -1,0 +1,289 @@
+"""First-hit feature buffers and the edge-aware a-trous denoise on the GPU (rtpbr_render_features, rtpbr_denoise), held bit for
+bit to the CPU reference tests/feature_ref/feature_ref.c, plus the buffer lifetime, ordering and error rules of include/rtpbr.h."""
+import numpy as np
+import pytest
+
+import feature_ref_lib as fr
+from raytracingpbr_amd import SHAPE, Camera, Config, Renderer, bunny, cornell_box, src_scene
+from raytracingpbr_amd._capi import RtpbrError
+from raytracingpbr_amd.ibl import load_bunny_weights, synthetic_env
+from raytracingpbr_amd.renderer import (BUF_DENOISED_PIXELS, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS, BUF_FEAT_ALBEDO, BUF_FEAT_DEPTH,
+                                        BUF_FEAT_NORMAL, BUF_FEAT_OBJECT, BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER)
+
+pytestmark = pytest.mark.gpu
+
+ESTATE, EINVAL = -4, -1
+W, H = 97, 61      # odd, and W * H is no multiple of the 256-lane blocks
+
+
+def _scenes(w, h):
+    a = w / h
+    return {
+        "cornell_v3": (cornell_box("v3", aspect=a), Config.cornell_v3(w, h, 0, 3)),
+        "cornell_v1": (cornell_box("v1", aspect=a), Config.cornell_v1(w, h, 2, 8)),
+        "cornell_v2": (cornell_box("v2", aspect=a), Config.cornell_v2(w, h, 1, 3)),
+        "src_tokyo": (src_scene(aspect=a), Config.src(w, h, 7, steps_per_launch=1)),
+        "bunny_glass_frame17": (bunny(aspect=a), Config.bunny_glass(w, h, 12, 8, frame=17).copy(max_raymarch=512)),
+        "scene_demo": (src_scene(aspect=a, tokyo=True), Config.scene_demo(w, h, 5, 16)),
+        "cornell_shortest": (cornell_box("shortest", aspect=a), Config.cornell_shortest(w, h, 4, 3)),
+    }
+
+
+def _renderer(scene, cfg):
+    r = Renderer(scene, cfg)
+    if any(o.type == SHAPE.BUNNY for o in scene.objects):
+        r.set_shape_data(SHAPE.BUNNY, load_bunny_weights())
+    if cfg.sky_kind == 1:      # RTPBR_SKY_ENVMAP
+        r.set_env(synthetic_env(192, 96, seed=0), 1.4, 2.2)
+    return r
+
+
+def _ref_features(scene, cfg, camera=None):
+    return fr.features(scene, cfg, camera, load_bunny_weights() if any(o.type == SHAPE.BUNNY for o in scene.objects) else None)
+
+
+def _gpu_features(r):
+    return {"albedo": r.feature_albedo, "normal": r.feature_normal, "depth": r.feature_depth, "object": r.feature_object}
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def _assert_features_equal(g, ref):
+    for k in ("albedo", "normal", "depth", "object"):
+        bad = ~np.equal(g[k].view(np.uint32), ref[k].view(np.uint32))
+        assert not bad.any(), f"{k}: {int(bad.sum())} elements differ, first at {np.argwhere(bad)[:4].tolist()}"
+
+
+@pytest.mark.parametrize("name", list(_scenes(W, H)))
+def test_features_bit_identical_to_reference(name):
+    scene, cfg = _scenes(W, H)[name]
+    r = _renderer(scene, cfg)
+    r.render_features()
+    g = _gpu_features(r)
+    ref = _ref_features(scene, cfg)
+    _assert_features_equal(g, ref)
+    assert (ref["object"] >= 0).any()
+
+
+def test_features_bit_identical_at_1080p():
+    scene, cfg = cornell_box("v3", aspect=1920 / 1080), Config.cornell_v3(1920, 1080, 0, 3)
+    r = _renderer(scene, cfg)
+    r.render_features()
+    _assert_features_equal(_gpu_features(r), _ref_features(scene, cfg))
+
+
+def _cornell(w=W, h=H, spp=4):
+    scene, cfg = cornell_box("v3", aspect=w / h), Config.cornell_v3(w, h, 0, 3)
+    r = _renderer(scene, cfg)
+    r.sample(spp)
+    r.post_process()
+    return scene, cfg, r
+
+
+@pytest.mark.parametrize("iterations", [1, 3, 5])
+@pytest.mark.parametrize("demodulate", [0, 1])
+def test_denoise_bit_identical_to_reference(iterations, demodulate):
+    scene, cfg, r = _cornell()
+    ib = r.image_buffer
+    ib[10:14, 20:27] = 0.0             # pixels without samples: shown as post_process shows them, nobody's neighbour
+    ib[60, 5] = 0.0
+    r.image_buffer = ib
+    r.denoise(iterations=iterations, demodulate=demodulate, sigma_color=0.5, sigma_normal=0.3, sigma_depth=0.05, sigma_albedo=0.1)
+    got = r.denoised_pixels
+    ref = fr.denoise(cfg, ib, _gpu_features(r), iterations, demodulate, 0.5, 0.3, 0.05, 0.1)
+    assert _same_bits(got, ref), f"{int((got.view(np.uint32) != ref.view(np.uint32)).sum())} words differ"
+    assert np.isnan(got[11, 21]).all() or _same_bits(got[11, 21], ref[11, 21])
+
+
+def test_denoise_defaults_bit_identical_at_1080p():
+    scene, cfg, r = _cornell(1920, 1080, 4)
+    r.denoise()
+    ref = fr.denoise(cfg, r.image_buffer, _ref_features(scene, cfg))
+    assert _same_bits(r.denoised_pixels, ref)
+
+
+def test_zero_levels_are_post_process_and_denoise_writes_nothing_else():
+    scene, cfg, r = _cornell()
+    ib = r.image_buffer
+    ib[3:5, 7:9] = 0.0
+    r.image_buffer = ib
+    r.post_process()
+    before = {b: r._read(b) for b in (BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS)}
+    r.denoise(iterations=0, demodulate=0)
+    assert _same_bits(r.denoised_pixels, before[BUF_IMAGE_PIXELS])
+    r.denoise()
+    for b, a in before.items():
+        assert _same_bits(r._read(b), a), b
+
+
+def test_features_leave_the_work_counters_alone():
+    _, _, r = _cornell()
+    c0 = r.counters()
+    r.render_features()
+    c1 = r.counters()
+    assert [getattr(c0, f) for f, _ in c0._fields_] == [getattr(c1, f) for f, _ in c1._fields_]
+
+
+def test_stale_features_are_rendered_again_after_set_camera():
+    scene, cfg, r = _cornell()
+    r.render_features()
+    cam = Camera(lookfrom=(6.0, 4.0, 33.0), lookat=(0.0, -1.0, 0.0), vup=(0, 1, 0), vfov=35.0, aspect=W / H, aperture=0.01, focus=4.0)
+    r.set_camera(cam)
+    r.denoise()              # no render_features(): the features from the old pose are stale
+    ref_f = _ref_features(scene, cfg, cam)
+    _assert_features_equal(_gpu_features(r), ref_f)
+    assert _same_bits(r.denoised_pixels, fr.denoise(cfg, r.image_buffer, ref_f))
+
+
+@pytest.mark.parametrize("setter", ["set_config", "set_scene", "set_shape_data"])
+def test_stale_features_are_rendered_again_after_each_setter(setter):
+    """set_config (same resolution: the bunny's next frame), set_scene and set_shape_data make the features stale as well"""
+    if setter == "set_scene":
+        scene, cfg, r = _cornell()
+        r.render_features()
+        new = cornell_box("v2", aspect=W / H)       # other boxes, other materials; the camera stays
+        r.set_scene(new)
+        weights, scene = None, new
+    else:
+        scene, cfg = bunny(aspect=W / H), Config.bunny_glass(W, H, 12, 8, frame=17).copy(max_raymarch=512)
+        r = _renderer(scene, cfg)
+        r.sample(1)
+        r.render_features()
+        weights = load_bunny_weights()
+        if setter == "set_config":
+            cfg = cfg.copy(frame=40)
+            r.set_config(cfg)
+        else:
+            weights = (weights * np.float32(1.05)).astype(np.float32)
+            r.set_shape_data(SHAPE.BUNNY, weights)
+    r.denoise()              # no render_features()
+    ref_f = fr.features(scene, cfg, r.camera, weights)
+    _assert_features_equal(_gpu_features(r), ref_f)
+    assert _same_bits(r.denoised_pixels, fr.denoise(cfg, r.image_buffer, ref_f))
+
+
+def test_src_one_step_launches_then_denoise():
+    """the persistent-ray form in one-step launches (wavefront split, lazy shading), then denoise on its image_buffer"""
+    scene, cfg = src_scene(aspect=W / H), Config.src(W, H, 7, steps_per_launch=1)
+    r = _renderer(scene, cfg)
+    for _ in range(12):
+        r.sample(1)
+    r.post_process()
+    r.denoise()
+    ib = r.image_buffer
+    assert _same_bits(r.denoised_pixels, fr.denoise(cfg, ib, _ref_features(scene, cfg)))
+
+
+def _rmse(a, b, m):
+    return float(np.sqrt(np.mean(((a - b) ** 2)[m])))
+
+
+def _single_object_mask(obj):
+    Wd, Hd = obj.shape
+    p = np.pad(obj, 2, constant_values=-2)
+    m = np.ones_like(obj, bool)
+    for dx in range(5):
+        for dy in range(5):
+            m &= p[dx:dx + Wd, dy:dy + Hd] == obj
+    return m[..., None].repeat(3, axis=2)
+
+
+def test_denoise_quality_against_a_converged_frame():
+    scene, cfg = cornell_box("v3"), Config.cornell_v3(256, 256, 0, 3)
+    ref = _renderer(scene, cfg)
+    ref.set_option("sample_base", 1 << 20)      # samples independent of the noisy frame's
+    ref.sample(1024)
+    ref.post_process()
+    truth = ref.image_pixels
+    r = _renderer(scene, cfg)
+    r.sample(4)
+    r.post_process()
+    r.denoise()
+    m = _single_object_mask(r.feature_object)
+    noisy, den = _rmse(r.image_pixels, truth, m), _rmse(r.denoised_pixels, truth, m)
+    print(f"quality: display RMSE noisy {noisy:.4f}, denoised {den:.4f}, ratio {den / noisy:.3f}")
+    assert den <= 0.35 * noisy, (noisy, den)       # measured: 0.235 with the defaults
+
+
+def test_no_bleeding_between_objects():
+    scene, cfg, r = _cornell()
+    r.render_features()
+    obj = r.feature_object
+    rng = np.random.default_rng(1)
+    col = rng.uniform(0.05, 2.0, size=(len(scene.objects) + 1, 3)).astype(np.float32)
+    ib = np.empty((W, H, 4), np.float32)
+    ib[..., :3] = col[obj + 1] * 4.0
+    ib[..., 3] = 4.0
+    r.image_buffer = ib
+    r.post_process()
+    flat = r.image_pixels
+    for demod in (0, 1):
+        r.denoise(demodulate=demod)
+        np.testing.assert_allclose(r.denoised_pixels, flat, rtol=1e-6, atol=0)
+
+
+def test_denoised_pixels_zero_copy():
+    torch = pytest.importorskip("torch")
+    _, _, r = _cornell()
+    r.denoise()
+    r.sync()
+    t = torch.as_tensor(r.device_array(BUF_DENOISED_PIXELS), device="cuda")
+    assert np.array_equal(t.cpu().numpy().view(np.uint32), r.denoised_pixels.view(np.uint32))
+
+
+def test_async_read_is_ordered_before_the_next_denoise():
+    """a 100 MB read-back of denoised_pixels is still copying when the next one-level denoise (which writes the buffer from its
+    first wave on) is enqueued: only the device-side ordering keeps the copy intact"""
+    _, _, r = _cornell(3840, 2160, 1)
+    r.denoise(iterations=0, demodulate=0)
+    first = r.denoised_pixels
+    out = r.host_array(BUF_DENOISED_PIXELS)
+    t = r.read_async(BUF_DENOISED_PIXELS, out)
+    r.denoise(iterations=1)
+    r.read_wait(t)
+    assert _same_bits(out, first)
+    r.sync()
+    assert not _same_bits(r.denoised_pixels, first)
+
+
+def test_errors():
+    scene, cfg = cornell_box("v3"), Config.cornell_v3(32, 24, 0, 3)
+    r = _renderer(scene, cfg)
+    for b in (BUF_FEAT_ALBEDO, BUF_FEAT_NORMAL, BUF_FEAT_DEPTH, BUF_FEAT_OBJECT, BUF_DENOISED_PIXELS):
+        with pytest.raises(RtpbrError) as e:
+            r._read(b)
+        assert e.value.code == ESTATE
+        with pytest.raises(RtpbrError) as e:
+            r.device_ptr(b)
+        assert e.value.code == ESTATE
+    for bad in ({"iterations": 9}, {"iterations": -1}, {"sigma_color": -0.5}, {"sigma_depth": 0.0}, {"demodulate": 2},
+                {"sigma_normal": float("nan")}):
+        with pytest.raises(RtpbrError) as e:
+            r.denoise(**bad)
+        assert e.value.code == EINVAL, bad
+    # only the colour weight grows (by 4 per level): a tiny sigma_color is refused for many levels, not for one; tiny normal /
+    # depth / albedo sigmas with a finite 1/sigma^2 are accepted
+    with pytest.raises(RtpbrError) as e:
+        r.denoise(iterations=8, sigma_color=3e-18)
+    assert e.value.code == EINVAL
+    r.denoise(iterations=1, sigma_color=3e-18)
+    r.denoise(sigma_normal=1e-18, sigma_depth=1e-18, sigma_albedo=1e-18)
+    r.denoise()
+    with pytest.raises(RtpbrError) as e:
+        r._write(BUF_FEAT_DEPTH, np.zeros((32, 24), np.float32))
+    assert e.value.code == EINVAL
+    r.set_tiles(16, 16, 0, 2)
+    for call in (r.render_features, r.denoise):
+        with pytest.raises(RtpbrError) as e:
+            call()
+        assert e.value.code == ESTATE
+    # a new resolution frees the buffers: ESTATE again until the next call
+    r.set_tiles(0, 0, 0, 1)
+    r.set_config(Config.cornell_v3(40, 24, 0, 3))
+    with pytest.raises(RtpbrError) as e:
+        r._read(BUF_DENOISED_PIXELS)
+    assert e.value.code == ESTATE
+    r.denoise()
+    assert r.denoised_pixels.shape == (40, 24, 3)

@@ -761,6 +761,7 @@ int rto_sample(struct rto_ctx* c, int n) {
     unsigned long long mlp_total = 0;
     int persistent = c->cfg.kernel_form == RTPBR_FORM_PERSISTENT_RAY;
     int steps = persistent ? n * c->cfg.steps_per_launch : n;
+    if (steps < 0) steps = 0;                                  /* steps_per_launch < 0: no bounce-steps, the sample index stays */
     uint32_t base = c->sample_base;
 #ifdef _OPENMP
     int nt = c->threads > 0 ? c->threads : omp_get_max_threads();

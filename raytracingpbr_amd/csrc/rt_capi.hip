@@ -881,10 +881,12 @@ static int poll_plan_readback(rtpbr_ctx* c) {
 // src/ persistent-ray form: n launches of pathtrace() (src/renderer.py:29-30), each cfg.steps_per_launch bounce-steps.
 // A pixel's steps are sequential and the RNG is keyed by the absolute step index, so k launches of s steps equal one launch of
 // k*s steps bit for bit: fuse them (<= 256 steps per kernel) instead of paying a launch + an 80 B/pixel ray_buffer round
-// trip per step.
-static int sample_persistent(rtpbr_ctx* c, int n) {
+// trip per step.  *launched: whether a kernel was enqueued (n * steps_per_launch <= 0 enqueues none; the first kernel of every
+// launch zeroes the other counter buffer, P.counters_next).
+static int sample_persistent(rtpbr_ctx* c, int n, bool* launched) {
     Params& P = c->P;
     long long left = (long long)n * c->cfg.steps_per_launch;
+    *launched = false;
     while (left > 0) {
         int steps = (int)(left < tune::MAX_FUSED_STEPS ? left : tune::MAX_FUSED_STEPS);
         P.sample_base = c->sample_base;
@@ -1056,6 +1058,7 @@ static int sample_persistent(rtpbr_ctx* c, int n) {
             launch_persistent(P, c->kind, steps, c->stream);
         }
         if (c->timed) HIP_TRY(hipEventRecord(b, c->stream));
+        *launched = true;
         c->sample_base += (uint32_t)steps;
         left -= steps;
     }
@@ -1287,8 +1290,9 @@ extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
     c->evp_used = 0;
     c->timed = c->timing != 0;
     c->total1_recorded = false;
+    bool zeroed_next = false;
     if (c->cfg.kernel_form == RTPBR_FORM_PERSISTENT_RAY) {
-        if (int r = sample_persistent(c, n)) return r;
+        if (int r = sample_persistent(c, n, &zeroed_next)) return r;
     } else {
         if (int r = sample_complete_path(c, n)) return r;
     }
@@ -1299,8 +1303,9 @@ extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
         c->total1_recorded = true;
     }
     HIP_TRY(hipGetLastError());
-    // (the first kernel of every src/ path zeroed the other buffer: persistent pool / persistent steps / src_gen)
-    c->counters_clean[c->counters_turn] = n > 0 && c->cfg.kernel_form == RTPBR_FORM_PERSISTENT_RAY;
+    // (the first kernel of every src/ path zeroed the other buffer: persistent pool / persistent steps / src_gen; a persistent-ray call
+    // of no bounce-steps — n = 0 or steps_per_launch <= 0 — enqueued none, and the complete-path kernels zero nothing)
+    c->counters_clean[c->counters_turn] = zeroed_next;
     return RTPBR_OK;
 }
 

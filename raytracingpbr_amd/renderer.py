@@ -37,8 +37,10 @@ class Renderer:
 
     # ------------------------------------------------------------ setup
     def set_config(self, config: Config):
-        self.config = config.copy()
-        self.api.call("set_config", self._ctx, C.byref(self.config))
+        # (kept only once the library has taken it: a refused configuration leaves the buffers' shapes as they were)
+        c = config.copy()
+        self.api.call("set_config", self._ctx, C.byref(c))
+        self.config = c
 
     def set_scene(self, scene: Scene):
         n = len(scene.objects)

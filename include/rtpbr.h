@@ -220,7 +220,10 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
                                       *           cfg.normal_space: local-frame normals stay local), 0 on a miss     */
        RTPBR_BUF_FEAT_DEPTH   = 7,   /* (W,H)   f32 length(hit - ray origin), cfg.max_dis on a miss                 */
        RTPBR_BUF_FEAT_OBJECT  = 8,   /* (W,H)   i32 index of the hit object in the set_scene array, -1 on a miss    */
-       RTPBR_BUF_DENOISED_PIXELS = 9 };/* (W,H,3) f32 denoised display colour                                       */
+       RTPBR_BUF_DENOISED_PIXELS = 9, /* (W,H,3) f32 denoised display colour                                       */
+       /* written by rtpbr_reproject: allocated on its first call, RTPBR_ESTATE before; output only */
+       RTPBR_BUF_MOTION       = 10 };/* (W,H,2) f32 old-frame pixel coordinates each pixel drew its history from,
+                                      *           (-1,-1) = no history (rtpbr_reproject)                           */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -330,6 +333,69 @@ typedef struct rtpbr_denoise_params {   /* 4-byte members, no padding */
 #define RTPBR_DENOISE_DEFAULT_SIGMA_ALBEDO 0.1f
 int rtpbr_render_features(rtpbr_ctx* ctx);
 int rtpbr_denoise(rtpbr_ctx* ctx, const rtpbr_denoise_params* p);
+
+/* ---- Temporal reuse: keep the accumulated samples across a camera move by reprojecting them into the new view.
+ *
+ * rtpbr_reproject(ctx, new_cam, p) replaces rtpbr_set_camera(new_cam) + rtpbr_refresh() for a host that wants to keep
+ * history (the reference clears on every moving frame: src/renderer.py:25-32).  In order:
+ *   1. flushes lazy shading and orders itself behind asynchronous read-backs of image_buffer, ray_buffer and the diff
+ *      buffers (as rtpbr_refresh does; an outstanding rtpbr_read_buffer_async of image_buffer lands the pre-call contents);
+ *   2. renders the features of the current (old) camera if they are stale;
+ *   3-4. keeps the old camera frame, and copies image_buffer, the (normal, depth) records and the object indices into
+ *      internal history buffers (copies: every address rtpbr_buffer_device_ptr handed out stays valid);
+ *   5. applies new_cam exactly as rtpbr_set_camera does;
+ *   6. renders the features of the new camera into RTPBR_BUF_FEAT_* (a following rtpbr_denoise does not render them again);
+ *   7. gathers the history into image_buffer and writes RTPBR_BUF_MOTION (below);
+ *   8. resets what rtpbr_refresh resets except image_buffer: ray_buffer.depth = 0 (in-flight persistent-form paths belong
+ *      to the old camera) and, with adaptive sampling, diff_buffer = (1,1), diff_pixels = 1e32.
+ * sample_base is not reset (neither does rtpbr_refresh): samples taken afterwards continue the RNG sequence and never repeat
+ * the history's.  The work counters are untouched.
+ *
+ * The gather, per new pixel p = (x, y) with new features (z_new, n_new, obj_new) — every operation in f32, in this order,
+ * fused only where fma3(s, b, a) = (fmaf(s, b.x, a.x), ...) is written; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x*b.x)),
+ * length(a) = sqrtf(dot(a, a)), normalize(a) = a * (1 / sqrtf(dot(a, a))), cross as usual (no fma):
+ *   d = normalize(fma3(v, ver1, fma3(u, hor1, llc1)) - lf1), u, v as rtpbr_render_features computes them;
+ *   hit (obj_new >= 0): D = fma3(z_new, d, lf1) - lf0 (the first hit seen from the old eye);
+ *   miss (obj_new = -1): D = d (a point at infinity: every sky kind depends on the direction only);
+ *   N = cross(hor0, ver0);  s = dot(llc0 - lf0, N) / dot(D, N);  no history unless s > 0 (behind the old camera, or NaN);
+ *   P = D * s - (llc0 - lf0);  u0 = dot(P, hor0) / dot(hor0, hor0);  v0 = dot(P, ver0) / dot(ver0, ver0);
+ *   px = u0 * W - 0.5f, py = v0 * H - 0.5f;  no history unless -1 < px < W and -1 < py < H;
+ *   per axis: x0 = floorf(px), fx = px - x0; fx < 2^-10: fx = 0; fx > 1 - 2^-10: x0 = x0 + 1, fx = 0 (the snap: an
+ *     unchanged camera reproduces the buffer exactly); the same for y;
+ *   taps (0,0), (1,0), (0,1), (1,1) in this order at (x0 + i, y0 + j), weight ((1 - fx) or fx) * ((1 - fy) or fy); a tap of
+ *     weight 0 is skipped; a tap is accepted if it lies inside the frame, its old count is > 0, its old object equals
+ *     obj_new and, on a hit, |z_old - L| <= depth_tolerance * L with L = length(D), and (normal_cos <= -1 or
+ *     dot(n_old, n_new) >= normal_cos);
+ *   S = S + w * b_q, Wt = Wt + w over accepted taps (from 0, in tap order, per component); b = S / Wt per component;
+ *   if b.w > max_history: b = b * (max_history / b.w) (all four components, one quotient);
+ *   no accepted tap: b = 0, motion = (-1, -1); otherwise motion = (x0 + fx, y0 + fy) after the snap.
+ * lf/llc/hor/ver: the camera frames of rtpbr_set_camera (0 = old, 1 = new).  Counts become fractional; rtpbr_post_process and
+ * rtpbr_denoise divide by the count as before.
+ *
+ * Known bias.  History is reused as if radiance did not depend on the view: on glossy and refractive surfaces the history
+ * shows the old view's reflections until new samples outweigh it.  A thin-lens camera's history was rendered with defocus
+ * but is reprojected through the lens centre.  max_history bounds both: the history never weighs more than max_history
+ * samples.  Moving objects, an animated frame and tiles of world > 1 are out of scope (see the errors).
+ *
+ * Errors: RTPBR_EINVAL for a NULL context or camera and for bad parameters (max_history not finite and > 0,
+ * depth_tolerance not finite and >= 0, normal_cos not within -1..1); RTPBR_ESTATE before set_config / set_scene /
+ * set_camera, with tiles of world > 1, for the bunny without its shape data, and when rtpbr_set_config, set_scene,
+ * set_shape_data or set_env ran since the last rtpbr_refresh or rtpbr_reproject: history from another scene,
+ * configuration, animation frame or environment is not history.  A refused call changes nothing. */
+typedef struct rtpbr_reproject_params {   /* 4-byte members, no padding */
+    float max_history;       /* cap on a pixel's count after the warp (> 0, finite)                 */
+    float depth_tolerance;   /* relative: |z_old - |X - lookfrom_old|| <= tol * |X - lookfrom_old|  */
+    float normal_cos;        /* a tap needs dot(n_old, n_new) >= normal_cos (-1 disables the test)  */
+} rtpbr_reproject_params;
+/* Defaults (p == NULL), measured over an 11-move pan plus dolly on Cornell v3 (256x256, 4 spp per frame) and the src/ Tokyo
+ * scene (256x144, 4 bounce-steps per frame) against converged frames: the best of 45 settings, display RMSE 0.516x / 0.324x
+ * that of refreshing on every move (examples/reproject_flythrough.py --sweep).  On these scenes the
+ * object test does most of the work: with the normal test off (-1) and a loose depth tolerance the score is 0.8 % better than
+ * with (64, 0.05, 0.9).  raytracingpbr_amd.dataclass.ReprojectParams.DEFAULTS mirrors them (tests/test_reproject_ref.py checks). */
+#define RTPBR_REPROJECT_DEFAULT_MAX_HISTORY     64.0f
+#define RTPBR_REPROJECT_DEFAULT_DEPTH_TOLERANCE 0.2f
+#define RTPBR_REPROJECT_DEFAULT_NORMAL_COS      -1.0f
+int rtpbr_reproject(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtpbr_reproject_params* p);
 
 /* Block until everything enqueued on the context has finished (its stream, and the copies of rtpbr_read_buffer_async). */
 int rtpbr_sync(rtpbr_ctx* ctx);

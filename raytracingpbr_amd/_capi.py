@@ -12,7 +12,7 @@ import ctypes as C
 import os
 
 from .config import Config
-from .dataclass import Camera, Counters, DenoiseParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseParams, ReprojectParams, SDFObject
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPBR_HIP_LIB overrides the path (A/B of differently built HIP libraries); it must still be a HIP build
@@ -26,10 +26,10 @@ ENTRY_POINTS = [
     "packed_bytes", "pack_tiles", "unpack_tiles",
     "get_counters", "get_counter", "last_sample_ms", "last_primary_ms", "get_stream", "set_option", "set_shape_data",
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
-    "render_features", "denoise",
+    "render_features", "denoise", "reproject",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
-ALWAYS_OPTIONAL = ("render_features", "denoise")
+ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject")
 
 
 class RtpbrError(RuntimeError):
@@ -89,6 +89,7 @@ class CApi:
             "test_math": (C.c_int, [p, C.c_int, p, p, p, p, C.c_int]),
             "render_features": (C.c_int, [p]),
             "denoise": (C.c_int, [p, C.POINTER(DenoiseParams)]),
+            "reproject": (C.c_int, [p, C.POINTER(Camera), C.POINTER(ReprojectParams)]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

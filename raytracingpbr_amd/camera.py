@@ -48,9 +48,16 @@ class SmoothCamera:
         return self.moving
 
 
-def render_interactive_frame(renderer, smooth: SmoothCamera, refreshing: bool = False):
-    """src/renderer.py:25-32 with the smoothed pose: upload the pose, refresh if asked or moving, sample, tone map"""
+def render_interactive_frame(renderer, smooth: SmoothCamera, refreshing: bool = False, reproject: bool = False):
+    """src/renderer.py:25-32 with the smoothed pose: upload the pose, refresh if asked or moving, sample, tone map.
+    ``reproject=True``: a moving frame (not asked to refresh) keeps the accumulated samples the new pose can reuse
+    (Renderer.reproject) instead of starting from none."""
     from .dataclass import Camera
     c = renderer.camera
-    renderer.set_camera(Camera(tuple(smooth.position), tuple(smooth.lookat), tuple(smooth.up), c.vfov, c.aspect, c.aperture, c.focus))
+    cam = Camera(tuple(smooth.position), tuple(smooth.lookat), tuple(smooth.up), c.vfov, c.aspect, c.aperture, c.focus)
+    if reproject and smooth.moving and not refreshing:
+        renderer.reproject(cam)
+        renderer.render(refreshing=False)
+        return
+    renderer.set_camera(cam)
     renderer.render(refreshing=bool(refreshing or smooth.moving))

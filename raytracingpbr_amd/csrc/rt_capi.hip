@@ -15,6 +15,7 @@
 
 #include "rt_ctx.hpp"
 #include "rt_features.hpp"
+#include "rt_reproject.hpp"
 
 using namespace rt;
 
@@ -109,9 +110,14 @@ static void free_features(rtpbr_ctx* c) {
     (void)hipFree(c->feat_guides);
     (void)hipFree(c->denoised);
     (void)hipFree(c->denoise_scratch);
+    (void)hipFree(c->hist_image);
+    (void)hipFree(c->hist_guides);
+    (void)hipFree(c->hist_object);
+    (void)hipFree(c->motion);
     c->feat_albedo = c->feat_normal = c->feat_depth = c->denoised = nullptr;
-    c->feat_object = nullptr;
-    c->feat_guides = c->denoise_scratch = nullptr;
+    c->feat_object = c->hist_object = nullptr;
+    c->feat_guides = c->denoise_scratch = c->hist_image = c->hist_guides = nullptr;
+    c->motion = nullptr;
     c->feat_valid = false;
 }
 
@@ -216,6 +222,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
     c->P.cfg = *cfg;
     c->have_cfg = true;
     c->feat_valid = false;
+    c->history_ok = false;
     if (realloc_buf) {
         size_t n = (size_t)cfg->width * cfg->height;
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -339,6 +346,7 @@ extern "C" int rtpbr_set_scene(rtpbr_ctx* c, const rtpbr_object* objs, int n, in
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
     c->feat_valid = false;
+    c->history_ok = false;
     ObjFull full[MAX_OBJ];
     memset(full, 0, sizeof full);
     bool all_box = true, all_bunny = true, any_bunny = false;
@@ -580,6 +588,7 @@ extern "C" int rtpbr_set_env(rtpbr_ctx* c, const void* texels, int w, int h, int
     if (fmt != RTPBR_ENV_RGB8 && fmt != RTPBR_ENV_RGB32F) return fail(RTPBR_EINVAL, "bad env format");
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
+    c->history_ok = false;
     size_t n = (size_t)w * h;
     std::vector<float4> host(n);
     if (fmt == RTPBR_ENV_RGB8) {
@@ -633,6 +642,7 @@ extern "C" int rtpbr_set_shape_data(rtpbr_ctx* c, int shape, const float* data, 
                     for (int j = 0; j < 4; j++)
                         dev[64 + layer * 272 + k * 68 + i * 16 + m * 4 + j] = data[64 + layer * 272 + k * 68 + m * 16 + i * 4 + j];
     c->feat_valid = false;
+    c->history_ok = false;
     if (!c->bunny) HIP_TRY(hipMalloc(&c->bunny, 625 * sizeof(float)));
     HIP_TRY(hipMemcpy(c->bunny, dev, 625 * sizeof(float), hipMemcpyHostToDevice));
     c->P.bunny = c->bunny;
@@ -658,7 +668,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b < 10; b++)
+    for (int b = 0; b < 11; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -684,6 +694,7 @@ extern "C" int rtpbr_refresh(rtpbr_ctx* c) {
     size_t n = (size_t)c->cfg.width * c->cfg.height;
     launch_refresh(c->image_buffer, c->ray_buffer, c->diff_buffer, c->diff_pixels, c->cfg.adaptive_sampling, n, c->stream);
     HIP_TRY(hipGetLastError());
+    c->history_ok = true;
     return RTPBR_OK;
 }
 
@@ -1435,6 +1446,76 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
     return RTPBR_OK;
 }
 
+// ---- temporal reuse (rt_reproject.hip): rtpbr_set_camera + rtpbr_refresh that keeps what the new view can reuse
+enum : unsigned { W_MOTION = 1u << RTPBR_BUF_MOTION };
+
+extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_reproject_params* p) {
+    if (!c || !cam) return fail(RTPBR_EINVAL, "null argument");
+    rtpbr_reproject_params d;
+    if (p) {
+        d = *p;
+    } else {
+        d.max_history = RTPBR_REPROJECT_DEFAULT_MAX_HISTORY;
+        d.depth_tolerance = RTPBR_REPROJECT_DEFAULT_DEPTH_TOLERANCE;
+        d.normal_cos = RTPBR_REPROJECT_DEFAULT_NORMAL_COS;
+    }
+    if (!(d.max_history > 0.0f) || !std::isfinite(d.max_history)) return fail(RTPBR_EINVAL, "reproject max_history must be finite and > 0");
+    if (!(d.depth_tolerance >= 0.0f) || !std::isfinite(d.depth_tolerance)) return fail(RTPBR_EINVAL, "reproject depth_tolerance must be finite and >= 0");
+    if (!(d.normal_cos >= -1.0f && d.normal_cos <= 1.0f)) return fail(RTPBR_EINVAL, "reproject normal_cos must be within -1..1");
+    // every refusal before anything changes
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, "rtpbr_reproject works on the whole frame: not with tiles of world > 1");
+    for (int i = 0; i < c->n_obj; i++)
+        if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
+    if (!c->history_ok)
+        return fail(RTPBR_ESTATE, "rtpbr_reproject: set_config / set_scene / set_shape_data / set_env ran since the last refresh or reproject: "
+                                  "image_buffer is no history of this scene (call rtpbr_refresh)");
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | W_DIFF_PIXELS)) return r;
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;      // the features of the old camera
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->hist_image) HIP_TRY(hipMalloc(&c->hist_image, n * sizeof(float4)));
+    if (!c->hist_guides) HIP_TRY(hipMalloc(&c->hist_guides, n * sizeof(float4)));
+    if (!c->hist_object) HIP_TRY(hipMalloc(&c->hist_object, n * sizeof(int32_t)));
+    if (!c->motion) HIP_TRY(hipMalloc(&c->motion, n * sizeof(float2)));
+    const CamFrame old_frame = c->P.cam;
+    // copies, not pointer swaps: the public buffers keep the addresses rtpbr_buffer_device_ptr handed out
+    HIP_TRY(hipMemcpyAsync(c->hist_image, c->image_buffer, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->hist_guides, c->feat_guides, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->hist_object, c->feat_object, n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (int r = rtpbr_set_camera(c, cam)) return r;
+    if (int r = rtpbr_render_features(c)) return r;          // the features of the new camera (feat_valid from here on)
+    if (int r = rt_order_after_reads(c, W_MOTION)) return r;
+    ReprojArgs A;
+    A.cam0 = old_frame;
+    A.cam1 = c->P.cam;
+    A.cam1.inv_w = 1.0f / (float)c->cfg.width;
+    A.cam1.inv_h = 1.0f / (float)c->cfg.height;
+    A.hist_image = c->hist_image;
+    A.hist_nz = c->hist_guides;
+    A.hist_object = c->hist_object;
+    A.new_nz = c->feat_guides;
+    A.new_object = c->feat_object;
+    A.image_buffer = c->image_buffer;
+    A.motion = c->motion;
+    A.ray_buffer = c->ray_buffer;
+    A.diff_buffer = c->diff_buffer;
+    A.diff_pixels = c->diff_pixels;
+    A.max_history = d.max_history;
+    A.depth_tol = d.depth_tolerance;
+    A.normal_cos = d.normal_cos;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    A.pinhole = c->cfg.camera_kind == RTPBR_CAMERA_PINHOLE;
+    A.adaptive = c->cfg.adaptive_sampling;
+    launch_reproject(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->history_ok = true;
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_sync(rtpbr_ctx* c) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (int r = set_dev(c)) return r;
@@ -1458,10 +1539,12 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_FEAT_DEPTH: *p = c->feat_depth; *n = np * 4; break;
         case RTPBR_BUF_FEAT_OBJECT: *p = c->feat_object; *n = np * 4; break;
         case RTPBR_BUF_DENOISED_PIXELS: *p = c->denoised; *n = np * 12; break;
+        case RTPBR_BUF_MOTION: *p = c->motion; *n = np * 8; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
-    // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise first");
+    // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
+    // rtpbr_reproject)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject first");
     return 0;
 }
 
@@ -1562,8 +1645,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_DENOISED_PIXELS)
-        return fail(RTPBR_EINVAL, "the feature and denoise buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_MOTION)
+        return fail(RTPBR_EINVAL, "the feature, denoise and motion buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

@@ -1,0 +1,123 @@
+// rt_reproject.hip — the gather kernel of rtpbr_reproject (see rt_reproject.hpp; the arithmetic is fixed in include/rtpbr.h).
+#include <hip/hip_runtime.h>
+
+#include "rt_reproject.hpp"
+
+namespace rt {
+
+RT_D vec3 v3f(const float (&a)[3]) { return mk(a[0], a[1], a[2]); }
+
+// Snap of one axis (include/rtpbr.h): a fractional offset within 2^-10 of 0 or 1 moves onto that pixel
+RT_D void snap_axis(float p, int& x0, float& fx) {
+    const float fl = floorf(p);
+    x0 = (int)fl;
+    fx = p - fl;
+    if (fx < 0.0009765625f) {
+        fx = 0.0f;
+    } else if (fx > 0.9990234375f) {
+        x0 = x0 + 1;
+        fx = 0.0f;
+    }
+}
+
+// One lane per pixel, i = x * H + y: lanes of a wave walk down a column, so the new features are read and the outputs written
+// contiguously; the four taps of neighbouring lanes share old pixels (the history is read where the motion takes it, through
+// the caches: for a small move a wave's taps cover about two columns' worth of old pixels).  A tap loads the 4-byte old object
+// first, then the 16-byte history texel, then (hits only) the 16-byte (normal, depth) record.
+__global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
+    const int H = A.height, W = A.width;
+    const uint32_t n = (uint32_t)W * (uint32_t)H;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
+    const CamFrame& f0 = A.cam0;
+    const CamFrame& f1 = A.cam1;
+    // the new pixel's centre ray, as feature_rays forms it
+    float u, v;
+    if (A.pinhole) {
+        u = ((float)x + 0.5f) / (float)W;
+        v = ((float)y + 0.5f) / (float)H;
+    } else {
+        u = ((float)x + 0.5f) * f1.inv_w;
+        v = ((float)y + 0.5f) * f1.inv_h;
+    }
+    const vec3 lf1 = v3f(f1.lf), lf0 = v3f(f0.lf);
+    const vec3 d = normalize(fma3(v, v3f(f1.ver), fma3(u, v3f(f1.hor), v3f(f1.llc))) - lf1);
+    const int obj = A.new_object[i];
+    const bool hit = obj >= 0;
+    vec3 D = d;                                   // a miss: the direction, a point at infinity
+    vec3 nn = mk(0.0f, 0.0f, 0.0f);
+    if (hit) {
+        const float4 nz = A.new_nz[i];
+        D = fma3(nz.w, d, lf1) - lf0;             // the first hit as the old eye sees it
+        nn = mk(nz.x, nz.y, nz.z);
+    }
+    // into the old image plane: the ray lf0 + s D meets the plane of llc0 / hor0 / ver0
+    const vec3 hor0 = v3f(f0.hor), ver0 = v3f(f0.ver);
+    const vec3 q = v3f(f0.llc) - lf0;
+    const vec3 N = cross(hor0, ver0);
+    const float s = dot(q, N) / dot(D, N);
+    float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float Wt = 0.0f;
+    float2 mv = make_float2(-1.0f, -1.0f);
+    if (s > 0.0f) {
+        const vec3 P = D * s - q;
+        const float u0 = dot(P, hor0) / dot(hor0, hor0);
+        const float v0 = dot(P, ver0) / dot(ver0, ver0);
+        const float px = u0 * (float)W - 0.5f, py = v0 * (float)H - 0.5f;
+        if (px > -1.0f && px < (float)W && py > -1.0f && py < (float)H) {      // (also false on NaN): floorf below fits an int
+            int x0, y0;
+            float fx, fy;
+            snap_axis(px, x0, fx);
+            snap_axis(py, y0, fy);
+            const float L = hit ? length(D) : 0.0f;
+            const float tolL = A.depth_tol * L;
+            const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int ti = t & 1, tj = t >> 1;
+                const float w = wx[ti] * wy[tj];
+                const int xq = x0 + ti, yq = y0 + tj;
+                if (w == 0.0f || xq < 0 || xq >= W || yq < 0 || yq >= H) continue;
+                const size_t qi = (size_t)xq * (size_t)H + (size_t)yq;
+                if (A.hist_object[qi] != obj) continue;
+                const float4 b = A.hist_image[qi];
+                if (!(b.w > 0.0f)) continue;
+                if (hit) {
+                    const float4 g = A.hist_nz[qi];
+                    if (!(fabsf(g.w - L) <= tolL)) continue;
+                    if (!(A.normal_cos <= -1.0f || dot(mk(g.x, g.y, g.z), nn) >= A.normal_cos)) continue;
+                }
+                S.x = S.x + w * b.x;
+                S.y = S.y + w * b.y;
+                S.z = S.z + w * b.z;
+                S.w = S.w + w * b.w;
+                Wt = Wt + w;
+            }
+            if (Wt > 0.0f) mv = make_float2((float)x0 + fx, (float)y0 + fy);
+        }
+    }
+    float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (Wt > 0.0f) {
+        b = make_float4(S.x / Wt, S.y / Wt, S.z / Wt, S.w / Wt);
+        if (b.w > A.max_history) {
+            const float k = A.max_history / b.w;
+            b = make_float4(b.x * k, b.y * k, b.z * k, b.w * k);
+        }
+    }
+    A.image_buffer[i] = b;
+    A.motion[i] = mv;
+    // what rtpbr_refresh resets besides image_buffer (refresh_kernel, rt_kernels.hip)
+    A.ray_buffer[i].depth = 0;
+    if (A.adaptive) {
+        A.diff_buffer[i] = make_float2(1.0f, 1.0f);
+        A.diff_pixels[i] = 1e32f;
+    }
+}
+
+void launch_reproject(const ReprojArgs& A, hipStream_t st) {
+    const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
+    hipLaunchKernelGGL(reproject_gather, dim3(grid), dim3(256), 0, st, A);
+}
+
+}  // namespace rt

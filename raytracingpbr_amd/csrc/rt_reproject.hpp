@@ -1,0 +1,35 @@
+// rt_reproject.hpp — the gather kernel of rtpbr_reproject: temporal reuse of the accumulated samples across a camera move.
+//
+//   reproject_gather   one lane per pixel (the buffers' contiguous index i = x * H + y, 256-lane blocks, as feature_rays): the
+//                      new pixel's first hit (or, on a miss, its direction) is projected into the old camera; the history
+//                      (image_buffer before the move) is gathered bilinearly from the 2x2 old pixels around it, keeping only
+//                      taps on the same object with a matching depth and normal; the sum is renormalised and capped.
+//                      The same lane resets what rtpbr_refresh resets except image_buffer (ray_buffer.depth, the diff buffers).
+// The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_reproject) so that a CPU restatement matches bit for
+// bit (tests/reproject_ref/reproject_ref.c).
+#pragma once
+#include "rt_types.hpp"
+
+namespace rt {
+
+struct ReprojArgs {
+    CamFrame cam0, cam1;            // old and new camera frames (rtpbr_set_camera; inv_w / inv_h of the new one filled in)
+    const float4* hist_image;       // (W,H): image_buffer before the move
+    const float4* hist_nz;          // (W,H): the old features' (normal, depth) records
+    const int32_t* hist_object;     // (W,H): the old features' object indices
+    const float4* new_nz;           // (W,H): the new features' (normal, depth) records
+    const int32_t* new_object;      // (W,H)
+    float4* image_buffer;           // out
+    float2* motion;                 // out (RTPBR_BUF_MOTION)
+    rtpbr_ray* ray_buffer;          // out: depth = 0
+    float2* diff_buffer;            // out when adaptive: (1, 1)
+    float* diff_pixels;             // out when adaptive: 1e32
+    float max_history, depth_tol, normal_cos;
+    int32_t width, height;
+    int32_t pinhole;                // cfg.camera_kind == RTPBR_CAMERA_PINHOLE (how the new centre ray's u, v are formed)
+    int32_t adaptive;
+};
+
+void launch_reproject(const ReprojArgs& A, hipStream_t st);
+
+}  // namespace rt

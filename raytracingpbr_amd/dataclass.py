@@ -104,3 +104,12 @@ class DenoiseParams(_Pod):
     # include/rtpbr.h RTPBR_DENOISE_DEFAULT_*, what rtpbr_denoise(ctx, NULL) uses; Renderer.denoise() fills the parameters not
     # given from here (tests/test_feature_ref.py::test_python_denoise_defaults_match_the_header keeps the two equal)
     DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 2.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "sigma_albedo": 0.1}
+
+
+class ReprojectParams(_Pod):
+    """rtpbr_reproject_params (include/rtpbr.h): the history cap and the depth and normal tests of a reprojection tap."""
+    _fields_ = [("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float)]
+
+    # include/rtpbr.h RTPBR_REPROJECT_DEFAULT_*, what rtpbr_reproject(ctx, cam, NULL) uses; Renderer.reproject() fills the
+    # parameters not given from here (tests/test_reproject_ref.py keeps the two equal)
+    DEFAULTS = {"max_history": 64.0, "depth_tolerance": 0.2, "normal_cos": -1.0}

@@ -14,12 +14,14 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseParams, Ray, SDFObject
+from .dataclass import Camera, Counters, DenoiseParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
 # first-hit features (render_features) and the denoised display image (denoise); they exist from the first of those calls on
 BUF_FEAT_ALBEDO, BUF_FEAT_NORMAL, BUF_FEAT_DEPTH, BUF_FEAT_OBJECT, BUF_DENOISED_PIXELS = 5, 6, 7, 8, 9
+# old-frame pixel coordinates each pixel's history came from (reproject); exists from the first reproject() on
+BUF_MOTION = 10
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -127,6 +129,21 @@ class Renderer:
                           float(v["sigma_depth"]), float(v["sigma_albedo"]))
         self.api.call("denoise", self._ctx, C.byref(p))
 
+    # ------------------------------------------------------------ temporal reuse (include/rtpbr.h rtpbr_reproject)
+    def reproject(self, camera: Camera, max_history=None, depth_tolerance=None, normal_cos=None):
+        """set_camera(camera) + refresh() that keeps what the new view can reuse: the accumulated image_buffer is warped into
+        the new view (first-hit depth, object and normal tests; count capped at ``max_history``), ``motion`` says where each
+        pixel's history came from.  Needs a refresh() (or an earlier reproject()) since the last set_config / set_scene /
+        set_shape_data / set_env.  ``None`` = the library's default for that parameter."""
+        given = {"max_history": max_history, "depth_tolerance": depth_tolerance, "normal_cos": normal_cos}
+        if all(v is None for v in given.values()):
+            self.api.call("reproject", self._ctx, C.byref(camera), None)
+        else:
+            v = {k: (ReprojectParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+            p = ReprojectParams(float(v["max_history"]), float(v["depth_tolerance"]), float(v["normal_cos"]))
+            self.api.call("reproject", self._ctx, C.byref(camera), C.byref(p))
+        self.camera = camera
+
     # ------------------------------------------------------------ buffers (field.to_numpy())
     def _shape(self, which):
         W, H = self.config.width, self.config.height
@@ -134,7 +151,7 @@ class Renderer:
                 BUF_RAY_BUFFER: ((W, H, 10), np.float32), BUF_DIFF_BUFFER: ((W, H, 2), np.float32),
                 BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),
                 BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
-                BUF_DENOISED_PIXELS: ((W, H, 3), np.float32)}[which]
+                BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -260,6 +277,11 @@ class Renderer:
     @property
     def denoised_pixels(self):
         return self._read(BUF_DENOISED_PIXELS)
+
+    @property
+    def motion(self):
+        """(W,H,2): the old-frame pixel coordinates the last reproject() took each pixel's history from, (-1,-1) = none"""
+        return self._read(BUF_MOTION)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

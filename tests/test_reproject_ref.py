@@ -1,0 +1,125 @@
+"""CPU tier: the restatement of rtpbr_reproject's gather (tests/reproject_ref/reproject_ref.c) that the GPU tests hold the
+kernel to, checked against what the header promises: an unchanged camera reproduces the buffer, a one-pixel pan shifts it by one
+pixel, disoccluded pixels start from nothing and the cap scales sums and counts together."""
+import os
+import re
+
+import numpy as np
+
+import feature_ref_lib as fr
+import reproject_ref_lib as rr
+from oracle_backend import OracleRenderer
+from raytracingpbr_amd import Camera, Config, cornell_box
+from raytracingpbr_amd.dataclass import ReprojectParams
+
+W, H = 48, 40
+
+
+def _history(w=W, h=H, spp=2, hit_eps=None):
+    cfg = Config.cornell_v3(w, h, seed=3, max_raytrace=3)
+    if hit_eps is not None:
+        cfg = cfg.copy(hit_eps=hit_eps)
+    sc = cornell_box("v3", aspect=w / h)
+    o = OracleRenderer(sc, cfg)
+    o.sample(spp)
+    return sc, cfg, o.image_buffer
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _moved(cam, dx):
+    """the camera translated by dx along its x axis (+x: the Cornell camera looks down -z with y up)"""
+    return Camera(tuple(np.float32(cam.lookfrom[k]) + np.float32(dx if k == 0 else 0) for k in range(3)),
+                  tuple(np.float32(cam.lookat[k]) + np.float32(dx if k == 0 else 0) for k in range(3)),
+                  tuple(cam.vup), cam.vfov, cam.aspect, cam.aperture, cam.focus)
+
+
+def _pixel_width_at_wall(sc, cfg, feats):
+    """the width of one pixel at the back wall's depth (the wall is fronto-parallel: the camera looks down -z)"""
+    cam = sc.camera
+    x, y = 28, 27                                      # between and above the blocks: the back wall
+    assert feats["object"][x, y] == 0
+    th = np.tan(np.radians(np.float64(cam.vfov)) / 2)
+    u, v = (x + 0.5) / W, (y + 0.5) / H
+    d = np.array([(2 * u - 1) * th * cam.aspect, (2 * v - 1) * th, -1.0])
+    z = float(feats["depth"][x, y]) / np.linalg.norm(d)   # distance along -z to the wall
+    return z * 2 * th * cam.aspect / W
+
+
+def test_reference_builds():
+    assert os.path.exists(rr.build())
+    assert hasattr(rr.lib(), "rr_reproject")
+
+
+def test_identical_camera_returns_the_buffer_bitwise():
+    sc, cfg, ib = _history()
+    ib[3:6, 10:12] = 0.0                                # pixels without samples stay without
+    f = fr.features(sc, cfg)
+    out, motion = rr.reproject(cfg, sc.camera, sc.camera, ib, f, f, max_history=1e6)
+    assert np.array_equal(_bits(out), _bits(ib))
+    has = ib[..., 3] > 0
+    xs, ys = np.meshgrid(np.arange(W), np.arange(H), indexing="ij")
+    assert np.array_equal(motion[has], np.stack([xs, ys], -1)[has].astype(np.float32))
+    assert (motion[~has] == -1).all()
+
+
+def test_one_pixel_pan_shifts_history_by_one_pixel():
+    """the camera moves right by one pixel's width at the wall's depth: a wall point the old pixel x + 1 saw, the new pixel x sees
+    (hits to 1e-6: the default hit tolerance of a 48-pixel frame leaves the hit points a few hundredths off the wall)"""
+    sc, cfg, ib = _history(hit_eps=1e-6)
+    f0 = fr.features(sc, cfg)
+    for sign in (1, -1):
+        cam1 = _moved(sc.camera, sign * _pixel_width_at_wall(sc, cfg, f0))
+        f1 = fr.features(sc, cfg, cam1)
+        out, motion = rr.reproject(cfg, sc.camera, cam1, ib, f0, f1, max_history=1e6)
+        checked = 0
+        for x in range(W):
+            xs = x + sign
+            if not 0 <= xs < W:
+                continue
+            for y in range(H):
+                if f1["object"][x, y] == 0 and f0["object"][xs, y] == 0 and ib[xs, y, 3] > 0:
+                    assert motion[x, y].tolist() == [xs, y], (x, y, motion[x, y])
+                    assert np.array_equal(_bits(out[x, y]), _bits(ib[xs, y])), (x, y)
+                    checked += 1
+        assert checked >= 150, checked
+        # the column that comes into view at the frame's edge has no history
+        edge = W - 1 if sign > 0 else 0
+        assert (out[edge, :, 3] == 0).all() and (motion[edge] == -1).all()
+
+
+def test_disoccluded_pixels_start_from_nothing():
+    """after a four-pixel pan, wall pixels whose old counterpart was a block (the wall behind it was not seen) get count 0"""
+    sc, cfg, ib = _history(hit_eps=1e-6)
+    f0 = fr.features(sc, cfg)
+    cam1 = _moved(sc.camera, 4 * _pixel_width_at_wall(sc, cfg, f0))
+    f1 = fr.features(sc, cfg, cam1)
+    out, motion = rr.reproject(cfg, sc.camera, cam1, ib, f0, f1, max_history=1e6)
+    dis = np.zeros((W, H), bool)
+    dis[:-4] = (f1["object"][:-4] == 0) & (f0["object"][4:] >= 5)
+    kept = np.zeros((W, H), bool)
+    kept[:-4] = (f1["object"][:-4] == 0) & (f0["object"][4:] == 0)
+    assert dis.sum() >= 3 and kept.sum() >= 100, (dis.sum(), kept.sum())
+    assert (out[dis] == 0).all() and (motion[dis] == -1).all()
+    assert (out[kept][:, 3] > 0).all()
+
+
+def test_cap_scales_sums_and_counts():
+    sc, cfg, ib = _history(spp=8)
+    f = fr.features(sc, cfg)
+    out, _ = rr.reproject(cfg, sc.camera, sc.camera, ib, f, f, max_history=2.0)
+    k = (np.float32(2.0) / ib[..., 3]).astype(np.float32)[..., None]
+    assert np.array_equal(_bits(out), _bits((ib * k).astype(np.float32)))
+    np.testing.assert_allclose(out[..., 3], 2.0, rtol=1e-6)
+    # a cap above the counts changes nothing
+    out, _ = rr.reproject(cfg, sc.camera, sc.camera, ib, f, f, max_history=8.0)
+    assert np.array_equal(_bits(out), _bits(ib))
+
+
+def test_python_reproject_defaults_match_the_header():
+    hdr = open(os.path.join(os.path.dirname(rr.DIR), "..", "include", "rtpbr.h")).read()
+    found = {m.group(1).lower(): float(m.group(2)) for m in re.finditer(r"#define RTPBR_REPROJECT_DEFAULT_([A-Z_]+)\s+(-?[0-9.]+)f?", hdr)}
+    assert found == {k: float(v) for k, v in ReprojectParams.DEFAULTS.items()}
+    assert set(found) == {"max_history", "depth_tolerance", "normal_cos"}

@@ -222,8 +222,12 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_FEAT_OBJECT  = 8,   /* (W,H)   i32 index of the hit object in the set_scene array, -1 on a miss    */
        RTPBR_BUF_DENOISED_PIXELS = 9, /* (W,H,3) f32 denoised display colour                                       */
        /* written by rtpbr_reproject: allocated on its first call, RTPBR_ESTATE before; output only */
-       RTPBR_BUF_MOTION       = 10 };/* (W,H,2) f32 old-frame pixel coordinates each pixel drew its history from,
+       RTPBR_BUF_MOTION       = 10,  /* (W,H,2) f32 old-frame pixel coordinates each pixel drew its history from,
                                       *           (-1,-1) = no history (rtpbr_reproject)                           */
+       /* noise estimation (rtpbr_noise_update / rtpbr_noise_estimate): allocated on first use, RTPBR_ESTATE before;
+        * outputs only */
+       RTPBR_BUF_MOMENTS      = 11,  /* (W,H,4) f32 moments of the batch means' linear luminance: (sum c L, sum c L^2, sum c, K) */
+       RTPBR_BUF_NOISE        = 12 };/* (W,H)   f32 estimated standard deviation of lum(r(displayed average))          */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -396,6 +400,91 @@ typedef struct rtpbr_reproject_params {   /* 4-byte members, no padding */
 #define RTPBR_REPROJECT_DEFAULT_DEPTH_TOLERANCE 0.2f
 #define RTPBR_REPROJECT_DEFAULT_NORMAL_COS      -1.0f
 int rtpbr_reproject(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtpbr_reproject_params* p);
+
+/* ---- Per-pixel noise estimation and a variance-guided a-trous (the spatial half of SVGF, Schied et al. 2017).
+ *
+ * Notation: r(c) = c / (1 + c) per channel (as rtpbr_denoise); lum(c) = (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z.  Every
+ * operation is f32, in the order written, nothing fused.
+ *
+ * rtpbr_noise_update folds the samples deposited into image_buffer since the last update into RTPBR_BUF_MOMENTS, using an
+ *   internal snapshot s of image_buffer (both allocated zeroed on the first call: everything accumulated until then is the
+ *   first batch).  Per pixel, b = image_buffer:
+ *     d = b - s per component; cnt = d.w;
+ *     if cnt > 0: m = (d.x / cnt, d.y / cnt, d.z / cnt); L = lum(m) (linear: see below); cL = cnt * L;
+ *                 M.x = M.x + cL; M.y = M.y + cL * L; M.z = M.z + cnt; M.w = M.w + 1;
+ *     s = b (in every case).
+ *   So M = (sum c L, sum c L^2, sum c, K) over K batches of c_k samples.  It flushes lazy shading, is ordered behind
+ *   asynchronous reads of the moments, and writes nothing else.
+ *   rtpbr_refresh zeroes M and s when they exist; rtpbr_set_config with a new resolution frees them;
+ *   rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) re-takes s (written data is no batch); rtpbr_reproject warps M (below).
+ *
+ * rtpbr_noise_estimate writes RTPBR_BUF_NOISE = sqrt(v) (correctly rounded) per pixel and, if out != NULL, the statistics;
+ *   it blocks like rtpbr_get_counters.  It renders the features first when they are stale, as rtpbr_denoise does, and
+ *   allocates M (zeroed) when rtpbr_noise_update has not run.  Per pixel p with b = image_buffer:
+ *     b.w > 0 is false:     v = 0, the pixel is not counted as estimated;
+ *     M.w >= 2 (temporal):  mu = M.x / M.z;  sd = sqrt(max((M.y - (M.x * M.x) / M.z) / ((M.w - 1) * M.z), 0));
+ *                           hi = mu + sd; lo = max(mu - sd, 0);  hw = 0.5f * (hi / (1 + hi) - lo / (1 + lo));
+ *                           v = max(hw * hw, 0)   [fmaxf: NaN gives 0].
+ *                           With s2 the per-sample variance of the batch-mean luminance, sum c_k (L_k - mu)^2 has expectation
+ *                           (K - 1) s2, so sd^2 estimates the variance of the mean of M.z samples; the displayed value is
+ *                           r(mean), so sd is carried through r by its two sigma points: for small sd this is r'(mu)^2 sd^2,
+ *                           and v <= 1/4 whatever a firefly does to the moments.  (Moments of lum(r(batch mean)) measure the
+ *                           mean of compressed batch means instead, which one bright sample moves by 1/K while it saturates
+ *                           the display: 12 times too little variance at 8 x 4 spp on Cornell v3)
+ *     otherwise (spatial):  over q = p + (dx, dy), dy = -3..3 (outer), dx = -3..3 (inner), inside the frame, with
+ *                           RTPBR_BUF_FEAT_OBJECT equal to p's and b_q.w > 0:  L = lum(r((b_q.x / b_q.w, b_q.y / b_q.w,
+ *                           b_q.z / b_q.w))); n = n + 1; s1 = s1 + L; s2 = s2 + L * L;
+ *                           v = n >= 2 ? max((s2 - (s1 * s1) / n) / (n - 1), 0) : 0.
+ *   pixels_estimated counts the pixels with b.w > 0, pixels_above those of them with sqrt(v) > threshold, max_noise is the
+ *   largest sqrt(v) (integer atomics, and an unsigned atomic maximum over the bit patterns, which order like the values
+ *   because they are >= +0: the three are independent of the order of execution).
+ *
+ * rtpbr_denoise_guided writes RTPBR_BUF_DENOISED_PIXELS like rtpbr_denoise (and RTPBR_BUF_NOISE: the estimate above is
+ *   recomputed by every call with iterations > 0 — image_buffer has writers the library does not see, and the pass is cheap).
+ *   The same taps, skip rules, tap order, normal and depth terms, average / demodulation / remodulation / tone map as
+ *   rtpbr_denoise.  Beside its colour every pixel carries a variance, v_0 = v above.  Level k, pixel p with samples:
+ *     g = sum K v_q / sum K over q = p + (dx, dy), dy = -1..1 (outer), dx = -1..1 (inner; stride 1 at every level), inside the
+ *       frame, with samples and on p's object; K = {1, 2, 1; 2, 4, 2; 1, 2, 1}; both sums in tap order;
+ *     ic_p = 1 / ((sigma_color * sigma_color) * max(g, variance_floor))    (no 4^k schedule);
+ *     e = ((|r(c_p) - r(c_q)|^2 ic_p + |n_p - n_q|^2 in) + ((z_p - z_q) / max(z_p, 1e-6f))^2 iz);  w = h exp(-min(e, 80));
+ *     c_p <- sum w c_q / sum w;  v_p <- sum (w * w) v_q / ((sum w) * (sum w)), all sums in tap order.
+ *   iterations = 0 is rtpbr_denoise's iterations = 0.  With demodulate = 1 the colours are compared demodulated while v stays
+ *   the variance of the modulated luminance (the albedo is constant per object, so this rescales sigma_color per object).
+ *
+ * rtpbr_reproject with moments (they exist): M is gathered with exactly the accepted taps and weights of the image,
+ *   SM = SM + w * M_q per component in tap order, M = SM / Wt; when the cap applies (b.w > max_history before scaling, f =
+ *   max_history / b.w, the image's quotient): M.x, M.y, M.z are multiplied by f and M.w = M.w > 1 ? 1 + (M.w - 1) * f : M.w,
+ *   which leaves s2 unchanged; no accepted tap: M = 0.  The snapshot becomes the warped image_buffer.  image_buffer,
+ *   RTPBR_BUF_MOTION and the features are bit for bit what they are without moments.
+ *
+ * Errors: RTPBR_ESTATE before set_config (estimate / guided: set_scene and set_camera too) and with tiles of world > 1;
+ * RTPBR_EINVAL for a NULL context, a threshold that is not >= 0, iterations outside 0..8, demodulate not 0/1, a sigma or
+ * variance_floor that is not finite and > 0, or whose 1/sigma^2 or 1/(sigma_color^2 variance_floor) overflows.  A refused call
+ * changes nothing. */
+typedef struct rtpbr_noise_stats {   /* 4-byte members, no padding */
+    uint32_t pixels_estimated;   /* pixels with samples                          */
+    uint32_t pixels_above;       /* ... whose noise exceeds the threshold        */
+    float    max_noise;          /* the largest value of RTPBR_BUF_NOISE         */
+} rtpbr_noise_stats;
+typedef struct rtpbr_denoise_guided_params {   /* 4-byte members, no padding */
+    int32_t iterations;      /* a-trous levels 0..8, step 2^k; 0 = tone map only                           */
+    int32_t demodulate;      /* 1: filter radiance / max(albedo, 1e-3), multiply back                      */
+    float   sigma_color;     /* colour distance in standard deviations of the centre's luminance           */
+    float   sigma_normal, sigma_depth;
+    float   variance_floor;  /* lower bound of the filtered variance in the colour term (> 0)              */
+} rtpbr_denoise_guided_params;
+/* Defaults (p == NULL): the best worst case of the 40 settings of examples/noise_guided.py --sweep on the two still frames of
+ * section 6b (0.329 x / 0.290 x the noisy frame's display RMSE; rtpbr_denoise's defaults score 0.235 / 0.279 there: at two batches
+ * of 2 spp the estimate has one degree of freedom per pixel and the plain filter is the better one — DESIGN.md section 6d).  raytracingpbr_amd.dataclass.DenoiseGuidedParams.DEFAULTS mirrors them (tests/test_noise_ref.py checks). */
+#define RTPBR_DENOISE_GUIDED_DEFAULT_ITERATIONS     4
+#define RTPBR_DENOISE_GUIDED_DEFAULT_DEMODULATE     0
+#define RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_COLOR    16.0f
+#define RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_NORMAL   0.3f
+#define RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_DEPTH    0.2f
+#define RTPBR_DENOISE_GUIDED_DEFAULT_VARIANCE_FLOOR 1e-3f
+int rtpbr_noise_update(rtpbr_ctx* ctx);
+int rtpbr_noise_estimate(rtpbr_ctx* ctx, float threshold, rtpbr_noise_stats* out);
+int rtpbr_denoise_guided(rtpbr_ctx* ctx, const rtpbr_denoise_guided_params* p);
 
 /* Block until everything enqueued on the context has finished (its stream, and the copies of rtpbr_read_buffer_async). */
 int rtpbr_sync(rtpbr_ctx* ctx);

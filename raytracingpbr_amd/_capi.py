@@ -12,7 +12,7 @@ import ctypes as C
 import os
 
 from .config import Config
-from .dataclass import Camera, Counters, DenoiseParams, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseStats, ReprojectParams, SDFObject
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPBR_HIP_LIB overrides the path (A/B of differently built HIP libraries); it must still be a HIP build
@@ -26,10 +26,10 @@ ENTRY_POINTS = [
     "packed_bytes", "pack_tiles", "unpack_tiles",
     "get_counters", "get_counter", "last_sample_ms", "last_primary_ms", "get_stream", "set_option", "set_shape_data",
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
-    "render_features", "denoise", "reproject",
+    "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
-ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject")
+ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided")
 
 
 class RtpbrError(RuntimeError):
@@ -90,6 +90,9 @@ class CApi:
             "render_features": (C.c_int, [p]),
             "denoise": (C.c_int, [p, C.POINTER(DenoiseParams)]),
             "reproject": (C.c_int, [p, C.POINTER(Camera), C.POINTER(ReprojectParams)]),
+            "noise_update": (C.c_int, [p]),
+            "noise_estimate": (C.c_int, [p, C.c_float, C.POINTER(NoiseStats)]),
+            "denoise_guided": (C.c_int, [p, C.POINTER(DenoiseGuidedParams)]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

@@ -16,6 +16,7 @@
 #include "rt_ctx.hpp"
 #include "rt_features.hpp"
 #include "rt_reproject.hpp"
+#include "rt_noise.hpp"
 
 using namespace rt;
 
@@ -121,6 +122,17 @@ static void free_features(rtpbr_ctx* c) {
     c->feat_valid = false;
 }
 
+// buffers of rtpbr_noise_update / rtpbr_noise_estimate / rtpbr_denoise_guided (allocated on first use)
+static void free_noise(rtpbr_ctx* c) {
+    (void)hipFree(c->noise_moments);
+    (void)hipFree(c->noise_snapshot);
+    (void)hipFree(c->hist_moments);
+    (void)hipFree(c->noise_map);
+    (void)hipFree(c->noise_var);
+    c->noise_moments = c->noise_snapshot = c->hist_moments = nullptr;
+    c->noise_map = c->noise_var = nullptr;
+}
+
 extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     if (!c) return RTPBR_OK;
     (void)hipSetDevice(c->device);
@@ -141,6 +153,8 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->cost_buffer);
     (void)hipFree(c->march_out);
     free_features(c);
+    free_noise(c);
+    (void)hipFree(c->noise_stats);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
     rt_rccl_release(c);
@@ -239,6 +253,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
         c->diff_buffer = nullptr;
         c->diff_pixels = nullptr;
         free_features(c);
+        free_noise(c);
         HIP_TRY(hipMalloc(&c->image_buffer, n * sizeof(float4)));
         HIP_TRY(hipMalloc(&c->image_pixels, n * 3 * sizeof(float)));
         HIP_TRY(hipMalloc(&c->ray_buffer, n * sizeof(rtpbr_ray)));
@@ -668,7 +683,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b < 11; b++)
+    for (int b = 0; b < 13; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -690,8 +705,12 @@ extern "C" int rtpbr_refresh(rtpbr_ctx* c) {
     if (!c || !c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
-    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | W_DIFF_PIXELS)) return r;
+    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | W_DIFF_PIXELS | (c->noise_moments ? 1u << RTPBR_BUF_MOMENTS : 0u))) return r;
     size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (c->noise_moments) {      // the noise estimate starts over with the image
+        HIP_TRY(hipMemsetAsync(c->noise_moments, 0, n * sizeof(float4), c->stream));
+        HIP_TRY(hipMemsetAsync(c->noise_snapshot, 0, n * sizeof(float4), c->stream));
+    }
     launch_refresh(c->image_buffer, c->ray_buffer, c->diff_buffer, c->diff_pixels, c->cfg.adaptive_sampling, n, c->stream);
     HIP_TRY(hipGetLastError());
     c->history_ok = true;
@@ -1480,6 +1499,11 @@ extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpb
     if (!c->hist_guides) HIP_TRY(hipMalloc(&c->hist_guides, n * sizeof(float4)));
     if (!c->hist_object) HIP_TRY(hipMalloc(&c->hist_object, n * sizeof(int32_t)));
     if (!c->motion) HIP_TRY(hipMalloc(&c->motion, n * sizeof(float2)));
+    if (c->noise_moments) {      // the moments move with the image
+        if (!c->hist_moments) HIP_TRY(hipMalloc(&c->hist_moments, n * sizeof(float4)));
+        if (int r = rt_order_after_reads(c, 1u << RTPBR_BUF_MOMENTS)) return r;
+        HIP_TRY(hipMemcpyAsync(c->hist_moments, c->noise_moments, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    }
     const CamFrame old_frame = c->P.cam;
     // copies, not pointer swaps: the public buffers keep the addresses rtpbr_buffer_device_ptr handed out
     HIP_TRY(hipMemcpyAsync(c->hist_image, c->image_buffer, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
@@ -1510,9 +1534,187 @@ extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpb
     A.height = c->cfg.height;
     A.pinhole = c->cfg.camera_kind == RTPBR_CAMERA_PINHOLE;
     A.adaptive = c->cfg.adaptive_sampling;
+    A.hist_moments = c->noise_moments ? c->hist_moments : nullptr;
+    A.moments = c->noise_moments;
+    A.snapshot = c->noise_snapshot;
     launch_reproject(A, c->stream);
     HIP_TRY(hipGetLastError());
     c->history_ok = true;
+    return RTPBR_OK;
+}
+
+// ---- noise estimation and the variance-guided a-trous (rt_noise.hip)
+enum : unsigned { W_MOMENTS = 1u << RTPBR_BUF_MOMENTS, W_NOISE = 1u << RTPBR_BUF_NOISE };
+static const char* const NOISE_TILES = "rtpbr_noise_update / rtpbr_noise_estimate / rtpbr_denoise_guided work on the whole frame: not with tiles of world > 1";
+
+static int noise_alloc(rtpbr_ctx* c) {
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->noise_moments) {
+        HIP_TRY(hipMalloc(&c->noise_moments, n * sizeof(float4)));
+        HIP_TRY(hipMemsetAsync(c->noise_moments, 0, n * sizeof(float4), c->stream));
+    }
+    if (!c->noise_snapshot) {
+        HIP_TRY(hipMalloc(&c->noise_snapshot, n * sizeof(float4)));
+        HIP_TRY(hipMemsetAsync(c->noise_snapshot, 0, n * sizeof(float4), c->stream));
+    }
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_noise_update(rtpbr_ctx* c) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, NOISE_TILES);
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    if (int r = noise_alloc(c)) return r;
+    if (int r = rt_order_after_reads(c, W_MOMENTS)) return r;
+    NoiseArgs A{};
+    A.image_buffer = c->image_buffer;
+    A.snapshot = c->noise_snapshot;
+    A.moments = c->noise_moments;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    launch_noise_update(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
+// the estimate pass on the stream (no read-back): RTPBR_BUF_NOISE, the guided filter's level-0 variance and the statistics
+static int noise_estimate_enqueue(rtpbr_ctx* c, float threshold) {
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    if (int r = noise_alloc(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->noise_map) HIP_TRY(hipMalloc(&c->noise_map, n * sizeof(float)));
+    if (!c->noise_var) HIP_TRY(hipMalloc(&c->noise_var, 3 * n * sizeof(float)));
+    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
+    if (int r = rt_order_after_reads(c, W_NOISE)) return r;
+    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    NoiseArgs A{};
+    A.image_buffer = c->image_buffer;
+    A.moments = c->noise_moments;
+    A.object = c->feat_object;
+    A.noise = c->noise_map;
+    A.var0 = c->noise_var;
+    A.stats = c->noise_stats;
+    A.threshold = threshold;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    launch_noise_estimate(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
+static int noise_state_check(rtpbr_ctx* c) {
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, NOISE_TILES);
+    for (int i = 0; i < c->n_obj; i++)
+        if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_noise_estimate(rtpbr_ctx* c, float threshold, rtpbr_noise_stats* out) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "noise threshold must be >= 0");
+    if (int r = noise_state_check(c)) return r;
+    if (int r = noise_estimate_enqueue(c, threshold)) return r;
+    static_assert(sizeof(NoiseStats) == 128, "one line per shard");
+    std::vector<NoiseStats> sh(NOISE_SHARDS);
+    HIP_TRY(hipMemcpyAsync(sh.data(), c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (out) {
+        uint32_t est = 0, above = 0, mx = 0;
+        for (const NoiseStats& s : sh) {
+            est += s.estimated;
+            above += s.above;
+            mx = s.max_bits > mx ? s.max_bits : mx;
+        }
+        out->pixels_estimated = est;
+        out->pixels_above = above;
+        memcpy(&out->max_noise, &mx, sizeof(float));
+    }
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_params* p) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_guided_params d;
+    if (p) {
+        d = *p;
+    } else {
+        d.iterations = RTPBR_DENOISE_GUIDED_DEFAULT_ITERATIONS;
+        d.demodulate = RTPBR_DENOISE_GUIDED_DEFAULT_DEMODULATE;
+        d.sigma_color = RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_COLOR;
+        d.sigma_normal = RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_NORMAL;
+        d.sigma_depth = RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_DEPTH;
+        d.variance_floor = RTPBR_DENOISE_GUIDED_DEFAULT_VARIANCE_FLOOR;
+    }
+    if (d.iterations < 0 || d.iterations > 8) return fail(RTPBR_EINVAL, "denoise iterations must be 0..8");
+    if (d.demodulate != 0 && d.demodulate != 1) return fail(RTPBR_EINVAL, "denoise demodulate must be 0 or 1");
+    const float sig[3] = {d.sigma_color, d.sigma_normal, d.sigma_depth};
+    float inv[3];
+    for (int k = 0; k < 3; k++) {
+        inv[k] = 1.0f / (sig[k] * sig[k]);
+        if (!(sig[k] > 0.0f) || !std::isfinite(sig[k]) || !std::isfinite(inv[k]))
+            return fail(RTPBR_EINVAL, "denoise sigmas must be finite and > 0 (and not so small that 1/sigma^2 overflows)");
+    }
+    const float sc2 = d.sigma_color * d.sigma_color;
+    if (!(d.variance_floor > 0.0f) || !std::isfinite(d.variance_floor) || !std::isfinite(1.0f / (sc2 * d.variance_floor)))
+        return fail(RTPBR_EINVAL, "denoise variance_floor must be finite and > 0 (and 1/(sigma_color^2 variance_floor) must not overflow)");
+    if (int r = noise_state_check(c)) return r;
+    if (d.iterations > 0) {
+        if (int r = noise_estimate_enqueue(c, 0.0f)) return r;
+    } else if (!c->feat_valid) {
+        if (int r = rtpbr_render_features(c)) return r;
+    }
+    if (int r = set_dev(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->denoised) HIP_TRY(hipMalloc(&c->denoised, n * 3 * sizeof(float)));
+    if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
+    if (int r = rt_order_after_reads(c, W_DENOISED)) return r;
+    if (d.iterations == 0) {      // rtpbr_denoise's tone-map-only pass
+        DenoiseArgs Z{};
+        Z.cfg = c->cfg;
+        Z.image_buffer = c->image_buffer;
+        Z.guide_nz = c->feat_guides;
+        Z.albedo = c->feat_albedo;
+        Z.object = c->feat_object;
+        Z.out = c->denoised;
+        Z.demodulate = d.demodulate;
+        Z.width = c->cfg.width;
+        Z.height = c->cfg.height;
+        Z.step = 0;
+        launch_atrous_level(Z, true, true, c->stream);
+        HIP_TRY(hipGetLastError());
+        return RTPBR_OK;
+    }
+    GuidedArgs A{};
+    A.cfg = c->cfg;
+    A.image_buffer = c->image_buffer;
+    A.guide_nz = c->feat_guides;
+    A.albedo = c->feat_albedo;
+    A.object = c->feat_object;
+    A.var0 = c->noise_var;
+    A.out = c->denoised;
+    A.sc2 = sc2;
+    A.in = inv[1];
+    A.iz = inv[2];
+    A.floor = d.variance_floor;
+    A.demodulate = d.demodulate;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    for (int k = 0; k < d.iterations; k++) {
+        const bool last = k + 1 == d.iterations;
+        A.src = k == 0 ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
+        A.vsrc = k == 0 ? nullptr : c->noise_var + (size_t)(1 + ((k - 1) & 1)) * n;
+        A.dst = last ? nullptr : c->denoise_scratch + (size_t)(k & 1) * n;
+        A.vdst = last ? nullptr : c->noise_var + (size_t)(1 + (k & 1)) * n;
+        A.step = 1 << k;
+        launch_guided_level(A, k == 0, last, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
     return RTPBR_OK;
 }
 
@@ -1540,11 +1742,13 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_FEAT_OBJECT: *p = c->feat_object; *n = np * 4; break;
         case RTPBR_BUF_DENOISED_PIXELS: *p = c->denoised; *n = np * 12; break;
         case RTPBR_BUF_MOTION: *p = c->motion; *n = np * 8; break;
+        case RTPBR_BUF_MOMENTS: *p = c->noise_moments; *n = np * 16; break;
+        case RTPBR_BUF_NOISE: *p = c->noise_map; *n = np * 4; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
-    // rtpbr_reproject)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject first");
+    // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* first");
     return 0;
 }
 
@@ -1645,14 +1849,16 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_MOTION)
-        return fail(RTPBR_EINVAL, "the feature, denoise and motion buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_NOISE)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments and noise buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
     if (int r = rt_order_after_reads(c, 1u << which)) return r;
     HIP_TRY(hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, c->stream));
+    if (which == RTPBR_BUF_IMAGE_BUFFER && c->noise_snapshot)      // written data is no batch of the noise estimate
+        HIP_TRY(hipMemcpyAsync(c->noise_snapshot, c->image_buffer, n, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RTPBR_OK;
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "rt_device.hpp"
+#include "rt_noise.hpp"
 
 namespace rt {
 void launch_trace(const Params& P, int kind, int grid, hipStream_t st);
@@ -169,7 +170,7 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[11] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[13] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
     float* feat_albedo = nullptr;      // (W,H,3)
@@ -186,6 +187,13 @@ struct rtpbr_ctx {
     int32_t* hist_object = nullptr;    // (W,H): the old camera's object indices
     float2* motion = nullptr;          // (W,H): RTPBR_BUF_MOTION
     bool history_ok = false;           // no set_config / set_scene / set_shape_data / set_env since the last refresh or reproject
+    // noise estimation and the guided filter (rt_noise.hip): allocated on first use, freed with the context or a new resolution
+    float4* noise_moments = nullptr;   // (W,H): RTPBR_BUF_MOMENTS
+    float4* noise_snapshot = nullptr;  // (W,H): image_buffer at the last rtpbr_noise_update
+    float4* hist_moments = nullptr;    // (W,H): the moments before a reprojection
+    float* noise_map = nullptr;        // (W,H): RTPBR_BUF_NOISE
+    float* noise_var = nullptr;        // 3 x (W,H): the estimate's variance (-1: no samples), then the guided levels' ping-pong
+    rt::NoiseStats* noise_stats = nullptr;
     size_t march_np = 0;
     int src_chain = 1;            // src/ form, fused launches: the plan's chain set runs in the chain kernel beside the pool kernel (rt_chain.hpp)
     long long chain_np_max = 2500000;   // ... frames of more local pixels than this are throughput-bound: no chain set

@@ -1,0 +1,68 @@
+// rt_noise.hpp — per-pixel noise estimation and the variance-guided a-trous (rtpbr_noise_update, rtpbr_noise_estimate,
+// rtpbr_denoise_guided).
+//
+//   noise_update        one lane per pixel along the contiguous index: the samples deposited into image_buffer since the
+//                       snapshot are one batch; its mean's LINEAR luminance goes into the moments (sum c L, sum c L^2,
+//                       sum c, K).  A streaming pass: 32 bytes read, 32 written per pixel.  (Moments of the compressed
+//                       luminance r(mean) of each batch were measured first: they describe the mean of compressed batch means,
+//                       not the displayed r(mean of everything), and under-estimate its variance 12-fold at 32 spp: DESIGN.md 6d.)
+//   noise_estimate      the variance of the displayed luminance per pixel: from the moments (K >= 2) — the standard deviation
+//                       of the mean linear luminance carried through r(c) = c / (1 + c) by its two sigma points, so the
+//                       estimate is bounded by 1/4 whatever a firefly does to the moments —, else from the 7x7
+//                       neighbourhood on the pixel's object (young pixels, as SVGF does); writes RTPBR_BUF_NOISE = sqrt(v), the
+//                       filter's level-0 variance (v, -1 = pixel without samples) and the three statistics.
+//   guided_level<F,L>   atrous_level (rt_features.hip) with the colour term scaled by the 3x3-filtered variance of the centre
+//                       and the variance filtered along with the squared weights.  The variance travels in a record of its
+//                       own, 4 bytes, loaded only on taps that pass the object test.
+// The arithmetic is fixed operation by operation (include/rtpbr.h) so that a CPU restatement matches bit for bit
+// (tests/noise_ref/noise_ref.c).
+#pragma once
+#include "rt_types.hpp"
+
+namespace rt {
+
+// rtpbr_noise_stats as the kernel accumulates it: NOISE_SHARDS copies, one 128-byte line each, block b adds to shard b % 64 and
+// the host folds them (sums and a maximum: still independent of the order).  One copy for all 8100 blocks of a 1080p frame
+// serialised 24 300 atomics on one line: 0.23 ms for a pass that moves 40 bytes per pixel.
+constexpr int NOISE_SHARDS = 64;
+struct NoiseStats {
+    uint32_t estimated, above, max_bits, pad[29];
+};
+
+struct NoiseArgs {
+    const float4* image_buffer;
+    float4* snapshot;             // noise_update: in / out
+    float4* moments;              // noise_update: in / out; noise_estimate: in
+    const int32_t* object;        // noise_estimate: the spatial fallback's object test
+    float* noise;                 // noise_estimate: out, sqrt(v)
+    float* var0;                  // noise_estimate: out, v (-1: no samples)
+    NoiseStats* stats;            // noise_estimate: out (zeroed before the launch)
+    float threshold;
+    int32_t width, height;
+};
+
+struct GuidedArgs {
+    rtpbr_config cfg;             // tone map
+    const float4* image_buffer;
+    const float4* guide_nz;
+    const float* albedo;
+    const int32_t* object;
+    const float* var0;            // level 0: v of noise_estimate (-1: no samples)
+    const float4* src;            // levels > 0: (colour, object word), as atrous_level
+    const float* vsrc;            // levels > 0: the previous level's variance
+    float4* dst;                  // every level but the last
+    float* vdst;
+    float* out;                   // the last level
+    float sc2;                    // sigma_color * sigma_color
+    float in, iz;                 // 1/sigma^2 of normal and depth
+    float floor;                  // variance_floor
+    int32_t step;
+    int32_t demodulate;
+    int32_t width, height;
+};
+
+void launch_noise_update(const NoiseArgs& A, hipStream_t st);
+void launch_noise_estimate(const NoiseArgs& A, hipStream_t st);
+void launch_guided_level(const GuidedArgs& A, bool first, bool last, hipStream_t st);
+
+}  // namespace rt

@@ -24,6 +24,9 @@ RT_D void snap_axis(float p, int& x0, float& fx) {
 // contiguously; the four taps of neighbouring lanes share old pixels (the history is read where the motion takes it, through
 // the caches: for a small move a wave's taps cover about two columns' worth of old pixels).  A tap loads the 4-byte old object
 // first, then the 16-byte history texel, then (hits only) the 16-byte (normal, depth) record.
+// MOMENTS: the luminance moments of the noise estimate (rt_noise.hpp) ride along — the same accepted taps and weights, 16 more
+// bytes per accepted tap; the image's arithmetic is untouched.
+template <bool MOMENTS>
 __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
@@ -58,6 +61,7 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
     const vec3 N = cross(hor0, ver0);
     const float s = dot(q, N) / dot(D, N);
     float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 SM = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float Wt = 0.0f;
     float2 mv = make_float2(-1.0f, -1.0f);
     if (s > 0.0f) {
@@ -93,19 +97,34 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
                 S.z = S.z + w * b.z;
                 S.w = S.w + w * b.w;
                 Wt = Wt + w;
+                if constexpr (MOMENTS) {
+                    const float4 m = A.hist_moments[qi];
+                    SM.x = SM.x + w * m.x;
+                    SM.y = SM.y + w * m.y;
+                    SM.z = SM.z + w * m.z;
+                    SM.w = SM.w + w * m.w;
+                }
             }
             if (Wt > 0.0f) mv = make_float2((float)x0 + fx, (float)y0 + fy);
         }
     }
     float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 M = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (Wt > 0.0f) {
         b = make_float4(S.x / Wt, S.y / Wt, S.z / Wt, S.w / Wt);
+        if constexpr (MOMENTS) M = make_float4(SM.x / Wt, SM.y / Wt, SM.z / Wt, SM.w / Wt);
         if (b.w > A.max_history) {
             const float k = A.max_history / b.w;
             b = make_float4(b.x * k, b.y * k, b.z * k, b.w * k);
+            // the history weighs max_history samples in the estimate as in the image; the per-sample variance stays
+            if constexpr (MOMENTS) M = make_float4(M.x * k, M.y * k, M.z * k, M.w > 1.0f ? 1.0f + (M.w - 1.0f) * k : M.w);
         }
     }
     A.image_buffer[i] = b;
+    if constexpr (MOMENTS) {
+        A.moments[i] = M;
+        A.snapshot[i] = b;      // what is in image_buffer now is no batch
+    }
     A.motion[i] = mv;
     // what rtpbr_refresh resets besides image_buffer (refresh_kernel, rt_kernels.hip)
     A.ray_buffer[i].depth = 0;
@@ -117,7 +136,8 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
 
 void launch_reproject(const ReprojArgs& A, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    hipLaunchKernelGGL(reproject_gather, dim3(grid), dim3(256), 0, st, A);
+    if (A.hist_moments) hipLaunchKernelGGL(reproject_gather<true>, dim3(grid), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(reproject_gather<false>, dim3(grid), dim3(256), 0, st, A);
 }
 
 }  // namespace rt

@@ -5,6 +5,7 @@
 //                      (image_buffer before the move) is gathered bilinearly from the 2x2 old pixels around it, keeping only
 //                      taps on the same object with a matching depth and normal; the sum is renormalised and capped.
 //                      The same lane resets what rtpbr_refresh resets except image_buffer (ray_buffer.depth, the diff buffers).
+//                      reproject_gather<true> also warps the noise estimate's moments (rtpbr_noise_update) with the same taps.
 // The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_reproject) so that a CPU restatement matches bit for
 // bit (tests/reproject_ref/reproject_ref.c).
 #pragma once
@@ -28,6 +29,10 @@ struct ReprojArgs {
     int32_t width, height;
     int32_t pinhole;                // cfg.camera_kind == RTPBR_CAMERA_PINHOLE (how the new centre ray's u, v are formed)
     int32_t adaptive;
+    // the noise estimate's moments (rt_noise.hpp), when the context tracks them: nullptr otherwise
+    const float4* hist_moments;     // (W,H): the moments before the move
+    float4* moments;                // out: warped with the image's taps and weights, capped with it
+    float4* snapshot;               // out: the warped image_buffer
 };
 
 void launch_reproject(const ReprojArgs& A, hipStream_t st);

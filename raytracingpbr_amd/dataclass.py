@@ -113,3 +113,19 @@ class ReprojectParams(_Pod):
     # include/rtpbr.h RTPBR_REPROJECT_DEFAULT_*, what rtpbr_reproject(ctx, cam, NULL) uses; Renderer.reproject() fills the
     # parameters not given from here (tests/test_reproject_ref.py keeps the two equal)
     DEFAULTS = {"max_history": 64.0, "depth_tolerance": 0.2, "normal_cos": -1.0}
+
+
+class NoiseStats(_Pod):
+    """rtpbr_noise_stats (include/rtpbr.h): what rtpbr_noise_estimate counts over the frame."""
+    _fields_ = [("pixels_estimated", C.c_uint32), ("pixels_above", C.c_uint32), ("max_noise", C.c_float)]
+
+
+class DenoiseGuidedParams(_Pod):
+    """rtpbr_denoise_guided_params (include/rtpbr.h): the a-trous whose colour term is measured in standard deviations of the
+    pixel's estimated noise."""
+    _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("variance_floor", C.c_float)]
+
+    # include/rtpbr.h RTPBR_DENOISE_GUIDED_DEFAULT_*, what rtpbr_denoise_guided(ctx, NULL) uses; Renderer.denoise_guided() fills
+    # the parameters not given from here (tests/test_noise_ref.py keeps the two equal)
+    DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 16.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "variance_floor": 1e-3}

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseParams, Ray, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseStats, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -22,6 +22,8 @@ BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PI
 BUF_FEAT_ALBEDO, BUF_FEAT_NORMAL, BUF_FEAT_DEPTH, BUF_FEAT_OBJECT, BUF_DENOISED_PIXELS = 5, 6, 7, 8, 9
 # old-frame pixel coordinates each pixel's history came from (reproject); exists from the first reproject() on
 BUF_MOTION = 10
+# luminance moments of the batch means (noise_update) and the per-pixel noise map (noise_estimate); they exist from the first of those calls on
+BUF_MOMENTS, BUF_NOISE = 11, 12
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -33,6 +35,7 @@ class Renderer:
         self.device = device
         self.samples_per_frame = 1           # SAMPLES_PER_FRAME, src/config.py:9
         self._host_arrays = {}               # address -> bytes of the page-locked blocks handed out by host_array()
+        self.track_noise = False             # True: every sample() call is one batch of the noise estimate (noise_update() after it)
         self.set_config(config)
         self.set_scene(scene)
         self.set_camera(camera if camera is not None else scene.camera)
@@ -94,6 +97,8 @@ class Renderer:
     def sample(self, n: int = 1):
         """complete-path form: n samples per pixel; persistent-ray form: n pathtrace() launches."""
         self.api.call("sample", self._ctx, int(n))
+        if self.track_noise:
+            self.noise_update()
 
     pathtrace = sample
 
@@ -144,6 +149,55 @@ class Renderer:
             self.api.call("reproject", self._ctx, C.byref(camera), C.byref(p))
         self.camera = camera
 
+    # ------------------------------------------------------------ noise estimation (include/rtpbr.h rtpbr_noise_*)
+    def noise_update(self):
+        """Fold the samples deposited since the last call into ``moments`` as one batch (the first call's batch is everything
+        accumulated so far).  The estimate needs two batches per pixel; before that ``noise_estimate`` looks at the neighbours."""
+        self.api.call("noise_update", self._ctx)
+
+    def noise_estimate(self, threshold: float = 0.0) -> NoiseStats:
+        """Write ``noise`` (the estimated standard deviation of each pixel's displayed luminance, in the c / (1 + c) domain) and
+        return how many pixels have samples, how many of them are noisier than ``threshold``, and the largest value.  Blocks."""
+        s = NoiseStats()
+        self.api.call("noise_estimate", self._ctx, float(threshold), C.byref(s))
+        return s
+
+    def denoise_guided(self, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, variance_floor=None):
+        """The a-trous of ``denoise`` with the colour distance measured in standard deviations of each pixel's estimated noise
+        (``sigma_color`` of them), the variance filtered along level by level.  Writes ``denoised_pixels`` and ``noise``.
+        ``None`` = the library's default for that parameter."""
+        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
+                 "sigma_depth": sigma_depth, "variance_floor": variance_floor}
+        if all(v is None for v in given.values()):
+            self.api.call("denoise_guided", self._ctx, None)
+            return
+        v = {k: (DenoiseGuidedParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+        p = DenoiseGuidedParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                                float(v["sigma_depth"]), float(v["variance_floor"]))
+        self.api.call("denoise_guided", self._ctx, C.byref(p))
+
+    def render_until(self, noise: float, max_spp: int, batch_spp: int = 16):
+        """Sample in batches of ``batch_spp`` (sample() calls of that size, each one batch of the noise estimate) until no pixel's
+        estimated noise exceeds ``noise`` or ``max_spp`` is spent; never fewer than two batches, which the estimate needs.
+        Returns (spp used, NoiseStats of the last estimate).  Continues whatever is accumulated: refresh() first for a new frame."""
+        if not (batch_spp >= 1 and max_spp >= 1):
+            raise ValueError("batch_spp and max_spp must be >= 1")
+        keep, self.track_noise = self.track_noise, False
+        try:
+            used, batches, stats = 0, 0, None
+            while used < max_spp:
+                n = min(int(batch_spp), int(max_spp) - used)
+                self.sample(n)
+                self.noise_update()
+                used, batches = used + n, batches + 1
+                if batches >= 2 or used >= max_spp:
+                    stats = self.noise_estimate(noise)
+                    if stats.pixels_above == 0:
+                        break
+            return used, stats
+        finally:
+            self.track_noise = keep
+
     # ------------------------------------------------------------ buffers (field.to_numpy())
     def _shape(self, which):
         W, H = self.config.width, self.config.height
@@ -151,7 +205,8 @@ class Renderer:
                 BUF_RAY_BUFFER: ((W, H, 10), np.float32), BUF_DIFF_BUFFER: ((W, H, 2), np.float32),
                 BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),
                 BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
-                BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32)}[which]
+                BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
+                BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -282,6 +337,17 @@ class Renderer:
     def motion(self):
         """(W,H,2): the old-frame pixel coordinates the last reproject() took each pixel's history from, (-1,-1) = none"""
         return self._read(BUF_MOTION)
+
+    @property
+    def moments(self):
+        """(W,H,4): (sum c L, sum c L^2, sum c, K) over the K batches noise_update() has folded in, c samples each, L the
+        compressed luminance of the batch mean"""
+        return self._read(BUF_MOMENTS)
+
+    @property
+    def noise(self):
+        """(W,H): the last noise_estimate() / denoise_guided()'s standard deviation of each pixel's displayed luminance"""
+        return self._read(BUF_NOISE)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

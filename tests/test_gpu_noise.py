@@ -1,0 +1,278 @@
+"""Noise estimation and the variance-guided a-trous on the GPU (rtpbr_noise_update, rtpbr_noise_estimate, rtpbr_denoise_guided,
+the moment warp of rtpbr_reproject), held bit for bit to the CPU restatement tests/noise_ref/noise_ref.c, plus the state and
+error rules of include/rtpbr.h and Renderer.render_until."""
+import numpy as np
+import pytest
+
+import feature_ref_lib as fr
+import noise_ref_lib as nr
+import test_gpu_features_denoise as fd
+import test_gpu_reproject as rp
+from raytracingpbr_amd import Config, cornell_box, src_scene
+from raytracingpbr_amd._capi import RtpbrError
+from raytracingpbr_amd.renderer import (BUF_DIFF_BUFFER, BUF_DIFF_PIXELS, BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_MOMENTS, BUF_NOISE,
+                                        BUF_RAY_BUFFER)
+
+pytestmark = pytest.mark.gpu
+
+ESTATE, EINVAL = -4, -1
+W, H = 97, 61
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _same(got, want, what):
+    bad = _bits(got) != _bits(want)
+    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
+
+
+def _batches(r, t, n, per):
+    """n sample() calls of `per`, each one batch on the GPU and in the CPU tracker"""
+    for _ in range(n):
+        r.sample(per)
+        r.noise_update()
+        t.update(r.image_buffer)
+
+
+def _check_estimate_and_guided(r, cfg, t, threshold=0.02, **params):
+    ib = r.image_buffer
+    _same(r.moments, t.moments, "moments")
+    st = r.noise_estimate(threshold)
+    feats = fd._gpu_features(r)
+    noise, var0, want = nr.estimate(ib, t.moments, feats["object"], threshold)
+    _same(r.noise, noise, "noise")
+    assert (st.pixels_estimated, st.pixels_above) == want[:2]
+    assert np.float32(st.max_noise).view(np.uint32) == np.float32(want[2]).view(np.uint32)
+    r.denoise_guided(**params)
+    _same(r.denoised_pixels, nr.guided(cfg, ib, feats, var0, **params), "guided")
+    _same(r.noise, noise, "noise after denoise_guided")
+    return st, var0
+
+
+@pytest.mark.parametrize("name", list(fd._scenes(W, H)))
+def test_bit_identical_on_every_scene_kind(name):
+    scene, cfg = fd._scenes(W, H)[name]
+    r = fd._renderer(scene, cfg)
+    t = nr.Tracker(W, H)
+    _batches(r, t, 3, 2 if cfg.kernel_form == 0 else 6)
+    r.noise_estimate(0.0)              # renders the features, which were never asked for
+    fd._assert_features_equal(fd._gpu_features(r), fd._ref_features(scene, cfg))
+    st, var0 = _check_estimate_and_guided(r, cfg, t)
+    assert st.pixels_estimated > 0 and (var0 > 0).any()
+
+
+def test_persistent_form_with_adaptive_sampling():
+    """per-pixel batch counts differ: pixels the adaptive sampler leaves alone deposit nothing in some batches"""
+    scene, cfg = src_scene(aspect=W / H), Config.src(W, H, 7, steps_per_launch=1).copy(adaptive_sampling=1)
+    r = fd._renderer(scene, cfg)
+    r.refresh()                    # (diff_pixels = 1e32: the adaptive mask lets every pixel start)
+    t = nr.Tracker(W, H)
+    for k in range(10):
+        r.sample(3)
+        r.post_process()           # the adaptive statistics are kept by post_process
+        r.noise_update()
+        t.update(r.image_buffer)
+    K = t.moments[..., 3]
+    print("batches per pixel:", np.unique(K, return_counts=True))
+    assert len(np.unique(K)) > 1 and (K >= 2).any()
+    _check_estimate_and_guided(r, cfg, t)
+
+
+@pytest.mark.parametrize("iterations", [1, 3, 5])
+@pytest.mark.parametrize("demodulate", [0, 1])
+def test_guided_levels_and_demodulation(iterations, demodulate):
+    scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    r = fd._renderer(scene, cfg)
+    t = nr.Tracker(W, H)
+    _batches(r, t, 4, 2)
+    ib = r.image_buffer
+    ib[10:14, 20:27] = 0.0             # pixels without samples
+    ib[60, 5] = 0.0
+    r.image_buffer = ib
+    t.written(ib)
+    _check_estimate_and_guided(r, cfg, t, iterations=iterations, demodulate=demodulate, sigma_color=2.0, sigma_normal=0.3, sigma_depth=0.05,
+                               variance_floor=1e-5)
+    assert (r.noise[10:14, 20:27] == 0).all()
+    # the zeroed pixels' next batch counts from the written state
+    _batches(r, t, 1, 2)
+    _same(r.moments, t.moments, "moments after a write and another batch")
+
+
+def test_young_pixels_use_the_neighbourhood():
+    scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    r = fd._renderer(scene, cfg)
+    r.sample(4)
+    t = nr.Tracker(W, H)               # no noise_update: every pixel takes the spatial estimate
+    r.noise_estimate(0.0)              # (allocates the moments, zeroed)
+    st, var0 = _check_estimate_and_guided(r, cfg, t)
+    assert (r.moments == 0).all() and (var0 > 0).any()
+    _batches(r, t, 1, 4)               # one batch (all 8 samples): still spatial
+    _check_estimate_and_guided(r, cfg, t)
+
+
+def test_defaults_bit_identical_at_1080p():
+    scene, cfg = cornell_box("v3", aspect=1920 / 1080), Config.cornell_v3(1920, 1080, 0, 3)
+    r = fd._renderer(scene, cfg)
+    t = nr.Tracker(1920, 1080)
+    _batches(r, t, 3, 2)
+    _check_estimate_and_guided(r, cfg, t)
+
+
+def test_state_rules():
+    scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    r = fd._renderer(scene, cfg)
+    for b in (BUF_MOMENTS, BUF_NOISE):
+        with pytest.raises(RtpbrError) as e:
+            r._read(b)
+        assert e.value.code == ESTATE
+    t = nr.Tracker(W, H)
+    _batches(r, t, 2, 2)
+    assert (r.moments[..., 3] == 2).all()
+    r.refresh()
+    assert (r.moments == 0).all()
+    r.sample(2)
+    r.noise_update()
+    assert (r.moments[..., 3] == 1).all() and (r.moments[..., 2] == 2).all()      # the snapshot was zeroed too
+    # write_buffer re-takes the snapshot: written data is no batch
+    M = r.moments
+    ib = r.image_buffer
+    ib[..., :3] *= 2
+    ib[..., 3] += 5
+    r.image_buffer = ib
+    r.noise_update()
+    _same(r.moments, M, "moments after write_buffer + noise_update")
+    for b in (BUF_MOMENTS, BUF_NOISE):
+        with pytest.raises(RtpbrError) as e:
+            r._write(b, np.zeros(r._shape(b)[0], np.float32))
+        assert e.value.code == EINVAL
+    # a new resolution frees the buffers
+    r.set_config(Config.cornell_v3(40, 24, 0, 3))
+    for b in (BUF_MOMENTS, BUF_NOISE):
+        with pytest.raises(RtpbrError) as e:
+            r._read(b)
+        assert e.value.code == ESTATE
+    r.sample(1)
+    r.noise_update()
+    assert r.moments.shape == (40, 24, 4)
+    assert r.noise_estimate(0.0).pixels_estimated == 40 * 24 and r.noise.shape == (40, 24)
+
+
+def test_errors_and_a_refused_call_changes_nothing():
+    scene, cfg = cornell_box("v3"), Config.cornell_v3(32, 24, 0, 3)
+    r = fd._renderer(scene, cfg)
+    for _ in range(2):
+        r.sample(1)
+        r.noise_update()
+    r.noise_estimate(0.01)
+    r.denoise_guided()
+    keep = {b: r._read(b) for b in (BUF_MOMENTS, BUF_NOISE, BUF_IMAGE_BUFFER)}
+    den = r.denoised_pixels
+    nan, inf = float("nan"), float("inf")
+    for bad in ({"iterations": 9}, {"iterations": -1}, {"demodulate": 2}, {"sigma_color": -0.5}, {"sigma_color": 0.0}, {"sigma_color": nan},
+                {"sigma_normal": inf}, {"sigma_normal": 0.0}, {"sigma_depth": 0.0}, {"sigma_depth": nan}, {"variance_floor": 0.0},
+                {"variance_floor": -1.0}, {"variance_floor": inf}, {"variance_floor": nan}, {"variance_floor": 1e-45, "sigma_color": 1e-3}):
+        with pytest.raises(RtpbrError) as e:
+            r.denoise_guided(**bad)
+        assert e.value.code == EINVAL, bad
+    for bad in (-1.0, nan):
+        with pytest.raises(RtpbrError) as e:
+            r.noise_estimate(bad)
+        assert e.value.code == EINVAL
+    r.set_tiles(16, 16, 0, 2)
+    for call in (r.noise_update, r.noise_estimate, r.denoise_guided):
+        with pytest.raises(RtpbrError) as e:
+            call()
+        assert e.value.code == ESTATE
+    r.set_tiles(0, 0, 0, 1)
+    for b, a in keep.items():
+        _same(r._read(b), a, f"buffer {b} after refused calls")
+    _same(r.denoised_pixels, den, "denoised_pixels after refused calls")
+
+
+@pytest.mark.parametrize("form", ["complete", "persistent"])
+def test_the_calls_leave_everything_else_untouched(form):
+    if form == "complete":
+        scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    else:
+        scene, cfg = src_scene(aspect=W / H), Config.src(W, H, 7, steps_per_launch=1).copy(adaptive_sampling=1)
+    r = fd._renderer(scene, cfg)
+    r.sample(3)
+    r.post_process()
+    r.sample(2)
+    others = (BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS)
+    before = {b: r._read(b) for b in others}
+    c0 = r.counters()
+    r.noise_update()
+    r.noise_estimate(0.01)
+    r.denoise_guided()
+    r.noise_update()
+    c1 = r.counters()
+    assert [getattr(c0, f) for f, _ in c0._fields_] == [getattr(c1, f) for f, _ in c1._fields_]
+    for b, a in before.items():
+        _same(r._read(b), a, f"buffer {b}")
+
+
+@pytest.mark.parametrize("move", ["translate", "yaw", "vfov"])
+def test_reproject_warps_the_moments(move):
+    scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    old, new = rp.MOVES[move](scene.camera)
+    r, plain = rp._with_history(scene, cfg, old, 0), rp._with_history(scene, cfg, old, 0)
+    t = nr.Tracker(W, H)
+    _batches(r, t, 4, 2)
+    for _ in range(4):
+        plain.sample(2)
+    ib = r.image_buffer
+    params = dict(max_history=5.0)             # 8 samples of history: the cap applies
+    r.reproject(new, **params)
+    plain.reproject(new, **params)
+    f0, f1 = fr.features(scene, cfg, old), fr.features(scene, cfg, new)
+    want_ib, want_M = nr.reproject(cfg, old, new, ib, t.moments, f0, f1, **params)
+    _same(r.moments, want_M, "moments")
+    _same(r.image_buffer, want_ib, "image_buffer")
+    _same(r.image_buffer, plain.image_buffer, "image_buffer against a context that never tracked noise")
+    _same(r.motion, plain.motion, "motion")
+    fd._assert_features_equal(fd._gpu_features(r), fd._gpu_features(plain))
+    kept = want_ib[..., 3] > 0
+    assert kept.any() and (~kept).any() and (want_M[~kept] == 0).all() and (want_M[kept][:, 3] > 1).all()
+    # the snapshot is the warped image: the next batch holds the new samples only
+    t.moments[:], t.snapshot[:] = want_M, want_ib
+    _batches(r, t, 1, 2)
+    _same(r.moments, t.moments, "moments one batch after the reprojection")
+
+
+def test_an_unchanged_camera_reproduces_the_moments():
+    scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    r = rp._with_history(scene, cfg, scene.camera, 0)
+    t = nr.Tracker(W, H)
+    _batches(r, t, 3, 2)
+    r.reproject(scene.camera, max_history=1e6)
+    _same(r.moments, t.moments, "moments after an identical reprojection")
+
+
+def test_render_until():
+    scene, cfg = cornell_box("v3", aspect=1), Config.cornell_v3(64, 64, 0, 3)
+    used = []
+    for thr in (0.5, 0.3, 0.0):        # the estimate never exceeds 1/2: the first is met at once, the last never
+        r = fd._renderer(scene, cfg)
+        r.refresh()
+        spp, st = r.render_until(thr, max_spp=320, batch_spp=16)
+        print(f"threshold {thr}: {spp} spp, {st.pixels_above} pixels above, max noise {st.max_noise:.4f}")
+        assert st.pixels_above == 0 or spp == 320
+        assert spp <= 320 and (spp == 320 or st.max_noise <= thr)
+        assert float(r.image_buffer[..., 3].max()) == spp
+        used.append(spp)
+    assert used == sorted(used) and used[0] == 32 and used[-1] == 320      # a tighter threshold never uses fewer samples
+
+
+def test_track_noise_makes_every_sample_call_a_batch():
+    scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    r = fd._renderer(scene, cfg)
+    r.track_noise = True
+    t = nr.Tracker(W, H)
+    for n in (1, 3, 2):
+        r.sample(n)
+        t.update(r.image_buffer)
+    _same(r.moments, t.moments, "moments")
+    assert (r.moments[..., 3] == 3).all()

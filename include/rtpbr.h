@@ -227,7 +227,10 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        /* noise estimation (rtpbr_noise_update / rtpbr_noise_estimate): allocated on first use, RTPBR_ESTATE before;
         * outputs only */
        RTPBR_BUF_MOMENTS      = 11,  /* (W,H,4) f32 moments of the batch means' linear luminance: (sum c L, sum c L^2, sum c, K) */
-       RTPBR_BUF_NOISE        = 12 };/* (W,H)   f32 estimated standard deviation of lum(r(displayed average))          */
+       RTPBR_BUF_NOISE        = 12,  /* (W,H)   f32 estimated standard deviation of lum(r(displayed average))          */
+       /* the pixel selection (rtpbr_select_mask / rtpbr_select_noisy): allocated on the first select call, RTPBR_ESTATE before;
+        * output only */
+       RTPBR_BUF_SELECTION    = 13 };/* (W,H)   u8  1 = selected: what rtpbr_sample_selected traces                           */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -485,6 +488,37 @@ typedef struct rtpbr_denoise_guided_params {   /* 4-byte members, no padding */
 int rtpbr_noise_update(rtpbr_ctx* ctx);
 int rtpbr_noise_estimate(rtpbr_ctx* ctx, float threshold, rtpbr_noise_stats* out);
 int rtpbr_denoise_guided(rtpbr_ctx* ctx, const rtpbr_denoise_guided_params* p);
+
+/* ---- Adaptive sampling of the complete-path form: select pixels, then trace samples through the selected pixels only.
+ *
+ * Both select calls write RTPBR_BUF_SELECTION (one byte per pixel, 0 / 1) and build, on the device, the list of the selected
+ * pixels in ascending buffer index x * H + y; its length comes back through n_selected (4 bytes are all that cross to the host).
+ * They block.  The selection stays until the next select call; rtpbr_set_config with a new resolution frees the buffer and drops it.
+ *
+ * rtpbr_select_mask takes a host mask in the field layout ([x][y], y fastest), nbytes = W * H; nonzero = selected: the
+ *   region-of-interest entry.
+ * rtpbr_select_noisy recomputes the noise estimate exactly as rtpbr_noise_estimate(threshold) does (features rendered first when
+ *   stale; writes RTPBR_BUF_NOISE), then selects pixel p when
+ *     image_buffer[p].w > 0 is false (no samples: for example no history after rtpbr_reproject), or
+ *     some pixel q inside the frame with max(|dx|, |dy|) <= dilate has noise[q] > threshold          (dilate 0..3).
+ *   Comparisons only, no arithmetic.  dilate > 0 keeps the neighbours of a noisy pixel sampling: the mitigation of the bias of
+ *   stopping a pixel on an estimate made from its own samples.
+ *
+ * rtpbr_sample_selected is rtpbr_sample(n) restricted to the list: every selected pixel receives the samples with absolute
+ *   indices sample_base .. sample_base + n - 1, added in sample order; every other pixel of image_buffer stays as it is, bit for
+ *   bit; sample_base advances by n (unselected pixels skip those indices, so a pixel's sample k is the same ray whatever the
+ *   selection history was).  An empty selection traces nothing and still advances sample_base; a full one gives the image_buffer
+ *   and the work counters of rtpbr_sample(n).  Counters: samples = deposits = n_selected * n.  Asynchronous, ordered behind
+ *   asynchronous reads, flushes lazy shading and is timed (rtpbr_last_sample_ms) like rtpbr_sample.  It runs the general
+ *   ahead-of-time kernels with item-linear staging whatever the scheduler, jit, jit_bake, primary_split and stage_dense options
+ *   say: same bits.
+ *
+ * Errors: RTPBR_ESTATE before set_config / set_scene / set_camera and with tiles of world > 1; rtpbr_sample_selected also before
+ * any select call, in the persistent-ray form (it has cfg.adaptive_sampling) and with option precision = 1.  RTPBR_EINVAL for
+ * NULL pointers, nbytes != W * H, n < 0, a threshold that is not >= 0, dilate outside 0..3.  A refused call changes nothing. */
+int rtpbr_select_mask(rtpbr_ctx* ctx, const uint8_t* mask, size_t nbytes, uint32_t* n_selected);
+int rtpbr_select_noisy(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
+int rtpbr_sample_selected(rtpbr_ctx* ctx, int n);
 
 /* Block until everything enqueued on the context has finished (its stream, and the copies of rtpbr_read_buffer_async). */
 int rtpbr_sync(rtpbr_ctx* ctx);

@@ -27,9 +27,11 @@ ENTRY_POINTS = [
     "get_counters", "get_counter", "last_sample_ms", "last_primary_ms", "get_stream", "set_option", "set_shape_data",
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
     "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
+    "select_mask", "select_noisy", "sample_selected",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
-ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided")
+ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
+                   "select_mask", "select_noisy", "sample_selected")
 
 
 class RtpbrError(RuntimeError):
@@ -93,6 +95,9 @@ class CApi:
             "noise_update": (C.c_int, [p]),
             "noise_estimate": (C.c_int, [p, C.c_float, C.POINTER(NoiseStats)]),
             "denoise_guided": (C.c_int, [p, C.POINTER(DenoiseGuidedParams)]),
+            "select_mask": (C.c_int, [p, p, C.c_size_t, C.POINTER(C.c_uint32)]),
+            "select_noisy": (C.c_int, [p, C.c_float, C.c_int, C.POINTER(C.c_uint32)]),
+            "sample_selected": (C.c_int, [p, C.c_int]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

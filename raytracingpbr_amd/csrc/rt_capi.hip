@@ -17,6 +17,7 @@
 #include "rt_features.hpp"
 #include "rt_reproject.hpp"
 #include "rt_noise.hpp"
+#include "rt_select.hpp"
 
 using namespace rt;
 
@@ -133,6 +134,17 @@ static void free_noise(rtpbr_ctx* c) {
     c->noise_map = c->noise_var = nullptr;
 }
 
+// the selection of rtpbr_select_mask / rtpbr_select_noisy (allocated on the first select call)
+static void free_selection(rtpbr_ctx* c) {
+    (void)hipFree(c->sel_mask);
+    (void)hipFree(c->sel_list);
+    (void)hipFree(c->sel_blocks);
+    c->sel_mask = nullptr;
+    c->sel_list = c->sel_blocks = nullptr;
+    c->sel_count = 0;
+    c->have_selection = false;
+}
+
 extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     if (!c) return RTPBR_OK;
     (void)hipSetDevice(c->device);
@@ -154,6 +166,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->march_out);
     free_features(c);
     free_noise(c);
+    free_selection(c);
     (void)hipFree(c->noise_stats);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
@@ -254,6 +267,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
         c->diff_pixels = nullptr;
         free_features(c);
         free_noise(c);
+        free_selection(c);
         HIP_TRY(hipMalloc(&c->image_buffer, n * sizeof(float4)));
         HIP_TRY(hipMalloc(&c->image_pixels, n * 3 * sizeof(float)));
         HIP_TRY(hipMalloc(&c->ray_buffer, n * sizeof(rtpbr_ray)));
@@ -683,7 +697,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b < 13; b++)
+    for (int b = 0; b < 14; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -767,9 +781,10 @@ static int next_event_of(std::vector<hipEvent_t>& pool, int& used, hipEvent_t* o
     hipEvent_t var = nullptr;                                         \
     if (int r_ = next_event_of(pool, used, &var)) return r_
 
-static int trace_grid(rtpbr_ctx* c, uint32_t total_items) {
-    int per_cu = c->jit_mod ? c->jit_mod->trace_blocks_per_cu
-                            : trace_blocks_per_cu(c->kind, c->n_obj, c->P.box_sig, c->scheduler < 0 ? 1 : c->scheduler);
+static int trace_grid(rtpbr_ctx* c, uint32_t total_items, bool selected = false) {
+    int per_cu = selected ? trace_selected_blocks_per_cu(c->kind, c->n_obj, c->P.scheduler)
+                 : c->jit_mod ? c->jit_mod->trace_blocks_per_cu
+                              : trace_blocks_per_cu(c->kind, c->n_obj, c->P.box_sig, c->scheduler < 0 ? 1 : c->scheduler);
     if (per_cu <= 0) per_cu = 2;
     if (c->waves_per_cu > 0) per_cu = (c->waves_per_cu + 3) / 4;
     long long grid = (long long)per_cu * c->n_cu;
@@ -1164,14 +1179,16 @@ static int launch_split_steps(rtpbr_ctx* c, int steps) {
 }
 
 // complete-path form: `n` samples per owned pixel (the spp loop of cornell_box_v3/renderer.py:31-36), in sub-launches of as
-// many samples per pixel as the staging budget holds
-static int sample_complete_path(rtpbr_ctx* c, int n) {
+// many samples per pixel as the staging budget holds.  `selected` (rtpbr_sample_selected): the caller has set P.np to the selection
+// list's length (> 0) and P.order to the list — the general ahead-of-time instances with the list indirection, item-linear staging,
+// no primary split, no run-time instance (c->jit_mod is nullptr, P.box_sig 0).
+static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
     Params& P = c->P;
     int left = n;
     if (int r = flush_shade(c)) return r;
     c->dense_launches = 0;
     while (left > 0) {
-        const bool split_ok = c->primary_split && P.scheduler == 1 && c->kind != KIND_BUNNY && c->kind != KIND_MIXED;
+        const bool split_ok = !selected && c->primary_split && P.scheduler == 1 && c->kind != KIND_BUNNY && c->kind != KIND_MIXED;
         // the tolerance flavour accumulates in LDS and adds to image_buffer directly: no staging, no accumulate kernel
         const bool unstaged = c->precision != 0 && c->jit_mod != nullptr && P.scheduler == 1;
         long long per_spp = (long long)P.np * (long long)((unstaged ? 0 : STAGE_ITEM_BYTES) + (split_ok ? PRIMARY_REC_BYTES : 0));
@@ -1200,7 +1217,7 @@ static int sample_complete_path(rtpbr_ctx* c, int n) {
         P.K = K;
         P.sample_base = c->sample_base;
         P.total_items = (uint32_t)((long long)P.np * K);
-        int grid = trace_grid(c, P.total_items);
+        int grid = trace_grid(c, P.total_items, selected);
         long long waves = (long long)grid * tune::WAVES_PER_BLOCK;
         long long chunk = (long long)P.total_items / (waves * 64);
         if (chunk < tune::CHUNK_MIN) chunk = (long long)P.total_items < waves * tune::CHUNK_MIN ? tune::CHUNK_TINY : tune::CHUNK_MIN;
@@ -1246,22 +1263,23 @@ static int sample_complete_path(rtpbr_ctx* c, int n) {
         NEXT_EVENT(c->ev, c->ev_used, a);
         NEXT_EVENT(c->ev, c->ev_used, b);
         if (c->timed) HIP_TRY(hipEventRecord(a, c->stream));
-        if (c->jit_mod) {
+        if (selected) {
+            launch_trace_selected(P, c->kind, grid, c->stream);
+        } else if (c->jit_mod) {
             if (int r = rt_jit_launch(c->jit_mod->trace, P, (unsigned)grid, c->stream)) return r;
         } else
             launch_trace(P, c->kind, grid, c->stream);
         if (c->timed) HIP_TRY(hipEventRecord(b, c->stream));
-        if (!unstaged) launch_accumulate(P, c->n_cu, c->stream);
+        if (selected) launch_accumulate_selected(P, c->stream);
+        else if (!unstaged) launch_accumulate(P, c->n_cu, c->stream);
         c->sample_base += (uint32_t)K;
         left -= K;
     }
     return RTPBR_OK;
 }
 
-extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
-    if (!c) return fail(RTPBR_EINVAL, "null ctx");
-    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
-    if (n < 0) return fail(RTPBR_EINVAL, "n must be >= 0");
+// rtpbr_sample and rtpbr_sample_selected (`selected`: every refusal of its own has been made by the caller)
+static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     if (int r = set_dev(c)) return r;
     // (diff_buffer: instrumented builds write their per-wave records over it)
     if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER)) return r;
@@ -1282,7 +1300,11 @@ extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
     // A run-time compiled instance of THIS scene (rt_jit.hip), when no listed ahead-of-time signature serves it
     rt_jit_release(c->jit_mod);
     c->jit_mod = nullptr;
-    if (want_jit) {
+    if (selected) {
+        // a selected launch runs the general ahead-of-time instances (rt_kernels.hip launch_trace_selected), whatever the jit,
+        // jit_bake and specialize options say: same bits (the next rtpbr_sample derives its own instance again)
+        P.box_sig = 0;
+    } else if (want_jit) {
         RtJitModule* jm = nullptr;
         const int r = rt_jit_acquire(c, key, &jm);
         if (r == RTPBR_OK) {
@@ -1295,7 +1317,7 @@ extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
         return fail(RTPBR_ESTATE, "option jit = 2 (strict): no run-time instance exists for this scene (needs <= 8 analytic shapes, "
                                   "or the neural shape with jit_bake, and the pool scheduler)");
     }
-    if (c->precision && !c->jit_mod)
+    if (c->precision && !c->jit_mod && !selected)
         return fail(RTPBR_ESTATE, "option precision = 1 (the tolerance flavour) exists as a run-time compiled instance only: needs hipcc and the kernel "
                                   "sources on this machine, option jit != 0, a scene of <= 8 analytic shapes (or the neural shape with jit_bake = 1, jit >= 1) "
                                   "and the pool scheduler");
@@ -1321,7 +1343,24 @@ extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
     c->timed = c->timing != 0;
     c->total1_recorded = false;
     bool zeroed_next = false;
-    if (c->cfg.kernel_form == RTPBR_FORM_PERSISTENT_RAY) {
+    if (selected) {
+        // the work geometry of the list for this call only: the context's own comes back for later full-frame calls
+        const int32_t np_keep = P.np;
+        const uint32_t* const order_keep = P.order;
+        int r = RTPBR_OK;
+        if (c->sel_count > 0) {
+            P.np = (int32_t)c->sel_count;
+            P.order = c->sel_list;
+            r = sample_complete_path(c, n, true);
+            P.np = np_keep;
+            P.order = order_keep;
+        } else {
+            r = flush_shade(c);
+            c->dense_launches = 0;
+            c->sample_base += (uint32_t)n;      // the unselected pixels skip these indices: here that is all of them
+        }
+        if (r) return r;
+    } else if (c->cfg.kernel_form == RTPBR_FORM_PERSISTENT_RAY) {
         if (int r = sample_persistent(c, n, &zeroed_next)) return r;
     } else {
         if (int r = sample_complete_path(c, n)) return r;
@@ -1337,6 +1376,13 @@ extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
     // of no bounce-steps — n = 0 or steps_per_launch <= 0 — enqueued none, and the complete-path kernels zero nothing)
     c->counters_clean[c->counters_turn] = zeroed_next;
     return RTPBR_OK;
+}
+
+extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (n < 0) return fail(RTPBR_EINVAL, "n must be >= 0");
+    return sample_call(c, n, false);
 }
 
 extern "C" int rtpbr_post_process(rtpbr_ctx* c) {
@@ -1638,6 +1684,81 @@ extern "C" int rtpbr_noise_estimate(rtpbr_ctx* c, float threshold, rtpbr_noise_s
     return RTPBR_OK;
 }
 
+// ---- adaptive sampling of the complete-path form (rt_select.hip): select pixels, trace only those
+enum : unsigned { W_SELECTION = 1u << RTPBR_BUF_SELECTION };
+static const char* const SELECT_TILES = "rtpbr_select_mask / rtpbr_select_noisy / rtpbr_sample_selected work on the whole frame: not with tiles of world > 1";
+
+static int selection_alloc(rtpbr_ctx* c) {
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->sel_mask) HIP_TRY(hipMalloc(&c->sel_mask, n));
+    if (!c->sel_list) HIP_TRY(hipMalloc(&c->sel_list, n * sizeof(uint32_t)));
+    if (!c->sel_blocks) HIP_TRY(hipMalloc(&c->sel_blocks, ((size_t)select_blocks(c->cfg.width, c->cfg.height) + 1) * sizeof(uint32_t)));
+    return RTPBR_OK;
+}
+
+// mark, scan, scatter on the stream, then the list's length (4 bytes) comes back: blocks
+static int selection_build(rtpbr_ctx* c, SelectArgs& A, bool noisy, uint32_t* n_selected) {
+    A.mask = c->sel_mask;
+    A.blocks = c->sel_blocks;
+    A.list = c->sel_list;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    c->have_selection = false;      // (until the new list's length is known)
+    c->sel_count = 0;
+    launch_select(A, noisy, c->stream);
+    HIP_TRY(hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, c->sel_blocks + select_blocks(c->cfg.width, c->cfg.height), sizeof total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->sel_count = total;
+    c->have_selection = true;
+    *n_selected = total;
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_select_mask(rtpbr_ctx* c, const uint8_t* mask, size_t nbytes, uint32_t* n_selected) {
+    if (!c || !mask || !n_selected) return fail(RTPBR_EINVAL, "null argument");
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, SELECT_TILES);
+    if (nbytes != (size_t)c->cfg.width * c->cfg.height) return fail(RTPBR_EINVAL, "rtpbr_select_mask: the mask must hold width * height bytes");
+    if (int r = set_dev(c)) return r;
+    if (int r = selection_alloc(c)) return r;
+    if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
+    // the caller's bytes go straight into RTPBR_BUF_SELECTION; the mark pass makes them 0 / 1 in place
+    HIP_TRY(hipMemcpyAsync(c->sel_mask, mask, nbytes, hipMemcpyHostToDevice, c->stream));
+    SelectArgs A{};
+    A.host_mask = c->sel_mask;
+    return selection_build(c, A, false, n_selected);
+}
+
+extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
+    if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
+    if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "noise threshold must be >= 0");
+    if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_noisy: dilate must be 0..3");
+    if (int r = noise_state_check(c)) return r;
+    if (int r = noise_estimate_enqueue(c, threshold)) return r;
+    if (int r = selection_alloc(c)) return r;
+    if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
+    SelectArgs A{};
+    A.image_buffer = c->image_buffer;
+    A.noise = c->noise_map;
+    A.threshold = threshold;
+    A.dilate = dilate;
+    return selection_build(c, A, true, n_selected);
+}
+
+extern "C" int rtpbr_sample_selected(rtpbr_ctx* c, int n) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (n < 0) return fail(RTPBR_EINVAL, "n must be >= 0");
+    if (c->world > 1) return fail(RTPBR_ESTATE, SELECT_TILES);
+    if (c->cfg.kernel_form != RTPBR_FORM_COMPLETE_PATH)
+        return fail(RTPBR_ESTATE, "rtpbr_sample_selected: the complete-path form only (the persistent-ray form has cfg.adaptive_sampling)");
+    if (c->precision) return fail(RTPBR_ESTATE, "rtpbr_sample_selected: not with option precision = 1 (the tolerance flavour has no selected instances)");
+    if (!c->have_selection) return fail(RTPBR_ESTATE, "rtpbr_sample_selected: no selection yet (rtpbr_select_mask / rtpbr_select_noisy first)");
+    return sample_call(c, n, true);
+}
+
 extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_params* p) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     rtpbr_denoise_guided_params d;
@@ -1744,11 +1865,12 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_MOTION: *p = c->motion; *n = np * 8; break;
         case RTPBR_BUF_MOMENTS: *p = c->noise_moments; *n = np * 16; break;
         case RTPBR_BUF_NOISE: *p = c->noise_map; *n = np * 4; break;
+        case RTPBR_BUF_SELECTION: *p = c->sel_mask; *n = np; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
     // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* first");
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* first");
     return 0;
 }
 
@@ -1849,8 +1971,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_NOISE)
-        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments and noise buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_SELECTION)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise and selection buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

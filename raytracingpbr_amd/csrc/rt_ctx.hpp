@@ -10,10 +10,14 @@
 
 #include "rt_device.hpp"
 #include "rt_noise.hpp"
+#include "rt_select.hpp"
 
 namespace rt {
 void launch_trace(const Params& P, int kind, int grid, hipStream_t st);
 void launch_accumulate(const Params& P, int n_cu, hipStream_t st);
+void launch_trace_selected(const Params& P, int kind, int grid, hipStream_t st);      // rtpbr_sample_selected: P.order = the selection list, P.np = its length
+void launch_accumulate_selected(const Params& P, hipStream_t st);
+int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler);
 void launch_zero(void* p, size_t bytes, hipStream_t st);      // a small fill as a kernel of our own (bytes % 16 == 0)
 void launch_persistent(const Params& P, int kind, int steps, hipStream_t st);
 void launch_persistent_pool(const Params& P, int kind, int steps, int grid, hipStream_t st);
@@ -170,7 +174,7 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[13] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[14] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
     float* feat_albedo = nullptr;      // (W,H,3)
@@ -194,6 +198,12 @@ struct rtpbr_ctx {
     float* noise_map = nullptr;        // (W,H): RTPBR_BUF_NOISE
     float* noise_var = nullptr;        // 3 x (W,H): the estimate's variance (-1: no samples), then the guided levels' ping-pong
     rt::NoiseStats* noise_stats = nullptr;
+    // the selection of rtpbr_select_mask / rtpbr_select_noisy (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
+    uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
+    uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)
+    uint32_t* sel_blocks = nullptr;    // per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them
+    uint32_t sel_count = 0;            // entries of sel_list
+    bool have_selection = false;
     size_t march_np = 0;
     int src_chain = 1;            // src/ form, fused launches: the plan's chain set runs in the chain kernel beside the pool kernel (rt_chain.hpp)
     long long chain_np_max = 2500000;   // ... frames of more local pixels than this are throughput-bound: no chain set

@@ -70,6 +70,28 @@ __global__ void __launch_bounds__(256) accumulate_samples(const Params P) {
     *dst = acc;
 }
 
+// ... of a selected launch (rtpbr_sample_selected): local pixel q is entry q of the selection list, a buffer index; every
+// other pixel of image_buffer is left alone.  Item-linear staging only.
+__global__ void __launch_bounds__(256) accumulate_selected(const Params P) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = q < (uint32_t)P.np;
+    {
+        const uint32_t n = wave_sum(valid ? (uint32_t)P.K : 0u);
+        if ((threadIdx.x & 63) == 0 && n) atomicAdd(&P.counters->shard[blockIdx.x & 63u][5], (unsigned long long)n);
+    }
+    if (!valid) return;
+    float4* dst = P.image_buffer + P.order[q];
+    float4 acc = *dst;
+    const float* src = P.stage + (size_t)q * (size_t)P.K * 3u;
+    for (int k = 0; k < P.K; k++) {      // strictly in sample order
+        acc.x += src[3 * k];
+        acc.y += src[3 * k + 1];
+        acc.z += src[3 * k + 2];
+        acc.w += 1.0f;
+    }
+    *dst = acc;
+}
+
 // The same sum over the DENSE staging (rt_trace.hpp stage_sample): a block takes `acc_batch` consecutive items at a time (a multiple
 // of K and of the chunk: whole pixels, whole chunks), reads the chunks' records as they lie — in completion order, coalesced — and
 // drops each at its sample's place in LDS (the byte beside the record says which sample of the chunk it is); then one thread per
@@ -426,6 +448,33 @@ void launch_plan(uint32_t* cost, uint32_t* order, PlanBuf* plan, uint32_t np, ui
 void launch_trace(const Params& P, int kind, int grid, hipStream_t st) {
     if (P.scheduler == 1) RT_DISPATCH_KIND(trace_paths_pool, hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, P));
     else RT_DISPATCH_KIND(trace_paths, hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, P));
+}
+// selected launches (P.order = the selection list, P.np = its length): the general instances, item-linear staging
+template <int KIND, int NOBJ>
+constexpr auto trace_paths_selected = trace_paths<KIND, NOBJ, 0, true>;
+#define RT_DISPATCH_SELECTED(KERNEL, ...)                                                   \
+    do {                                                                                    \
+        if (kind == KIND_BOXES && P.n_obj == 8) { auto k = KERNEL<KIND_BOXES, 8>; __VA_ARGS__; }       \
+        else if (kind == KIND_BOXES) { auto k = KERNEL<KIND_BOXES, 0>; __VA_ARGS__; }        \
+        else if (kind == KIND_BUNNY) { auto k = KERNEL<KIND_BUNNY, 0>; __VA_ARGS__; }        \
+        else if (kind == KIND_MIXED) { auto k = KERNEL<KIND_MIXED, 0>; __VA_ARGS__; }        \
+        else { auto k = KERNEL<KIND_GENERIC, 0>; __VA_ARGS__; }                              \
+    } while (0)
+void launch_trace_selected(const Params& P, int kind, int grid, hipStream_t st) {
+    if (P.scheduler == 1) RT_DISPATCH_SELECTED(trace_paths_pool_selected, hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, P));
+    else RT_DISPATCH_SELECTED(trace_paths_selected, hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, P));
+}
+void launch_accumulate_selected(const Params& P, hipStream_t st) {
+    hipLaunchKernelGGL(accumulate_selected, dim3((unsigned)((P.np + 255) / 256)), dim3(256), 0, st, P);
+}
+int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler) {
+    int per_cu = 0;
+    hipError_t e = hipSuccess;
+    Params P;
+    P.n_obj = n_obj;
+    if (scheduler == 1) RT_DISPATCH_SELECTED(trace_paths_pool_selected, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0));
+    else RT_DISPATCH_SELECTED(trace_paths_selected, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0));
+    return e == hipSuccess ? per_cu : 0;
 }
 void launch_primary(const Params& P, int kind, int n_cu, hipStream_t st) {
     long long need = ((long long)P.total_items + 255) / 256;

@@ -1,0 +1,32 @@
+// rt_select.hpp — the pixel selection of rtpbr_select_mask / rtpbr_select_noisy: RTPBR_BUF_SELECTION and the compacted,
+// ordered list rtpbr_sample_selected traces.
+//
+//   select_mark_*       one lane per pixel along the contiguous index i = x * H + y: decide "selected" (the host mask's byte, or the
+//                       rule of rtpbr_select_noisy: comparisons only), write the byte of RTPBR_BUF_SELECTION, and count per block of
+//                       256 pixels — a wave64 ballot + popcount per wave, four LDS words, ONE plain store per block: no global atomics.
+//   select_scan         one block: the exclusive prefix sum of the block counts in place (tiles of 256 with a carry: 8100 counts at
+//                       1080p are 32 tiles), the total behind them.
+//   select_scatter      one lane per pixel again: rank inside the wave from the ballot (mbcnt), the earlier waves' counts from LDS,
+//                       the block's start from the scan: list[start + rank] = i.  Ascending i by construction, whatever the schedule.
+// Only the total comes back to the host (4 bytes).
+#pragma once
+#include "rt_types.hpp"
+
+namespace rt {
+
+struct SelectArgs {
+    const float4* image_buffer;   // noisy: pixels without samples are selected
+    const float* noise;           // noisy: RTPBR_BUF_NOISE of the estimate just made
+    const uint8_t* host_mask;     // mask: the caller's bytes, uploaded (nonzero = selected); may be `mask` itself
+    uint8_t* mask;                // out: RTPBR_BUF_SELECTION, 0 / 1
+    uint32_t* blocks;             // n_blocks counts -> starts, then the total
+    uint32_t* list;               // out: the selected buffer indices, ascending
+    float threshold;
+    int32_t dilate;               // 0..3: Chebyshev radius
+    int32_t width, height;
+};
+
+void launch_select(const SelectArgs& A, bool noisy, hipStream_t st);      // the three passes; A.blocks[n_blocks] = the list's length afterwards
+inline uint32_t select_blocks(int w, int h) { return (uint32_t)(((size_t)w * (size_t)h + 255) / 256); }
+
+}  // namespace rt

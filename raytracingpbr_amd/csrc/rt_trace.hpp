@@ -212,11 +212,20 @@ RT_D void acc_flush_all(const Params& P, const AccView& A, int lane, uint32_t& n
 
 // renderer.py:32-35: jitter, get_ray, color = 1, then roulette at i = 0 (p = 0, the draw is consumed).
 // returns 1 = ray ready to march, 0 = finished already, -1 = padding pixel of an edge tile (nothing to trace)
+// LIST (selected launches, rtpbr_sample_selected): local pixel q is entry q of the selection list (P.order: buffer indices
+// x * H + y, whole frame, no padding pixels) — a compile-time choice, the unlisted instances do not know about it
+template <bool LIST = false>
 RT_D int start_item(const Params& P, PathRay& R) {
     uint32_t q = R.item / (uint32_t)P.K;
     uint32_t k = R.item - q * (uint32_t)P.K;
     int px, py;
-    if (!pixel_of(P, q, px, py)) return -1;
+    if constexpr (LIST) {
+        const uint32_t i = P.order[q];
+        px = (int)(i / (uint32_t)P.cfg.height);
+        py = (int)(i - (uint32_t)px * (uint32_t)P.cfg.height);
+    } else {
+        if (!pixel_of(P, q, px, py)) return -1;
+    }
     R.key = rng_key(P.cfg.seed, (uint32_t)px, (uint32_t)py, P.sample_base + k);
     R.cnt = 0;
     gen_ray(P, px, py, R.key, R.cnt, R.o, R.d);
@@ -274,7 +283,8 @@ RT_D bool claim_items(const Params& P, WorkRange& wr, bool want, int lane, uint3
 
 // -------------------------------------------------------------------------------------------
 // Scheduler 0: in-register refill (no LDS ray pool).
-template <int KIND, int NOBJ, uint32_t SIG = 0>
+// (LIST: see start_item; a parameter of the kernel itself — as a wrapper round a shared body the unlisted instances compiled to different code)
+template <int KIND, int NOBJ, uint32_t SIG = 0, bool LIST = false>
 __global__ void __launch_bounds__(256) trace_paths(const Params P) {
     __shared__ ObjFull lds_obj[MAX_OBJ];
     stage_objects(P, lds_obj);
@@ -319,7 +329,7 @@ __global__ void __launch_bounds__(256) trace_paths(const Params P) {
             bool got = claim_items(P, wr, L.state == ST_IDLE, lane, R.item);
             if (L.state == ST_IDLE) {
                 if (got) {
-                    int r = start_item(P, R);
+                    int r = start_item<LIST>(P, R);
                     if (r == 1) alive = true;
                     else if (r == 0) { write_sample(P, R.item, R.col); n_samples++; }
                     // (r < 0: padding pixel of an edge tile, nothing to record: the lane stays idle until the next refill)
@@ -652,7 +662,7 @@ RT_D uint32_t meta_cnt(uint32_t m) { return m >> 16; }
 constexpr int pool_waves(int kind) {
     return kind == KIND_BOXES ? RT_POOL_WAVES : kind == KIND_GENERIC ? RT_POOL_WAVES_GENERIC : kind == KIND_BUNNY ? RT_POOL_WAVES_BUNNY : 1;
 }
-template <int KIND, int NOBJ, uint32_t SIG = 0>
+template <int KIND, int NOBJ, uint32_t SIG = 0, bool LIST = false>
 RT_D void trace_paths_pool_impl(const Params& P) {
     __shared__ ObjFull lds_obj[NOBJ > 0 ? NOBJ : (KIND == KIND_BUNNY ? 1 : MAX_OBJ)];   // KIND_BUNNY: exactly one object
     __shared__ uint32_t pool_all[4][F_COUNT][64];
@@ -820,7 +830,7 @@ RT_D void trace_paths_pool_impl(const Params& P) {
 #endif
                 }
                 if (got) {
-                    int r = start_item(P, R);
+                    int r = start_item<LIST>(P, R);
                     if (r == 1) {
                         if (P.primary_split) {
                             R.t_eval = rec_t;
@@ -1048,6 +1058,9 @@ RT_D void trace_paths_pool_impl(const Params& P) {
 }
 template <int KIND, int NOBJ, uint32_t SIG = 0>
 __global__ void __launch_bounds__(256, pool_waves(KIND)) trace_paths_pool(const Params P) { trace_paths_pool_impl<KIND, NOBJ, SIG>(P); }
+// ... of a selected launch: the general instances only (results are bit-identical across instances)
+template <int KIND, int NOBJ>
+__global__ void __launch_bounds__(256, pool_waves(KIND)) trace_paths_pool_selected(const Params P) { trace_paths_pool_impl<KIND, NOBJ, 0, true>(P); }
 
 }  // namespace rt
 

@@ -24,6 +24,8 @@ BUF_FEAT_ALBEDO, BUF_FEAT_NORMAL, BUF_FEAT_DEPTH, BUF_FEAT_OBJECT, BUF_DENOISED_
 BUF_MOTION = 10
 # luminance moments of the batch means (noise_update) and the per-pixel noise map (noise_estimate); they exist from the first of those calls on
 BUF_MOMENTS, BUF_NOISE = 11, 12
+# the pixel selection (select_mask / select_noisy): 1 = sample_selected traces the pixel; exists from the first select call on
+BUF_SELECTION = 13
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -198,6 +200,64 @@ class Renderer:
         finally:
             self.track_noise = keep
 
+    # ------------------------------------------------------------ adaptive sampling (include/rtpbr.h rtpbr_select_* / rtpbr_sample_selected)
+    def select_mask(self, mask) -> int:
+        """Select the pixels where ``mask`` (W,H) is nonzero — a region of interest.  Returns how many."""
+        W, H = self.config.width, self.config.height
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (W, H):
+            raise ValueError(f"expected a mask of shape {(W, H)}, got {m.shape}")
+        n = C.c_uint32()
+        self.api.call("select_mask", self._ctx, m.ctypes.data_as(C.c_void_p), m.nbytes, C.byref(n))
+        return int(n.value)
+
+    def select_noisy(self, threshold: float, dilate: int = 0) -> int:
+        """Select the pixels without samples and those with a pixel noisier than ``threshold`` within ``dilate`` (0..3) pixels
+        (Chebyshev distance), from a fresh noise estimate (``noise`` is written).  Returns how many.  Blocks."""
+        n = C.c_uint32()
+        self.api.call("select_noisy", self._ctx, float(threshold), int(dilate), C.byref(n))
+        return int(n.value)
+
+    def sample_selected(self, n: int = 1):
+        """``sample(n)`` through the selected pixels only: every other pixel keeps its bits, the sample index advances by ``n``
+        for all of them.  Complete-path form."""
+        self.api.call("sample_selected", self._ctx, int(n))
+        if self.track_noise:
+            self.noise_update()
+
+    def render_adaptive(self, noise: float, max_spp: int, batch_spp: int = 16, dilate: int = 0):
+        """``render_until`` that stops sampling a pixel once it is done: two full-frame batches of ``batch_spp`` (the temporal
+        estimate needs two), then select_noisy(noise, dilate) -> sample_selected(batch_spp) -> noise_update() until nothing is
+        selected or another batch would take a pixel past ``max_spp``.  Returns (pixel-samples traced, NoiseStats of the last
+        estimate).  Continues whatever is accumulated: refresh() first for a new frame.  Stopping a pixel on an estimate made
+        from its own samples favours pixels whose batches agree by chance: with ``dilate`` = 0 a pixel whose first two batches
+        both missed the light stops there and stays too dark (Cornell v3: five times the display RMSE of render_until);
+        ``dilate`` >= 1 keeps the neighbours of a noisy pixel sampling and removes most of it."""
+        if not (batch_spp >= 1 and max_spp >= 1):
+            raise ValueError("batch_spp and max_spp must be >= 1")
+        batch = int(batch_spp)
+        n_pix = self.config.width * self.config.height
+        keep, self.track_noise = self.track_noise, False
+        try:
+            traced, used = 0, 0
+            for _ in range(2):
+                n = min(batch, int(max_spp) - used)
+                if n <= 0:
+                    break
+                self.sample(n)
+                self.noise_update()
+                traced, used = traced + n_pix * n, used + n
+            while used + batch <= int(max_spp):
+                n_sel = self.select_noisy(noise, dilate)
+                if n_sel == 0:
+                    break
+                self.sample_selected(batch)
+                self.noise_update()
+                traced, used = traced + n_sel * batch, used + batch
+            return traced, self.noise_estimate(noise)
+        finally:
+            self.track_noise = keep
+
     # ------------------------------------------------------------ buffers (field.to_numpy())
     def _shape(self, which):
         W, H = self.config.width, self.config.height
@@ -206,7 +266,7 @@ class Renderer:
                 BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),
                 BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
                 BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
-                BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32)}[which]
+                BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -348,6 +408,11 @@ class Renderer:
     def noise(self):
         """(W,H): the last noise_estimate() / denoise_guided()'s standard deviation of each pixel's displayed luminance"""
         return self._read(BUF_NOISE)
+
+    @property
+    def selection(self):
+        """(W,H) uint8: 1 = selected by the last select_mask() / select_noisy()"""
+        return self._read(BUF_SELECTION)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

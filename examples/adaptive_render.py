@@ -3,7 +3,8 @@
 sampling each pixel when it is done (Renderer.render_adaptive: select_noisy -> sample_selected -> noise_update).
 
     python examples/adaptive_render.py --size 256 256 --noise 0.1 --out adaptive.png --counts adaptive_counts.png
-    python examples/adaptive_render.py --bench               # the measurements of DESIGN.md section 6e
+    python examples/adaptive_render.py --pool-batches 16 --min-samples 64      # the pooled estimator
+    python examples/adaptive_render.py --bench               # the measurements of DESIGN.md sections 6e and 6f
 
 Headless.  Writes the image and a map of how many samples each pixel took (white = the most).  Runs on the HIP library only.
 """
@@ -25,6 +26,9 @@ ap.add_argument("--max-spp", type=int, default=2048)
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--dilate", type=int, default=1)
 ap.add_argument("--bounces", type=int, default=3)
+ap.add_argument("--pool-batches", type=int, default=0, help="0 = off; 3..64: pixels younger than this pool their variance over the neighbours")
+ap.add_argument("--pool-radius", type=int, default=3)
+ap.add_argument("--min-samples", type=int, default=0, help="select_noisy keeps every pixel selected up to this count")
 ap.add_argument("--out", default="out/adaptive.png")
 ap.add_argument("--counts", default="out/adaptive_counts.png")
 ap.add_argument("--bench", action="store_true")
@@ -51,6 +55,9 @@ def wall_ms(r, call, reps=5):
         dt = (time.perf_counter() - t0) * 1e3
         best = dt if rep and (best is None or dt < best) else best
     return best
+
+
+POOLED = (16, 3, 64)      # pool_batches, pool_radius, min_samples (4 batches of 16): the best point of the grid of DESIGN.md 6f
 
 
 def bench():
@@ -81,6 +88,10 @@ def bench():
     st = r.noise_estimate(0.0)
     thr = float(np.quantile(r.noise, 0.9))
     print(f"noise_estimate: {wall_ms(r, lambda: r.noise_estimate(thr)):.3f} ms wall")
+    for radius in (1, 3):
+        r.set_noise_estimator(64, radius, 0)      # two batches so far: every pixel is young
+        print(f"noise_estimate, pooled over radius {radius}: {wall_ms(r, lambda: r.noise_estimate(thr)):.3f} ms wall")
+    r.set_noise_estimator()
     for d in range(4):
         print(f"select_noisy dilate {d}: {wall_ms(r, lambda: r.select_noisy(thr, d)):.3f} ms wall ({r.select_noisy(thr, d)} pixels)")
     del st
@@ -94,9 +105,12 @@ def bench():
     truth = t.image_pixels
     print("# Cornell v3 256x256, batches of 16, max 4096 spp; RMSE of image_pixels against 65536 spp")
     for noise in (0.1, 0.05):
-        rows = [("render_until", None)] + [(f"render_adaptive dilate {d}", d) for d in (0, 1, 2)]
-        for label, d in rows:
+        rows = [("render_until", None, None)] + [(f"render_adaptive dilate {d}", d, None) for d in (0, 1, 2)]
+        rows += [(f"render_adaptive dilate {d}, pooled {POOLED}", d, POOLED) for d in (0, 1)]
+        for label, d, est in rows:
             r = Renderer(scene, cfg)
+            if est:
+                r.set_noise_estimator(*est)
             best, res = None, None
             for rep in range(2):
                 r.refresh()
@@ -126,6 +140,7 @@ if a.bench:
 W, H = a.size
 scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, a.bounces)
 r = Renderer(scene, cfg)
+r.set_noise_estimator(a.pool_batches, a.pool_radius, a.min_samples)
 r.refresh()
 t0 = time.perf_counter()
 traced, st = r.render_adaptive(a.noise, a.max_spp, a.batch, a.dilate)
@@ -138,7 +153,7 @@ for p in (a.out, a.counts):
         os.makedirs(os.path.dirname(p), exist_ok=True)
 imwrite(r.image_pixels, a.out)
 imwrite(np.repeat((count / max(float(count.max()), 1.0))[..., None], 3, axis=2).astype(np.float32), a.counts)
-print(f"{W}x{H} to noise {a.noise} (dilate {a.dilate}): {traced} pixel-samples = {traced / (W * H):.1f} spp mean, {count.min():.0f}..{count.max():.0f} "
+print(f"{W}x{H} to noise {a.noise} (dilate {a.dilate}, pool_batches {a.pool_batches}, min_samples {a.min_samples}): {traced} pixel-samples = {traced / (W * H):.1f} spp mean, {count.min():.0f}..{count.max():.0f} "
       f"per pixel, {st.pixels_above} pixels above, max noise {st.max_noise:.4f}, {dt * 1e3:.0f} ms; a full frame of {count.max():.0f} spp "
       f"is {count.max() * W * H:.0f} pixel-samples")
 print("wrote", a.out, "and", a.counts)

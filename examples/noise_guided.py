@@ -34,6 +34,8 @@ ap.add_argument("--frames", type=int, default=12)
 ap.add_argument("--sweep", action="store_true")
 ap.add_argument("--bench", action="store_true")
 ap.add_argument("--out", default="noise_guided_sweep.json")
+ap.add_argument("--pool-batches", type=int, default=8, help="the pooled estimator of the 'pooled' columns (set_noise_estimator)")
+ap.add_argument("--pool-radius", type=int, default=3)
 a = ap.parse_args()
 
 
@@ -109,7 +111,13 @@ for name, (scene, cfg, per_batch, truth_run) in stills.items():
     r.denoise()
     plain = rmse(r.denoised_pixels, truth, m) / base
     r.denoise_guided()
-    print(f"{name}: noisy {base:.4f}; relative to it: denoise() {plain:.3f}, denoise_guided() {rmse(r.denoised_pixels, truth, m) / base:.3f}")
+    guided = rmse(r.denoised_pixels, truth, m) / base
+    r.set_noise_estimator(a.pool_batches, a.pool_radius)
+    r.denoise_guided()
+    pooled = rmse(r.denoised_pixels, truth, m) / base
+    r.set_noise_estimator()
+    print(f"{name}: noisy {base:.4f}; relative to it: denoise() {plain:.3f}, denoise_guided() {guided:.3f}, "
+          f"denoise_guided() with the estimate pooled ({a.pool_batches} batches, radius {a.pool_radius}) {pooled:.3f}")
     if a.sweep:
         for g in grid:
             r.denoise_guided(iterations=g[0], sigma_color=g[1], variance_floor=g[2])
@@ -148,7 +156,7 @@ for name, (scene, cfg, per_frame, converge) in fly.items():
     r.refresh()
     per_frame(r)
     print(f"{name}: fly-through, display RMSE against a converged frame")
-    print("frame  reproject  +denoise  +guided")
+    print("frame  reproject  +denoise  +guided  +guided, pooled")
     rows = []
     for k in range(1, len(cams)):
         t.set_camera(cams[k])
@@ -164,10 +172,14 @@ for name, (scene, cfg, per_frame, converge) in fly.items():
         e1 = rmse(display(r.denoised_pixels), truth)
         r.denoise_guided()
         e2 = rmse(display(r.denoised_pixels), truth)
-        rows.append((e0, e1, e2))
-        print(f"{k:5d}  {e0:9.4f}  {e1:8.4f}  {e2:7.4f}")
+        r.set_noise_estimator(a.pool_batches, a.pool_radius)
+        r.denoise_guided()
+        e3 = rmse(display(r.denoised_pixels), truth)
+        r.set_noise_estimator()
+        rows.append((e0, e1, e2, e3))
+        print(f"{k:5d}  {e0:9.4f}  {e1:8.4f}  {e2:7.4f}  {e3:15.4f}")
     mrow = np.mean(np.array(rows), axis=0)
-    print(f" mean  {mrow[0]:9.4f}  {mrow[1]:8.4f}  {mrow[2]:7.4f}")
+    print(f" mean  {mrow[0]:9.4f}  {mrow[1]:8.4f}  {mrow[2]:7.4f}  {mrow[3]:15.4f}")
 
 scene, cfg = cornell_box("v3"), Config.cornell_v3(256, 256, 0, 3)
 for thr in (0.1, 0.05, 0.03):

@@ -1648,8 +1648,23 @@ static int noise_estimate_enqueue(rtpbr_ctx* c, float threshold) {
     A.threshold = threshold;
     A.width = c->cfg.width;
     A.height = c->cfg.height;
+    A.pool_batches = c->noise_estimator.pool_batches;
+    A.pool_radius = c->noise_estimator.pool_radius;
     launch_noise_estimate(A, c->stream);
     HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_set_noise_estimator(rtpbr_ctx* c, const rtpbr_noise_estimator* e) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    static_assert(sizeof(rtpbr_noise_estimator) == 12, "three 4-byte members");
+    rtpbr_noise_estimator d{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
+                            RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};
+    if (e) d = *e;
+    if (d.pool_batches != 0 && (d.pool_batches < 3 || d.pool_batches > 64)) return fail(RTPBR_EINVAL, "noise estimator: pool_batches must be 0 or 3..64");
+    if (d.pool_radius < 1 || d.pool_radius > 3) return fail(RTPBR_EINVAL, "noise estimator: pool_radius must be 1..3");
+    if (d.min_samples < 0 || d.min_samples > 16777216) return fail(RTPBR_EINVAL, "noise estimator: min_samples must be 0..16777216");
+    c->noise_estimator = d;
     return RTPBR_OK;
 }
 
@@ -1744,6 +1759,7 @@ extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uin
     A.noise = c->noise_map;
     A.threshold = threshold;
     A.dilate = dilate;
+    A.min_samples = (float)c->noise_estimator.min_samples;
     return selection_build(c, A, true, n_selected);
 }
 

@@ -198,6 +198,8 @@ struct rtpbr_ctx {
     float* noise_map = nullptr;        // (W,H): RTPBR_BUF_NOISE
     float* noise_var = nullptr;        // 3 x (W,H): the estimate's variance (-1: no samples), then the guided levels' ping-pong
     rt::NoiseStats* noise_stats = nullptr;
+    rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
+                                          RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};      // rtpbr_set_noise_estimator: plain state, kept across refresh / set_config / set_scene / reproject
     // the selection of rtpbr_select_mask / rtpbr_select_noisy (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
     uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
     uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)

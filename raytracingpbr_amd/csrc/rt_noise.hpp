@@ -11,6 +11,10 @@
 //                       estimate is bounded by 1/4 whatever a firefly does to the moments —, else from the 7x7
 //                       neighbourhood on the pixel's object (young pixels, as SVGF does); writes RTPBR_BUF_NOISE = sqrt(v), the
 //                       filter's level-0 variance (v, -1 = pixel without samples) and the three statistics.
+//   noise_estimate_pooled<R>  the same pass with rtpbr_set_noise_estimator's pooling on: a 2-D tile per block, (sum of squares,
+//                       degrees of freedom, object) of the tile and an R-pixel halo staged in LDS once, and every young
+//                       temporal pixel (2 <= K < pool_batches) takes max(own, pooled over its (2R+1)^2 window).  Every other
+//                       pixel takes noise_estimate's path.  launch_noise_estimate picks it only when pool_batches > 0.
 //   guided_level<F,L>   atrous_level (rt_features.hip) with the colour term scaled by the 3x3-filtered variance of the centre
 //                       and the variance filtered along with the squared weights.  The variance travels in a record of its
 //                       own, 4 bytes, loaded only on taps that pass the object test.
@@ -39,6 +43,8 @@ struct NoiseArgs {
     NoiseStats* stats;            // noise_estimate: out (zeroed before the launch)
     float threshold;
     int32_t width, height;
+    int32_t pool_batches;         // noise_estimate: rtpbr_noise_estimator (0 = off: the plain kernel)
+    int32_t pool_radius;          // 1..3
 };
 
 struct GuidedArgs {

@@ -21,7 +21,8 @@ __global__ void __launch_bounds__(256) select_mark(const SelectArgs A) {
     bool sel = false;
     if (i < n) {
         if constexpr (NOISY) {
-            sel = !(A.image_buffer[i].w > 0.0f);
+            const float cnt = A.image_buffer[i].w;
+            sel = !(cnt > 0.0f) || cnt < A.min_samples;
             if (!sel) {
                 const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
                 const int d = A.dilate;

@@ -23,6 +23,7 @@ struct SelectArgs {
     uint32_t* list;               // out: the selected buffer indices, ascending
     float threshold;
     int32_t dilate;               // 0..3: Chebyshev radius
+    float min_samples;            // noisy: pixels with fewer samples are selected too (0 = off: no count is below it)
     int32_t width, height;
 };
 

@@ -120,6 +120,16 @@ class NoiseStats(_Pod):
     _fields_ = [("pixels_estimated", C.c_uint32), ("pixels_above", C.c_uint32), ("max_noise", C.c_float)]
 
 
+class NoiseEstimator(_Pod):
+    """rtpbr_noise_estimator (include/rtpbr.h): the optional estimator setting of a context — pooling of the young pixels'
+    within-pixel sums of squares over the neighbours on the same object, and a minimum sample count for select_noisy."""
+    _fields_ = [("pool_batches", C.c_int32), ("pool_radius", C.c_int32), ("min_samples", C.c_int32)]
+
+    # include/rtpbr.h RTPBR_NOISE_ESTIMATOR_DEFAULT_*, what rtpbr_set_noise_estimator(ctx, NULL) sets: off
+    # (tests/test_pool_ref.py keeps the two equal)
+    DEFAULTS = {"pool_batches": 0, "pool_radius": 3, "min_samples": 0}
+
+
 class DenoiseGuidedParams(_Pod):
     """rtpbr_denoise_guided_params (include/rtpbr.h): the a-trous whose colour term is measured in standard deviations of the
     pixel's estimated noise."""

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseStats, Ray, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseEstimator, NoiseStats, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -37,6 +37,7 @@ class Renderer:
         self.device = device
         self.samples_per_frame = 1           # SAMPLES_PER_FRAME, src/config.py:9
         self._host_arrays = {}               # address -> bytes of the page-locked blocks handed out by host_array()
+        self.noise_estimator = NoiseEstimator(**NoiseEstimator.DEFAULTS)      # what set_noise_estimator() last set
         self.track_noise = False             # True: every sample() call is one batch of the noise estimate (noise_update() after it)
         self.set_config(config)
         self.set_scene(scene)
@@ -157,9 +158,21 @@ class Renderer:
         accumulated so far).  The estimate needs two batches per pixel; before that ``noise_estimate`` looks at the neighbours."""
         self.api.call("noise_update", self._ctx)
 
+    def set_noise_estimator(self, pool_batches: int = 0, pool_radius: int = 3, min_samples: int = 0):
+        """The estimator behind noise_estimate / select_noisy / denoise_guided (and so render_until / render_adaptive); the
+        defaults are off.  ``pool_batches`` 3..64: a pixel with fewer batches than this (but two or more) takes the larger of
+        its own variance and the one pooled from the within-pixel sums of squares of the pixels on its object within
+        ``pool_radius`` (1..3), so a pixel whose few batches agree by chance is not taken for converged.  ``min_samples`` > 0:
+        select_noisy also selects every pixel with fewer samples.  Kept across refresh / set_config / set_scene / reproject."""
+        e = NoiseEstimator(int(pool_batches), int(pool_radius), int(min_samples))
+        self.api.call("set_noise_estimator", self._ctx, C.byref(e))
+        self.noise_estimator = e
+
     def noise_estimate(self, threshold: float = 0.0) -> NoiseStats:
         """Write ``noise`` (the estimated standard deviation of each pixel's displayed luminance, in the c / (1 + c) domain) and
-        return how many pixels have samples, how many of them are noisier than ``threshold``, and the largest value.  Blocks."""
+        return how many pixels have samples, how many of them are noisier than ``threshold``, and the largest value.  Blocks.
+        With ``set_noise_estimator(pool_batches=...)`` a pixel of two or more but fewer batches than that takes
+        max(its own variance, the variance pooled over its neighbours on the same object): include/rtpbr.h has the rule."""
         s = NoiseStats()
         self.api.call("noise_estimate", self._ctx, float(threshold), C.byref(s))
         return s
@@ -232,7 +245,10 @@ class Renderer:
         estimate).  Continues whatever is accumulated: refresh() first for a new frame.  Stopping a pixel on an estimate made
         from its own samples favours pixels whose batches agree by chance: with ``dilate`` = 0 a pixel whose first two batches
         both missed the light stops there and stays too dark (Cornell v3: five times the display RMSE of render_until);
-        ``dilate`` >= 1 keeps the neighbours of a noisy pixel sampling and removes most of it."""
+        ``dilate`` >= 1 keeps the neighbours of a noisy pixel sampling and removes most of it.  The estimator of
+        ``set_noise_estimator`` applies: with pooling a pixel that stopped can be selected again in a later round (its
+        neighbours' spread counts while it is young), and ``min_samples`` keeps every pixel selected up to that count
+        (DESIGN.md 6f)."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch = int(batch_spp)

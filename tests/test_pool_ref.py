@@ -1,0 +1,287 @@
+"""CPU tier of the pooled noise estimator (rtpbr_set_noise_estimator): the restatement tests/pool_ref/pool_ref.c that the GPU
+tests hold the kernel to, checked against today's estimate (noise_ref.c), against hand-computed answers, against what
+include/rtpbr.h declares and — the point of the feature — in an adaptive loop driven on the oracle."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import feature_ref_lib as fr
+import noise_ref_lib as nr
+import pool_ref_lib as pl
+import select_ref_lib as sr
+from oracle_backend import OracleRenderer
+from raytracingpbr_amd import Config, NoiseEstimator, _capi, cornell_box
+
+ROOT = pl.ROOT
+EINVAL = -1
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _random_frame(rng, w, h):
+    """plausible and implausible moments: K in 0..6 (some fractional, as after a reprojection), sums of squares a little above and a
+    little below the square of the mean, pixels without samples, three objects in blobs"""
+    cnt = rng.integers(1, 9, (w, h)).astype(np.float32) * 2
+    K = rng.choice(np.array([0, 1, 2, 2, 2.5, 3, 3, 4.75, 6], np.float32), (w, h))
+    mu = rng.uniform(0.05, 3.0, (w, h)).astype(np.float32)
+    spread = rng.uniform(-0.01, 0.6, (w, h)).astype(np.float32)
+    M = np.stack([cnt * mu, cnt * mu * mu * (1 + spread), cnt, K], -1).astype(np.float32)
+    M[K == 0] = 0
+    ib = np.empty((w, h, 4), np.float32)
+    ib[..., :3] = rng.uniform(0.0, 3.0, (w, h, 3)) * cnt[..., None]
+    ib[..., 3] = cnt
+    ib[rng.random((w, h)) < 0.1] = 0
+    obj = (rng.integers(0, 3, ((w + 3) // 4, (h + 3) // 4)).repeat(4, 0).repeat(4, 1)[:w, :h]).astype(np.int32)
+    obj[rng.random((w, h)) < 0.05] = -1
+    return ib, M, obj
+
+
+def test_reference_builds_and_exports_only_pr():
+    assert os.path.exists(pl.build()) and hasattr(pl.lib(), "pr_estimate")
+    assert not hasattr(pl.lib(), "lum_of_mean")
+
+
+@pytest.mark.parametrize("size", [(1, 1), (2, 5), (5, 3), (9, 7), (33, 20)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_off_equals_today(size):
+    for seed in range(4):
+        ib, M, obj = _random_frame(np.random.default_rng(seed), *size)
+        for radius in (1, 3):
+            got = pl.estimate(ib, M, obj, 0.1, 0, radius)
+            want = nr.estimate(ib, M, obj, 0.1)
+            assert np.array_equal(_bits(got[0]), _bits(want[0])) and np.array_equal(_bits(got[1]), _bits(want[1]))
+            assert got[2][:2] == want[2][:2] and np.float32(got[2][2]).view(np.uint32) == np.float32(want[2][2]).view(np.uint32)
+
+
+def _v(mu, var):
+    """v of include/rtpbr.h from the mean and the variance of the mean, in float64"""
+    sd = np.sqrt(var)
+    hi, lo = mu + sd, max(mu - sd, 0.0)
+    hw = 0.5 * (hi / (1 + hi) - lo / (1 + lo))
+    return hw * hw
+
+
+def _hand_frame(K=2.0):
+    """5x3 on one object, 8 samples per pixel.  Everywhere but two pixels a single batch (M.w = 1: not eligible).  The centre
+    (2, 1): K batches that agree, mean 0.5: M = (4, 2, 8, K), sum of squares 2 - 16 / 8 = 0.  Its neighbour (3, 1): two batches of 4
+    samples of luminance 0.25 and 0.75: M = (4, 2.5, 8, K), sum of squares 0.5."""
+    ib = np.empty((5, 3, 4), np.float32)
+    ib[..., :3] = 4.0
+    ib[..., 3] = 8.0
+    M = np.empty((5, 3, 4), np.float32)
+    M[:] = (4.0, 2.0, 8.0, 1.0)
+    M[2, 1] = (4.0, 2.0, 8.0, K)
+    M[3, 1] = (4.0, 2.5, 8.0, K)
+    return ib, M, np.zeros((5, 3), np.int32)
+
+
+def test_known_answers():
+    ib, M, obj = _hand_frame()
+    # off: the centre's own batches agree: 0; the neighbour: 0.5 / ((2 - 1) * 8)
+    _, var0, _ = pl.estimate(ib, M, obj, 0.0, 0, 1)
+    assert var0[2, 1] == 0
+    np.testing.assert_allclose(var0[3, 1], _v(0.5, 0.5 / 8), rtol=2e-6)
+    # pooled: SS = 0 + 0.5, DF = 1 + 1, pooled = 0.5 / (2 * 8); the neighbour keeps its own, larger, value
+    for radius in (1, 2, 3):
+        _, var1, _ = pl.estimate(ib, M, obj, 0.0, 4, radius)
+        np.testing.assert_allclose(var1[2, 1], _v(0.5, 0.5 / 16), rtol=2e-6)
+        assert var1[3, 1] == var0[3, 1]
+        keep = np.ones((5, 3), bool)
+        keep[2, 1] = False
+        assert np.array_equal(_bits(var1[keep]), _bits(var0[keep]))      # single-batch pixels: the spatial branch, untouched
+    # a neighbour on another object, with M.w < 2, or without samples does not contribute
+    o2 = obj.copy()
+    o2[3, 1] = 1
+    assert pl.estimate(ib, M, o2, 0.0, 4, 1)[1][2, 1] == 0
+    M2 = M.copy()
+    M2[3, 1, 3] = 1.5
+    assert pl.estimate(ib, M2, obj, 0.0, 4, 1)[1][2, 1] == 0
+    ib2 = ib.copy()
+    ib2[3, 1] = 0
+    got = pl.estimate(ib2, M, obj, 0.0, 4, 1)
+    assert got[1][2, 1] == 0 and got[1][3, 1] == -1 and got[0][3, 1] == 0 and got[2][0] == 14
+    # a neighbour outside the radius: (4, 1) is two pixels from the centre
+    M3 = M.copy()
+    M3[3, 1], M3[4, 1] = M[0, 0], M[3, 1]
+    assert pl.estimate(ib, M3, obj, 0.0, 4, 1)[1][2, 1] == 0
+    np.testing.assert_allclose(pl.estimate(ib, M3, obj, 0.0, 4, 2)[1][2, 1], _v(0.5, 0.5 / 16), rtol=2e-6)
+
+
+def test_the_age_test_is_strict_and_fractional_counts_work():
+    ib, M, obj = _hand_frame(K=3.0)
+    assert pl.estimate(ib, M, obj, 0.0, 3, 1)[1][2, 1] == 0                      # M.w == pool_batches: own alone
+    # M.w = 3 < 4: DF = 2 + 2, pooled = 0.5 / (4 * 8)
+    np.testing.assert_allclose(pl.estimate(ib, M, obj, 0.0, 4, 1)[1][2, 1], _v(0.5, 0.5 / 32), rtol=2e-6)
+    ib, M, obj = _hand_frame(K=2.5)                                               # as after rtpbr_reproject
+    np.testing.assert_allclose(pl.estimate(ib, M, obj, 0.0, 3, 1)[1][2, 1], _v(0.5, 0.5 / (3 * 8)), rtol=2e-6)
+    # own of the neighbour: 0.5 / ((2.5 - 1) * 8) > pooled
+    np.testing.assert_allclose(pl.estimate(ib, M, obj, 0.0, 3, 1)[1][3, 1], _v(0.5, 0.5 / (1.5 * 8)), rtol=2e-6)
+
+
+@pytest.mark.parametrize("radius", [1, 2, 3])
+def test_frame_borders_clip_the_window(radius):
+    """every pixel has two agreeing batches but the corner (0, 0), whose sum of squares is 0.5: pixel (x, y) sees it when
+    max(x, y) <= R, and DF is the number of window pixels inside the frame"""
+    ib, M, obj = _hand_frame()
+    M[:] = (4.0, 2.0, 8.0, 2.0)
+    M[0, 0] = (4.0, 2.5, 8.0, 2.0)
+    _, var0, _ = pl.estimate(ib, M, obj, 0.0, 4, radius)
+    R = radius
+    for x in range(5):
+        for y in range(3):
+            df = (min(x + R, 4) - max(x - R, 0) + 1) * (min(y + R, 2) - max(y - R, 0) + 1)
+            pooled = 0.5 / (df * 8) if max(x, y) <= R else 0.0
+            want = _v(0.5, max(pooled, 0.5 / 8 if (x, y) == (0, 0) else 0.0))
+            np.testing.assert_allclose(var0[x, y], want, rtol=2e-6, err_msg=f"pixel {(x, y)}")
+
+
+def test_never_below_today():
+    for seed in range(6):
+        ib, M, obj = _random_frame(np.random.default_rng(100 + seed), 33, 20)
+        noise0, var0, st0 = nr.estimate(ib, M, obj, 0.1)
+        for pb, radius in ((3, 1), (4, 3), (64, 2)):
+            noise1, var1, st1 = pl.estimate(ib, M, obj, 0.1, pb, radius)
+            assert (var1 >= var0).all() and (noise1 >= noise0).all()
+            old = (M[..., 3] >= pb) | (M[..., 3] < 2)
+            assert np.array_equal(_bits(var1[old]), _bits(var0[old]))
+            assert st1[0] == st0[0] and st1[1] >= st0[1] and st1[2] >= st0[2]
+        assert (pl.estimate(ib, M, obj, 0.1, 64, 3)[1] > var0).any()
+
+
+def test_selection_with_min_samples():
+    rng = np.random.default_rng(2)
+    noise = rng.uniform(0, 0.2, (9, 7)).astype(np.float32)
+    count = rng.integers(0, 6, (9, 7)).astype(np.float32) * 4
+    assert (count == 0).any() and (count == 8).any()
+    for d in range(4):
+        assert np.array_equal(pl.select(noise, count, 0.18, d, 0), sr.select(noise, count, 0.18, d))
+        for ms in (1, 8, 9, 100):
+            got = pl.select(noise, count, 0.18, d, ms)
+            want = sr.select(noise, count, 0.18, d).astype(bool) | ~(count > 0) | (count < ms)
+            assert np.array_equal(got, want.astype(np.uint8)) and got.dtype == np.uint8
+    strict = pl.select(np.zeros((9, 7), np.float32), count, 0.18, 0, 8)
+    assert (strict[count == 8] == 0).all() and (strict[count == 4] == 1).all() and (strict[count == 0] == 1).all()
+    assert pl.select(noise, count, 0.18, 0, 100).all()
+    with pytest.raises(ValueError):
+        pl.select(noise, count, 0.18, 0, -1)
+
+
+def test_header_library_and_binding_agree():
+    """(that a refused call leaves a context's setting as it was needs a context, so a GPU: tests/test_gpu_pool.py)"""
+    hdr = open(os.path.join(ROOT, "include", "rtpbr.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"int rtpbr_set_noise_estimator\(rtpbr_ctx\* ctx, const rtpbr_noise_estimator\* e\);", code)
+    assert re.search(r"typedef struct rtpbr_noise_estimator \{\s*int32_t pool_batches;\s*int32_t pool_radius;\s*int32_t min_samples;\s*\} "
+                     r"rtpbr_noise_estimator;", code)
+    found = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define RTPBR_NOISE_ESTIMATOR_DEFAULT_([A-Z_]+)\s+(-?[0-9]+)\b", hdr)}
+    assert found == NoiseEstimator.DEFAULTS == {"pool_batches": 0, "pool_radius": 3, "min_samples": 0}
+    assert C.sizeof(NoiseEstimator) == 12 and [f for f, _ in NoiseEstimator._fields_] == ["pool_batches", "pool_radius", "min_samples"]
+    lib = C.CDLL(_capi.HIP_LIB_PATH)
+    assert hasattr(lib, "rtpbr_set_noise_estimator")
+    assert "set_noise_estimator" in _capi.ENTRY_POINTS
+    api = _capi.hip_api()
+    assert api.fn["set_noise_estimator"].argtypes == [C.c_void_p, C.POINTER(NoiseEstimator)]
+    for e in (None, NoiseEstimator(0, 3, 0), NoiseEstimator(2, 3, 0), NoiseEstimator(8, 4, 0), NoiseEstimator(8, 3, -1)):
+        assert api.fn["set_noise_estimator"](None, None if e is None else C.byref(e)) == EINVAL      # NULL context
+    # the restatement refuses the same ranges
+    ib, M, obj = _hand_frame()
+    out = [np.empty((5, 3), np.float32), np.empty((5, 3), np.float32), np.zeros(3, np.uint32)]
+    for pb, radius, ok in ((0, 3, True), (3, 1, True), (64, 3, True), (1, 3, False), (2, 3, False), (65, 3, False), (-1, 3, False),
+                           (0, 0, False), (0, 4, False), (8, 0, False), (8, 4, False)):
+        rc = pl.lib().pr_estimate(5, 3, pl._ptr(ib), pl._ptr(M), pl._ptr(obj), 0.0, pb, radius, *[pl._ptr(a) for a in out])
+        assert (rc == 0) == ok, (pb, radius)
+
+
+# ------------------------------------------------------------------ the adaptive loop on the oracle
+W = H = 32
+THRESHOLD, BATCH, MAX_SPP = 0.1, 16, 1024
+POOLED = (16, 3, 4 * BATCH)      # pool_batches, pool_radius, min_samples: the setting of examples/adaptive_render.py --bench
+GROUP = 4                        # seeds per group
+
+
+def _truth():
+    """lum-free reference: the display image of 16 384 spp of other seeds (4 x 4096, seeds 1000..1003), kept as a fixture because
+    it costs 25 s of CPU: tests/golden/pool_truth_cornell_v3_32.npy is exactly what this returns"""
+    sc = cornell_box("v3", aspect=W / H)
+    acc = np.zeros((W, H, 4), np.float64)
+    for s in (1000, 1001, 1002, 1003):
+        o = OracleRenderer(sc, Config.cornell_v3(W, H, seed=s, max_raytrace=3))
+        o.refresh()
+        o.sample(4096)
+        acc += o.image_buffer
+    o.image_buffer = acc.astype(np.float32)
+    o.post_process()
+    return o.image_pixels
+
+
+def _adaptive_on_the_oracle(seed, obj, pool_batches, pool_radius, min_samples):
+    """Renderer.render_adaptive(THRESHOLD, MAX_SPP, BATCH, dilate = 0) on the CPU: two full-frame batches, then rounds of a
+    full-frame sample(BATCH) at the running sample base composed with np.where(mask, after, before), the mask from pool_ref_lib.
+    Returns (display image, samples per pixel)."""
+    sc = cornell_box("v3", aspect=W / H)
+    o = OracleRenderer(sc, Config.cornell_v3(W, H, seed=seed, max_raytrace=3))
+    o.refresh()
+    t = nr.Tracker(W, H)
+    used = 0
+    for _ in range(2):
+        o.sample(BATCH)
+        ib = o.image_buffer
+        t.update(ib)
+        used += BATCH
+    while used + BATCH <= MAX_SPP:
+        noise, _, _ = pl.estimate(ib, t.moments, obj, THRESHOLD, pool_batches, pool_radius)
+        mask = pl.select(noise, ib[..., 3], THRESHOLD, 0, min_samples)
+        if not mask.any():
+            break
+        o.sample(BATCH)
+        ib = np.where((mask != 0)[..., None], o.image_buffer, ib)
+        o.image_buffer = ib
+        t.update(ib)
+        used += BATCH
+    o.post_process()
+    return o.image_pixels, ib[..., 3]
+
+
+def _first_half(px, cnt, truth):
+    """(mean signed display error, RMSE, pixel-samples) over the half of the pixels with the fewest samples"""
+    e = (px - truth).astype(np.float64)
+    low = cnt <= np.quantile(cnt, 0.5)
+    return float(np.mean(e[low])), float(np.sqrt(np.mean(e[low] ** 2))), float(cnt.sum())
+
+
+def _group(g, setting, truth, obj):
+    return np.mean([_first_half(*_adaptive_on_the_oracle(s, obj, *setting), truth) for s in range(GROUP * g, GROUP * (g + 1))], 0)
+
+
+def test_pooling_moves_the_early_stopped_half_towards_the_truth():
+    """Cornell v3 at 32x32 on the oracle, render_adaptive's loop (noise 0.1, batches of 16, budget 1024 spp, dilate = 0) with the
+    estimator off and with POOLED = (pool_batches 16, pool_radius 3, min_samples 64), against the 16 384-spp frame of other
+    seeds.  Per run: over the half of the pixels with the fewest samples, the mean signed display error and the RMSE; a group is
+    the mean over 4 consecutive seeds.
+
+    Measured on the CPU, six disjoint groups (seeds 0..23), mean error of the first half:
+        off      -0.2077 -0.2066 -0.2050 -0.2021 -0.2066 -0.2054   mean -0.2056, standard deviation 0.0019
+        pooled   -0.0617 -0.0605 -0.0585 -0.0556 -0.0645 -0.0576   mean -0.0597, standard deviation 0.0032
+    RMSE of the first half:
+        off       0.2771  0.2752  0.2764  0.2741  0.2769  0.2749   mean  0.2758, standard deviation 0.0012
+        pooled    0.1599  0.1539  0.1598  0.1560  0.1611  0.1566   mean  0.1579, standard deviation 0.0028
+    pixel-samples per frame: off 79 380 .. 82 820 (78 spp mean), pooled 204 896 .. 207 764 (201 spp mean, 2.59 x).
+    The pooled run is closer to zero in every group (and in each of the 24 seeds).  POOLED is the best of the grid pool_batches
+    {4, 8, 16} x pool_radius {1, 2, 3} x min_samples {0, 32, 64} by this measurement (DESIGN.md 6f has all 27 rows; every one of
+    them is closer to zero than off in every group; 4 batches: -0.17, 8: -0.10..-0.11, 16: -0.06..-0.08).  The bands are the
+    groups' mean +- 5 of their standard deviations, asserted on the first group."""
+    truth = np.load(os.path.join(ROOT, "tests", "golden", "pool_truth_cornell_v3_32.npy"))
+    obj = fr.features(cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, seed=0, max_raytrace=3))["object"]
+    off = _group(0, (0, 3, 0), truth, obj)
+    on = _group(0, POOLED, truth, obj)
+    print(f"first half, group 0: mean error off {off[0]:+.4f} pooled {on[0]:+.4f}; RMSE off {off[1]:.4f} pooled {on[1]:.4f}; "
+          f"pixel-samples off {off[2]:.0f} pooled {on[2]:.0f}")
+    assert abs(on[0]) < abs(off[0])
+    assert -0.2056 - 5 * 0.0019 <= off[0] <= -0.2056 + 5 * 0.0019, off[0]
+    assert -0.0597 - 5 * 0.0032 <= on[0] <= -0.0597 + 5 * 0.0032, on[0]
+    assert 0.2758 - 5 * 0.0012 <= off[1] <= 0.2758 + 5 * 0.0012, off[1]
+    assert 0.1579 - 5 * 0.0028 <= on[1] <= 0.1579 + 5 * 0.0028, on[1]

@@ -230,7 +230,10 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_NOISE        = 12,  /* (W,H)   f32 estimated standard deviation of lum(r(displayed average))          */
        /* the pixel selection (rtpbr_select_mask / rtpbr_select_noisy): allocated on the first select call, RTPBR_ESTATE before;
         * output only */
-       RTPBR_BUF_SELECTION    = 13 };/* (W,H)   u8  1 = selected: what rtpbr_sample_selected traces                           */
+       RTPBR_BUF_SELECTION    = 13,  /* (W,H)   u8  1 = selected: what rtpbr_sample_selected traces                           */
+       /* the packed 8-bit frame (rtpbr_present): allocated on the first present, RTPBR_ESTATE before; output only.  NOT in the
+        * field layout: (H,W,C) u8, row 0 = the TOP row of the picture, x fastest, C = 3 or 4 as the last present said */
+       RTPBR_BUF_PRESENT      = 14 };
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -548,6 +551,63 @@ int rtpbr_set_noise_estimator(rtpbr_ctx* ctx, const rtpbr_noise_estimator* e);  
 int rtpbr_select_mask(rtpbr_ctx* ctx, const uint8_t* mask, size_t nbytes, uint32_t* n_selected);
 int rtpbr_select_noisy(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 int rtpbr_sample_selected(rtpbr_ctx* ctx, int n);
+
+/* ---- The present stage: a display buffer becomes a packed 8-bit frame on the device, in one kernel.
+ *
+ * Every display buffer above is in the field layout — (W,H,3) f32, [x][y], y = 0 at the BOTTOM, y fastest — which no window,
+ * encoder or image file takes: a host finishes the frame with a clamp, a quantisation and a transpose (what ti.tools.imwrite and
+ * canvas.set_image do inside Taichi, src/main.py:55,64).  rtpbr_present does that step on the device and writes
+ * RTPBR_BUF_PRESENT: (H,W,C) u8, row 0 = the TOP row of the picture, x fastest, C = 3 (RGB8) or 4 (RGBA8, alpha = 255): 3 or 4
+ * bytes per pixel cross to the host instead of 12, and a consumer on the device takes the frame as it is.
+ *
+ * Every operation is f32, in this order, nothing fused.  Output element [r][x][c], r = 0 .. H-1 from the top:
+ *   the field pixel is (x, y = H - 1 - r), buffer index x * H + y;
+ *   v = channel c of the source there: RTPBR_PRESENT_PIXELS: image_pixels; RTPBR_PRESENT_DENOISED: denoised_pixels;
+ *       RTPBR_PRESENT_ACCUM: tone_map(cfg, image_buffer[x * H + y]), the function rtpbr_post_process applies — what it WOULD write
+ *       to image_pixels, bit for bit, without writing image_pixels, diff_buffer or diff_pixels;
+ *   v = (v != v) ? 0 : v;   v = fminf(fmaxf(v, 0), 1);
+ *   q = (uint8_t)(v * 255.0f + t)        (the product is rounded to f32 before the sum; the conversion truncates);
+ *   dither = 0: t = 0.5f;
+ *   dither = 1: t = (B[r & 7][x & 7] + 0.5f) * 0.015625f — the row is the TOP-DOWN row r, the column is x, the three channels of a
+ *     pixel share t — with the 8 x 8 Bayer matrix
+ *       B = {  0, 32,  8, 40,  2, 34, 10, 42,
+ *             48, 16, 56, 24, 50, 18, 58, 26,
+ *             12, 44,  4, 36, 14, 46,  6, 38,
+ *             60, 28, 52, 20, 62, 30, 54, 22,
+ *              3, 35, 11, 43,  1, 33,  9, 41,
+ *             51, 19, 59, 27, 49, 17, 57, 25,
+ *             15, 47,  7, 39, 13, 45,  5, 37,
+ *             63, 31, 55, 23, 61, 29, 53, 21 };
+ *     t runs over (k + 0.5) / 64, k = 0 .. 63: 0 < t < 1, so 0 stays 0 and 1 stays 255 in both modes, and the dithered value is at
+ *     most one level from the undithered one.
+ * With dither = 0 and source = RTPBR_PRESENT_PIXELS these are the bytes of the host path
+ * (clip(nan_to_num(a, nan = 0), 0, 1) * 255 + 0.5 as uint8, then swapaxes(0, 1)[::-1]), byte for byte.
+ *
+ * The call is asynchronous on the context's stream and ordered behind an outstanding rtpbr_read_buffer_async of
+ * RTPBR_BUF_PRESENT (that copy lands the previous frame).  It writes RTPBR_BUF_PRESENT and nothing else, leaves the work counters
+ * alone, needs no flush of lazy shading (it reads image buffers only) and works with tiles of world > 1: it reads whole buffers,
+ * as rtpbr_post_process does.  The buffer is allocated once, W * H * 4 bytes, by the first present; its size as
+ * rtpbr_read_buffer / rtpbr_read_buffer_async / rtpbr_buffer_device_ptr report and require it is W * H * C of the LAST present.
+ * rtpbr_write_buffer refuses it (RTPBR_EINVAL); rtpbr_set_config with a new resolution frees it.
+ *
+ * Errors: RTPBR_EINVAL for a NULL context or a field outside its range; RTPBR_ESTATE before rtpbr_set_config, and for
+ * RTPBR_PRESENT_DENOISED before rtpbr_denoise / rtpbr_denoise_guided has made the buffer.  A refused call changes nothing. */
+enum { RTPBR_PRESENT_PIXELS = 0,     /* RTPBR_BUF_IMAGE_PIXELS as it is                                         */
+       RTPBR_PRESENT_DENOISED = 1,   /* RTPBR_BUF_DENOISED_PIXELS as it is                                      */
+       RTPBR_PRESENT_ACCUM = 2 };    /* tone_map(cfg, image_buffer): rtpbr_post_process's colour, nothing written */
+enum { RTPBR_PRESENT_RGB8 = 0,
+       RTPBR_PRESENT_RGBA8 = 1 };    /* alpha = 255                                                             */
+typedef struct rtpbr_present_params {   /* 4-byte members, no padding */
+    int32_t source;        /* RTPBR_PRESENT_PIXELS / _DENOISED / _ACCUM     */
+    int32_t format;        /* RTPBR_PRESENT_RGB8 / _RGBA8                   */
+    int32_t dither;        /* 0: round to nearest; 1: ordered (Bayer 8 x 8) */
+} rtpbr_present_params;
+/* Defaults (p == NULL): image_pixels as RGBA8, no dither.  raytracingpbr_amd.dataclass.PresentParams.DEFAULTS mirrors them
+ * (tests/test_present_ref.py checks). */
+#define RTPBR_PRESENT_DEFAULT_SOURCE 0
+#define RTPBR_PRESENT_DEFAULT_FORMAT 1
+#define RTPBR_PRESENT_DEFAULT_DITHER 0
+int rtpbr_present(rtpbr_ctx* ctx, const rtpbr_present_params* p);   /* NULL = the defaults */
 
 /* Block until everything enqueued on the context has finished (its stream, and the copies of rtpbr_read_buffer_async). */
 int rtpbr_sync(rtpbr_ctx* ctx);

@@ -5,10 +5,10 @@ Host-side mirror of the Scene / Camera / render() surface of HK-SHAO/RayTracingP
 hand-written gfx950 HIP kernels through the C ABI in include/rtpbr.h.
 """
 from .config import Config, FORM, MARCH, PRIMARY, SKY, TONEMAP
-from .dataclass import SHAPE, Camera, Counters, Material, NoiseEstimator, Ray, SDFObject, Transform, vec3
+from .dataclass import SHAPE, Camera, Counters, Material, NoiseEstimator, PresentParams, Ray, SDFObject, Transform, vec3
 from .renderer import Renderer, display_image
 from .scene import Scene, bunny, cornell_box, src_scene
 
 __all__ = ["Config", "FORM", "MARCH", "PRIMARY", "SKY", "TONEMAP", "SHAPE", "Camera", "Counters",
-           "Material", "NoiseEstimator", "Ray", "SDFObject", "Transform", "vec3", "Renderer", "display_image", "Scene",
+           "Material", "NoiseEstimator", "PresentParams", "Ray", "SDFObject", "Transform", "vec3", "Renderer", "display_image", "Scene",
            "bunny", "cornell_box", "src_scene"]

@@ -12,7 +12,7 @@ import ctypes as C
 import os
 
 from .config import Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseEstimator, NoiseStats, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseEstimator, NoiseStats, PresentParams, ReprojectParams, SDFObject
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPBR_HIP_LIB overrides the path (A/B of differently built HIP libraries); it must still be a HIP build
@@ -27,11 +27,11 @@ ENTRY_POINTS = [
     "get_counters", "get_counter", "last_sample_ms", "last_primary_ms", "get_stream", "set_option", "set_shape_data",
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
     "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
-    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator",
+    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
 ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
-                   "select_mask", "select_noisy", "sample_selected", "set_noise_estimator")
+                   "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present")
 
 
 class RtpbrError(RuntimeError):
@@ -99,6 +99,7 @@ class CApi:
             "select_noisy": (C.c_int, [p, C.c_float, C.c_int, C.POINTER(C.c_uint32)]),
             "sample_selected": (C.c_int, [p, C.c_int]),
             "set_noise_estimator": (C.c_int, [p, C.POINTER(NoiseEstimator)]),
+            "present": (C.c_int, [p, C.POINTER(PresentParams)]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

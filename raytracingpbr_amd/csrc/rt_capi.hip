@@ -17,6 +17,7 @@
 #include "rt_features.hpp"
 #include "rt_reproject.hpp"
 #include "rt_noise.hpp"
+#include "rt_present.hpp"
 #include "rt_select.hpp"
 
 using namespace rt;
@@ -145,6 +146,13 @@ static void free_selection(rtpbr_ctx* c) {
     c->have_selection = false;
 }
 
+// the frame of rtpbr_present (allocated on the first present)
+static void free_present(rtpbr_ctx* c) {
+    (void)hipFree(c->present);
+    c->present = nullptr;
+    c->present_channels = 0;
+}
+
 extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     if (!c) return RTPBR_OK;
     (void)hipSetDevice(c->device);
@@ -167,6 +175,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     free_features(c);
     free_noise(c);
     free_selection(c);
+    free_present(c);
     (void)hipFree(c->noise_stats);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
@@ -268,6 +277,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
         free_features(c);
         free_noise(c);
         free_selection(c);
+        free_present(c);
         HIP_TRY(hipMalloc(&c->image_buffer, n * sizeof(float4)));
         HIP_TRY(hipMalloc(&c->image_pixels, n * 3 * sizeof(float)));
         HIP_TRY(hipMalloc(&c->ray_buffer, n * sizeof(rtpbr_ray)));
@@ -697,7 +707,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b < 14; b++)
+    for (int b = 0; b <= RTPBR_BUF_PRESENT; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -1855,6 +1865,39 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
     return RTPBR_OK;
 }
 
+// ---- the present stage (rt_present.hip): a display buffer -> the packed 8-bit top-down frame, on the device
+extern "C" int rtpbr_present(rtpbr_ctx* c, const rtpbr_present_params* p) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_present_params d;
+    if (p) {
+        d = *p;
+    } else {
+        d.source = RTPBR_PRESENT_DEFAULT_SOURCE;
+        d.format = RTPBR_PRESENT_DEFAULT_FORMAT;
+        d.dither = RTPBR_PRESENT_DEFAULT_DITHER;
+    }
+    if (d.source < RTPBR_PRESENT_PIXELS || d.source > RTPBR_PRESENT_ACCUM) return fail(RTPBR_EINVAL, "present source must be RTPBR_PRESENT_PIXELS, _DENOISED or _ACCUM");
+    if (d.format != RTPBR_PRESENT_RGB8 && d.format != RTPBR_PRESENT_RGBA8) return fail(RTPBR_EINVAL, "present format must be RTPBR_PRESENT_RGB8 or _RGBA8");
+    if (d.dither != 0 && d.dither != 1) return fail(RTPBR_EINVAL, "present dither must be 0 or 1");
+    if (!c->have_cfg || c->headless) return fail(RTPBR_ESTATE, "set_config first");
+    if (d.source == RTPBR_PRESENT_DENOISED && !c->denoised) return fail(RTPBR_ESTATE, "rtpbr_present: no denoised image yet (rtpbr_denoise / rtpbr_denoise_guided first)");
+    if (int r = set_dev(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->present) HIP_TRY(hipMalloc(&c->present, n * 4));
+    if (int r = rt_order_after_reads(c, 1u << RTPBR_BUF_PRESENT)) return r;
+    PresentArgs A{};
+    A.cfg = c->cfg;
+    A.src3 = d.source == RTPBR_PRESENT_DENOISED ? c->denoised : c->image_pixels;
+    A.src4 = c->image_buffer;
+    A.out = c->present;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    launch_present(A, d.source == RTPBR_PRESENT_ACCUM, d.format == RTPBR_PRESENT_RGBA8, d.dither != 0, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->present_channels = d.format == RTPBR_PRESENT_RGBA8 ? 4 : 3;
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_sync(rtpbr_ctx* c) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (int r = set_dev(c)) return r;
@@ -1882,11 +1925,13 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_MOMENTS: *p = c->noise_moments; *n = np * 16; break;
         case RTPBR_BUF_NOISE: *p = c->noise_map; *n = np * 4; break;
         case RTPBR_BUF_SELECTION: *p = c->sel_mask; *n = np; break;
+        case RTPBR_BUF_PRESENT: *p = c->present; *n = np * (size_t)c->present_channels; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
-    // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* first");
+    // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate,
+    // the packed frame from the first rtpbr_present)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present first");
     return 0;
 }
 
@@ -1987,8 +2032,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_SELECTION)
-        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise and selection buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_PRESENT)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection and present buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

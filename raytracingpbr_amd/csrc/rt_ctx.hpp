@@ -10,6 +10,7 @@
 
 #include "rt_device.hpp"
 #include "rt_noise.hpp"
+#include "rt_present.hpp"
 #include "rt_select.hpp"
 
 namespace rt {
@@ -174,7 +175,7 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[14] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[15] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
     float* feat_albedo = nullptr;      // (W,H,3)
@@ -206,6 +207,9 @@ struct rtpbr_ctx {
     uint32_t* sel_blocks = nullptr;    // per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them
     uint32_t sel_count = 0;            // entries of sel_list
     bool have_selection = false;
+    // the packed 8-bit frame of rtpbr_present (rt_present.hip): allocated on the first present, freed with the context or a new resolution
+    uint8_t* present = nullptr;        // (H,W,C) top-down, room for C = 4: RTPBR_BUF_PRESENT
+    int present_channels = 0;          // C of the last present (the buffer's reported size is W * H * C)
     size_t march_np = 0;
     int src_chain = 1;            // src/ form, fused launches: the plan's chain set runs in the chain kernel beside the pool kernel (rt_chain.hpp)
     long long chain_np_max = 2500000;   // ... frames of more local pixels than this are throughput-bound: no chain set

@@ -139,3 +139,15 @@ class DenoiseGuidedParams(_Pod):
     # include/rtpbr.h RTPBR_DENOISE_GUIDED_DEFAULT_*, what rtpbr_denoise_guided(ctx, NULL) uses; Renderer.denoise_guided() fills
     # the parameters not given from here (tests/test_noise_ref.py keeps the two equal)
     DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 16.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "variance_floor": 1e-3}
+
+
+class PresentParams(_Pod):
+    """rtpbr_present_params (include/rtpbr.h): which display buffer becomes the packed 8-bit frame, its pixel format, and
+    whether the quantisation is ordered-dithered."""
+    _fields_ = [("source", C.c_int32), ("format", C.c_int32), ("dither", C.c_int32)]
+
+    # include/rtpbr.h RTPBR_PRESENT_DEFAULT_*, what rtpbr_present(ctx, NULL) uses: image_pixels as RGBA8, no dither
+    # (tests/test_present_ref.py keeps the two equal)
+    DEFAULTS = {"source": 0, "format": 1, "dither": 0}
+    SOURCES = {"pixels": 0, "denoised": 1, "accum": 2}      # RTPBR_PRESENT_PIXELS / _DENOISED / _ACCUM
+    FORMATS = {"rgb8": 0, "rgba8": 1}                        # RTPBR_PRESENT_RGB8 / _RGBA8

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseEstimator, NoiseStats, Ray, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -26,6 +26,8 @@ BUF_MOTION = 10
 BUF_MOMENTS, BUF_NOISE = 11, 12
 # the pixel selection (select_mask / select_noisy): 1 = sample_selected traces the pixel; exists from the first select call on
 BUF_SELECTION = 13
+# the packed 8-bit frame (present): (H,W,C) uint8, top-down, C = 3 or 4 as the last present() said; exists from the first present() on
+BUF_PRESENT = 14
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -274,9 +276,36 @@ class Renderer:
         finally:
             self.track_noise = keep
 
+    # ------------------------------------------------------------ the present stage (include/rtpbr.h rtpbr_present)
+    def present(self, source="pixels", format="rgba8", dither=False):
+        """Enqueue the display frame: ``source`` ("pixels" = image_pixels, "denoised" = denoised_pixels, "accum" = the tone map of
+        image_buffer, i.e. what post_process() would show, without running it) is clamped, quantised to 8 bit (``dither``: ordered,
+        Bayer 8 x 8) and transposed into ``presented``: (H, W, 3 | 4) uint8, top row first — what a window, an encoder or an
+        image file takes.  Asynchronous; returns nothing."""
+        try:
+            p = PresentParams(PresentParams.SOURCES[source], PresentParams.FORMATS[format], 1 if dither else 0)
+        except KeyError as e:
+            raise ValueError(f"present: unknown source or format {e.args[0]!r}") from None
+        self.api.call("present", self._ctx, C.byref(p))
+
+    @property
+    def presented(self):
+        """(H, W, C) uint8: the frame of the last present(), top row first (blocking read)"""
+        return self._read(BUF_PRESENT)
+
+    def save_image(self, path, source="pixels", dither=False):
+        """present(source, "rgb8", dither) and write the frame to ``path`` (any format Pillow knows by the extension): the bytes
+        imageio.imwrite(image_pixels, path) writes, without the host's clamp / quantise / transpose."""
+        from PIL import Image
+        self.present(source, "rgb8", dither)
+        Image.fromarray(self.presented).save(path)
+
     # ------------------------------------------------------------ buffers (field.to_numpy())
     def _shape(self, which):
         W, H = self.config.width, self.config.height
+        if which == BUF_PRESENT:      # not a field: (H, W, C) with the last present's C, which the library knows (ESTATE before the first)
+            _, n = self.device_ptr(which)
+            return (H, W, n // (W * H)), np.uint8
         return {BUF_IMAGE_BUFFER: ((W, H, 4), np.float32), BUF_IMAGE_PIXELS: ((W, H, 3), np.float32),
                 BUF_RAY_BUFFER: ((W, H, 10), np.float32), BUF_DIFF_BUFFER: ((W, H, 2), np.float32),
                 BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),

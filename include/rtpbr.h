@@ -421,12 +421,13 @@ int rtpbr_reproject(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtpbr_rep
  *     s = b (in every case).
  *   So M = (sum c L, sum c L^2, sum c, K) over K batches of c_k samples.  It flushes lazy shading, is ordered behind
  *   asynchronous reads of the moments, and writes nothing else.
- *   rtpbr_refresh zeroes M and s when they exist; rtpbr_set_config with a new resolution frees them;
+ *   rtpbr_refresh zeroes M and s when they exist; rtpbr_set_config with a new resolution frees them and RTPBR_BUF_NOISE;
  *   rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) re-takes s (written data is no batch); rtpbr_reproject warps M (below).
  *
  * rtpbr_noise_estimate writes RTPBR_BUF_NOISE = sqrt(v) (correctly rounded) per pixel and, if out != NULL, the statistics;
  *   it blocks like rtpbr_get_counters.  It renders the features first when they are stale, as rtpbr_denoise does, and
- *   allocates M (zeroed) when rtpbr_noise_update has not run.  Per pixel p with b = image_buffer:
+ *   allocates M and s (both zeroed, as the first rtpbr_noise_update would) when they do not exist: from then on
+ *   rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) re-takes s.  Per pixel p with b = image_buffer:
  *     b.w > 0 is false:     v = 0, the pixel is not counted as estimated;
  *     M.w >= 2 (temporal):  mu = M.x / M.z;  sd = sqrt(max((M.y - (M.x * M.x) / M.z) / ((M.w - 1) * M.z), 0));
  *                           hi = mu + sd; lo = max(mu - sd, 0);  hw = 0.5f * (hi / (1 + hi) - lo / (1 + lo));
@@ -467,7 +468,8 @@ int rtpbr_reproject(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtpbr_rep
  *     ic_p = 1 / ((sigma_color * sigma_color) * max(g, variance_floor))    (no 4^k schedule);
  *     e = ((|r(c_p) - r(c_q)|^2 ic_p + |n_p - n_q|^2 in) + ((z_p - z_q) / max(z_p, 1e-6f))^2 iz);  w = h exp(-min(e, 80));
  *     c_p <- sum w c_q / sum w;  v_p <- sum (w * w) v_q / ((sum w) * (sum w)), all sums in tap order.
- *   iterations = 0 is rtpbr_denoise's iterations = 0.  With demodulate = 1 the colours are compared demodulated while v stays
+ *   iterations = 0 is rtpbr_denoise's iterations = 0: no estimate is made, RTPBR_BUF_NOISE and M are neither written nor
+ *   allocated.  With demodulate = 1 the colours are compared demodulated while v stays
  *   the variance of the modulated luminance (the albedo is constant per object, so this rescales sigma_color per object).
  *
  * rtpbr_reproject with moments (they exist): M is gathered with exactly the accepted taps and weights of the image,

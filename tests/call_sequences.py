@@ -11,6 +11,12 @@ with the same RtpbrError code.  Every operation prints as the Python statement t
 the message holds the seed, the operation's index, the operations since the last observation that matched and where the buffers
 differ, and ``replay(script(seed, ...), upto=i)`` reruns the prefix.
 
+``post_script(seed)`` draws from the same grammar and, for about half of its operations, from the calls that keep state beside
+the sample path: rtpbr_reproject, rtpbr_noise_update / _estimate / rtpbr_denoise_guided, rtpbr_set_noise_estimator, the select
+calls, rtpbr_sample_selected, rtpbr_present and a "post" observation of the buffers they own.  Those run on the HIP library
+against the model of tests/post_model.py (``run_post``), whose refusal codes are written from include/rtpbr.h.  script() itself
+draws what it always drew (tests/test_oracle_call_sequences.py pins a hash of its scripts).
+
 The generator keeps clear of the argument checks only the HIP library makes (max_raymarch / max_raytrace <= 0, the per-rank
 pixel limit).  The bunny's weights are a process-wide global in the oracle, so every script that renders the bunny sets the
 weights it means to use on both backends first."""
@@ -23,6 +29,7 @@ from raytracingpbr_amd.ibl import load_bunny_weights, synthetic_env
 
 EINVAL, ESTATE = -1, -4
 SIZES = ((23, 17), (40, 24), (31, 9))
+POST_SIZES = SIZES + ((67, 45),)      # a multiple of neither the pooled estimator's 16 x 16 tile nor the present kernel's 64 x 64, wider than 64
 COUNTERS = ("samples", "raycasts", "march_steps", "hits", "sky_lookups", "deposits")
 BUFFERS = ("image_buffer", "image_pixels", "ray_buffer", "diff_buffer", "diff_pixels")
 
@@ -73,11 +80,16 @@ def scene(name):
     return _scene_cache[name]
 
 
-def camera(name, offset=(0.0, 0.0, 0.0)):
-    """the scene's own camera, its eye moved by `offset`"""
+def camera(name, offset=(0.0, 0.0, 0.0), vfov=1.0):
+    """the scene's own camera, its eye moved by `offset`, its field of view scaled by `vfov`"""
     c = scene(name).camera
     lf = tuple(float(np.float32(a + b)) for a, b in zip(c.lookfrom, offset))
-    return Camera(lf, tuple(c.lookat), tuple(c.vup), c.vfov, c.aspect, c.aperture, c.focus)
+    return Camera(lf, tuple(c.lookat), tuple(c.vup), float(np.float32(c.vfov * vfov)), c.aspect, c.aperture, c.focus)
+
+
+def mask(w, h, seed, share):
+    """a host mask for select_mask: about `share` of the pixels (0.0: none, 1.0: all)"""
+    return (np.random.default_rng(seed).random((w, h)) < share).astype(np.uint8)
 
 
 def env(w, h, seed, f32):
@@ -107,8 +119,9 @@ def base_config(kind, w, h, seed):
 class Op:
     """one call of the grammar: `kind`, its arguments, the RtpbrError code it must raise (None: it must succeed)"""
 
-    def __init__(self, kind, expect=None, **args):
+    def __init__(self, kind, expect=None, why=(), **args):
         self.kind, self.expect, self.args = kind, expect, args
+        self.why = tuple(why)               # the reasons for `expect` (post_script: the coverage conditions read them)
 
     def code(self):
         a, k = self.args, self.kind
@@ -142,15 +155,31 @@ class Op:
             return "r.render_features()   # HIP only, against tests/feature_ref_lib.py"
         if k == "denoise":
             return f"r.denoise(**{a['params']!r})   # HIP only, against tests/feature_ref_lib.py"
-        return f"r.{k}()"
+        if k == "noise_estimate":
+            return f"r.noise_estimate({a['threshold']})"
+        if k == "denoise_guided":
+            return f"r.denoise_guided(**{a['params']!r})"
+        if k == "set_noise_estimator":
+            return "r.api.call('set_noise_estimator', r._ctx, None)   # NULL: the defaults" if a["e"] is None else f"r.set_noise_estimator(*{a['e']!r})"
+        if k == "select_mask":
+            return f"r.select_mask(cs.mask(r.config.width, r.config.height, {a['seed']}, {a['share']}))"
+        if k == "select_noisy":
+            return f"r.select_noisy({a['threshold']}, {a['dilate']})"
+        if k == "sample_selected":
+            return f"r.sample_selected({a['n']})"
+        if k == "reproject":
+            return f"r.reproject(cs.camera({a['name']!r}, {a['offset']!r}, {a['vfov']}), **{a['params']!r})"
+        if k == "present":
+            return f"r.present({a['source']!r}, {a['format']!r}, {a['dither']})"
+        return f"r.{k}()"                   # refresh, post_process, noise_update
 
     def __repr__(self):
         return self.code() + ("" if self.expect is None else f"   # must raise RtpbrError {self.expect}")
 
 
 class Script:
-    def __init__(self, seed, base, scene0, ops, jit=0):
-        self.seed, self.base, self.scene0, self.ops, self.jit = seed, base, scene0, ops, jit
+    def __init__(self, seed, base, scene0, ops, jit=0, post=False):
+        self.seed, self.base, self.scene0, self.ops, self.jit, self.post = seed, base, scene0, ops, jit, post
 
     def header(self):
         b = self.base
@@ -174,35 +203,44 @@ class Mirror:
         return {k: getattr(cfg, k) for k, _ in Config._fields_ if getattr(cfg, k) != getattr(b, k)}
 
 
-def script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
-    """A reproducible call sequence: seed -> Script.  `scenes`: the scene pool (all of SCENES by default); `forms`: the kernel
-    forms set_config may switch between."""
-    rng = np.random.default_rng(seed)
-    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]      # noqa: E731
-    pool = list(scenes or SCENES)
-    w, h = pick(SIZES)
-    base = base_config(pick(("cornell", "src", "demo")), w, h, seed)
-    base.kernel_form = pick(forms)
-    scene0 = pick([s for s in pool if s != "bunny"])
-    m = Mirror(base, scene0)
-    ops = []
+class _Grammar:
+    """the random stream of one script and the operations drawn from it so far; `state_cls`: the mirror's class (post_script passes
+    post_model.PostState, which follows every operation that is meant to succeed through its note())"""
 
-    def add(op):
-        ops.append(op)
+    def __init__(self, seed, scenes, forms, sizes, state_cls=None):
+        self.rng = np.random.default_rng(seed)
+        self.pool, self.forms, self.sizes = list(scenes or SCENES), forms, sizes
+        w, h = self.pick(sizes)
+        self.base = base_config(self.pick(("cornell", "src", "demo")), w, h, seed)
+        self.base.kernel_form = self.pick(forms)
+        self.scene0 = self.pick([s for s in self.pool if s != "bunny"])
+        self.m = (state_cls or Mirror)(self.base, self.scene0)
+        self.ops = []
+
+    def pick(self, seq):
+        return seq[int(self.rng.integers(0, len(seq)))]
+
+    def add(self, op):
+        self.ops.append(op)
+        if op.expect is None and hasattr(self.m, "note"):
+            self.m.note(op)
         return op
 
-    def set_config(cfg):
-        add(Op("set_config", over=m.over(cfg)))
-        m.cfg = cfg
+    def old_op(self):
+        """one draw of the grammar up to render_features / denoise (one or a few operations)"""
+        rng, pick, pool, forms, m, ops, add = self.rng, self.pick, self.pool, self.forms, self.m, self.ops, self.add
 
-    while len(ops) < n_ops:
+        def set_config(cfg):
+            add(Op("set_config", over=m.over(cfg)))
+            m.cfg = cfg
+
         u = rng.random()
         cfg = m.cfg.copy()
         if u < 0.16:                                                        # sample(n)
             n = pick((0, 1, 1, 1, 2, 3, 3, 17, 40)) if m.scene != "bunny" else pick((0, 1, 2))
             if rng.random() < 0.03:
                 add(Op("sample", EINVAL, n=-1))
-                continue
+                return
             add(Op("sample", None if (m.cfg.sky_kind != 1 or m.env) else ESTATE, n=n))
             if rng.random() < 0.5:
                 add(Op("observe", what=pick(("image", "image", "all"))))
@@ -235,7 +273,7 @@ def script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
             if k == 5 and rng.random() < 0.5:
                 add(Op("refresh"))
         elif u < 0.48:                                                      # set_config at a new resolution: buffers reallocated
-            cfg.width, cfg.height = pick([s for s in SIZES if s != (cfg.width, cfg.height)])
+            cfg.width, cfg.height = pick([s for s in self.sizes if s != (cfg.width, cfg.height)])
             set_config(cfg)
         elif u < 0.54:                                                      # set_scene (+ its camera, mostly)
             name = pick(pool)
@@ -295,10 +333,199 @@ def script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
             else:
                 add(Op("bad_scene", EINVAL))
             add(Op("observe", what="all"))
+
+
+def script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
+    """A reproducible call sequence: seed -> Script.  `scenes`: the scene pool (all of SCENES by default); `forms`: the kernel
+    forms set_config may switch between."""
+    g = _Grammar(seed, scenes, forms, SIZES)
+    while len(g.ops) < n_ops:
+        g.old_op()
+    g.add(Op("post_process"))
+    g.add(Op("observe", what="all"))
+    return Script(seed, g.base, g.scene0, g.ops, jit)
+
+
+THRESHOLDS = (0.0, 0.02, 0.08, 0.3)       # fixed: a script prints before it runs, so no quantile of the run's own noise
+GUIDED = ({}, {"iterations": 0}, {"iterations": 0, "demodulate": 1}, {"iterations": 1, "sigma_color": 4.0},
+          {"iterations": 2, "demodulate": 1, "variance_floor": 1e-5}, {"iterations": 3, "sigma_color": 2.0, "sigma_depth": 0.05})
+ESTIMATORS = ((4, 1, 0), (8, 2, 0), (8, 3, 6), (64, 3, 0), (0, 3, 4), (3, 2, 16), None)
+BAD_ESTIMATORS = ((2, 3, 0), (65, 3, 0), (8, 0, 0), (0, 4, 0), (8, 3, -1), (8, 3, 16777217))
+REPROJECT = ({}, {"max_history": 2.0}, {"max_history": 5.0, "depth_tolerance": 0.02}, {"max_history": 1e6, "normal_cos": 0.9},
+             {"max_history": 3.0, "depth_tolerance": 0.0, "normal_cos": -1.0})
+POST_KINDS = ("noise_update", "noise_estimate", "denoise_guided", "set_noise_estimator", "select_mask", "select_noisy", "sample_selected",
+              "reproject", "present")
+
+
+def post_script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
+    """A call sequence over the whole stateful surface: about half of the draws are those of script() (its state changes land
+    between the new calls), the other half are rtpbr_reproject, the noise calls, the estimator setting, the select calls,
+    rtpbr_sample_selected, rtpbr_present and the "post" observation.  The expected code of every new operation comes from
+    post_model.PostState, which follows the script as it is drawn.  Its random stream is its own: script() draws what it drew."""
+    import post_model as pm
+    g = _Grammar(seed, scenes, forms, POST_SIZES, pm.PostState)
+    rng, pick, m, add = g.rng, g.pick, g.m, g.add
+
+    def new(kind, **args):
+        op = Op(kind, **args)
+        op.expect, why = m.refusal(op)
+        op.why = tuple(why)
+        return add(op)
+
+    def spp():
+        return int(pick((1, 2)) if m.scene == "bunny" else pick((1, 2, 3)) if m.cfg.kernel_form == 0 else pick((2, 4, 6)))
+
+    def sample(n):
+        add(Op("sample", None if (m.cfg.sky_kind != 1 or m.env) else ESTATE, n=n))
+
+    def whole_frame(p=0.75):
+        if m.tiles[3] > 1 and rng.random() < p:
+            add(Op("set_tiles", tiles=(0, 0, 0, 1)))
+
+    def clean():
+        """no reason for ESTATE may hold where a bad argument is drawn"""
+        return m.tiles[3] == 1
+
+    def reproject(**over):
+        scale = float(pick((1.0, 1.0, 3.0)))
+        off = tuple(float(np.float32(x * scale)) for x in rng.uniform(-0.3, 0.3, 3))
+        vfov = float(pick((1.0, 1.0, 1.0, 1.1, 0.9)))
+        a = dict(name=m.scene, offset=off, vfov=vfov, params=dict(pick(REPROJECT)))
+        a.update(over)
+        return new("reproject", **a)
+
+    def one(kind):
+        if kind == "noise_update":
+            new(kind)
+        elif kind == "noise_estimate":
+            new(kind, threshold=float(pick(THRESHOLDS)))
+        elif kind == "denoise_guided":
+            new(kind, params=dict(pick(GUIDED)))
+        elif kind == "select_mask":
+            new(kind, seed=int(rng.integers(0, 1000)), share=float(pick((0.0, 0.1, 0.3, 0.5, 1.0))))
+        elif kind == "select_noisy":
+            new(kind, threshold=float(pick(THRESHOLDS)), dilate=int(rng.integers(0, 4)))
+        elif kind == "sample_selected":
+            new(kind, n=int(pick((0, 1, 2)) if m.scene == "bunny" else pick((0, 1, 1, 2, 3))))
+        elif kind == "reproject":
+            reproject()
+        elif kind == "present":
+            new(kind, source=pick(("pixels", "denoised", "accum")), format=pick(("rgb8", "rgba8")), dither=bool(rng.random() < 0.5))
+
+    while len(g.ops) < n_ops:
+        if rng.random() < 0.5:
+            g.old_op()
+            continue
+        u = rng.random()
+        if u < 0.17:                                                        # one batch of the noise estimate
+            whole_frame()
+            sample(spp())
+            new("noise_update")
+        elif u < 0.26:                                                      # noise_estimate
+            whole_frame()
+            if clean() and rng.random() < 0.06:
+                new("noise_estimate", threshold=float(pick((-1.0, -0.02))))
+            else:
+                one("noise_estimate")
+        elif u < 0.35:                                                      # denoise_guided (+ the denoised frame presented)
+            whole_frame()
+            if clean() and rng.random() < 0.06:
+                new("denoise_guided", params=dict(pick(({"iterations": 9}, {"demodulate": 2}, {"sigma_color": 0.0}, {"variance_floor": -1.0}))))
+            else:
+                one("denoise_guided")
+                if rng.random() < 0.5:
+                    new("present", source="denoised", format=pick(("rgb8", "rgba8")), dither=bool(rng.random() < 0.5))
+        elif u < 0.42:                                                      # the estimator setting: plain state, valid in any state
+            e = pick(BAD_ESTIMATORS) if rng.random() < 0.15 else pick(ESTIMATORS)
+            new("set_noise_estimator", e=e)
+            if rng.random() < 0.5:
+                whole_frame()
+                one("noise_estimate")
+        elif u < 0.48:
+            whole_frame()
+            one("select_mask")
+        elif u < 0.58:                                                      # select_noisy, from moments of two batches mostly
+            whole_frame()
+            if clean() and rng.random() < 0.06:
+                new("select_noisy", threshold=float(pick(THRESHOLDS)), dilate=int(pick((-1, 4))))
+            else:
+                if "moments" not in m.exists and rng.random() < 0.7:
+                    for _ in range(2):
+                        sample(spp())
+                        new("noise_update")
+                one("select_noisy")
+        elif u < 0.70:                                                      # sample_selected
+            whole_frame()
+            if m.cfg.kernel_form != 0 and 0 in forms and rng.random() < 0.7:
+                cfg = m.cfg.copy(kernel_form=0)
+                add(Op("set_config", over=m.over(cfg)))
+                m.cfg = cfg
+            if not m.selected and clean() and rng.random() < 0.8:
+                one(pick(("select_mask", "select_noisy")))
+            if not m.state_reasons(Op("sample_selected", n=1)) and rng.random() < 0.04:
+                new("sample_selected", n=-1)
+            else:
+                one("sample_selected")
+                if rng.random() < 0.6:
+                    add(Op("observe", what=pick(("image", "all"))))
+        elif u < 0.82:                                                      # reproject, mostly with history to warp
+            whole_frame()
+            if m.dirty and rng.random() < 0.8:
+                add(Op("refresh"))
+                sample(spp())
+                if rng.random() < 0.5:
+                    new("noise_update")
+            if not m.state_reasons(Op("reproject")) and rng.random() < 0.05:
+                reproject(params=dict(pick(({"max_history": 0.0}, {"depth_tolerance": -0.1}, {"normal_cos": 1.5}, {"max_history": -2.0}))))
+            else:
+                ok = reproject().expect is None
+                if ok and rng.random() < 0.4:                               # the warped moments take the next batch
+                    sample(spp())
+                    new("noise_update")
+                    one("noise_estimate")
+                elif ok and rng.random() < 0.5:
+                    add(Op("observe", what="all"))
+        elif u < 0.90:                                                      # present; then nothing else has moved
+            one("present")
+            if rng.random() < 0.4:
+                add(Op("observe", what="all"))
+                add(Op("observe", what="post"))
+        elif u < 0.94:
+            add(Op("observe", what="post"))
+        elif u < 0.97:                                                      # every whole-frame call is refused with tiles of world > 1
+            add(Op("set_tiles", tiles=(int(pick((5, 7, 9, 13, 19))), int(pick((3, 7, 11))), int(rng.integers(0, 2)), 2)))
+            for i in rng.permutation(len(POST_KINDS))[:4]:
+                one(POST_KINDS[int(i)])                                     # ... except present
+            add(Op("set_tiles", tiles=(0, 0, 0, 1)))
+        else:                                                               # reproject after each of the four calls that end a history
+            whole_frame(1.0)
+            add(Op("refresh"))
+            who = pick(("set_config", "set_scene", "set_shape_data", "set_env"))
+            if who == "set_config":
+                cfg = m.cfg.copy(exposure=float(pick((0.7, 0.9, 1.1))))
+                add(Op("set_config", over=m.over(cfg)))
+                m.cfg = cfg
+            elif who == "set_scene":
+                add(Op("set_scene", name=m.scene))
+            elif who == "set_shape_data":
+                v = int(rng.integers(0, 2))
+                add(Op("set_shape_data", variant=v, n=625))
+                m.weights = v
+            else:
+                add(Op("set_env", w=16, h=8, seed=int(rng.integers(0, 3)), f32=False, exposure=1.0, gamma=2.2))
+                m.env = True
+            reproject()
     add(Op("post_process"))
     add(Op("observe", what="all"))
-    return Script(seed, base, scene0, ops, jit)
+    add(Op("observe", what="post"))
+    return Script(seed, g.base, g.scene0, g.ops, jit, post=True)
 
+
+def jit_post_script():
+    """the post script that runs through run-time compiled instances: jit = -1 over two scenes that no ahead-of-time specialisation
+    serves, both kernel forms (sample_selected promises the same bits whatever jit says; reproject changes the camera, which a
+    baked instance may carry)"""
+    return post_script(2020, n_ops=50, jit=-1, scenes=("mixed7", "mixed8"), forms=(0, 1))
 
 
 # ------------------------------------------------------------------ the lock-step driver
@@ -370,11 +597,18 @@ def observe(r, what):
     return out
 
 
+def _short(v):
+    return v if isinstance(v, (str, tuple, int)) else f"a {v.dtype} buffer of shape {v.shape}"
+
+
 def _first_diff(x, y):
-    if isinstance(x, tuple):
-        return None if x == y else f"{x} != {y}"
-    if x.shape != y.shape:
-        return f"shapes {x.shape} != {y.shape}"
+    if isinstance(x, (tuple, int, str)) or isinstance(y, (tuple, int, str)):
+        return None if type(x) is type(y) and x == y else f"{_short(x)} != {_short(y)}"
+    if x.shape != y.shape or x.dtype != y.dtype:
+        return f"{x.dtype} {x.shape} != {y.dtype} {y.shape}"
+    if x.dtype.itemsize != 4:
+        bad = x != y
+        return None if not bad.any() else f"{int(bad.sum())} of {bad.size} bytes differ, first at {[tuple(int(v) for v in p) for p in np.argwhere(bad)[:4]]}"
     bad = np.ascontiguousarray(x).view(np.uint32) != np.ascontiguousarray(y).view(np.uint32)
     if not bad.any():
         return None
@@ -471,11 +705,104 @@ def run(s, a, b, upto=None, features=True):
 
 
 def replay(s, upto=None, threads=0):
-    """rerun a script (or its first `upto` operations) on a fresh HIP renderer against a fresh oracle"""
+    """rerun a script (or its first `upto` operations) on a fresh HIP renderer against a fresh oracle (a post_script: against a
+    fresh post_model.PostModel)"""
     from raytracingpbr_amd import Renderer
+    if s.post:
+        import post_model as pm
+        a, b = new_renderer(s, Renderer), pm.PostModel(s, threads)
+        try:
+            return run_post(s, a, b, upto)
+        finally:
+            a.close()
+            b.close()
     a, b = new_renderer(s, Renderer), new_renderer(s, OracleRenderer, threads=threads)
     try:
         return run(s, a, b, upto)
     finally:
         a.close()
         b.close()
+
+
+# ------------------------------------------------------------------ the driver of post_script: HIP against tests/post_model.py
+def _apply_post(op, r):
+    """apply one operation to the HIP renderer; (code or None, {name: value} of what the call itself returned)"""
+    a, k = op.args, op.kind
+    try:
+        if k == "noise_update":
+            r.noise_update()
+        elif k == "noise_estimate":
+            st = r.noise_estimate(a["threshold"])
+            return None, {"stats": (st.pixels_estimated, st.pixels_above, int(np.float32(st.max_noise).view(np.uint32)))}
+        elif k == "denoise_guided":
+            r.denoise_guided(**a["params"])
+        elif k == "set_noise_estimator":
+            if a["e"] is None:
+                r.api.call("set_noise_estimator", r._ctx, None)
+            else:
+                r.set_noise_estimator(*a["e"])
+        elif k == "select_mask":
+            return None, {"n_selected": r.select_mask(mask(r.config.width, r.config.height, a["seed"], a["share"]))}
+        elif k == "select_noisy":
+            return None, {"n_selected": r.select_noisy(a["threshold"], a["dilate"])}
+        elif k == "sample_selected":
+            r.sample_selected(a["n"])
+        elif k == "reproject":
+            r.reproject(camera(a["name"], a["offset"], a["vfov"]), **a["params"])
+        elif k == "present":
+            r.present(a["source"], a["format"], a["dither"])
+        else:
+            res = _apply(op, r)
+            return (None if res is None else res[1]), {}
+    except RtpbrError as e:
+        return e.code, {}
+    return None, {}
+
+
+def _read_post(r, name):
+    """what the HIP renderer holds under an expected value's name; a buffer that does not exist reads as post_model.MISSING"""
+    import post_model as pm
+    if name.startswith("counters"):
+        c = r.counters()
+        return (c.samples, c.deposits) if name == "counters.samples_deposits" else tuple(getattr(c, k) for k in COUNTERS)
+    try:
+        return getattr(r, name)
+    except RtpbrError as e:
+        if e.code != ESTATE:
+            raise
+        return pm.MISSING
+
+
+def run_post(s, hip, model, upto=None):
+    """Apply a post_script to the HIP renderer `hip` and the PostModel `model` in lock step: every call must return the code the
+    script and the model expect, and everything the model expects of it — returned values and buffers — must be there bit for
+    bit.  `hip` None: the model alone (the code against the script's).  Raises Mismatch with a replayable report; returns the
+    list of (operation index, name, expected value)."""
+    seen, last_ok_of = [], {}
+    ops = s.ops if upto is None else s.ops[:upto]
+
+    def fail(i, what, key=None):
+        start = last_ok_of.get(key, -1)
+        lines = [f"post call sequence seed {s.seed}, operation #{i}: {what}", s.header(),
+                 f"operations since " + (f"{key} last matched" if key else "the start") + f" (#{start + 1}..#{i}):"]
+        lines += [f"  [{j}] {s.ops[j]!r}" for j in range(start + 1, i + 1)]
+        lines.append(f"replay: call_sequences.replay(call_sequences.post_script({s.seed}, ...), upto={i + 1})")
+        raise Mismatch("\n".join(lines))
+
+    for i, op in enumerate(ops):
+        want_code, want = model.apply(op)
+        if want_code != op.expect:
+            fail(i, f"{op.kind}: the model expects {want_code}, the script {op.expect}")
+        got = {}
+        if hip is not None:
+            code, got = _apply_post(op, hip)
+            if code != op.expect:
+                fail(i, f"{op.kind} returned {code}, expected {op.expect}")
+        for k, y in want.items():
+            if hip is not None:
+                d = _first_diff(got[k] if k in got else _read_post(hip, k), y)
+                if d is not None:
+                    fail(i, f"{k} differs from the model: {d}", k)
+            seen.append((i, k, y))
+            last_ok_of[k] = i
+    return seen

@@ -1,10 +1,12 @@
 """State changes between C-ABI calls, HIP against the CPU oracle (run with -m gpu): the random call sequences of
-tests/call_sequences.py in lock step, one sequence through the run-time compiled instances, and named regressions for what such
+tests/call_sequences.py in lock step, the post sequences (reproject, noise, selection, present) against the model of
+tests/post_model.py, one sequence of each kind through the run-time compiled instances, and named regressions for what such
 sequences found.  Frames are tiny and max_raytrace <= 4, so the oracle answers every observation in milliseconds."""
 import numpy as np
 import pytest
 
 import call_sequences as cs
+import post_model as pm
 from oracle_backend import OracleRenderer
 from raytracingpbr_amd import Renderer
 from raytracingpbr_amd.ibl import synthetic_env
@@ -47,6 +49,31 @@ def test_jit_call_sequence_matches_oracle(tmp_path, monkeypatch):
     finally:
         a.close()
         b.close()
+
+
+def _run_post(s):
+    a, b = cs.new_renderer(s, Renderer), pm.PostModel(s)
+    try:
+        return cs.run_post(s, a, b), a
+    finally:
+        a.close()
+        b.close()
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_post_sequence_matches_model(seed):
+    """~60 random operations, half of them those of the sequences above, half rtpbr_reproject, the noise calls, the estimator
+    setting, the select calls, rtpbr_sample_selected, rtpbr_present and reads of the buffers they own: every call refused or
+    accepted as include/rtpbr.h says, every value it returns or leaves behind bit for bit the model's"""
+    seen, _ = _run_post(cs.post_script(seed))
+    assert any(k == "image_buffer" for _, k, _ in seen) and any(k == "presented" or k == "moments" for _, k, _ in seen)
+
+
+def test_jit_post_sequence_matches_model(tmp_path, monkeypatch):
+    """the same through run-time compiled instances (jit = -1, 7 and 8 mixed shapes, both kernel forms)"""
+    monkeypatch.setenv("RTPBR_JIT_CACHE", str(tmp_path))
+    seen, _ = _run_post(cs.jit_post_script())
+    assert any(k == "motion" for _, k, _ in seen)
 
 
 def _counters(r):

@@ -1,10 +1,15 @@
 """The call-sequence generator of tests/call_sequences.py on the CPU alone: scripts are reproducible from their seed, every
 operation is legal where it is meant to be, the illegal ones are refused with the code the script expects, and two oracles of
-different thread counts driven in lock step observe the same bits throughout."""
+different thread counts driven in lock step observe the same bits throughout.  The post scripts (reproject, noise, selection,
+present) run on the model of tests/post_model.py alone: it is executable, deterministic and independent of the oracle's thread
+count, and the 24 committed seeds meet the coverage conditions."""
+import hashlib
+
 import numpy as np
 import pytest
 
 import call_sequences as cs
+import post_model as pm
 from oracle_backend import OracleRenderer
 from raytracingpbr_amd import Config, cornell_box
 from raytracingpbr_amd._capi import RtpbrError
@@ -104,3 +109,163 @@ def test_oracle_call_without_bounce_steps_changes_nothing(steps):
     b.sample(2)
     assert np.array_equal(a.image_buffer.view(np.uint32), b.image_buffer.view(np.uint32))
     assert np.array_equal(a.ray_buffer.view(np.uint32), b.ray_buffer.view(np.uint32))
+
+
+# ------------------------------------------------------------------ the post scripts on the model alone
+# sha256 over repr() of every operation of script(0..23) and of the JIT script, one per line, computed at the commit before
+# post_script existed (dced5ff): the old scripts draw what they drew.
+OLD_SCRIPTS_SHA256 = "e199981cde07179b809aa7b220afd0c7753f1efd5243eb1245396f51c893b6d4"
+POST_SEEDS = range(24)
+
+
+def test_the_old_scripts_are_unchanged():
+    h = hashlib.sha256()
+    for s in [cs.script(seed) for seed in range(24)] + [cs.script(1001, n_ops=50, jit=-1, scenes=("mixed7", "mixed8"), forms=(1,))]:
+        h.update(("\n".join(repr(o) for o in s.ops) + "\n").encode())
+    assert h.hexdigest() == OLD_SCRIPTS_SHA256
+
+
+def _model_run(s, threads):
+    m = pm.PostModel(s, threads)
+    try:
+        return cs.run_post(s, None, m), m.events
+    finally:
+        m.close()
+
+
+_runs = {}
+
+
+def _run(seed):
+    """(script, expected values, events) of a committed seed on a 1-thread model, computed once"""
+    if seed not in _runs:
+        s = cs.post_script(seed)
+        _runs[seed] = (s,) + _model_run(s, 1)
+    return _runs[seed]
+
+
+@pytest.mark.parametrize("seed", POST_SEEDS)
+def test_post_model_is_deterministic_across_thread_counts(seed):
+    """every expected output and every expected refusal of a post script is the same on a 1-thread and a 4-thread oracle, and
+    the script is reproducible from its seed"""
+    s, seen, events = _run(seed)
+    again = cs.post_script(seed)
+    assert [repr(o) for o in again.ops] == [repr(o) for o in s.ops] and bytes(again.base) == bytes(s.base)
+    seen4, events4 = _model_run(again, 4)
+    assert [(i, k) for i, k, _ in seen4] == [(i, k) for i, k, _ in seen] and events4 == events
+    for (i, k, x), (_, _, y) in zip(seen, seen4):
+        assert cs._first_diff(x, y) is None, (i, k)
+    assert {k for _, k, _ in seen} >= {"image_buffer", "counters"}
+
+
+def test_the_jit_post_script_runs_on_the_model():
+    """... and holds what it is there for: selected launches and reprojections that succeed, in both kernel forms"""
+    s = cs.jit_post_script()
+    seen, _ = _model_run(s, 2)
+    assert sum(o.kind == "sample_selected" and o.expect is None for o in s.ops) >= 2
+    assert sum(o.kind == "reproject" and o.expect is None for o in s.ops) >= 2
+    assert {s.base.kernel_form} | {o.args["over"].get("kernel_form", s.base.kernel_form) for o in s.ops if o.kind == "set_config"} == {0, 1}
+    assert s.jit == -1 and {o.args["name"] for o in s.ops if o.kind == "set_scene"} <= {"mixed7", "mixed8"} and seen
+
+
+def test_a_post_mismatch_report_names_seed_operation_and_replay():
+    """the report of a difference, on a script whose expectation is edited by hand: seed, operation index, the operations up to
+    it as replayable statements, and the replay call"""
+    s = cs.post_script(0, n_ops=30)
+    i = next(i for i, o in enumerate(s.ops) if o.kind in cs.POST_KINDS and o.expect is None)
+    s.ops[i].expect = cs.EINVAL
+    m = pm.PostModel(s, 1)
+    with pytest.raises(cs.Mismatch) as e:
+        cs.run_post(s, None, m)
+    m.close()
+    msg = str(e.value)
+    assert f"post call sequence seed 0, operation #{i}: {s.ops[i].kind}" in msg and "BASE = Config.from_buffer_copy" in msg
+    assert f"replay: call_sequences.replay(call_sequences.post_script(0, ...), upto={i + 1})" in msg and f"[{i}] r." in msg
+
+
+def _wanted_refusals():
+    """every refusal reason of the sentences of include/rtpbr.h, as (operation, reason)"""
+    want = {("reproject", f"dirty:{d}") for d in pm.DIRTY_BY} | {("present", "no_denoised")}
+    want |= {("sample_selected", w) for w in ("persistent", "no_selection", "tiles")}
+    want |= {(k, "tiles") for k in ("reproject", "noise_update", "noise_estimate", "denoise_guided", "select_mask", "select_noisy")}
+    return want | {(k, "argument") for k in ("set_noise_estimator", "noise_estimate", "denoise_guided", "select_noisy", "sample_selected", "reproject")}
+
+
+def _coverage():
+    """{condition: (figure, minimum)} over the 24 committed seeds; figures count scripts unless the name says otherwise"""
+    scripts = [_run(seed) for seed in POST_SEEDS]
+    new = [o for s, _, _ in scripts for o in s.ops if o.kind in cs.POST_KINDS]
+    refused = [o for o in new if o.expect is not None]
+
+    def count(pred):
+        return sum(1 for s, _, ev in scripts if pred(s, ev))
+
+    def rep(ev):                # (kind, kept any, lost any, cap applied, with moments)
+        return [e for e in ev if e[0] == "reproject"]
+
+    out = {f"{kind} succeeds": (count(lambda s, ev: any(o.kind == kind and o.expect is None for o in s.ops)), 8) for kind in cs.POST_KINDS}
+    out["observe post"] = (count(lambda s, ev: any(o.kind == "observe" and o.args["what"] == "post" for o in s.ops)), 8)
+    reasons = {(o.kind, w) for o in refused for w in o.why}
+    out["refusal reasons missing: " + repr(sorted(_wanted_refusals() - reasons))] = (-len(_wanted_refusals() - reasons), 0)
+    # ... one cause at a time for the reproject rule, and present is the call that tiles do not refuse
+    alone = {o.why for o in refused if o.kind == "reproject"}
+    out["reproject refused for each single cause (causes)"] = (sum((f"dirty:{d}",) in alone for d in pm.DIRTY_BY), 4)
+    out["present succeeds with tiles of world > 1 (operations)"] = (sum(o.kind == "present" and o.expect is None and _tiled(s, i) for s, _, _ in scripts
+                                                                      for i, o in enumerate(s.ops)), 1)
+    out["new operations that succeed per refusal (x 3 at least)"] = (len(new) - len(refused), 3 * len(refused))
+    sizes = {(s.base.width, s.base.height) for s, _, _ in scripts}
+    sizes |= {_size_after(s, o) for s, _, _ in scripts for o in s.ops if o.kind == "set_config" and o.expect is None}
+    out["frame sizes"] = (len(sizes & set(cs.POST_SIZES)), len(cs.POST_SIZES))
+    out["reproject keeps some pixels and loses some"] = (count(lambda s, ev: any(e[1] and e[2] for e in rep(ev))), 6)
+    out["reproject applies the max_history cap"] = (count(lambda s, ev: any(e[3] for e in rep(ev))), 3)
+    out["reproject with moments, then noise_update + noise_estimate"] = (count(_reproject_then_batch_and_estimate), 3)
+    out["pooling changes a noise value"] = (count(lambda s, ev: ("pooling_changed_noise",) in ev), 4)
+    out["select_noisy selects a part"] = (count(lambda s, ev: any(e[0] == "select_noisy" and 0 < e[1] < e[2] for e in ev)), 6)
+    out["sample_selected on a partial selection"] = (count(lambda s, ev: any(e[0] == "sample_selected" and 0 < e[1] < e[2] and e[3] > 0 for e in ev)), 6)
+    out["present(denoised) after a guided denoise"] = (count(lambda s, ev: ("present_denoised_after_guided",) in ev), 4)
+    out["new resolution with moments, selection and presented frame"] = (count(lambda s, ev: ("new_resolution_with_moments_selection_presented",) in ev), 4)
+    return out
+
+
+def test_the_post_grammar_meets_its_coverage_conditions():
+    """Conditions over the 24 committed seeds; the generator's weights were tuned until the model run met them."""
+    cov = _coverage()
+    print("\n".join(f"{v:4d} >= {lo:3d}  {k}" for k, (v, lo) in cov.items()))
+    assert not [k for k, (v, lo) in cov.items() if v < lo], {k: v for k, v in cov.items() if v[0] < v[1]}
+
+
+def _tiled(s, i):
+    """tiles of world > 1 are set when operation i runs"""
+    tiles = [o.args["tiles"] for o in s.ops[:i] if o.kind == "set_tiles" and o.expect is None]
+    return bool(tiles) and tiles[-1][3] > 1
+
+
+def _reproject_then_batch_and_estimate(s, ev):
+    """a reproject that ran with moments present, followed by noise_update and noise_estimate before the next refresh, reproject
+    or new resolution"""
+    with_moments = iter([e[4] for e in ev if e[0] == "reproject"])
+    ops = [o for o in s.ops if o.expect is None]
+    for i, o in enumerate(ops):
+        if o.kind == "reproject" and next(with_moments):
+            tail = []
+            for q in ops[i + 1:]:
+                if q.kind in ("refresh", "reproject") or (q.kind == "set_config" and _size_after(s, q) != _size_before(s, q)):
+                    break
+                tail.append(q.kind)
+            if "noise_update" in tail and "noise_estimate" in tail[tail.index("noise_update"):]:
+                return True
+    return False
+
+
+def _size_after(s, op):
+    return op.args["over"].get("width", s.base.width), op.args["over"].get("height", s.base.height)
+
+
+def _size_before(s, op):
+    size = s.base.width, s.base.height
+    for o in s.ops:
+        if o is op:
+            return size
+        if o.kind == "set_config" and o.expect is None:
+            size = _size_after(s, o)
+    return size

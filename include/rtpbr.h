@@ -221,7 +221,7 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_FEAT_DEPTH   = 7,   /* (W,H)   f32 length(hit - ray origin), cfg.max_dis on a miss                 */
        RTPBR_BUF_FEAT_OBJECT  = 8,   /* (W,H)   i32 index of the hit object in the set_scene array, -1 on a miss    */
        RTPBR_BUF_DENOISED_PIXELS = 9, /* (W,H,3) f32 denoised display colour                                       */
-       /* written by rtpbr_reproject: allocated on its first call, RTPBR_ESTATE before; output only */
+       /* written by rtpbr_reproject / rtpbr_reproject_scene: allocated on the first such call, RTPBR_ESTATE before; output only */
        RTPBR_BUF_MOTION       = 10,  /* (W,H,2) f32 old-frame pixel coordinates each pixel drew its history from,
                                       *           (-1,-1) = no history (rtpbr_reproject)                           */
        /* noise estimation (rtpbr_noise_update / rtpbr_noise_estimate): allocated on first use, RTPBR_ESTATE before;
@@ -385,7 +385,8 @@ int rtpbr_denoise(rtpbr_ctx* ctx, const rtpbr_denoise_params* p);
  * Known bias.  History is reused as if radiance did not depend on the view: on glossy and refractive surfaces the history
  * shows the old view's reflections until new samples outweigh it.  A thin-lens camera's history was rendered with defocus
  * but is reprojected through the lens centre.  max_history bounds both: the history never weighs more than max_history
- * samples.  Moving objects, an animated frame and tiles of world > 1 are out of scope (see the errors).
+ * samples.  Objects that moved rigidly: rtpbr_reproject_scene below.  An animated frame, changes of shape or material and
+ * tiles of world > 1 are out of scope (see the errors).
  *
  * Errors: RTPBR_EINVAL for a NULL context or camera and for bad parameters (max_history not finite and > 0,
  * depth_tolerance not finite and >= 0, normal_cos not within -1..1); RTPBR_ESTATE before set_config / set_scene /
@@ -406,6 +407,62 @@ typedef struct rtpbr_reproject_params {   /* 4-byte members, no padding */
 #define RTPBR_REPROJECT_DEFAULT_DEPTH_TOLERANCE 0.2f
 #define RTPBR_REPROJECT_DEFAULT_NORMAL_COS      -1.0f
 int rtpbr_reproject(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtpbr_reproject_params* p);
+
+/* ---- Temporal reuse across rigid object motion.
+ *
+ * rtpbr_reproject_scene(ctx, new_cam, new_objects, n, scale10, p) replaces rtpbr_set_scene(new_objects, n, scale10) + an
+ * optional rtpbr_set_camera(new_cam) + rtpbr_refresh() for a host whose objects moved rigidly (translated and / or rotated) and
+ * that wants to keep history.  new_cam == NULL: the camera stays.  p == NULL: rtpbr_reproject's defaults.
+ *
+ * Only rigid motion is accepted.  The check is made on the table as rtpbr_set_scene would store it (after scale10 has
+ * multiplied position and scale by ten): n must equal the current object count, and for every i the type, the three scale
+ * words and the ten material words must equal the current table's bit for bit.  Anything else: RTPBR_EINVAL, "not a rigid
+ * motion: use rtpbr_set_scene + rtpbr_refresh".
+ * Object k is MOVED when any of its 3 position words or 9 matrix words differs bitwise between the old and the new stored
+ * table (the matrix as rtpbr_set_scene computes it from `rotation`: a turn of 360 degrees that yields the same matrix is no
+ * move, whatever the rotation words say).
+ *
+ * In order — steps 1-4 and 6-8 are those of rtpbr_reproject:
+ *   1. flushes lazy shading and orders itself behind asynchronous read-backs, as rtpbr_reproject does;
+ *   2. renders the features of the current (old) scene and camera if they are stale;
+ *   3-4. keeps the old camera frame and the old stored position and matrix of every object, and copies image_buffer, the
+ *      (normal, depth) records and the object indices into the internal history buffers;
+ *   5. applies new_objects exactly as rtpbr_set_scene does (matrices, rotation signature, scene kind, upload; the host waits
+ *      for the stream there, as in rtpbr_set_scene), then new_cam exactly as rtpbr_set_camera does if it is not NULL;
+ *   6. renders the features of the new scene and camera into RTPBR_BUF_FEAT_*;
+ *   7. gathers the history into image_buffer and writes RTPBR_BUF_MOTION (below);
+ *   8. resets what rtpbr_reproject resets: ray_buffer.depth = 0 and, with adaptive sampling, the diff buffers; with moments
+ *      (rtpbr_noise_update) they are warped with the image and the snapshot becomes the warped image_buffer.
+ * The call ends with valid history and valid features; sample_base and the work counters are untouched.
+ *
+ * The gather is rtpbr_reproject's, operation for operation (dot, fma3, length, the projection, the snap, the four taps, the
+ * acceptance tests, the weights, the max_history cap, the moments rule), except for D and the normal compared on a hit
+ * (obj_new = k >= 0) on a MOVED object.  R = the row-major world-to-local matrix, p = the position, 0 = old, 1 = new:
+ *   X1 = fma3(z_new, d, lf1);  a = X1 - p1 (per component);
+ *   l = (dot(R1 row 0, a), dot(R1 row 1, a), dot(R1 row 2, a))                      (the hit in the object's frame)
+ *   X0.c = dot((R0[0][c], R0[1][c], R0[2][c]), l) + p0.c  for c = x, y, z           (where that point was in the old world)
+ *   D = X0 - lf0;  L = length(D) enters the depth test as before;
+ *   the normal of the normal_cos test: with cfg.normal_space == RTPBR_NORMAL_WORLD, m = (dot(R1 row r, n_new)) for r = 0..2,
+ *     n' = (dot(R0 column c, m)) for c = 0..2, and the test is dot(n_old, n') >= normal_cos; with RTPBR_NORMAL_LOCAL the
+ *     stored normals are in the object's frame already and n_new is compared as it is.
+ * A hit on an object that did not move: D = fma3(z_new, d, lf1) - lf0 and n_new; a miss: D = d — rtpbr_reproject's
+ * expressions, so with no moved object the call writes exactly what rtpbr_reproject(new_cam) writes (image_buffer,
+ * RTPBR_BUF_MOTION, the moments, the snapshot).  RTPBR_BUF_MOTION now carries object motion too: a pixel on a moved object
+ * under a still camera reports where that surface point was in the old frame.
+ *
+ * Known bias, beyond rtpbr_reproject's.  The history of EVERY pixel, on a moved object or not, was lit by the old scene: it
+ * carries the old frame's shadows and interreflections of the moved objects (the shadow a box left behind fades, the one
+ * where it went builds up), and a moved object's own history carries the light of where it was.  No test detects this;
+ * max_history is the only bound, so use a smaller value than for camera moves (DESIGN.md section 6h has the measured
+ * numbers, examples/reproject_moving.py --sweep reproduces them).
+ *
+ * Errors, every one before anything changes: all RTPBR_EINVAL and RTPBR_ESTATE cases of rtpbr_reproject (a NULL new_cam is
+ * valid here), RTPBR_EINVAL also for NULL new_objects and for a table that fails the rigidity check; RTPBR_ESTATE when the
+ * history is not valid — this call does not repair history an earlier rtpbr_set_scene (or set_config, a changed cfg.frame
+ * included, set_shape_data, set_env) broke — and with tiles of world > 1.  Changes of shape, scale or material and the
+ * bunny's animation frame stay out of scope: rtpbr_set_scene / rtpbr_set_config + rtpbr_refresh. */
+int rtpbr_reproject_scene(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtpbr_object* new_objects, int n, int scale10,
+                          const rtpbr_reproject_params* p);
 
 /* ---- Per-pixel noise estimation and a variance-guided a-trous (the spatial half of SVGF, Schied et al. 2017).
  *

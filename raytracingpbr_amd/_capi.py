@@ -27,11 +27,11 @@ ENTRY_POINTS = [
     "get_counters", "get_counter", "last_sample_ms", "last_primary_ms", "get_stream", "set_option", "set_shape_data",
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
     "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
-    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present",
+    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
 ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
-                   "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present")
+                   "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene")
 
 
 class RtpbrError(RuntimeError):
@@ -92,6 +92,7 @@ class CApi:
             "render_features": (C.c_int, [p]),
             "denoise": (C.c_int, [p, C.POINTER(DenoiseParams)]),
             "reproject": (C.c_int, [p, C.POINTER(Camera), C.POINTER(ReprojectParams)]),
+            "reproject_scene": (C.c_int, [p, C.POINTER(Camera), p, C.c_int, C.c_int, C.POINTER(ReprojectParams)]),
             "noise_update": (C.c_int, [p]),
             "noise_estimate": (C.c_int, [p, C.c_float, C.POINTER(NoiseStats)]),
             "denoise_guided": (C.c_int, [p, C.POINTER(DenoiseGuidedParams)]),

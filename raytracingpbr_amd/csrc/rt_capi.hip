@@ -117,6 +117,8 @@ static void free_features(rtpbr_ctx* c) {
     (void)hipFree(c->hist_guides);
     (void)hipFree(c->hist_object);
     (void)hipFree(c->motion);
+    (void)hipFree(c->scene_motion);
+    c->scene_motion = nullptr;
     c->feat_albedo = c->feat_normal = c->feat_depth = c->denoised = nullptr;
     c->feat_object = c->hist_object = nullptr;
     c->feat_guides = c->denoise_scratch = c->hist_image = c->hist_guides = nullptr;
@@ -377,6 +379,20 @@ static void pack_table(const ObjM* src, int n, uint32_t sig, ObjM* dst_table) {
     }
 }
 
+// An object as rtpbr_set_scene stores it: position and scale times ten if asked, the world->local matrix from `rotation`
+static rtpbr_object stored_object(const rtpbr_object& in, int scale10) {
+    rtpbr_object o = in;
+    rtpbr_transform& t = o.transform;
+    if (scale10)
+        for (int k = 0; k < 3; k++) {
+            t.position[k] *= 10.0f;
+            t.scale[k] *= 10.0f;
+        }
+    float rad[3] = {t.rotation[0] * DEG2RAD, t.rotation[1] * DEG2RAD, t.rotation[2] * DEG2RAD};
+    rotate(rad, t.matrix);
+    return o;
+}
+
 extern "C" int rtpbr_set_scene(rtpbr_ctx* c, const rtpbr_object* objs, int n, int scale10) {
     if (!c || !objs) return fail(RTPBR_EINVAL, "null argument");
     if (n <= 0 || n > MAX_OBJ) return fail(RTPBR_EINVAL, "object count must be 1..32");
@@ -390,15 +406,8 @@ extern "C" int rtpbr_set_scene(rtpbr_ctx* c, const rtpbr_object* objs, int n, in
     memset(full, 0, sizeof full);
     bool all_box = true, all_bunny = true, any_bunny = false;
     for (int i = 0; i < n; i++) {
-        c->obj[i] = objs[i];
-        rtpbr_transform& t = c->obj[i].transform;
-        if (scale10)
-            for (int k = 0; k < 3; k++) {
-                t.position[k] *= 10.0f;
-                t.scale[k] *= 10.0f;
-            }
-        float rad[3] = {t.rotation[0] * DEG2RAD, t.rotation[1] * DEG2RAD, t.rotation[2] * DEG2RAD};
-        rotate(rad, t.matrix);
+        c->obj[i] = stored_object(objs[i], scale10);
+        const rtpbr_transform& t = c->obj[i].transform;
         ObjM& m = c->objm[i];
         m.px = t.position[0]; m.py = t.position[1]; m.pz = t.position[2];
         memcpy(m.m, t.matrix, sizeof m.m);
@@ -1524,9 +1533,8 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
 // ---- temporal reuse (rt_reproject.hip): rtpbr_set_camera + rtpbr_refresh that keeps what the new view can reuse
 enum : unsigned { W_MOTION = 1u << RTPBR_BUF_MOTION };
 
-extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_reproject_params* p) {
-    if (!c || !cam) return fail(RTPBR_EINVAL, "null argument");
-    rtpbr_reproject_params d;
+// p == NULL: the defaults; RTPBR_EINVAL for a parameter out of range
+static int reproject_params(const rtpbr_reproject_params* p, rtpbr_reproject_params& d) {
     if (p) {
         d = *p;
     } else {
@@ -1537,24 +1545,37 @@ extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpb
     if (!(d.max_history > 0.0f) || !std::isfinite(d.max_history)) return fail(RTPBR_EINVAL, "reproject max_history must be finite and > 0");
     if (!(d.depth_tolerance >= 0.0f) || !std::isfinite(d.depth_tolerance)) return fail(RTPBR_EINVAL, "reproject depth_tolerance must be finite and >= 0");
     if (!(d.normal_cos >= -1.0f && d.normal_cos <= 1.0f)) return fail(RTPBR_EINVAL, "reproject normal_cos must be within -1..1");
-    // every refusal before anything changes
+    return RTPBR_OK;
+}
+
+// the states rtpbr_reproject and rtpbr_reproject_scene refuse (`who`: the call's name)
+static int reproject_state(rtpbr_ctx* c, const char* who) {
     if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
-    if (c->world > 1) return fail(RTPBR_ESTATE, "rtpbr_reproject works on the whole frame: not with tiles of world > 1");
+    if (c->world > 1) return fail(RTPBR_ESTATE, "%s works on the whole frame: not with tiles of world > 1", who);
     for (int i = 0; i < c->n_obj; i++)
         if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
     if (!c->history_ok)
-        return fail(RTPBR_ESTATE, "rtpbr_reproject: set_config / set_scene / set_shape_data / set_env ran since the last refresh or reproject: "
-                                  "image_buffer is no history of this scene (call rtpbr_refresh)");
+        return fail(RTPBR_ESTATE, "%s: set_config / set_scene / set_shape_data / set_env ran since the last refresh or reproject: "
+                                  "image_buffer is no history of this scene (call rtpbr_refresh)", who);
+    return RTPBR_OK;
+}
+
+// Steps 1..8 of rtpbr_reproject (include/rtpbr.h) after every refusal has been ruled out.  objs != nullptr (rtpbr_reproject_scene):
+// step 5 applies the new object table first, `table` (host, n * SCENE_MOTION_WORDS floats) is what the scene kernel reads and
+// cam may be nullptr (the camera stays).
+static int reproject_run(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_reproject_params& d, const rtpbr_object* objs = nullptr, int n_objs = 0,
+                         int scale10 = 0, const float* table = nullptr) {
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
     if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | W_DIFF_PIXELS)) return r;
     if (!c->feat_valid)
-        if (int r = rtpbr_render_features(c)) return r;      // the features of the old camera
+        if (int r = rtpbr_render_features(c)) return r;      // the features of the old camera (and the old scene)
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     if (!c->hist_image) HIP_TRY(hipMalloc(&c->hist_image, n * sizeof(float4)));
     if (!c->hist_guides) HIP_TRY(hipMalloc(&c->hist_guides, n * sizeof(float4)));
     if (!c->hist_object) HIP_TRY(hipMalloc(&c->hist_object, n * sizeof(int32_t)));
     if (!c->motion) HIP_TRY(hipMalloc(&c->motion, n * sizeof(float2)));
+    if (objs && !c->scene_motion) HIP_TRY(hipMalloc(&c->scene_motion, sizeof(float) * MAX_OBJ * SCENE_MOTION_WORDS));
     if (c->noise_moments) {      // the moments move with the image
         if (!c->hist_moments) HIP_TRY(hipMalloc(&c->hist_moments, n * sizeof(float4)));
         if (int r = rt_order_after_reads(c, 1u << RTPBR_BUF_MOMENTS)) return r;
@@ -1565,7 +1586,13 @@ extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpb
     HIP_TRY(hipMemcpyAsync(c->hist_image, c->image_buffer, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->hist_guides, c->feat_guides, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->hist_object, c->feat_object, n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-    if (int r = rtpbr_set_camera(c, cam)) return r;
+    if (objs) {
+        // (rtpbr_set_scene synchronises the stream after its own upload: the caller's `table` has been read by then)
+        HIP_TRY(hipMemcpyAsync(c->scene_motion, table, sizeof(float) * (size_t)n_objs * SCENE_MOTION_WORDS, hipMemcpyHostToDevice, c->stream));
+        if (int r = rtpbr_set_scene(c, objs, n_objs, scale10)) return r;
+    }
+    if (cam)
+        if (int r = rtpbr_set_camera(c, cam)) return r;
     if (int r = rtpbr_render_features(c)) return r;          // the features of the new camera (feat_valid from here on)
     if (int r = rt_order_after_reads(c, W_MOTION)) return r;
     ReprojArgs A;
@@ -1590,13 +1617,52 @@ extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpb
     A.height = c->cfg.height;
     A.pinhole = c->cfg.camera_kind == RTPBR_CAMERA_PINHOLE;
     A.adaptive = c->cfg.adaptive_sampling;
+    A.normal_local = c->cfg.normal_space == RTPBR_NORMAL_LOCAL;
     A.hist_moments = c->noise_moments ? c->hist_moments : nullptr;
     A.moments = c->noise_moments;
     A.snapshot = c->noise_snapshot;
-    launch_reproject(A, c->stream);
+    if (objs) launch_reproject_scene(A, c->scene_motion, n_objs, c->stream);
+    else launch_reproject(A, c->stream);
     HIP_TRY(hipGetLastError());
     c->history_ok = true;
     return RTPBR_OK;
+}
+
+extern "C" int rtpbr_reproject(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_reproject_params* p) {
+    if (!c || !cam) return fail(RTPBR_EINVAL, "null argument");
+    rtpbr_reproject_params d;
+    if (int r = reproject_params(p, d)) return r;
+    // every refusal before anything changes
+    if (int r = reproject_state(c, "rtpbr_reproject")) return r;
+    return reproject_run(c, cam, d);
+}
+
+// rtpbr_reproject for a scene whose objects moved rigidly (include/rtpbr.h): the new table must be the current one up to
+// positions and rotations; the old and new positions and matrices go to the scene kernel (rt_reproject.hip).
+extern "C" int rtpbr_reproject_scene(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_object* objs, int n, int scale10,
+                                     const rtpbr_reproject_params* p) {
+    if (!c || !objs) return fail(RTPBR_EINVAL, "null argument");
+    rtpbr_reproject_params d;
+    if (int r = reproject_params(p, d)) return r;
+    if (int r = reproject_state(c, "rtpbr_reproject_scene")) return r;
+    static const char* const NOT_RIGID = "not a rigid motion: use rtpbr_set_scene + rtpbr_refresh";
+    if (n != c->n_obj) return fail(RTPBR_EINVAL, NOT_RIGID);
+    float table[MAX_OBJ * SCENE_MOTION_WORDS];
+    for (int i = 0; i < n; i++) {
+        const rtpbr_object& o0 = c->obj[i];
+        const rtpbr_object o1 = stored_object(objs[i], scale10);
+        const rtpbr_transform &t0 = o0.transform, &t1 = o1.transform;
+        if (o1.type != o0.type || memcmp(t1.scale, t0.scale, sizeof t0.scale) || memcmp(&o1.material, &o0.material, sizeof o0.material))
+            return fail(RTPBR_EINVAL, NOT_RIGID);
+        float* t = table + i * SCENE_MOTION_WORDS;
+        const bool moved = memcmp(t1.position, t0.position, sizeof t0.position) || memcmp(t1.matrix, t0.matrix, sizeof t0.matrix);
+        t[0] = moved ? 1.0f : 0.0f;
+        memcpy(t + 1, t0.position, 12);
+        memcpy(t + 4, t1.position, 12);
+        memcpy(t + 7, t0.matrix, 36);
+        memcpy(t + 16, t1.matrix, 36);
+    }
+    return reproject_run(c, cam, d, objs, n, scale10, table);
 }
 
 // ---- noise estimation and the variance-guided a-trous (rt_noise.hip)

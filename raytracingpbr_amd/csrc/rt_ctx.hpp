@@ -191,6 +191,7 @@ struct rtpbr_ctx {
     float4* hist_guides = nullptr;     // (W,H): the old camera's (normal, depth) records
     int32_t* hist_object = nullptr;    // (W,H): the old camera's object indices
     float2* motion = nullptr;          // (W,H): RTPBR_BUF_MOTION
+    float* scene_motion = nullptr;     // rtpbr_reproject_scene's per-object table on the device (MAX_OBJ x 25 words, rt_reproject.hpp)
     bool history_ok = false;           // no set_config / set_scene / set_shape_data / set_env since the last refresh or reproject
     // noise estimation and the guided filter (rt_noise.hip): allocated on first use, freed with the context or a new resolution
     float4* noise_moments = nullptr;   // (W,H): RTPBR_BUF_MOMENTS

@@ -1,4 +1,4 @@
-// rt_reproject.hip — the gather kernel of rtpbr_reproject (see rt_reproject.hpp; the arithmetic is fixed in include/rtpbr.h).
+// rt_reproject.hip — the gather kernels of rtpbr_reproject and rtpbr_reproject_scene (see rt_reproject.hpp; the arithmetic is fixed in include/rtpbr.h).
 #include <hip/hip_runtime.h>
 
 #include "rt_reproject.hpp"
@@ -20,22 +20,10 @@ RT_D void snap_axis(float p, int& x0, float& fx) {
     }
 }
 
-// One lane per pixel, i = x * H + y: lanes of a wave walk down a column, so the new features are read and the outputs written
-// contiguously; the four taps of neighbouring lanes share old pixels (the history is read where the motion takes it, through
-// the caches: for a small move a wave's taps cover about two columns' worth of old pixels).  A tap loads the 4-byte old object
-// first, then the 16-byte history texel, then (hits only) the 16-byte (normal, depth) record.
-// MOMENTS: the luminance moments of the noise estimate (rt_noise.hpp) ride along — the same accepted taps and weights, 16 more
-// bytes per accepted tap; the image's arithmetic is untouched.
-template <bool MOMENTS>
-__global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
+// The new pixel's centre ray, as feature_rays forms it
+RT_D vec3 centre_ray(const ReprojArgs& A, int x, int y) {
     const int H = A.height, W = A.width;
-    const uint32_t n = (uint32_t)W * (uint32_t)H;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
-    const CamFrame& f0 = A.cam0;
     const CamFrame& f1 = A.cam1;
-    // the new pixel's centre ray, as feature_rays forms it
     float u, v;
     if (A.pinhole) {
         u = ((float)x + 0.5f) / (float)W;
@@ -44,17 +32,18 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
         u = ((float)x + 0.5f) * f1.inv_w;
         v = ((float)y + 0.5f) * f1.inv_h;
     }
-    const vec3 lf1 = v3f(f1.lf), lf0 = v3f(f0.lf);
-    const vec3 d = normalize(fma3(v, v3f(f1.ver), fma3(u, v3f(f1.hor), v3f(f1.llc))) - lf1);
-    const int obj = A.new_object[i];
+    return normalize(fma3(v, v3f(f1.ver), fma3(u, v3f(f1.hor), v3f(f1.llc))) - v3f(f1.lf));
+}
+
+// The gather of pixel i from D (the first hit as the old eye sees it; on a miss the direction) and nn (the normal the old
+// normals are compared with), and everything the pixel's lane writes: shared by reproject_gather and reproject_gather_scene.
+// A tap loads the 4-byte old object first, then the 16-byte history texel, then (hits only) the 16-byte (normal, depth) record.
+template <bool MOMENTS>
+RT_D void gather_taps(const ReprojArgs& A, uint32_t i, int obj, vec3 D, vec3 nn) {
+    const int H = A.height, W = A.width;
+    const CamFrame& f0 = A.cam0;
     const bool hit = obj >= 0;
-    vec3 D = d;                                   // a miss: the direction, a point at infinity
-    vec3 nn = mk(0.0f, 0.0f, 0.0f);
-    if (hit) {
-        const float4 nz = A.new_nz[i];
-        D = fma3(nz.w, d, lf1) - lf0;             // the first hit as the old eye sees it
-        nn = mk(nz.x, nz.y, nz.z);
-    }
+    const vec3 lf0 = v3f(f0.lf);
     // into the old image plane: the ray lf0 + s D meets the plane of llc0 / hor0 / ver0
     const vec3 hor0 = v3f(f0.hor), ver0 = v3f(f0.ver);
     const vec3 q = v3f(f0.llc) - lf0;
@@ -134,10 +123,86 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
     }
 }
 
+// One lane per pixel, i = x * H + y: lanes of a wave walk down a column, so the new features are read and the outputs written
+// contiguously; the four taps of neighbouring lanes share old pixels (the history is read where the motion takes it, through
+// the caches: for a small move a wave's taps cover about two columns' worth of old pixels).
+// MOMENTS: the luminance moments of the noise estimate (rt_noise.hpp) ride along — the same accepted taps and weights, 16 more
+// bytes per accepted tap; the image's arithmetic is untouched.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
+    const int H = A.height, W = A.width;
+    const uint32_t n = (uint32_t)W * (uint32_t)H;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
+    const vec3 d = centre_ray(A, x, y);
+    const int obj = A.new_object[i];
+    vec3 D = d;                                   // a miss: the direction, a point at infinity
+    vec3 nn = mk(0.0f, 0.0f, 0.0f);
+    if (obj >= 0) {
+        const float4 nz = A.new_nz[i];
+        D = fma3(nz.w, d, v3f(A.cam1.lf)) - v3f(A.cam0.lf);             // the first hit as the old eye sees it
+        nn = mk(nz.x, nz.y, nz.z);
+    }
+    gather_taps<MOMENTS>(A, i, obj, D, nn);
+}
+
+// reproject_gather with objects that moved rigidly between the old and the new frame (rtpbr_reproject_scene).  `table`: per
+// object SCENE_MOTION_WORDS words — the moved flag (as a float: 0 or 1), p0, p1, R0, R1 (positions and row-major world-to-local
+// matrices, 0 = old, 1 = new) — staged into LDS by the whole block: the lanes of a wave hit different objects, and a divergent
+// LDS read costs a few cycles where a divergent global read costs a cache line per object.  Every thread of the block takes
+// part in the staging and reaches the barrier, whether it owns a pixel or not (the last block of a frame, or a frame with
+// fewer pixels than table words).  A hit on an object that did not move, and a miss, take reproject_gather's expressions.
+template <bool MOMENTS>
+__global__ void __launch_bounds__(256) reproject_gather_scene(const ReprojArgs A, const float* __restrict__ table, const int n_obj) {
+    __shared__ float T[MAX_OBJ * SCENE_MOTION_WORDS];
+    const int words = (n_obj < MAX_OBJ ? n_obj : MAX_OBJ) * SCENE_MOTION_WORDS;
+    for (int k = (int)threadIdx.x; k < words; k += (int)blockDim.x) T[k] = table[k];
+    __syncthreads();
+    const int H = A.height, W = A.width;
+    const uint32_t n = (uint32_t)W * (uint32_t)H;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
+    const vec3 d = centre_ray(A, x, y);
+    const int obj = A.new_object[i];
+    vec3 D = d;
+    vec3 nn = mk(0.0f, 0.0f, 0.0f);
+    if (obj >= 0) {
+        const float4 nz = A.new_nz[i];
+        const vec3 X1 = fma3(nz.w, d, v3f(A.cam1.lf));
+        nn = mk(nz.x, nz.y, nz.z);
+        const float* t = T + (obj < n_obj ? obj : 0) * SCENE_MOTION_WORDS;      // (the features never name an object past the table)
+        if (obj < n_obj && t[0] != 0.0f) {
+            const vec3 p0 = mk(t[1], t[2], t[3]), p1 = mk(t[4], t[5], t[6]);
+            const float* R0 = t + 7;
+            const float* R1 = t + 16;
+            // world (new) -> the object's frame -> world (old): X0 = R0^T (R1 (X1 - p1)) + p0
+            const vec3 a = X1 - p1;
+            const vec3 l = mk(dot(mk(R1[0], R1[1], R1[2]), a), dot(mk(R1[3], R1[4], R1[5]), a), dot(mk(R1[6], R1[7], R1[8]), a));
+            const vec3 X0 = mk(dot(mk(R0[0], R0[3], R0[6]), l) + p0.x, dot(mk(R0[1], R0[4], R0[7]), l) + p0.y, dot(mk(R0[2], R0[5], R0[8]), l) + p0.z);
+            D = X0 - v3f(A.cam0.lf);
+            if (!A.normal_local) {      // world-space normals turn with the object; local-frame normals are the object's own
+                const vec3 m = mk(dot(mk(R1[0], R1[1], R1[2]), nn), dot(mk(R1[3], R1[4], R1[5]), nn), dot(mk(R1[6], R1[7], R1[8]), nn));
+                nn = mk(dot(mk(R0[0], R0[3], R0[6]), m), dot(mk(R0[1], R0[4], R0[7]), m), dot(mk(R0[2], R0[5], R0[8]), m));
+            }
+        } else {
+            D = X1 - v3f(A.cam0.lf);
+        }
+    }
+    gather_taps<MOMENTS>(A, i, obj, D, nn);
+}
+
 void launch_reproject(const ReprojArgs& A, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
     if (A.hist_moments) hipLaunchKernelGGL(reproject_gather<true>, dim3(grid), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(reproject_gather<false>, dim3(grid), dim3(256), 0, st, A);
+}
+
+void launch_reproject_scene(const ReprojArgs& A, const float* table, int n_obj, hipStream_t st) {
+    const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
+    if (A.hist_moments) hipLaunchKernelGGL(reproject_gather_scene<true>, dim3(grid), dim3(256), 0, st, A, table, n_obj);
+    else hipLaunchKernelGGL(reproject_gather_scene<false>, dim3(grid), dim3(256), 0, st, A, table, n_obj);
 }
 
 }  // namespace rt

@@ -1,4 +1,5 @@
-// rt_reproject.hpp — the gather kernel of rtpbr_reproject: temporal reuse of the accumulated samples across a camera move.
+// rt_reproject.hpp — the gather kernels of rtpbr_reproject and rtpbr_reproject_scene: temporal reuse of the accumulated samples
+// across a camera move and across rigid moves of objects.
 //
 //   reproject_gather   one lane per pixel (the buffers' contiguous index i = x * H + y, 256-lane blocks, as feature_rays): the
 //                      new pixel's first hit (or, on a miss, its direction) is projected into the old camera; the history
@@ -6,8 +7,11 @@
 //                      taps on the same object with a matching depth and normal; the sum is renormalised and capped.
 //                      The same lane resets what rtpbr_refresh resets except image_buffer (ray_buffer.depth, the diff buffers).
 //                      reproject_gather<true> also warps the noise estimate's moments (rtpbr_noise_update) with the same taps.
-// The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_reproject) so that a CPU restatement matches bit for
-// bit (tests/reproject_ref/reproject_ref.c).
+//   reproject_gather_scene   the same gather for rtpbr_reproject_scene: a first hit on an object that moved is carried through
+//                      the object's frame into the old world (and its world-space normal turned back) before it is projected;
+//                      the per-object table (old and new position and matrix) is staged in LDS by every block.
+// The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_reproject and rtpbr_reproject_scene) so that the CPU
+// restatements match bit for bit (tests/reproject_ref/reproject_ref.c, tests/reproject_scene_ref/reproject_scene_ref.c).
 #pragma once
 #include "rt_types.hpp"
 
@@ -29,12 +33,18 @@ struct ReprojArgs {
     int32_t width, height;
     int32_t pinhole;                // cfg.camera_kind == RTPBR_CAMERA_PINHOLE (how the new centre ray's u, v are formed)
     int32_t adaptive;
+    int32_t normal_local;           // cfg.normal_space == RTPBR_NORMAL_LOCAL (reproject_gather_scene: stored normals do not turn with the object)
     // the noise estimate's moments (rt_noise.hpp), when the context tracks them: nullptr otherwise
     const float4* hist_moments;     // (W,H): the moments before the move
     float4* moments;                // out: warped with the image's taps and weights, capped with it
     float4* snapshot;               // out: the warped image_buffer
 };
 
+// rtpbr_reproject_scene's per-object record: the moved flag (0.0f / 1.0f), p0, p1, R0, R1 (0 = old, 1 = new; R row major)
+constexpr int SCENE_MOTION_WORDS = 25;
+
 void launch_reproject(const ReprojArgs& A, hipStream_t st);
+// table: device memory, n_obj * SCENE_MOTION_WORDS floats (n_obj <= MAX_OBJ)
+void launch_reproject_scene(const ReprojArgs& A, const float* table, int n_obj, hipStream_t st);
 
 }  // namespace rt

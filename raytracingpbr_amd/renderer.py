@@ -154,6 +154,27 @@ class Renderer:
             self.api.call("reproject", self._ctx, C.byref(camera), C.byref(p))
         self.camera = camera
 
+    def reproject_scene(self, scene: Scene, camera: Camera = None, max_history=None, depth_tolerance=None, normal_cos=None):
+        """set_scene(scene) (+ set_camera(camera) if given) + refresh() that keeps history, for a scene whose objects moved
+        rigidly: same count, types, scales and materials, only positions and rotations changed (anything else: EINVAL, use
+        set_scene + refresh).  A first hit on a moved object is followed back to where that surface point was; every other
+        pixel is warped as reproject() warps it.  The history still shows the old shadows and interreflections of the moved
+        objects until new samples outweigh it: use a smaller ``max_history`` than for camera moves (include/rtpbr.h
+        rtpbr_reproject_scene).  ``None`` = the library's default for that parameter."""
+        n = len(scene.objects)
+        arr = (SDFObject * n)(*scene.objects)
+        cam = None if camera is None else C.byref(camera)
+        given = {"max_history": max_history, "depth_tolerance": depth_tolerance, "normal_cos": normal_cos}
+        if all(v is None for v in given.values()):
+            p = None
+        else:
+            v = {k: (ReprojectParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+            p = C.byref(ReprojectParams(float(v["max_history"]), float(v["depth_tolerance"]), float(v["normal_cos"])))
+        self.api.call("reproject_scene", self._ctx, cam, arr, n, 1 if scene.scale10 else 0, p)
+        self.scene = scene
+        if camera is not None:
+            self.camera = camera
+
     # ------------------------------------------------------------ noise estimation (include/rtpbr.h rtpbr_noise_*)
     def noise_update(self):
         """Fold the samples deposited since the last call into ``moments`` as one batch (the first call's batch is everything

@@ -1,0 +1,179 @@
+"""CPU tier: the restatement of rtpbr_reproject_scene's gather (tests/reproject_scene_ref/reproject_scene_ref.c) that the GPU tests
+hold the kernel to, checked against what the header promises: with no moved object it is rtpbr_reproject's restatement bit for
+bit, a box slid by k pixel widths carries its history k pixels along while everything else stays put, and the rigidity rule."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import feature_ref_lib as fr
+import reproject_ref_lib as rr
+import reproject_scene_ref_lib as rs
+from oracle_backend import OracleRenderer
+from raytracingpbr_amd import SHAPE, Camera, Config, Scene, _capi, cornell_box, src_scene
+from raytracingpbr_amd.ibl import synthetic_env
+from raytracingpbr_amd.dataclass import Material, ReprojectParams, SDFObject, Transform
+
+W, H = 97, 61
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _translated(c, dx):
+    return Camera(tuple(np.float32(c.lookfrom[k]) + np.float32(dx if k == 0 else 0) for k in range(3)),
+                  tuple(np.float32(c.lookat[k]) + np.float32(dx if k == 0 else 0) for k in range(3)),
+                  tuple(c.vup), c.vfov, c.aspect, c.aperture, c.focus)
+
+
+_SCENES = {
+    "cornell_v3": lambda: (cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3), 1),
+    "src": lambda: (src_scene(aspect=W / H), Config.src(W, H, 7, steps_per_launch=1), 6),
+}
+
+
+def test_reference_builds():
+    assert os.path.exists(rs.build())
+    assert hasattr(rs.lib(), "rs_reproject_scene") and hasattr(rs.lib(), "rs_moved")
+
+
+@pytest.mark.parametrize("name", list(_SCENES))
+@pytest.mark.parametrize("params", [{}, {"max_history": 3.0, "depth_tolerance": 0.05, "normal_cos": 0.9}])
+def test_unmoved_table_is_the_camera_restatement_bitwise(name, params):
+    sc, cfg, n = _SCENES[name]()
+    o = OracleRenderer(sc, cfg)
+    if cfg.sky_kind == 1:
+        o.set_env(synthetic_env(192, 96, seed=0), 1.4, 2.2)
+    o.sample(n)
+    ib = o.image_buffer
+    assert (ib[..., 3] > 0).any()
+    same = rs.moved_scene(sc, {})
+    assert not rs.moved(sc, same).any()
+    f0 = fr.features(sc, cfg)
+    for cam in (sc.camera, _translated(sc.camera, 0.02 * float(np.linalg.norm(np.subtract(sc.camera.lookfrom, sc.camera.lookat))))):
+        f1 = fr.features(sc, cfg, cam)
+        want, want_mv = rr.reproject(cfg, sc.camera, cam, ib, f0, f1, **params)
+        got, got_mv, mo = rs.reproject_scene(cfg, sc, same, sc.camera, cam, ib, f0, f1, **params)
+        assert mo is None
+        assert np.array_equal(_bits(got), _bits(want)) and np.array_equal(_bits(got_mv), _bits(want_mv))
+        assert (got[..., 3] > 0).any()
+
+
+def test_a_full_turn_that_gives_the_same_matrix_is_no_move():
+    """the rule looks at the stored matrix, not at the rotation words: 21 and 381 degrees give the same nine words in f32 (most
+    pairs a, a + 360 do not: sin(2 pi) is 1.7e-7 in f32, so a wall turned from 0 to 360 degrees counts as moved)"""
+    sc = cornell_box("v3")
+    at21 = rs.moved_scene(sc, {6: ((0, 0, 0), (0, 197 + 21, 0))})
+    assert at21.objects[6].transform.rotation[1] == 21.0
+    assert not rs.moved(at21, rs.moved_scene(at21, {6: ((0, 0, 0), (0, 360, 0))})).any()
+    assert rs.moved(sc, rs.moved_scene(sc, {0: ((0, 0, 0), (0, 0, 360))})).tolist() == [True] + [False] * 7
+    m = rs.moved(sc, rs.moved_scene(sc, {6: ((0, 0, 0), (0, 7, 0)), 5: ((0.01, 0, 0), (0, 0, 0))}))
+    assert m.tolist() == [False] * 5 + [True, True, False]
+
+
+def test_rigidity_rule():
+    sc = cornell_box("v3")
+
+    def variant(change):
+        objs = [SDFObject.from_buffer_copy(bytes(o)) for o in sc.objects]
+        change(objs)
+        return Scene(objs, sc.scale10, sc.camera, sc.name)
+
+    def set_type(objs):
+        objs[6].type = int(SHAPE.SPHERE)
+
+    def set_scale(objs):
+        objs[6].transform.scale[1] = 0.26
+
+    def set_material(objs):
+        objs[5].material.roughness = 0.5
+
+    assert rs.moved(sc, variant(lambda objs: objs.pop())) is None
+    for change in (set_type, set_scale, set_material):
+        assert rs.moved(sc, variant(change)) is None, change.__name__
+    assert rs.moved(sc, Scene(list(sc.objects), False, sc.camera)) is None      # without the x10 the scales differ
+
+
+def test_a_box_slid_by_k_pixels_carries_its_history_k_pixels_along():
+    """Pinhole, the camera unchanged, looking down -z: a wall (object 0) and in front of it a fronto-parallel box (object 1) that
+    slides along x by exactly k pixel widths at the depth of its front face.  A point of that face the new pixel x sees, the old
+    pixel x - k saw: motion = (x - k, y) up to the snap (hits to 1e-5, so the depth error moves the answer by 1e-5 pixels, far
+    inside the snap's 2^-10), the history is that pixel's; pixels that saw the wall before and after keep their own."""
+    w, h, k = 48, 40, 3
+    cfg = Config.cornell_shortest(w, h, 4, 3)
+    assert cfg.camera_kind == 1
+    cam = Camera((0, 0, 3.5), (0, 0, -1), (0, 1, 0), 35, w / h, 0.0, 1.0)
+    grey = Material((0.5, 0.5, 0.5), (1, 1, 1), 1, 0, 0, 1.0)
+    objs = [SDFObject(SHAPE.BOX, Transform((0, 0, -1), (0, 0, 0), (4, 4, 0.2)), grey),
+            SDFObject(SHAPE.BOX, Transform((-0.2, 0.05, 0.5), (0, 0, 0), (0.3, 0.25, 0.1)), grey)]
+    old = Scene(objs, False, cam)
+    pw = 2 * np.tan(np.radians(35.0) / 2) * (w / h) * (3.5 - 0.6) / w          # a pixel's width on the plane z = 0.6
+    new = rs.moved_scene(old, {1: ((k * pw, 0, 0), (0, 0, 0))})
+    assert rs.moved(old, new).tolist() == [False, True]
+    f0, f1 = fr.features(old, cfg, cam), fr.features(new, cfg, cam)
+    ib = np.random.default_rng(5).uniform(0.5, 2.0, (w, h, 4)).astype(np.float32)
+    out, mv, _ = rs.reproject_scene(cfg, old, new, cam, None, ib, f0, f1, max_history=1e6)
+    front = (f1["object"] == 1) & (f1["normal"][..., 2] > 0.999)
+    on_box, on_wall = 0, 0
+    for x in range(w):
+        for y in range(h):
+            if front[x, y] and x - k >= 0 and f0["object"][x - k, y] == 1 and f0["normal"][x - k, y, 2] > 0.999:
+                assert abs(mv[x, y, 0] - (x - k)) <= 2.0 ** -10 and abs(mv[x, y, 1] - y) <= 2.0 ** -10, (x, y, mv[x, y])
+                if mv[x, y].tolist() == [x - k, y]:
+                    assert np.array_equal(_bits(out[x, y]), _bits(ib[x - k, y])), (x, y)
+                on_box += 1
+            elif f1["object"][x, y] == 0 and f0["object"][x, y] == 0:
+                assert mv[x, y].tolist() == [x, y], (x, y, mv[x, y])
+                assert np.array_equal(_bits(out[x, y]), _bits(ib[x, y])), (x, y)
+                on_wall += 1
+    assert on_box >= 40 and on_wall >= 1000, (on_box, on_wall)
+    # the wall the box uncovered has no history
+    uncovered = (f1["object"] == 0) & (f0["object"] == 1)
+    assert uncovered.sum() >= 10 and (out[uncovered] == 0).all() and (mv[uncovered] == -1).all()
+
+
+def test_rotated_world_normal_passes_the_normal_test_and_the_unrotated_one_would_not():
+    """Cornell v3 (world-space normals): the small box turned by 40 degrees about y.  With normal_cos = 0.9 the restatement keeps
+    pixels on the box's faces (cos 40 = 0.77 < 0.9: comparing the new normal as it is would refuse every side-face tap)."""
+    sc, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    new = rs.moved_scene(sc, {6: ((0, 0, 0), (0, 40, 0))})
+    f0, f1 = fr.features(sc, cfg), fr.features(new, cfg)
+    ib = np.ones((W, H, 4), np.float32)
+    out, mv, _ = rs.reproject_scene(cfg, sc, new, sc.camera, None, ib, f0, f1, max_history=1e6, depth_tolerance=0.05, normal_cos=0.9)
+    side = (f1["object"] == 6) & (np.abs(f1["normal"][..., 1]) < 0.1)
+    assert side.sum() >= 20
+    assert (out[side][:, 3] > 0).sum() >= side.sum() // 2, ((out[side][:, 3] > 0).sum(), side.sum())
+
+
+def test_moments_ride_along_with_the_image():
+    sc, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+    new = rs.moved_scene(sc, {6: ((0.03, 0, 0), (0, 5, 0))})
+    f0, f1 = fr.features(sc, cfg), fr.features(new, cfg)
+    rng = np.random.default_rng(2)
+    ib = rng.uniform(0.5, 2.0, (W, H, 4)).astype(np.float32)
+    out, mv, mo = rs.reproject_scene(cfg, sc, new, sc.camera, None, ib, f0, f1, moments=ib, max_history=1e6)
+    out2, mv2, none = rs.reproject_scene(cfg, sc, new, sc.camera, None, ib, f0, f1, max_history=1e6)
+    assert none is None and np.array_equal(_bits(out), _bits(out2)) and np.array_equal(_bits(mv), _bits(mv2))
+    assert np.array_equal(_bits(mo), _bits(out))          # the same taps and weights on the same numbers (no cap)
+
+
+def test_header_binding_and_struct_sizes_in_step():
+    hdr = open(os.path.join(ROOT, "include", "rtpbr.h")).read()
+    m = re.search(r"int rtpbr_reproject_scene\(([^;]*)\);", hdr)
+    assert m, "rtpbr_reproject_scene is not declared"
+    args = [" ".join(a.split()) for a in m.group(1).split(",")]
+    assert args == ["rtpbr_ctx* ctx", "const rtpbr_camera* new_cam", "const rtpbr_object* new_objects", "int n", "int scale10",
+                    "const rtpbr_reproject_params* p"]
+    assert "reproject_scene" in _capi.ENTRY_POINTS
+    src = open(os.path.join(ROOT, "raytracingpbr_amd", "_capi.py")).read()
+    sig = re.search(r'"reproject_scene": \(C\.c_int, \[(.*)\]\)', src).group(1)
+    assert sig == "p, C.POINTER(Camera), p, C.c_int, C.c_int, C.POINTER(ReprojectParams)"
+    assert C.sizeof(ReprojectParams) == 12 and C.sizeof(SDFObject) == 116 and C.sizeof(Camera) == 52
+    hpp = open(os.path.join(ROOT, "raytracingpbr_amd", "csrc", "rt_reproject.hpp")).read()
+    assert re.search(r"SCENE_MOTION_WORDS = 25;", hpp)       # flag + p0 + p1 + R0 + R1
+    from raytracingpbr_amd import Renderer
+    assert callable(getattr(Renderer, "reproject_scene"))

@@ -540,6 +540,30 @@ int rtpbr_reproject_scene(rtpbr_ctx* ctx, const rtpbr_camera* new_cam, const rtp
  *   state: it survives rtpbr_refresh, rtpbr_set_config, rtpbr_set_scene and rtpbr_reproject, allocates nothing and enqueues
  *   nothing.  RTPBR_EINVAL for a NULL context or a field outside its range (pool_radius is checked even with pooling off).
  *
+ * rtpbr_set_noise_tracking(RTPBR_NOISE_TRACK_SAMPLES) makes every sample a batch of its own: while the mode is on, rtpbr_sample(n)
+ *   and rtpbr_sample_selected(n) of the complete-path form fold every staged sample into M inside the pass that adds it to
+ *   image_buffer.  For a pixel that receives samples, with c = (r, g, b) each of its records in sample order:
+ *     L = (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z;
+ *     M.x = M.x + L;  M.y = M.y + L * L;  M.z = M.z + 1;  M.w = M.w + 1;
+ *     b.x += c.x; b.y += c.y; b.z += c.z; b.w += 1;                              (rtpbr_sample's own sum, unchanged)
+ *   and after the pixel's last record of a sub-launch s = b.  This is rtpbr_noise_update's rule for cnt = 1, the batch mean being
+ *   the sample itself (1 * L = L exactly); the pass overwrites s without reading it.  Pixels that receive no samples (unselected
+ *   ones) keep M and s bit for bit.  So n spp give n - 1 degrees of freedom per pixel instead of (calls - 1), the estimate is
+ *   valid after the first call, and "batches" in pool_batches, M.w and everything above means samples: rtpbr_noise_estimate,
+ *   rtpbr_select_noisy, rtpbr_denoise_guided, the pooling and the moment warp of rtpbr_reproject / rtpbr_reproject_scene read the
+ *   same buffer by the same rules.  A tracked call allocates M and s (zeroed) when they do not exist, is ordered behind
+ *   asynchronous reads of the moments, and keeps item-linear staging whatever option stage_dense says (same bits, as
+ *   rtpbr_sample_selected).  image_buffer, the work counters, sample_base, the timing and every other buffer are bit for bit those
+ *   of the untracked call, and the result does not depend on how the staging budget splits the call into sub-launches (it
+ *   splits along samples).  An rtpbr_noise_update after a tracked call finds d = 0 and changes nothing: the two may be mixed.
+ *   The set call with RTPBR_NOISE_TRACK_SAMPLES first does exactly what rtpbr_noise_update does (same refusals: everything
+ *   deposited so far is one batch, s = image_buffer), then sets the mode; with RTPBR_NOISE_TRACK_OFF it sets the mode and does
+ *   nothing else.  The mode is plain context state: it survives rtpbr_refresh (which zeroes M and s as before), rtpbr_set_config
+ *   (a new resolution frees M and s; the next tracked call makes them again), rtpbr_set_scene and rtpbr_reproject*.
+ *   While the mode is on rtpbr_sample / rtpbr_sample_selected are refused with RTPBR_ESTATE, changing nothing, in the
+ *   persistent-ray form (no per-sample records), with option precision = 1 (its unstaged instance keeps no records) and with
+ *   tiles of world > 1.  RTPBR_EINVAL for a NULL context or another mode.
+ *
  * Errors: RTPBR_ESTATE before set_config (estimate / guided: set_scene and set_camera too) and with tiles of world > 1;
  * RTPBR_EINVAL for a NULL context, a threshold that is not >= 0, iterations outside 0..8, demodulate not 0/1, a sigma or
  * variance_floor that is not finite and > 0, or whose 1/sigma^2 or 1/(sigma_color^2 variance_floor) overflows.  A refused call
@@ -578,6 +602,9 @@ int rtpbr_noise_update(rtpbr_ctx* ctx);
 int rtpbr_noise_estimate(rtpbr_ctx* ctx, float threshold, rtpbr_noise_stats* out);
 int rtpbr_denoise_guided(rtpbr_ctx* ctx, const rtpbr_denoise_guided_params* p);
 int rtpbr_set_noise_estimator(rtpbr_ctx* ctx, const rtpbr_noise_estimator* e);   /* NULL = the defaults */
+enum { RTPBR_NOISE_TRACK_OFF = 0,       /* a batch is what rtpbr_noise_update finds deposited since the last one (the default) */
+       RTPBR_NOISE_TRACK_SAMPLES = 1 }; /* complete-path form: every sample is a batch, folded in by rtpbr_sample itself      */
+int rtpbr_set_noise_tracking(rtpbr_ctx* ctx, int mode);
 
 /* ---- Adaptive sampling of the complete-path form: select pixels, then trace samples through the selected pixels only.
  *

@@ -28,10 +28,12 @@ ENTRY_POINTS = [
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
     "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
     "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
+    "set_noise_tracking",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
 ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
-                   "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene")
+                   "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
+                   "set_noise_tracking")
 
 
 class RtpbrError(RuntimeError):
@@ -101,6 +103,7 @@ class CApi:
             "sample_selected": (C.c_int, [p, C.c_int]),
             "set_noise_estimator": (C.c_int, [p, C.POINTER(NoiseEstimator)]),
             "present": (C.c_int, [p, C.POINTER(PresentParams)]),
+            "set_noise_tracking": (C.c_int, [p, C.c_int]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

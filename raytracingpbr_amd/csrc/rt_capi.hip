@@ -23,6 +23,7 @@
 using namespace rt;
 
 static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_error);
+static int noise_alloc(rtpbr_ctx* c);
 extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value);
 extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world);
 extern "C" int rtpbr_set_camera(rtpbr_ctx* c, const rtpbr_camera* cam);
@@ -877,7 +878,7 @@ static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_
         const bool aot_special = c->kind == KIND_BOXES && c->n_obj == 8 && P.box_sig != 0;
         if (c->jit >= 1 || !aot_special || c->precision) {
             *key = make_jit_key(c->kind, c->n_obj, c->objm, c->cfg, P, persistent, c->jit_bake, c->jit_waves, jit_bunny, c->precision);
-            key->dense = (c->stage_dense && !persistent && !c->precision) ? 1 : 0;
+            key->dense = (c->stage_dense && !persistent && !c->precision && c->noise_tracking == RTPBR_NOISE_TRACK_OFF) ? 1 : 0;      // (a tracked launch keeps item-linear records)
             *want = true;
         }
     } else if (c->jit == 2) {
@@ -1206,6 +1207,9 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
     int left = n;
     if (int r = flush_shade(c)) return r;
     c->dense_launches = 0;
+    // per-sample noise tracking (rtpbr_set_noise_tracking): the accumulate pass folds every record into the moments (the callers
+    // have refused what keeps no records and have allocated the moments and the snapshot)
+    const bool tracked = c->noise_tracking == RTPBR_NOISE_TRACK_SAMPLES;
     while (left > 0) {
         const bool split_ok = !selected && c->primary_split && P.scheduler == 1 && c->kind != KIND_BUNNY && c->kind != KIND_MIXED;
         // the tolerance flavour accumulates in LDS and adds to image_buffer directly: no staging, no accumulate kernel
@@ -1246,7 +1250,7 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
         // dense staging (rt_trace.hpp stage_sample, accumulate_dense): the claim must be whole pixels or a whole fraction of one, and
         // fit the record's one-byte offset; a launch that has no such claim size near the one wanted keeps the item-linear records
         P.stage_dense = 0;
-        if (c->stage_dense && c->jit_mod != nullptr && !unstaged && P.scheduler == 1) {      // (compiled into run-time instances only: RtJitKey::dense)
+        if (c->stage_dense && c->jit_mod != nullptr && !unstaged && P.scheduler == 1 && !tracked) {      // (compiled into run-time instances only: RtJitKey::dense)
             long long lo = DENSE_CHUNK_MIN, hi = chunk < 64 ? 64 : chunk > (long long)DENSE_CHUNK_MAX ? (long long)DENSE_CHUNK_MAX : chunk, cc = 0;
             if (c->chunk > 0) lo = hi = c->chunk;       // a claim size that was asked for is kept as it is (or the records stay item-linear)
             if (lo >= (long long)DENSE_CHUNK_MIN && hi <= (long long)DENSE_CHUNK_MAX)
@@ -1289,7 +1293,9 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
         } else
             launch_trace(P, c->kind, grid, c->stream);
         if (c->timed) HIP_TRY(hipEventRecord(b, c->stream));
-        if (selected) launch_accumulate_selected(P, c->stream);
+        if (tracked && selected) launch_accumulate_selected_tracked(P, c->noise_moments, c->noise_snapshot, c->stream);
+        else if (tracked) launch_accumulate_tracked(P, c->noise_moments, c->noise_snapshot, c->stream);
+        else if (selected) launch_accumulate_selected(P, c->stream);
         else if (!unstaged) launch_accumulate(P, c->n_cu, c->stream);
         c->sample_base += (uint32_t)K;
         left -= K;
@@ -1300,8 +1306,9 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
 // rtpbr_sample and rtpbr_sample_selected (`selected`: every refusal of its own has been made by the caller)
 static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     if (int r = set_dev(c)) return r;
-    // (diff_buffer: instrumented builds write their per-wave records over it)
-    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER)) return r;
+    // (diff_buffer: instrumented builds write their per-wave records over it; a tracked call — rtpbr_set_noise_tracking — writes the moments)
+    const bool tracked = c->noise_tracking == RTPBR_NOISE_TRACK_SAMPLES;
+    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | (tracked ? 1u << RTPBR_BUF_MOMENTS : 0u))) return r;
     // A shading the previous call left pending (lazy shading of one-step launches) rides along only if this call is again a launch of the
     // wavefront split; otherwise it is launched now, while the previous call's work counters are still the current ones
     {
@@ -1344,6 +1351,9 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     for (int i = 0; i < c->n_obj; i++)
         if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
     if (c->cfg.sky_kind == RTPBR_SKY_ENVMAP && !c->env) return fail(RTPBR_ESTATE, "sky_kind ENVMAP needs rtpbr_set_env first");
+    // a tracked call folds into the moments and re-takes the snapshot: both exist (zeroed) from here on, as after rtpbr_noise_update
+    if (tracked)
+        if (int r = noise_alloc(c)) return r;
     static_assert((sizeof(Counters) + 64) % 16 == 0, "zero_next_counters / launch_zero fill 16-byte words");
     // This call's work counters (+ the claim counters behind them): the buffer whose turn it is, zeroed by the previous call's kernels
     // (or here, if that call launched none); this call's kernels zero the other one.
@@ -1397,10 +1407,23 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     return RTPBR_OK;
 }
 
+// what a sample call with per-sample noise tracking on (rtpbr_set_noise_tracking) refuses: there must be a record per sample
+static int tracked_sample_check(rtpbr_ctx* c) {
+    if (c->noise_tracking != RTPBR_NOISE_TRACK_SAMPLES) return RTPBR_OK;
+    if (c->cfg.kernel_form != RTPBR_FORM_COMPLETE_PATH)
+        return fail(RTPBR_ESTATE, "per-sample noise tracking: the complete-path form only (the persistent-ray form has no per-sample records): "
+                                  "rtpbr_set_noise_tracking(RTPBR_NOISE_TRACK_OFF) first");
+    if (c->precision)
+        return fail(RTPBR_ESTATE, "per-sample noise tracking: not with option precision = 1 (the tolerance flavour's unstaged instance keeps no records)");
+    if (c->world > 1) return fail(RTPBR_ESTATE, "per-sample noise tracking works on the whole frame: not with tiles of world > 1");
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_sample(rtpbr_ctx* c, int n) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
     if (n < 0) return fail(RTPBR_EINVAL, "n must be >= 0");
+    if (int r = tracked_sample_check(c)) return r;
     return sample_call(c, n, false);
 }
 
@@ -1701,6 +1724,16 @@ extern "C" int rtpbr_noise_update(rtpbr_ctx* c) {
     return RTPBR_OK;
 }
 
+extern "C" int rtpbr_set_noise_tracking(rtpbr_ctx* c, int mode) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (mode != RTPBR_NOISE_TRACK_OFF && mode != RTPBR_NOISE_TRACK_SAMPLES)
+        return fail(RTPBR_EINVAL, "rtpbr_set_noise_tracking: mode must be RTPBR_NOISE_TRACK_OFF or RTPBR_NOISE_TRACK_SAMPLES");
+    if (mode == RTPBR_NOISE_TRACK_SAMPLES)      // everything deposited so far is one batch; the samples to come are batches of one
+        if (int r = rtpbr_noise_update(c)) return r;
+    c->noise_tracking = mode;
+    return RTPBR_OK;
+}
+
 // the estimate pass on the stream (no read-back): RTPBR_BUF_NOISE, the guided filter's level-0 variance and the statistics
 static int noise_estimate_enqueue(rtpbr_ctx* c, float threshold) {
     if (!c->feat_valid)
@@ -1848,6 +1881,7 @@ extern "C" int rtpbr_sample_selected(rtpbr_ctx* c, int n) {
         return fail(RTPBR_ESTATE, "rtpbr_sample_selected: the complete-path form only (the persistent-ray form has cfg.adaptive_sampling)");
     if (c->precision) return fail(RTPBR_ESTATE, "rtpbr_sample_selected: not with option precision = 1 (the tolerance flavour has no selected instances)");
     if (!c->have_selection) return fail(RTPBR_ESTATE, "rtpbr_sample_selected: no selection yet (rtpbr_select_mask / rtpbr_select_noisy first)");
+    if (int r = tracked_sample_check(c)) return r;
     return sample_call(c, n, true);
 }
 

@@ -18,6 +18,9 @@ void launch_trace(const Params& P, int kind, int grid, hipStream_t st);
 void launch_accumulate(const Params& P, int n_cu, hipStream_t st);
 void launch_trace_selected(const Params& P, int kind, int grid, hipStream_t st);      // rtpbr_sample_selected: P.order = the selection list, P.np = its length
 void launch_accumulate_selected(const Params& P, hipStream_t st);
+// per-sample noise tracking (rtpbr_set_noise_tracking): the accumulate pass also folds every sample into the moments and re-takes the snapshot
+void launch_accumulate_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st);
+void launch_accumulate_selected_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st);
 int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler);
 void launch_zero(void* p, size_t bytes, hipStream_t st);      // a small fill as a kernel of our own (bytes % 16 == 0)
 void launch_persistent(const Params& P, int kind, int steps, hipStream_t st);
@@ -200,6 +203,7 @@ struct rtpbr_ctx {
     float* noise_map = nullptr;        // (W,H): RTPBR_BUF_NOISE
     float* noise_var = nullptr;        // 3 x (W,H): the estimate's variance (-1: no samples), then the guided levels' ping-pong
     rt::NoiseStats* noise_stats = nullptr;
+    int noise_tracking = RTPBR_NOISE_TRACK_OFF;      // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
     rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
                                           RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};      // rtpbr_set_noise_estimator: plain state, kept across refresh / set_config / set_scene / reproject
     // the selection of rtpbr_select_mask / rtpbr_select_noisy (rt_select.hip): allocated on the first select call, freed with the context or a new resolution

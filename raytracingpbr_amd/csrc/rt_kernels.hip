@@ -16,6 +16,8 @@
 //                            depend on the schedule.
 //   accumulate_samples       adds the staged samples of each pixel IN SAMPLE ORDER into
 //                            image_buffer (T7), exactly like "image_buffer[i,j] += vec4(color,1)".
+//   accumulate_*_tracked     the same pass with every sample folded into the noise moments as well
+//                            (rtpbr_set_noise_tracking).
 //   persistent_steps<KIND>   src/ form (F1-F4,F6,F7: src/pathtracer.py:16-103, src/scene.py:59-84):
 //                            one lane per pixel, ray state in ray_buffer between launches.
 //   refresh, post_process, pack/unpack tiles, math_probe (test hook).
@@ -26,8 +28,21 @@
 namespace rt {
 
 // -------------------------------------------------------------------------------------------
+// Per-sample noise tracking (rtpbr_set_noise_tracking): every record is also folded into the pixel's luminance moments as a batch
+// of one (rt_noise.hip noise_update with cnt = 1), in the order written in include/rtpbr.h; nothing fused (-ffp-contract=off).
+RT_D void fold_sample(float4& M, float r, float g, float b) {
+    const float L = (0.299f * r + 0.587f * g) + 0.114f * b;
+    M.x = M.x + L;
+    M.y = M.y + L * L;
+    M.z = M.z + 1.0f;
+    M.w = M.w + 1.0f;
+}
+
 // image_buffer[i,j] += vec4(color, 1) for k = 0..K-1 in order (renderer.py:36)
-__global__ void __launch_bounds__(256) accumulate_samples(const Params P) {
+// TRACK: moments / snapshot are RTPBR_BUF_MOMENTS and the noise snapshot, indexed like image_buffer (one 16-byte load and store of
+// M, one 16-byte store of s = the new image_buffer value per pixel); the untracked instance never looks at them.
+template <bool TRACK>
+RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snapshot) {
     uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     int x = 0, y = 0;
     const bool valid = q < (uint32_t)P.np && pixel_of(P, q, x, y);
@@ -39,6 +54,9 @@ __global__ void __launch_bounds__(256) accumulate_samples(const Params P) {
     if (!valid) return;
     float4* dst = P.image_buffer + ((size_t)x * P.cfg.height + y);
     float4 acc = *dst;
+    const size_t px = (size_t)(dst - P.image_buffer);      // the buffer index x * H + y: the moments and the snapshot lie like image_buffer
+    float4 M = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (TRACK) M = moments[px];
     // a pixel's K records (12 bytes each) are contiguous (item-linear staging): fetch them 8 at a time (96 B per lane as
     // six 16-byte loads when the pixel's run starts on a 16-byte boundary, i.e. K % 4 == 0) and add them strictly in
     // sample order
@@ -54,6 +72,7 @@ __global__ void __launch_bounds__(256) accumulate_samples(const Params P) {
                                  v[3].x, v[3].y, v[3].z, v[3].w, v[4].x, v[4].y, v[4].z, v[4].w, v[5].x, v[5].y, v[5].z, v[5].w};
 #pragma unroll
             for (int i = 0; i < 8; i++) {
+                if constexpr (TRACK) fold_sample(M, f[3 * i], f[3 * i + 1], f[3 * i + 2]);
                 acc.x += f[3 * i];
                 acc.y += f[3 * i + 1];
                 acc.z += f[3 * i + 2];
@@ -62,17 +81,27 @@ __global__ void __launch_bounds__(256) accumulate_samples(const Params P) {
         }
     }
     for (; k < P.K; k++) {
+        if constexpr (TRACK) fold_sample(M, src[3 * k], src[3 * k + 1], src[3 * k + 2]);
         acc.x += src[3 * k];
         acc.y += src[3 * k + 1];
         acc.z += src[3 * k + 2];
         acc.w += 1.0f;
     }
     *dst = acc;
+    if constexpr (TRACK) {
+        moments[px] = M;
+        snapshot[px] = acc;
+    }
+}
+__global__ void __launch_bounds__(256) accumulate_samples(const Params P) { accumulate_samples_body<false>(P, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) accumulate_samples_tracked(const Params P, float4* moments, float4* snapshot) {
+    accumulate_samples_body<true>(P, moments, snapshot);
 }
 
 // ... of a selected launch (rtpbr_sample_selected): local pixel q is entry q of the selection list, a buffer index; every
-// other pixel of image_buffer is left alone.  Item-linear staging only.
-__global__ void __launch_bounds__(256) accumulate_selected(const Params P) {
+// other pixel of image_buffer (and, TRACK, of the moments and the snapshot) is left alone.  Item-linear staging only.
+template <bool TRACK>
+RT_D void accumulate_selected_body(const Params& P, float4* moments, float4* snapshot) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = q < (uint32_t)P.np;
     {
@@ -80,16 +109,28 @@ __global__ void __launch_bounds__(256) accumulate_selected(const Params P) {
         if ((threadIdx.x & 63) == 0 && n) atomicAdd(&P.counters->shard[blockIdx.x & 63u][5], (unsigned long long)n);
     }
     if (!valid) return;
-    float4* dst = P.image_buffer + P.order[q];
+    const uint32_t px = P.order[q];
+    float4* dst = P.image_buffer + px;
     float4 acc = *dst;
+    float4 M = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (TRACK) M = moments[px];
     const float* src = P.stage + (size_t)q * (size_t)P.K * 3u;
     for (int k = 0; k < P.K; k++) {      // strictly in sample order
+        if constexpr (TRACK) fold_sample(M, src[3 * k], src[3 * k + 1], src[3 * k + 2]);
         acc.x += src[3 * k];
         acc.y += src[3 * k + 1];
         acc.z += src[3 * k + 2];
         acc.w += 1.0f;
     }
     *dst = acc;
+    if constexpr (TRACK) {
+        moments[px] = M;
+        snapshot[px] = acc;
+    }
+}
+__global__ void __launch_bounds__(256) accumulate_selected(const Params P) { accumulate_selected_body<false>(P, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) accumulate_selected_tracked(const Params P, float4* moments, float4* snapshot) {
+    accumulate_selected_body<true>(P, moments, snapshot);
 }
 
 // The same sum over the DENSE staging (rt_trace.hpp stage_sample): a block takes `acc_batch` consecutive items at a time (a multiple
@@ -467,6 +508,9 @@ void launch_trace_selected(const Params& P, int kind, int grid, hipStream_t st) 
 void launch_accumulate_selected(const Params& P, hipStream_t st) {
     hipLaunchKernelGGL(accumulate_selected, dim3((unsigned)((P.np + 255) / 256)), dim3(256), 0, st, P);
 }
+void launch_accumulate_selected_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st) {
+    hipLaunchKernelGGL(accumulate_selected_tracked, dim3((unsigned)((P.np + 255) / 256)), dim3(256), 0, st, P, moments, snapshot);
+}
 int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler) {
     int per_cu = 0;
     hipError_t e = hipSuccess;
@@ -531,6 +575,11 @@ void launch_accumulate(const Params& P, int n_cu, hipStream_t st) {
     }
     int grid = (P.np + 255) / 256;
     hipLaunchKernelGGL(accumulate_samples, dim3(grid), dim3(256), 0, st, P);
+}
+// per-sample noise tracking: item-linear staging only (the host never stages a tracked launch densely)
+void launch_accumulate_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st) {
+    int grid = (P.np + 255) / 256;
+    hipLaunchKernelGGL(accumulate_samples_tracked, dim3(grid), dim3(256), 0, st, P, moments, snapshot);
 }
 void launch_persistent_pool(const Params& P, int kind, int steps, int grid, hipStream_t st) {
     if (kind == KIND_BOXES) hipLaunchKernelGGL((persistent_pool<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, steps);

@@ -41,6 +41,7 @@ class Renderer:
         self._host_arrays = {}               # address -> bytes of the page-locked blocks handed out by host_array()
         self.noise_estimator = NoiseEstimator(**NoiseEstimator.DEFAULTS)      # what set_noise_estimator() last set
         self.track_noise = False             # True: every sample() call is one batch of the noise estimate (noise_update() after it)
+        self.noise_per_sample = False        # what set_noise_tracking() last set: every SAMPLE is a batch, folded in by sample() itself
         self.set_config(config)
         self.set_scene(scene)
         self.set_camera(camera if camera is not None else scene.camera)
@@ -181,6 +182,17 @@ class Renderer:
         accumulated so far).  The estimate needs two batches per pixel; before that ``noise_estimate`` looks at the neighbours."""
         self.api.call("noise_update", self._ctx)
 
+    def set_noise_tracking(self, per_sample: bool):
+        """``True``: from now on sample() and sample_selected() of the complete-path form fold every sample into ``moments`` as a
+        batch of its own, in the pass that adds it to image_buffer: n spp give the estimate n - 1 degrees of freedom per pixel
+        (not calls - 1), it is valid after the first call, and no noise_update() is needed (what was deposited before is folded
+        as one batch by this call; ``track_noise``'s extra noise_update() finds nothing new).  "Batches" in
+        ``set_noise_estimator(pool_batches=...)`` then means samples.  ``False``: back to batches per noise_update().  Refused by
+        sample() in the persistent-ray form, with option precision = 1 and with tiles of world > 1.  Kept across refresh /
+        set_config / set_scene / reproject."""
+        self.api.call("set_noise_tracking", self._ctx, 1 if per_sample else 0)
+        self.noise_per_sample = bool(per_sample)
+
     def set_noise_estimator(self, pool_batches: int = 0, pool_radius: int = 3, min_samples: int = 0):
         """The estimator behind noise_estimate / select_noisy / denoise_guided (and so render_until / render_adaptive); the
         defaults are off.  ``pool_batches`` 3..64: a pixel with fewer batches than this (but two or more) takes the larger of
@@ -214,12 +226,16 @@ class Renderer:
                                 float(v["sigma_depth"]), float(v["variance_floor"]))
         self.api.call("denoise_guided", self._ctx, C.byref(p))
 
-    def render_until(self, noise: float, max_spp: int, batch_spp: int = 16):
+    def render_until(self, noise: float, max_spp: int, batch_spp: int = 16, per_sample: bool = False):
         """Sample in batches of ``batch_spp`` (sample() calls of that size, each one batch of the noise estimate) until no pixel's
         estimated noise exceeds ``noise`` or ``max_spp`` is spent; never fewer than two batches, which the estimate needs.
-        Returns (spp used, NoiseStats of the last estimate).  Continues whatever is accumulated: refresh() first for a new frame."""
+        Returns (spp used, NoiseStats of the last estimate).  Continues whatever is accumulated: refresh() first for a new frame.
+        ``per_sample``: with set_noise_tracking(True) for the duration of the call (restored after), no noise_update(), and the
+        first estimate as soon as this call has traced two samples per pixel — after the first batch when ``batch_spp`` >= 2."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
+        if per_sample:
+            return self._render_until_per_sample(noise, int(max_spp), int(batch_spp))
         keep, self.track_noise = self.track_noise, False
         try:
             used, batches, stats = 0, 0, None
@@ -235,6 +251,25 @@ class Renderer:
             return used, stats
         finally:
             self.track_noise = keep
+
+    def _render_until_per_sample(self, noise, max_spp, batch_spp):
+        keep, self.track_noise = self.track_noise, False
+        mode = self.noise_per_sample
+        try:
+            self.set_noise_tracking(True)
+            used, stats = 0, None
+            while used < max_spp:
+                n = min(batch_spp, max_spp - used)
+                self.sample(n)
+                used += n
+                if used >= 2 or used >= max_spp:
+                    stats = self.noise_estimate(noise)
+                    if stats.pixels_above == 0:
+                        break
+            return used, stats
+        finally:
+            self.track_noise = keep
+            self.set_noise_tracking(mode)
 
     # ------------------------------------------------------------ adaptive sampling (include/rtpbr.h rtpbr_select_* / rtpbr_sample_selected)
     def select_mask(self, mask) -> int:
@@ -261,7 +296,7 @@ class Renderer:
         if self.track_noise:
             self.noise_update()
 
-    def render_adaptive(self, noise: float, max_spp: int, batch_spp: int = 16, dilate: int = 0):
+    def render_adaptive(self, noise: float, max_spp: int, batch_spp: int = 16, dilate: int = 0, per_sample: bool = False):
         """``render_until`` that stops sampling a pixel once it is done: two full-frame batches of ``batch_spp`` (the temporal
         estimate needs two), then select_noisy(noise, dilate) -> sample_selected(batch_spp) -> noise_update() until nothing is
         selected or another batch would take a pixel past ``max_spp``.  Returns (pixel-samples traced, NoiseStats of the last
@@ -271,11 +306,15 @@ class Renderer:
         ``dilate`` >= 1 keeps the neighbours of a noisy pixel sampling and removes most of it.  The estimator of
         ``set_noise_estimator`` applies: with pooling a pixel that stopped can be selected again in a later round (its
         neighbours' spread counts while it is young), and ``min_samples`` keeps every pixel selected up to that count
-        (DESIGN.md 6f)."""
+        (DESIGN.md 6f).  ``per_sample``: with set_noise_tracking(True) for the duration of the call (restored after): ONE
+        full-frame batch, whose ``batch_spp`` samples are that many batches of the estimate, then select_noisy ->
+        sample_selected as above without any noise_update()."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch = int(batch_spp)
         n_pix = self.config.width * self.config.height
+        if per_sample:
+            return self._render_adaptive_per_sample(noise, int(max_spp), batch, dilate, n_pix)
         keep, self.track_noise = self.track_noise, False
         try:
             traced, used = 0, 0
@@ -296,6 +335,25 @@ class Renderer:
             return traced, self.noise_estimate(noise)
         finally:
             self.track_noise = keep
+
+    def _render_adaptive_per_sample(self, noise, max_spp, batch, dilate, n_pix):
+        keep, self.track_noise = self.track_noise, False
+        mode = self.noise_per_sample
+        try:
+            self.set_noise_tracking(True)
+            used = min(batch, max_spp)
+            self.sample(used)
+            traced = n_pix * used
+            while used + batch <= max_spp:
+                n_sel = self.select_noisy(noise, dilate)
+                if n_sel == 0:
+                    break
+                self.sample_selected(batch)
+                traced, used = traced + n_sel * batch, used + batch
+            return traced, self.noise_estimate(noise)
+        finally:
+            self.track_noise = keep
+            self.set_noise_tracking(mode)
 
     # ------------------------------------------------------------ the present stage (include/rtpbr.h rtpbr_present)
     def present(self, source="pixels", format="rgba8", dither=False):
@@ -466,7 +524,8 @@ class Renderer:
 
     @property
     def moments(self):
-        """(W,H,4): (sum c L, sum c L^2, sum c, K) over the K batches noise_update() has folded in, c samples each, L the
+        """(W,H,4): (sum c L, sum c L^2, sum c, K) over the K batches noise_update() has folded in (with set_noise_tracking(True):
+        every sample is a batch, c = 1), c samples each, L the
         compressed luminance of the batch mean"""
         return self._read(BUF_MOMENTS)
 

@@ -1456,12 +1456,20 @@ static int features_alloc(rtpbr_ctx* c) {
 enum : unsigned { W_FEATURES = (1u << RTPBR_BUF_FEAT_ALBEDO) | (1u << RTPBR_BUF_FEAT_NORMAL) | (1u << RTPBR_BUF_FEAT_DEPTH) | (1u << RTPBR_BUF_FEAT_OBJECT),
                   W_DENOISED = 1u << RTPBR_BUF_DENOISED_PIXELS };
 
-extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
-    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+// The states every call on the whole frame refuses, in this order: no configuration, scene or camera yet; tiles of world > 1
+// (`tiles`: the call's message, `who` fills its %s if it has one); a bunny without its shape data.
+static int whole_frame_state(rtpbr_ctx* c, const char* tiles, const char* who = "") {
     if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
-    if (c->world > 1) return fail(RTPBR_ESTATE, "rtpbr_render_features / rtpbr_denoise work on the whole frame: not with tiles of world > 1");
+    if (c->world > 1) return fail(RTPBR_ESTATE, tiles, who);
     for (int i = 0; i < c->n_obj; i++)
         if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
+    return RTPBR_OK;
+}
+static const char* const FEATURE_TILES = "rtpbr_render_features / rtpbr_denoise work on the whole frame: not with tiles of world > 1";
+
+extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
     if (int r = set_dev(c)) return r;
     if (int r = features_alloc(c)) return r;
     if (int r = rt_order_after_reads(c, W_FEATURES)) return r;
@@ -1489,6 +1497,68 @@ extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
     return RTPBR_OK;
 }
 
+// iterations, demodulate and the sigmas (sig[0]: sigma_color) of either denoise call; inv[k] = 1 / sig[k]^2
+static int denoise_params_check(int iterations, int demodulate, const float* sig, float* inv, int n_sig) {
+    if (iterations < 0 || iterations > 8) return fail(RTPBR_EINVAL, "denoise iterations must be 0..8");
+    if (demodulate != 0 && demodulate != 1) return fail(RTPBR_EINVAL, "denoise demodulate must be 0 or 1");
+    for (int k = 0; k < n_sig; k++) {
+        inv[k] = 1.0f / (sig[k] * sig[k]);
+        if (!(sig[k] > 0.0f) || !std::isfinite(sig[k]) || !std::isfinite(inv[k]))
+            return fail(RTPBR_EINVAL, "denoise sigmas must be finite and > 0 (and not so small that 1/sigma^2 overflows)");
+    }
+    return RTPBR_OK;
+}
+
+// RTPBR_BUF_DENOISED_PIXELS and, from two levels on, the two halves of the levels' ping-pong; then ordered after the buffer's reads
+static int denoised_alloc(rtpbr_ctx* c, int iterations) {
+    if (int r = set_dev(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->denoised) HIP_TRY(hipMalloc(&c->denoised, n * 3 * sizeof(float)));
+    if (iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
+    return rt_order_after_reads(c, W_DENOISED);
+}
+
+// The levels of either filter, after every refusal: level k reads half (k - 1) & 1 of denoise_scratch and writes half k & 1; the
+// first reads image_buffer, the last writes denoised.  g != nullptr: the guided kernel, whose variance goes the same way through
+// the two planes of noise_var behind the estimate's (plane 0).  No level: the tone-map-only pass, the same for both.
+static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g) {
+    if (int r = denoised_alloc(c, iterations)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    DenoiseArgs A{};
+    A.cfg = c->cfg;
+    A.image_buffer = c->image_buffer;
+    A.guide_nz = c->feat_guides;
+    A.albedo = c->feat_albedo;
+    A.object = c->feat_object;
+    A.out = c->denoised;
+    A.in = inv[1];
+    A.iz = inv[2];
+    A.demodulate = demodulate;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    if (g) {
+        A.var0 = c->noise_var;
+        A.sc2 = g->sigma_color * g->sigma_color;
+        A.floor = g->variance_floor;
+    }
+    if (iterations == 0) launch_atrous_level(A, true, true, false, c->stream);      // (A.step = 0)
+    for (int k = 0; k < iterations; k++) {
+        const bool first = k == 0, last = k + 1 == iterations;
+        A.src = first ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
+        A.dst = last ? nullptr : c->denoise_scratch + (size_t)(k & 1) * n;
+        if (g) {
+            A.vsrc = first ? nullptr : c->noise_var + (size_t)(1 + ((k - 1) & 1)) * n;
+            A.vdst = last ? nullptr : c->noise_var + (size_t)(1 + (k & 1)) * n;
+        } else {
+            A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
+        }
+        A.step = 1 << k;
+        launch_atrous_level(A, first, last, g != nullptr, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     rtpbr_denoise_params d;
@@ -1502,55 +1572,16 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
         d.sigma_depth = RTPBR_DENOISE_DEFAULT_SIGMA_DEPTH;
         d.sigma_albedo = RTPBR_DENOISE_DEFAULT_SIGMA_ALBEDO;
     }
-    if (d.iterations < 0 || d.iterations > 8) return fail(RTPBR_EINVAL, "denoise iterations must be 0..8");
-    if (d.demodulate != 0 && d.demodulate != 1) return fail(RTPBR_EINVAL, "denoise demodulate must be 0 or 1");
     const float sig[4] = {d.sigma_color, d.sigma_normal, d.sigma_depth, d.sigma_albedo};
     float inv[4];
-    for (int k = 0; k < 4; k++) {
-        inv[k] = 1.0f / (sig[k] * sig[k]);
-        if (!(sig[k] > 0.0f) || !std::isfinite(sig[k]) || !std::isfinite(inv[k]))
-            return fail(RTPBR_EINVAL, "denoise sigmas must be finite and > 0 (and not so small that 1/sigma^2 overflows)");
-    }
+    if (int r = denoise_params_check(d.iterations, d.demodulate, sig, inv, 4)) return r;
     // the colour weight alone grows, by 4 per level: it must stay finite up to the last level, 4^(iterations-1)
     if (d.iterations > 1 && !std::isfinite(inv[0] * (float)(1u << (2 * (d.iterations - 1)))))
         return fail(RTPBR_EINVAL, "denoise sigma_color too small for this many levels: 1/sigma^2 * 4^(iterations-1) overflows");
-    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
-    if (c->world > 1) return fail(RTPBR_ESTATE, "rtpbr_render_features / rtpbr_denoise work on the whole frame: not with tiles of world > 1");
+    if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
-    if (int r = set_dev(c)) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->denoised) HIP_TRY(hipMalloc(&c->denoised, n * 3 * sizeof(float)));
-    if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
-    if (int r = rt_order_after_reads(c, W_DENOISED)) return r;
-    DenoiseArgs A;
-    A.cfg = c->cfg;
-    A.image_buffer = c->image_buffer;
-    A.guide_nz = c->feat_guides;
-    A.albedo = c->feat_albedo;
-    A.object = c->feat_object;
-    A.out = c->denoised;
-    A.in = inv[1];
-    A.iz = inv[2];
-    A.demodulate = d.demodulate;
-    A.width = c->cfg.width;
-    A.height = c->cfg.height;
-    if (d.iterations == 0) {
-        A.src = nullptr;
-        A.dst = nullptr;
-        A.ic = inv[0];
-        A.step = 0;
-        launch_atrous_level(A, true, true, c->stream);
-    }
-    for (int k = 0; k < d.iterations; k++) {
-        A.src = k == 0 ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
-        A.dst = k + 1 == d.iterations ? nullptr : c->denoise_scratch + (size_t)(k & 1) * n;
-        A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
-        A.step = 1 << k;
-        launch_atrous_level(A, k == 0, k + 1 == d.iterations, c->stream);
-    }
-    HIP_TRY(hipGetLastError());
-    return RTPBR_OK;
+    return denoise_levels(c, d.iterations, d.demodulate, inv, nullptr);
 }
 
 // ---- temporal reuse (rt_reproject.hip): rtpbr_set_camera + rtpbr_refresh that keeps what the new view can reuse
@@ -1573,10 +1604,7 @@ static int reproject_params(const rtpbr_reproject_params* p, rtpbr_reproject_par
 
 // the states rtpbr_reproject and rtpbr_reproject_scene refuse (`who`: the call's name)
 static int reproject_state(rtpbr_ctx* c, const char* who) {
-    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
-    if (c->world > 1) return fail(RTPBR_ESTATE, "%s works on the whole frame: not with tiles of world > 1", who);
-    for (int i = 0; i < c->n_obj; i++)
-        if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
+    if (int r = whole_frame_state(c, "%s works on the whole frame: not with tiles of world > 1", who)) return r;
     if (!c->history_ok)
         return fail(RTPBR_ESTATE, "%s: set_config / set_scene / set_shape_data / set_env ran since the last refresh or reproject: "
                                   "image_buffer is no history of this scene (call rtpbr_refresh)", who);
@@ -1777,18 +1805,10 @@ extern "C" int rtpbr_set_noise_estimator(rtpbr_ctx* c, const rtpbr_noise_estimat
     return RTPBR_OK;
 }
 
-static int noise_state_check(rtpbr_ctx* c) {
-    if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
-    if (c->world > 1) return fail(RTPBR_ESTATE, NOISE_TILES);
-    for (int i = 0; i < c->n_obj; i++)
-        if (c->obj[i].type == RTPBR_SHAPE_BUNNY && !c->bunny) return fail(RTPBR_ESTATE, "bunny shape needs rtpbr_set_shape_data first");
-    return RTPBR_OK;
-}
-
 extern "C" int rtpbr_noise_estimate(rtpbr_ctx* c, float threshold, rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "noise threshold must be >= 0");
-    if (int r = noise_state_check(c)) return r;
+    if (int r = whole_frame_state(c, NOISE_TILES)) return r;
     if (int r = noise_estimate_enqueue(c, threshold)) return r;
     static_assert(sizeof(NoiseStats) == 128, "one line per shard");
     std::vector<NoiseStats> sh(NOISE_SHARDS);
@@ -1842,6 +1862,7 @@ static int selection_build(rtpbr_ctx* c, SelectArgs& A, bool noisy, uint32_t* n_
 
 extern "C" int rtpbr_select_mask(rtpbr_ctx* c, const uint8_t* mask, size_t nbytes, uint32_t* n_selected) {
     if (!c || !mask || !n_selected) return fail(RTPBR_EINVAL, "null argument");
+    // (not whole_frame_state: a mask needs no shape data, and this call has never asked for it)
     if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
     if (c->world > 1) return fail(RTPBR_ESTATE, SELECT_TILES);
     if (nbytes != (size_t)c->cfg.width * c->cfg.height) return fail(RTPBR_EINVAL, "rtpbr_select_mask: the mask must hold width * height bytes");
@@ -1859,7 +1880,7 @@ extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uin
     if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "noise threshold must be >= 0");
     if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_noisy: dilate must be 0..3");
-    if (int r = noise_state_check(c)) return r;
+    if (int r = whole_frame_state(c, NOISE_TILES)) return r;
     if (int r = noise_estimate_enqueue(c, threshold)) return r;
     if (int r = selection_alloc(c)) return r;
     if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
@@ -1874,6 +1895,7 @@ extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uin
 
 extern "C" int rtpbr_sample_selected(rtpbr_ctx* c, int n) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    // (not whole_frame_state: n is checked between the two states, and missing shape data is sample_call's to refuse)
     if (!c->have_cfg || !c->have_scene || !c->have_cam) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
     if (n < 0) return fail(RTPBR_EINVAL, "n must be >= 0");
     if (c->world > 1) return fail(RTPBR_ESTATE, SELECT_TILES);
@@ -1898,71 +1920,19 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
         d.sigma_depth = RTPBR_DENOISE_GUIDED_DEFAULT_SIGMA_DEPTH;
         d.variance_floor = RTPBR_DENOISE_GUIDED_DEFAULT_VARIANCE_FLOOR;
     }
-    if (d.iterations < 0 || d.iterations > 8) return fail(RTPBR_EINVAL, "denoise iterations must be 0..8");
-    if (d.demodulate != 0 && d.demodulate != 1) return fail(RTPBR_EINVAL, "denoise demodulate must be 0 or 1");
     const float sig[3] = {d.sigma_color, d.sigma_normal, d.sigma_depth};
     float inv[3];
-    for (int k = 0; k < 3; k++) {
-        inv[k] = 1.0f / (sig[k] * sig[k]);
-        if (!(sig[k] > 0.0f) || !std::isfinite(sig[k]) || !std::isfinite(inv[k]))
-            return fail(RTPBR_EINVAL, "denoise sigmas must be finite and > 0 (and not so small that 1/sigma^2 overflows)");
-    }
+    if (int r = denoise_params_check(d.iterations, d.demodulate, sig, inv, 3)) return r;
     const float sc2 = d.sigma_color * d.sigma_color;
     if (!(d.variance_floor > 0.0f) || !std::isfinite(d.variance_floor) || !std::isfinite(1.0f / (sc2 * d.variance_floor)))
         return fail(RTPBR_EINVAL, "denoise variance_floor must be finite and > 0 (and 1/(sigma_color^2 variance_floor) must not overflow)");
-    if (int r = noise_state_check(c)) return r;
+    if (int r = whole_frame_state(c, NOISE_TILES)) return r;
     if (d.iterations > 0) {
         if (int r = noise_estimate_enqueue(c, 0.0f)) return r;
     } else if (!c->feat_valid) {
         if (int r = rtpbr_render_features(c)) return r;
     }
-    if (int r = set_dev(c)) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->denoised) HIP_TRY(hipMalloc(&c->denoised, n * 3 * sizeof(float)));
-    if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
-    if (int r = rt_order_after_reads(c, W_DENOISED)) return r;
-    if (d.iterations == 0) {      // rtpbr_denoise's tone-map-only pass
-        DenoiseArgs Z{};
-        Z.cfg = c->cfg;
-        Z.image_buffer = c->image_buffer;
-        Z.guide_nz = c->feat_guides;
-        Z.albedo = c->feat_albedo;
-        Z.object = c->feat_object;
-        Z.out = c->denoised;
-        Z.demodulate = d.demodulate;
-        Z.width = c->cfg.width;
-        Z.height = c->cfg.height;
-        Z.step = 0;
-        launch_atrous_level(Z, true, true, c->stream);
-        HIP_TRY(hipGetLastError());
-        return RTPBR_OK;
-    }
-    GuidedArgs A{};
-    A.cfg = c->cfg;
-    A.image_buffer = c->image_buffer;
-    A.guide_nz = c->feat_guides;
-    A.albedo = c->feat_albedo;
-    A.object = c->feat_object;
-    A.var0 = c->noise_var;
-    A.out = c->denoised;
-    A.sc2 = sc2;
-    A.in = inv[1];
-    A.iz = inv[2];
-    A.floor = d.variance_floor;
-    A.demodulate = d.demodulate;
-    A.width = c->cfg.width;
-    A.height = c->cfg.height;
-    for (int k = 0; k < d.iterations; k++) {
-        const bool last = k + 1 == d.iterations;
-        A.src = k == 0 ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
-        A.vsrc = k == 0 ? nullptr : c->noise_var + (size_t)(1 + ((k - 1) & 1)) * n;
-        A.dst = last ? nullptr : c->denoise_scratch + (size_t)(k & 1) * n;
-        A.vdst = last ? nullptr : c->noise_var + (size_t)(1 + (k & 1)) * n;
-        A.step = 1 << k;
-        launch_guided_level(A, k == 0, last, c->stream);
-    }
-    HIP_TRY(hipGetLastError());
-    return RTPBR_OK;
+    return denoise_levels(c, d.iterations, d.demodulate, inv, &d);
 }
 
 // ---- the present stage (rt_present.hip): a display buffer -> the packed 8-bit top-down frame, on the device

@@ -1,4 +1,4 @@
-// rt_features.hip — kernels of rtpbr_render_features / rtpbr_denoise (see rt_features.hpp).
+// rt_features.hip — kernels of rtpbr_render_features / rtpbr_denoise and the filter of rtpbr_denoise_guided (see rt_features.hpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_features.hpp"
@@ -82,7 +82,6 @@ __global__ void __launch_bounds__(256) feature_rays(const Params P, const FeatAr
 
 RT_D vec3 xyz(float4 v) { return mk(v.x, v.y, v.z); }
 RT_D float sq3(vec3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }      // |v|^2 in this order, no fma
-RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), c.z / (1.0f + c.z)); }
 RT_D vec3 albedo_clamped(const DenoiseArgs& A, uint32_t i) {
     return mk(fmax_(A.albedo[(size_t)i * 3 + 0], 1e-3f), fmax_(A.albedo[(size_t)i * 3 + 1], 1e-3f), fmax_(A.albedo[(size_t)i * 3 + 2], 1e-3f));
 }
@@ -99,8 +98,12 @@ constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pix
 // A tap is only taken on the centre's own object index and the albedo is a per-object constant (0 on a miss), so a_q = a_p on
 // every tap taken: the albedo term is exactly +0 (e + 0 = e) and the neighbour's demodulation divides by the centre's albedo.
 // Neither is loaded per tap: a tap reads the 4-byte object index (level 0) or the object word carried in the previous level's
-// record (colour, object), then — on the centre's object only — the 16-byte (normal, depth) record.
-template <bool FIRST, bool LAST>
+// record (colour, object), then — on the centre's object only — the 16-byte (normal, depth) record: 36 bytes per tap at level 0,
+// 32 later.
+// GUIDED: the colour term's ic is per pixel, 1 / (sigma_c^2 max(g, floor)), g the 3x3 Gaussian of the level's variance (nine
+// more taps of object word + variance, 8 bytes each), and the variance is filtered beside the colour with the squared weights:
+// 4 more bytes per tap taken (40 / 36), one more 4-byte record written.
+template <bool FIRST, bool LAST, bool GUIDED>
 __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
@@ -127,8 +130,38 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
             A.out[(size_t)i * 3 + 2] = t.z;
         } else {
             A.dst[i] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(NO_SAMPLES));
+            if constexpr (GUIDED) A.vdst[i] = 0.0f;
         }
         return;
+    }
+    float icp = A.ic;
+    if constexpr (GUIDED) {
+        // g: the 3x3 Gaussian of the level's variance over the neighbours with samples on the centre's object (stride 1)
+        float gs = 0.0f, gk = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++) {
+            const int yq = y + dy;
+            if (yq < 0 || yq >= H) continue;
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                const int xq = x + dx;
+                if (xq < 0 || xq >= W) continue;
+                const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+                float vq;
+                if constexpr (FIRST) {
+                    if (A.object[q] != op) continue;
+                    vq = A.var0[q];
+                    if (!(vq >= 0.0f)) continue;
+                } else {
+                    if (__float_as_int(A.src[q].w) != op) continue;
+                    vq = A.vsrc[q];
+                }
+                const float k = (dx == 0 ? 2.0f : 1.0f) * (dy == 0 ? 2.0f : 1.0f);
+                gs = gs + k * vq;
+                gk = gk + k;
+            }
+        }
+        icp = 1.0f / (A.sc2 * fmax_(gs / gk, A.floor));
     }
     const bool need_albedo = (FIRST || LAST) && A.demodulate;
     const vec3 ac = need_albedo ? albedo_clamped(A, i) : mk(1.0f, 1.0f, 1.0f);
@@ -139,7 +172,7 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     const float izp = fmax_(zp, 1e-6f);
     const vec3 rp = tonemap_r(cp);
     const int s = A.step;
-    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    float sw = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sv = 0.0f;
     constexpr float HK[3] = {0.375f, 0.25f, 0.0625f};
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
@@ -151,20 +184,23 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
             if (xq < 0 || xq >= W) continue;
             const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
             vec3 cq;
+            float vq = 0.0f;
             if constexpr (FIRST) {
                 if (A.object[q] != op) continue;
                 const float4 b = A.image_buffer[q];
                 if (!(b.w > 0.0f)) continue;
                 cq = start_colour(b, ac, A.demodulate);
+                if constexpr (GUIDED) vq = A.var0[q];
             } else {
                 const float4 c4 = A.src[q];
                 if (__float_as_int(c4.w) != op) continue;
                 cq = xyz(c4);
+                if constexpr (GUIDED) vq = A.vsrc[q];
             }
             const float4 gq_nz = A.guide_nz[q];
             const float h = HK[dx < 0 ? -dx : dx] * HK[dy < 0 ? -dy : dy];
             const float dz = (zp - gq_nz.w) / izp;
-            float e = sq3(rp - tonemap_r(cq)) * A.ic;
+            float e = sq3(rp - tonemap_r(cq)) * icp;
             e = e + sq3(np - xyz(gq_nz)) * A.in;
             e = e + (dz * dz) * A.iz;
             // (+ |a_p - a_q|^2 ia = + 0: see above)
@@ -175,6 +211,7 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
             sx = sx + w * cq.x;
             sy = sy + w * cq.y;
             sz = sz + w * cq.z;
+            if constexpr (GUIDED) sv = sv + (w * w) * vq;
         }
     }
     vec3 c = mk(sx / sw, sy / sw, sz / sw);
@@ -186,6 +223,7 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
         A.out[(size_t)i * 3 + 2] = t.z;
     } else {
         A.dst[i] = make_float4(c.x, c.y, c.z, __int_as_float(op));
+        if constexpr (GUIDED) A.vdst[i] = sv / (sw * sw);
     }
 }
 
@@ -217,14 +255,20 @@ void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t s
     else hipLaunchKernelGGL((feature_rays<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P, A);
 }
 
-// first && last with step 0 (no level) is the iterations = 0 pass
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, hipStream_t st) {
+template <bool GUIDED>
+static void launch_level(const DenoiseArgs& A, bool first, bool last, unsigned grid, hipStream_t st) {
+    if (first && last) hipLaunchKernelGGL((atrous_level<true, true, GUIDED>), dim3(grid), dim3(256), 0, st, A);
+    else if (first) hipLaunchKernelGGL((atrous_level<true, false, GUIDED>), dim3(grid), dim3(256), 0, st, A);
+    else if (last) hipLaunchKernelGGL((atrous_level<false, true, GUIDED>), dim3(grid), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((atrous_level<false, false, GUIDED>), dim3(grid), dim3(256), 0, st, A);
+}
+
+// step 0 (no level) is the iterations = 0 pass of both calls
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
     if (A.step == 0) hipLaunchKernelGGL(atrous_none, dim3(grid), dim3(256), 0, st, A);
-    else if (first && last) hipLaunchKernelGGL((atrous_level<true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (first) hipLaunchKernelGGL((atrous_level<true, false>), dim3(grid), dim3(256), 0, st, A);
-    else if (last) hipLaunchKernelGGL((atrous_level<false, true>), dim3(grid), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((atrous_level<false, false>), dim3(grid), dim3(256), 0, st, A);
+    else if (guided) launch_level<true>(A, first, last, grid, st);
+    else launch_level<false>(A, first, last, grid, st);
 }
 
 }  // namespace rt

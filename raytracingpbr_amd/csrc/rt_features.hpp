@@ -1,16 +1,22 @@
-// rt_features.hpp — first-hit feature buffers and the edge-aware a-trous denoise (rtpbr_render_features, rtpbr_denoise).
+// rt_features.hpp — first-hit feature buffers and the edge-aware a-trous filter (rtpbr_render_features, rtpbr_denoise and the
+// filter levels of rtpbr_denoise_guided: the plain and the variance-guided filter are instances of one kernel).
 //
 // The reference's post_process() (src/postprocessor.py:24-43) tone-maps the raw Monte Carlo average and leaves a
 // "# ToDo: Post Denoise" where a filter would go.  These kernels fill that gap without touching the sample path:
 //   feature_rays<KIND>   one lane per pixel: the primary ray through the pixel centre (gen_ray with both jitters 0.5, no
 //                        lens offset), marched with the configured march kind; writes albedo / shading normal / depth /
 //                        object index of the first hit (RTPBR_BUF_FEAT_*) and the packed (normal, depth) record the filter reads;
-//   atrous_level<F,L>    one a-trous level (Dammertz et al. 2010, "Edge-avoiding A-Trous wavelet transform for fast global
+//   atrous_level<F,L,G>  one a-trous level (Dammertz et al. 2010, "Edge-avoiding A-Trous wavelet transform for fast global
 //                        illumination filtering"): 5x5 B3-spline taps at stride 2^k, weighted by colour, normal, depth and
 //                        albedo distance (the last is 0 on every tap taken: see atrous_level), skipping other objects and empty
 //                        pixels.  A level's output record is (colour, object index).  The average / demodulation is fused into
-//                        the first level, remodulation and the tone map into the last.
-// The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_denoise) so that a CPU restatement matches bit for bit.
+//                        the first level, remodulation and the tone map into the last.  GUIDED (rtpbr_denoise_guided): the
+//                        colour term is scaled by the 3x3-filtered variance of the centre instead of a uniform sigma, and the
+//                        variance (rt_noise.hip's estimate at level 0) is filtered along with the squared weights; it travels
+//                        in a record of its own, 4 bytes, loaded only on taps that pass the object test.
+//   atrous_none          iterations = 0 of either call: the average, tone-mapped.
+// The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_denoise / rtpbr_denoise_guided) so that the CPU
+// restatements match bit for bit (tests/feature_ref, tests/noise_ref).
 #pragma once
 #include "rt_types.hpp"
 
@@ -36,13 +42,22 @@ struct DenoiseArgs {
     const float4* src;            // levels > 0: the previous level's (colour, object index as bits; -2 = pixel without samples)
     float4* dst;                  // every level but the last
     float* out;                   // the last level: denoised display colour (W,H,3)
-    float ic, in, iz;             // 1/sigma^2 of colour (already x 4^k), normal, depth (the albedo term is 0 on every tap taken)
+    float ic, in, iz;             // 1/sigma^2 of colour (already x 4^k; plain only), normal, depth (the albedo term is 0 on every tap taken)
     int32_t step;                 // 2^k
     int32_t demodulate;
     int32_t width, height;
+    // the guided instances only
+    const float* var0;            // level 0: v of noise_estimate (-1: no samples)
+    const float* vsrc;            // levels > 0: the previous level's variance
+    float* vdst;                  // every level but the last
+    float sc2;                    // sigma_color * sigma_color
+    float floor;                  // variance_floor
 };
 
+// r(c) = c / (1 + c): the compression the filter measures colour distances in and rt_noise.hip estimates the noise of
+RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), c.z / (1.0f + c.z)); }
+
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, hipStream_t st);
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st);
 
 }  // namespace rt

@@ -1,5 +1,5 @@
-// rt_noise.hpp — per-pixel noise estimation and the variance-guided a-trous (rtpbr_noise_update, rtpbr_noise_estimate,
-// rtpbr_denoise_guided).
+// rt_noise.hpp — per-pixel noise estimation (rtpbr_noise_update, rtpbr_noise_estimate).  The variance-guided a-trous of
+// rtpbr_denoise_guided, which reads this estimate, is the GUIDED instance of atrous_level: rt_features.hpp / rt_features.hip.
 //
 //   noise_update        one lane per pixel along the contiguous index: the samples deposited into image_buffer since the
 //                       snapshot are one batch; its mean's LINEAR luminance goes into the moments (sum c L, sum c L^2,
@@ -15,9 +15,6 @@
 //                       degrees of freedom, object) of the tile and an R-pixel halo staged in LDS once, and every young
 //                       temporal pixel (2 <= K < pool_batches) takes max(own, pooled over its (2R+1)^2 window).  Every other
 //                       pixel takes noise_estimate's path.  launch_noise_estimate picks it only when pool_batches > 0.
-//   guided_level<F,L>   atrous_level (rt_features.hip) with the colour term scaled by the 3x3-filtered variance of the centre
-//                       and the variance filtered along with the squared weights.  The variance travels in a record of its
-//                       own, 4 bytes, loaded only on taps that pass the object test.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that a CPU restatement matches bit for bit
 // (tests/noise_ref/noise_ref.c).
 #pragma once
@@ -47,28 +44,7 @@ struct NoiseArgs {
     int32_t pool_radius;          // 1..3
 };
 
-struct GuidedArgs {
-    rtpbr_config cfg;             // tone map
-    const float4* image_buffer;
-    const float4* guide_nz;
-    const float* albedo;
-    const int32_t* object;
-    const float* var0;            // level 0: v of noise_estimate (-1: no samples)
-    const float4* src;            // levels > 0: (colour, object word), as atrous_level
-    const float* vsrc;            // levels > 0: the previous level's variance
-    float4* dst;                  // every level but the last
-    float* vdst;
-    float* out;                   // the last level
-    float sc2;                    // sigma_color * sigma_color
-    float in, iz;                 // 1/sigma^2 of normal and depth
-    float floor;                  // variance_floor
-    int32_t step;
-    int32_t demodulate;
-    int32_t width, height;
-};
-
 void launch_noise_update(const NoiseArgs& A, hipStream_t st);
 void launch_noise_estimate(const NoiseArgs& A, hipStream_t st);
-void launch_guided_level(const GuidedArgs& A, bool first, bool last, hipStream_t st);
 
 }  // namespace rt

@@ -82,9 +82,10 @@ def _cornell(w=W, h=H, spp=4):
     return scene, cfg, r
 
 
-@pytest.mark.parametrize("iterations", [1, 3, 5])
+@pytest.mark.parametrize("iterations", [1, 2, 3, 4, 5])
 @pytest.mark.parametrize("demodulate", [0, 1])
 def test_denoise_bit_identical_to_reference(iterations, demodulate):
+    """(an even number of levels ends on the other half of the levels' ping-pong buffer than an odd one)"""
     scene, cfg, r = _cornell()
     ib = r.image_buffer
     ib[10:14, 20:27] = 0.0             # pixels without samples: shown as post_process shows them, nobody's neighbour

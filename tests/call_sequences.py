@@ -17,6 +17,13 @@ calls, rtpbr_sample_selected, rtpbr_present and a "post" observation of the buff
 against the model of tests/post_model.py (``run_post``), whose refusal codes are written from include/rtpbr.h.  script() itself
 draws what it always drew (tests/test_oracle_call_sequences.py pins a hash of its scripts).
 
+``motion_script(seed)`` draws a third of its operations from script()'s grammar, a third from post_script()'s and a third from
+the two newest stateful calls: rtpbr_reproject_scene — rigid moves on top of the pose the context is in (``posed``), with and
+without a camera, empty moves, turns of 360 degrees, tables that are no rigid motion (``nonrigid``), on every scene of the pool,
+in both normal spaces, under tiles, after a new resolution — and rtpbr_set_noise_tracking with the tracked rtpbr_sample /
+rtpbr_sample_selected calls and what they refuse.  It runs against post_model.MotionModel.  post_script() draws what it drew as
+well (a second pinned hash): its draws are _Grammar.post_op().
+
 The generator keeps clear of the argument checks only the HIP library makes (max_raymarch / max_raytrace <= 0, the per-rank
 pixel limit).  The bunny's weights are a process-wide global in the oracle, so every script that renders the bunny sets the
 weights it means to use on both backends first."""
@@ -85,6 +92,38 @@ def camera(name, offset=(0.0, 0.0, 0.0), vfov=1.0):
     c = scene(name).camera
     lf = tuple(float(np.float32(a + b)) for a, b in zip(c.lookfrom, offset))
     return Camera(lf, tuple(c.lookat), tuple(c.vup), float(np.float32(c.vfov * vfov)), c.aspect, c.aperture, c.focus)
+
+
+def posed(name, pose=()):
+    """scene `name` after the moves of `pose`, applied one after the other: each is {object index: (dpos, drot)} as
+    reproject_scene_ref_lib.moved_scene takes it (a pose is what rtpbr_reproject_scene calls have done since the last set_scene)"""
+    if not pose:
+        return scene(name)
+    key = (name, repr(pose))
+    if key not in _scene_cache:
+        import reproject_scene_ref_lib as rs
+        sc = scene(name)
+        for moves in pose:
+            sc = rs.moved_scene(sc, moves)
+        _scene_cache[key] = sc
+    return _scene_cache[key]
+
+
+def nonrigid(name, pose, what, k=0, other=None):
+    """a table that is no rigid motion of posed(name, pose): the table of scene `other` (another object count), or object k with
+    one scale word, one material word or its type changed"""
+    if what == "count":
+        return scene(other)
+    sc = posed(name, pose)
+    objs = [type(o).from_buffer_copy(bytes(o)) for o in sc.objects]
+    o = objs[k]
+    if what == "scale":
+        o.transform.scale[2] = o.transform.scale[2] * 1.25 + 0.01
+    elif what == "material":
+        o.material.albedo[1] = o.material.albedo[1] * 0.5 + 0.05
+    else:
+        o.type = int(SHAPE.BOX if o.type != SHAPE.BOX else SHAPE.SPHERE)
+    return Scene(objs, sc.scale10, sc.camera, sc.name)
 
 
 def mask(w, h, seed, share):
@@ -171,6 +210,13 @@ class Op:
             return f"r.reproject(cs.camera({a['name']!r}, {a['offset']!r}, {a['vfov']}), **{a['params']!r})"
         if k == "present":
             return f"r.present({a['source']!r}, {a['format']!r}, {a['dither']})"
+        if k == "reproject_scene":
+            cam = "None" if a["cam"] is None else f"cs.camera({a['cam'][0]!r}, {a['cam'][1]!r}, {a['cam'][2]})"
+            table = f"cs.posed({a['name']!r}, {a['pose']!r})" if a["bad"] is None else \
+                f"cs.nonrigid({a['name']!r}, {a['pose']!r}, {a['bad']!r}, {a['k']}, {a['other']!r})"
+            return f"r.reproject_scene({table}, {cam}, **{a['params']!r})"
+        if k == "set_noise_tracking":
+            return f"r.set_noise_tracking({bool(a['mode'])})" if a["mode"] in (0, 1) else f"r.api.call('set_noise_tracking', r._ctx, {a['mode']})"
         return f"r.{k}()"                   # refresh, post_process, noise_update
 
     def __repr__(self):
@@ -178,8 +224,9 @@ class Op:
 
 
 class Script:
-    def __init__(self, seed, base, scene0, ops, jit=0, post=False):
+    def __init__(self, seed, base, scene0, ops, jit=0, post=False, motion=False):
         self.seed, self.base, self.scene0, self.ops, self.jit, self.post = seed, base, scene0, ops, jit, post
+        self.motion = motion                # a motion_script: runs on post_model.MotionModel
 
     def header(self):
         b = self.base
@@ -221,6 +268,10 @@ class _Grammar:
         return seq[int(self.rng.integers(0, len(seq)))]
 
     def add(self, op):
+        if hasattr(self.m, "stamp"):        # the state may stamp an operation of old_op again, or drop it (None)
+            op = self.m.stamp(op)
+            if op is None:
+                return None
         self.ops.append(op)
         if op.expect is None and hasattr(self.m, "note"):
             self.m.note(op)
@@ -334,67 +385,40 @@ class _Grammar:
                 add(Op("bad_scene", EINVAL))
             add(Op("observe", what="all"))
 
-
-def script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
-    """A reproducible call sequence: seed -> Script.  `scenes`: the scene pool (all of SCENES by default); `forms`: the kernel
-    forms set_config may switch between."""
-    g = _Grammar(seed, scenes, forms, SIZES)
-    while len(g.ops) < n_ops:
-        g.old_op()
-    g.add(Op("post_process"))
-    g.add(Op("observe", what="all"))
-    return Script(seed, g.base, g.scene0, g.ops, jit)
-
-
-THRESHOLDS = (0.0, 0.02, 0.08, 0.3)       # fixed: a script prints before it runs, so no quantile of the run's own noise
-GUIDED = ({}, {"iterations": 0}, {"iterations": 0, "demodulate": 1}, {"iterations": 1, "sigma_color": 4.0},
-          {"iterations": 2, "demodulate": 1, "variance_floor": 1e-5}, {"iterations": 3, "sigma_color": 2.0, "sigma_depth": 0.05})
-ESTIMATORS = ((4, 1, 0), (8, 2, 0), (8, 3, 6), (64, 3, 0), (0, 3, 4), (3, 2, 16), None)
-BAD_ESTIMATORS = ((2, 3, 0), (65, 3, 0), (8, 0, 0), (0, 4, 0), (8, 3, -1), (8, 3, 16777217))
-REPROJECT = ({}, {"max_history": 2.0}, {"max_history": 5.0, "depth_tolerance": 0.02}, {"max_history": 1e6, "normal_cos": 0.9},
-             {"max_history": 3.0, "depth_tolerance": 0.0, "normal_cos": -1.0})
-POST_KINDS = ("noise_update", "noise_estimate", "denoise_guided", "set_noise_estimator", "select_mask", "select_noisy", "sample_selected",
-              "reproject", "present")
-
-
-def post_script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
-    """A call sequence over the whole stateful surface: about half of the draws are those of script() (its state changes land
-    between the new calls), the other half are rtpbr_reproject, the noise calls, the estimator setting, the select calls,
-    rtpbr_sample_selected, rtpbr_present and the "post" observation.  The expected code of every new operation comes from
-    post_model.PostState, which follows the script as it is drawn.  Its random stream is its own: script() draws what it drew."""
-    import post_model as pm
-    g = _Grammar(seed, scenes, forms, POST_SIZES, pm.PostState)
-    rng, pick, m, add = g.rng, g.pick, g.m, g.add
-
-    def new(kind, **args):
+    # ---- the draws of post_script (tests/test_oracle_call_sequences.py pins their order and their use of the random stream)
+    def new(self, kind, **args):
+        """an operation of the calls beside the sample path: the state stamps it with the code it must raise"""
         op = Op(kind, **args)
-        op.expect, why = m.refusal(op)
+        op.expect, why = self.m.refusal(op)
         op.why = tuple(why)
-        return add(op)
+        return self.add(op)
 
-    def spp():
+    def spp(self):
+        m, pick = self.m, self.pick
         return int(pick((1, 2)) if m.scene == "bunny" else pick((1, 2, 3)) if m.cfg.kernel_form == 0 else pick((2, 4, 6)))
 
-    def sample(n):
-        add(Op("sample", None if (m.cfg.sky_kind != 1 or m.env) else ESTATE, n=n))
+    def sample(self, n):
+        self.add(Op("sample", None if (self.m.cfg.sky_kind != 1 or self.m.env) else ESTATE, n=n))
 
-    def whole_frame(p=0.75):
-        if m.tiles[3] > 1 and rng.random() < p:
-            add(Op("set_tiles", tiles=(0, 0, 0, 1)))
+    def whole_frame(self, p=0.75):
+        if self.m.tiles[3] > 1 and self.rng.random() < p:
+            self.add(Op("set_tiles", tiles=(0, 0, 0, 1)))
 
-    def clean():
+    def clean(self):
         """no reason for ESTATE may hold where a bad argument is drawn"""
-        return m.tiles[3] == 1
+        return self.m.tiles[3] == 1
 
-    def reproject(**over):
+    def reproject(self, **over):
+        rng, pick, m = self.rng, self.pick, self.m
         scale = float(pick((1.0, 1.0, 3.0)))
         off = tuple(float(np.float32(x * scale)) for x in rng.uniform(-0.3, 0.3, 3))
         vfov = float(pick((1.0, 1.0, 1.0, 1.1, 0.9)))
         a = dict(name=m.scene, offset=off, vfov=vfov, params=dict(pick(REPROJECT)))
         a.update(over)
-        return new("reproject", **a)
+        return self.new("reproject", **a)
 
-    def one(kind):
+    def one(self, kind):
+        rng, pick, m, new = self.rng, self.pick, self.m, self.new
         if kind == "noise_update":
             new(kind)
         elif kind == "noise_estimate":
@@ -408,14 +432,14 @@ def post_script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
         elif kind == "sample_selected":
             new(kind, n=int(pick((0, 1, 2)) if m.scene == "bunny" else pick((0, 1, 1, 2, 3))))
         elif kind == "reproject":
-            reproject()
+            self.reproject()
         elif kind == "present":
             new(kind, source=pick(("pixels", "denoised", "accum")), format=pick(("rgb8", "rgba8")), dither=bool(rng.random() < 0.5))
 
-    while len(g.ops) < n_ops:
-        if rng.random() < 0.5:
-            g.old_op()
-            continue
+    def post_op(self):
+        """one draw of post_script beside old_op: the calls that keep state beside the sample path (one or a few operations)"""
+        rng, pick, m, add, forms = self.rng, self.pick, self.m, self.add, self.forms
+        new, spp, sample, whole_frame, clean, reproject, one = self.new, self.spp, self.sample, self.whole_frame, self.clean, self.reproject, self.one
         u = rng.random()
         if u < 0.17:                                                        # one batch of the noise estimate
             whole_frame()
@@ -515,9 +539,226 @@ def post_script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
                 add(Op("set_env", w=16, h=8, seed=int(rng.integers(0, 3)), f32=False, exposure=1.0, gamma=2.2))
                 m.env = True
             reproject()
-    add(Op("post_process"))
-    add(Op("observe", what="all"))
-    add(Op("observe", what="post"))
+
+    # ---- the draws of motion_script: rtpbr_reproject_scene, rtpbr_set_noise_tracking and the tracked sample calls
+    def set_config(self, **over):
+        cfg = self.m.cfg.copy(**over)
+        self.add(Op("set_config", over=self.m.over(cfg)))
+        self.m.cfg = cfg
+
+    def history(self, p=0.85):
+        """mostly: no reason left to refuse a reprojection, and samples to warp"""
+        rng, m = self.rng, self.m
+        self.whole_frame(0.9)
+        if m.dirty and rng.random() < p:
+            self.add(Op("refresh"))
+            if m.tracking and m.cfg.kernel_form != 0 and 0 in self.forms:
+                self.set_config(kernel_form=0)
+                self.add(Op("refresh"))
+            self.sample(self.spp())
+            if not m.tracking and rng.random() < 0.5:
+                self.new("noise_update")
+
+    def move(self):
+        """one move: {object index: (dpos, drot)} over one to three objects or all of them; now and then empty, now and then a
+        turn of exactly 360 degrees"""
+        rng, pick = self.rng, self.pick
+        n = len(scene(self.m.scene).objects)
+        u = rng.random()
+        if u < 0.08:
+            return {}
+        who = range(n) if u < 0.3 else sorted(int(i) for i in rng.permutation(n)[:int(rng.integers(1, 4))])
+        out = {}
+        for k in who:
+            step = float(pick((0.02, 0.02, 0.05, 0.05, 0.1, 0.2)))
+            dpos = tuple(round(float(x), 3) for x in rng.uniform(-step, step, 3))
+            drot = [0.0, 0.0, 0.0]
+            drot[int(rng.integers(0, 3))] = float(pick((0.0, 0.0, 3.0, -3.0, 7.0, -7.0)))
+            out[k] = (dpos, tuple(drot))
+        if rng.random() < 0.12:
+            k = int(pick(list(out)))
+            drot = [0.0, 0.0, 0.0]
+            drot[int(rng.integers(0, 3))] = 360.0
+            out[k] = (out[k][0] if rng.random() < 0.5 else (0.0, 0.0, 0.0), tuple(drot))
+        return out
+
+    def reproject_scene(self, bad=None, **over):
+        rng, pick, m = self.rng, self.pick, self.m
+        cam = None
+        if rng.random() < 0.5:
+            scale = float(pick((1.0, 1.0, 3.0)))
+            cam = (m.scene, tuple(float(np.float32(x * scale)) for x in rng.uniform(-0.3, 0.3, 3)), float(pick((1.0, 1.0, 1.0, 1.1, 0.9))))
+        a = dict(name=m.scene, pose=m.pose + (self.move(),), cam=cam, params=dict(pick(REPROJECT)), bad=bad, k=0, other=None)
+        if bad == "count":
+            n = len(scene(m.scene).objects)
+            a["other"] = pick([s for s in self.pool if len(scene(s).objects) != n])
+        elif bad is not None:
+            a["pose"], a["k"] = m.pose, int(rng.integers(0, len(scene(m.scene).objects)))
+        a.update(over)
+        return self.new("reproject_scene", **a)
+
+    def tracking_on(self):
+        """tracked mode on where a tracked sample can succeed: whole frame, complete-path form"""
+        m = self.m
+        self.whole_frame(1.0)
+        if m.cfg.kernel_form != 0 and 0 in self.forms:
+            self.set_config(kernel_form=0)
+        if m.cfg.sky_kind == 1 and not m.env:
+            self.set_config(sky_kind=2)
+        if not m.tracking:
+            self.new("set_noise_tracking", mode=1)
+
+    def tracked_n(self):
+        return int(self.pick((1, 2)) if self.m.scene == "bunny" else self.pick((1, 2, 3, 8, 12)))
+
+    def motion_op(self):
+        """one draw of the two newest stateful calls (one or a few operations)"""
+        rng, pick, m, add, new = self.rng, self.pick, self.m, self.add, self.new
+        u = rng.random()
+        if u < 0.36:                                                        # reproject_scene, mostly with history to warp
+            self.history()
+            if not m.state_reasons(Op("reproject_scene")) and rng.random() < 0.17:
+                if rng.random() < 0.2:
+                    self.reproject_scene(params=dict(pick(({"max_history": 0.0}, {"depth_tolerance": -0.1}, {"normal_cos": 1.5}, {"max_history": -2.0}))))
+                else:
+                    op = self.reproject_scene(bad=pick(("count", "scale", "material", "type")))
+                    assert op.expect == EINVAL, op
+                return
+            ok = self.reproject_scene().expect is None
+            v = rng.random()
+            if ok and v < 0.35:                                             # the warped moments take the next batch (or the next samples)
+                self.sample(self.tracked_n() if m.tracking else self.spp())
+                new("noise_update")
+                self.one("noise_estimate")
+            elif ok and v < 0.6:                                            # poses accumulate
+                if rng.random() < 0.5:
+                    self.sample(self.spp())
+                self.reproject_scene()
+                add(Op("observe", what="all"))
+            elif ok and v < 0.8:
+                add(Op("observe", what="all"))
+                if rng.random() < 0.5:
+                    add(Op("observe", what="post"))
+        elif u < 0.46:                                                      # the mode, on and off
+            if m.tiles[3] == 1 and rng.random() < 0.12:
+                new("set_noise_tracking", mode=2)
+            elif m.tracking and rng.random() < 0.75:
+                new("set_noise_tracking", mode=0)
+            else:
+                if rng.random() < 0.8:
+                    self.whole_frame(1.0)
+                new("set_noise_tracking", mode=1)
+                if rng.random() < 0.5:
+                    add(Op("observe", what="post"))
+        elif u < 0.74:                                                      # tracked samples
+            self.tracking_on()
+            v = rng.random()
+            if v < 0.2:                                                     # ... after what acts on the moments and the snapshot
+                what = pick(("write_image", "refresh", "resolution"))
+                if what == "resolution":
+                    w, h = pick([s for s in self.sizes if s != (m.cfg.width, m.cfg.height)])
+                    self.set_config(width=w, height=h)
+                else:
+                    add(Op(what))
+            if v < 0.55 or not (m.selected or self.clean()):
+                self.sample(self.tracked_n())
+                if rng.random() < 0.4:
+                    new("noise_update")
+                    self.sample(self.tracked_n())
+            else:
+                if not m.selected or rng.random() < 0.4:
+                    if rng.random() < 0.6 or "moments" not in m.exists:
+                        new("select_mask", seed=int(rng.integers(0, 1000)), share=float(pick((0.1, 0.3, 0.5, 1.0))))
+                    else:
+                        self.one("select_noisy")
+                new("sample_selected", n=self.tracked_n())
+            w = rng.random()
+            if w < 0.35:
+                self.one("noise_estimate")
+            elif w < 0.5:
+                new("set_noise_estimator", e=pick(ESTIMATORS[:4]))
+                self.one("noise_estimate")
+            if rng.random() < 0.5:
+                add(Op("observe", what=pick(("all", "post"))))
+        elif u < 0.80:                                                      # what tracked mode refuses, tiles and the persistent-ray form
+            self.tracking_on()
+            if rng.random() < 0.5 and 1 in self.forms:
+                self.set_config(kernel_form=1)
+                self.sample(self.tracked_n())
+                if rng.random() < 0.5:
+                    self.set_config(kernel_form=0)
+            else:
+                add(Op("set_tiles", tiles=(int(pick((5, 7, 9, 13, 19))), int(pick((3, 7, 11))), int(rng.integers(0, 2)), 2)))
+                for i in rng.permutation(4)[:3]:
+                    if i == 0:
+                        self.sample(self.tracked_n())
+                    elif i == 1:
+                        new("sample_selected", n=self.tracked_n())
+                    elif i == 2:
+                        new("set_noise_tracking", mode=1)
+                    else:
+                        self.reproject_scene()
+                add(Op("set_tiles", tiles=(0, 0, 0, 1)))
+            add(Op("observe", what="post"))
+        elif u < 0.92:                                                      # both normal rules of the scene gather
+            self.set_config(normal_space=1 - m.cfg.normal_space)
+            if rng.random() < 0.8:
+                self.history(1.0)
+                self.reproject_scene(params=dict(pick(REPROJECT[3:])))
+        else:                                                               # reproject_scene after each call that ends a history
+            self.whole_frame(1.0)
+            add(Op("refresh"))
+            who = pick(("set_config", "set_scene", "set_shape_data", "set_env"))
+            if who == "set_config":
+                self.set_config(exposure=float(pick((0.7, 0.9, 1.1))))
+            elif who == "set_scene":
+                add(Op("set_scene", name=m.scene))
+            elif who == "set_shape_data":
+                v = int(rng.integers(0, 2))
+                add(Op("set_shape_data", variant=v, n=625))
+                m.weights = v
+            else:
+                add(Op("set_env", w=16, h=8, seed=int(rng.integers(0, 3)), f32=False, exposure=1.0, gamma=2.2))
+                m.env = True
+            self.reproject_scene()
+
+def script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
+    """A reproducible call sequence: seed -> Script.  `scenes`: the scene pool (all of SCENES by default); `forms`: the kernel
+    forms set_config may switch between."""
+    g = _Grammar(seed, scenes, forms, SIZES)
+    while len(g.ops) < n_ops:
+        g.old_op()
+    g.add(Op("post_process"))
+    g.add(Op("observe", what="all"))
+    return Script(seed, g.base, g.scene0, g.ops, jit)
+
+
+THRESHOLDS = (0.0, 0.02, 0.08, 0.3)       # fixed: a script prints before it runs, so no quantile of the run's own noise
+GUIDED = ({}, {"iterations": 0}, {"iterations": 0, "demodulate": 1}, {"iterations": 1, "sigma_color": 4.0},
+          {"iterations": 2, "demodulate": 1, "variance_floor": 1e-5}, {"iterations": 3, "sigma_color": 2.0, "sigma_depth": 0.05})
+ESTIMATORS = ((4, 1, 0), (8, 2, 0), (8, 3, 6), (64, 3, 0), (0, 3, 4), (3, 2, 16), None)
+BAD_ESTIMATORS = ((2, 3, 0), (65, 3, 0), (8, 0, 0), (0, 4, 0), (8, 3, -1), (8, 3, 16777217))
+REPROJECT = ({}, {"max_history": 2.0}, {"max_history": 5.0, "depth_tolerance": 0.02}, {"max_history": 1e6, "normal_cos": 0.9},
+             {"max_history": 3.0, "depth_tolerance": 0.0, "normal_cos": -1.0})
+POST_KINDS = ("noise_update", "noise_estimate", "denoise_guided", "set_noise_estimator", "select_mask", "select_noisy", "sample_selected",
+              "reproject", "present")
+
+
+def post_script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
+    """A call sequence over the whole stateful surface: about half of the draws are those of script() (its state changes land
+    between the new calls), the other half are rtpbr_reproject, the noise calls, the estimator setting, the select calls,
+    rtpbr_sample_selected, rtpbr_present and the "post" observation.  The expected code of every new operation comes from
+    post_model.PostState, which follows the script as it is drawn.  Its random stream is its own: script() draws what it drew."""
+    import post_model as pm
+    g = _Grammar(seed, scenes, forms, POST_SIZES, pm.PostState)
+    while len(g.ops) < n_ops:
+        if g.rng.random() < 0.5:
+            g.old_op()
+        else:
+            g.post_op()
+    g.add(Op("post_process"))
+    g.add(Op("observe", what="all"))
+    g.add(Op("observe", what="post"))
     return Script(seed, g.base, g.scene0, g.ops, jit, post=True)
 
 
@@ -526,6 +767,36 @@ def jit_post_script():
     serves, both kernel forms (sample_selected promises the same bits whatever jit says; reproject changes the camera, which a
     baked instance may carry)"""
     return post_script(2020, n_ops=50, jit=-1, scenes=("mixed7", "mixed8"), forms=(0, 1))
+
+
+MOTION_KINDS = ("reproject_scene", "set_noise_tracking")
+
+
+def motion_script(seed, n_ops=60, jit=0, scenes=None, forms=(0, 1)):
+    """A call sequence over the two newest stateful calls: about a third of the draws are those of script(), a third those of
+    post_script() and a third rtpbr_reproject_scene (rigid moves on top of the pose so far, with and without a camera, tables that
+    are no rigid motion), rtpbr_set_noise_tracking and tracked rtpbr_sample / rtpbr_sample_selected calls with what they refuse.
+    Expected codes come from post_model.MotionState; the script runs on post_model.MotionModel.  Its random stream is its own."""
+    import post_model as pm
+    g = _Grammar(seed, scenes, forms, POST_SIZES, pm.MotionState)
+    while len(g.ops) < n_ops:
+        u = g.rng.random()
+        if u < 0.3:
+            g.old_op()
+        elif u < 0.6:
+            g.post_op()
+        else:
+            g.motion_op()
+    g.add(Op("post_process"))
+    g.add(Op("observe", what="all"))
+    g.add(Op("observe", what="post"))
+    return Script(seed, g.base, g.scene0, g.ops, jit, post=True, motion=True)
+
+
+def jit_motion_script():
+    """the motion script through run-time compiled instances: jit = -1 over two scenes that no ahead-of-time specialisation serves,
+    both kernel forms (a moved table is a scene the instance was not acquired for; a tracked launch keeps item-linear staging)"""
+    return motion_script(3030, n_ops=40, jit=-1, scenes=("mixed7", "mixed8"), forms=(0, 1))
 
 
 # ------------------------------------------------------------------ the lock-step driver
@@ -710,7 +981,7 @@ def replay(s, upto=None, threads=0):
     from raytracingpbr_amd import Renderer
     if s.post:
         import post_model as pm
-        a, b = new_renderer(s, Renderer), pm.PostModel(s, threads)
+        a, b = new_renderer(s, Renderer), pm.model(s, threads)
         try:
             return run_post(s, a, b, upto)
         finally:
@@ -751,6 +1022,14 @@ def _apply_post(op, r):
             r.reproject(camera(a["name"], a["offset"], a["vfov"]), **a["params"])
         elif k == "present":
             r.present(a["source"], a["format"], a["dither"])
+        elif k == "reproject_scene":
+            table = posed(a["name"], a["pose"]) if a["bad"] is None else nonrigid(a["name"], a["pose"], a["bad"], a["k"], a["other"])
+            r.reproject_scene(table, None if a["cam"] is None else camera(*a["cam"]), **a["params"])
+        elif k == "set_noise_tracking":
+            if a["mode"] in (0, 1):
+                r.set_noise_tracking(bool(a["mode"]))
+            else:
+                r.api.call("set_noise_tracking", r._ctx, a["mode"])
         else:
             res = _apply(op, r)
             return (None if res is None else res[1]), {}
@@ -786,7 +1065,7 @@ def run_post(s, hip, model, upto=None):
         lines = [f"post call sequence seed {s.seed}, operation #{i}: {what}", s.header(),
                  f"operations since " + (f"{key} last matched" if key else "the start") + f" (#{start + 1}..#{i}):"]
         lines += [f"  [{j}] {s.ops[j]!r}" for j in range(start + 1, i + 1)]
-        lines.append(f"replay: call_sequences.replay(call_sequences.post_script({s.seed}, ...), upto={i + 1})")
+        lines.append(f"replay: call_sequences.replay(call_sequences.{'motion' if s.motion else 'post'}_script({s.seed}, ...), upto={i + 1})")
         raise Mismatch("\n".join(lines))
 
     for i, op in enumerate(ops):

@@ -1,7 +1,7 @@
 """State changes between C-ABI calls, HIP against the CPU oracle (run with -m gpu): the random call sequences of
-tests/call_sequences.py in lock step, the post sequences (reproject, noise, selection, present) against the model of
-tests/post_model.py, one sequence of each kind through the run-time compiled instances, and named regressions for what such
-sequences found.  Frames are tiny and max_raytrace <= 4, so the oracle answers every observation in milliseconds."""
+tests/call_sequences.py in lock step, the post sequences (reproject, noise, selection, present) and the motion sequences
+(reproject_scene, set_noise_tracking, tracked sample calls) against the models of tests/post_model.py, one sequence of each kind
+through the run-time compiled instances, and named regressions for what such sequences found.  Frames are tiny and max_raytrace <= 4, so the oracle answers every observation in milliseconds."""
 import numpy as np
 import pytest
 
@@ -52,7 +52,7 @@ def test_jit_call_sequence_matches_oracle(tmp_path, monkeypatch):
 
 
 def _run_post(s):
-    a, b = cs.new_renderer(s, Renderer), pm.PostModel(s)
+    a, b = cs.new_renderer(s, Renderer), pm.model(s)
     try:
         return cs.run_post(s, a, b), a
     finally:
@@ -74,6 +74,24 @@ def test_jit_post_sequence_matches_model(tmp_path, monkeypatch):
     monkeypatch.setenv("RTPBR_JIT_CACHE", str(tmp_path))
     seen, _ = _run_post(cs.jit_post_script())
     assert any(k == "motion" for _, k, _ in seen)
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_motion_sequence_matches_model(seed):
+    """~60 random operations, a third of them those of the first sequences, a third those of the post sequences, a third
+    rtpbr_reproject_scene on an accumulating pose (fuzz scenes, both normal spaces, tables that are no rigid motion),
+    rtpbr_set_noise_tracking and tracked rtpbr_sample / rtpbr_sample_selected calls with what they refuse: every call refused or
+    accepted as include/rtpbr.h says, every value it returns or leaves behind bit for bit the model's"""
+    seen, _ = _run_post(cs.motion_script(seed))
+    assert any(k == "image_buffer" for _, k, _ in seen) and any(k == "moments" for _, k, _ in seen)
+
+
+def test_jit_motion_sequence_matches_model(tmp_path, monkeypatch):
+    """the same through run-time compiled instances (jit = -1, 7 and 8 mixed shapes, both kernel forms): a moved table is a scene
+    the instance was not acquired for"""
+    monkeypatch.setenv("RTPBR_JIT_CACHE", str(tmp_path))
+    seen, _ = _run_post(cs.jit_motion_script())
+    assert any(k == "motion" for _, k, _ in seen) and any(k == "moments" for _, k, _ in seen)
 
 
 def _counters(r):

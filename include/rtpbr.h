@@ -233,7 +233,11 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_SELECTION    = 13,  /* (W,H)   u8  1 = selected: what rtpbr_sample_selected traces                           */
        /* the packed 8-bit frame (rtpbr_present): allocated on the first present, RTPBR_ESTATE before; output only.  NOT in the
         * field layout: (H,W,C) u8, row 0 = the TOP row of the picture, x fastest, C = 3 or 4 as the last present said */
-       RTPBR_BUF_PRESENT      = 14 };
+       RTPBR_BUF_PRESENT      = 14,
+       /* the two halves and the error estimate of the denoised frame (rtpbr_half_update / rtpbr_denoise_error): each allocated on
+        * the first such call, RTPBR_ESTATE before; outputs only */
+       RTPBR_BUF_HALF_BUFFER  = 15,  /* (W,H,4) f32 half A's (sum r, sum g, sum b, count); half B = image_buffer - A per component */
+       RTPBR_BUF_DENOISED_ERROR = 16 }; /* (W,H) f32 estimated standard deviation of lum(rtpbr_denoise's display colour)         */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -637,6 +641,70 @@ int rtpbr_set_noise_tracking(rtpbr_ctx* ctx, int mode);
 int rtpbr_select_mask(rtpbr_ctx* ctx, const uint8_t* mask, size_t nbytes, uint32_t* n_selected);
 int rtpbr_select_noisy(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 int rtpbr_sample_selected(rtpbr_ctx* ctx, int n);
+
+/* ---- The error of the DENOISED frame from two half buffers, and sampling driven by it.
+ *
+ * rtpbr_noise_estimate and rtpbr_select_noisy describe the raw average in image_buffer; a host that displays
+ * RTPBR_BUF_DENOISED_PIXELS would sample on long after that picture stopped changing.  Here the samples are kept in two
+ * independent halves A and B, both are filtered exactly as rtpbr_denoise filters image_buffer, and the difference of the two
+ * results measures the variance of the filtered full frame — correlations between neighbours included, whatever the filter does.
+ * IT MEASURES VARIANCE ONLY: the filter's bias (blur inside one object) is the same in both halves and no difference of them
+ * sees it.  The estimate answers "has the denoised picture stopped moving", not "is it right" (on Cornell
+ * v3 the denoised frame's error against the converged frame stops falling near 0.066 while the estimate goes to 0).
+ * lum(c) = (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z as in the noise section; every operation is f32, nothing fused.
+ *
+ * rtpbr_half_update deals what was deposited into image_buffer since the last update to one half.  Half A is stored
+ *   (RTPBR_BUF_HALF_BUFFER); half B never is: it is image_buffer - A per component.  A and an internal snapshot sh are allocated
+ *   zeroed on the first call, so everything accumulated until then is the first batch.  Per pixel, with b = image_buffer:
+ *     d = b - sh per component;
+ *     if d.w > 0: cB = sh.w - A.w; if A.w <= cB then A = A + d per component (otherwise the batch stays in B);
+ *     sh = b in every case.
+ *   The half with fewer samples takes the batch, so equal batches alternate A, B, A, ... per pixel, and a pixel
+ *   rtpbr_sample_selected skipped keeps its bits.  Like rtpbr_noise_update the call flushes lazy shading, is ordered behind
+ *   asynchronous reads of RTPBR_BUF_HALF_BUFFER, is asynchronous and writes nothing else; it is independent of the moments and
+ *   their snapshot.  Once A exists: rtpbr_refresh zeroes A and sh; rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) zeroes A and sets
+ *   sh to the written data (written data is no batch: it lies in B); rtpbr_reproject and rtpbr_reproject_scene zero A after the
+ *   gather and set sh to the warped image_buffer (the history is one body of samples: it lies in B; A is not warped).  Until
+ *   their next batch such pixels have an empty half and count as not estimated below.  rtpbr_set_config with a new resolution
+ *   frees both buffers.  image_buffer, the motion buffer, the moments and the features are bit for bit what they are without.
+ *   Errors: RTPBR_EINVAL for NULL; RTPBR_ESTATE before rtpbr_set_config and with tiles of world > 1.
+ *
+ * rtpbr_denoise_error writes RTPBR_BUF_DENOISED_ERROR and, if out != NULL, the statistics; it blocks like rtpbr_noise_estimate.
+ *   p == NULL: rtpbr_denoise's defaults; e == NULL: radius = RTPBR_ERROR_DEFAULT_RADIUS.  In order: lazy shading is flushed, the
+ *   call is ordered behind asynchronous reads of the error buffer, the features are rendered if stale; DA = rtpbr_denoise's
+ *   filter with p applied to A in place of image_buffer, DB = the same applied to B = image_buffer - A (materialised per
+ *   component), "has samples" meaning that buffer's own count > 0 in either run.  RTPBR_BUF_DENOISED_PIXELS, image_buffer, the
+ *   moments, RTPBR_BUF_NOISE and the work counters are untouched.  Per pixel q, cA = A.w, cB = image_buffer.w - A.w:
+ *     q is valid when cA > 0 and cB > 0;
+ *     dl = lum(DA_q) - lum(DB_q);   e_q = fmaxf((dl * dl) * ((cA * cB) / ((cA + cB) * (cA + cB))), 0)   (a NaN gives 0).
+ *   (With s2 the per-sample variance of the filtered value E[(DA - DB)^2] = s2 (1/cA + 1/cB) and the full frame's variance is
+ *   s2 / (cA + cB): hence the factor, 1/4 for equal halves.)  Per pixel p: S = 0, n = 0; over q = p + (dx, dy), dy = -R..R
+ *   (outer), dx = -R..R (inner), inside the frame, on p's RTPBR_BUF_FEAT_OBJECT, valid: S = S + e_q, n = n + 1;
+ *     error_p = sqrt(S / n), correctly rounded, when p itself is valid; otherwise error_p = 0 and p is not estimated.
+ *   One degree of freedom per pixel, averaged over the window: calibrated within 0.9 .. 1.2 of the empirical variance of the
+ *   denoised luminance on Cornell v3.  pixels_estimated counts the valid pixels, pixels_above those with
+ *   error > threshold, max_noise is the largest value.
+ *   Errors: RTPBR_EINVAL for a NULL context, parameters rtpbr_denoise refuses, a radius outside 1..3, a threshold that is not
+ *   >= 0; RTPBR_ESTATE before set_config / set_scene / set_camera, with tiles of world > 1 and before the first rtpbr_half_update.
+ *
+ * rtpbr_select_error is rtpbr_select_noisy's counterpart: same list order, same blocking, same RTPBR_BUF_SELECTION.  It reads
+ *   RTPBR_BUF_DENOISED_ERROR as the last rtpbr_denoise_error wrote it (it does not recompute it: that costs two filter runs) and
+ *   selects pixel p when, with the current buffer contents,
+ *     image_buffer[p].w > 0 is false, or
+ *     A[p].w > 0 is false, or image_buffer[p].w - A[p].w > 0 is false (a half is empty), or
+ *     some pixel q inside the frame with max(|dx|, |dy|) <= dilate has error[q] > threshold          (dilate 0..3), or
+ *     image_buffer[p].w < (float)min_samples                   (rtpbr_set_noise_estimator).
+ *   Errors as rtpbr_select_noisy, and RTPBR_ESTATE before the first rtpbr_denoise_error.
+ * A refused call changes nothing. */
+typedef struct rtpbr_error_params {   /* 4-byte members, no padding */
+    int32_t radius;        /* 1..3: the window of the error estimate is (2 radius + 1)^2 */
+} rtpbr_error_params;
+/* Default (e == NULL): the 5x5 window of the calibration in DESIGN.md section 6j.
+ * raytracingpbr_amd.dataclass.ErrorParams.DEFAULTS mirrors it (tests/test_half_ref.py checks). */
+#define RTPBR_ERROR_DEFAULT_RADIUS 2
+int rtpbr_half_update(rtpbr_ctx* ctx);
+int rtpbr_denoise_error(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_error_params* e, float threshold, rtpbr_noise_stats* out);
+int rtpbr_select_error(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 
 /* ---- The present stage: a display buffer becomes a packed 8-bit frame on the device, in one kernel.
  *

@@ -17,6 +17,7 @@
 #include "rt_features.hpp"
 #include "rt_reproject.hpp"
 #include "rt_noise.hpp"
+#include "rt_half.hpp"
 #include "rt_present.hpp"
 #include "rt_select.hpp"
 
@@ -24,6 +25,8 @@ using namespace rt;
 
 static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_error);
 static int noise_alloc(rtpbr_ctx* c);
+static int half_restart(rtpbr_ctx* c, bool snapshot_image);
+static int noise_stats_read(rtpbr_ctx* c, rtpbr_noise_stats* out);
 extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value);
 extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world);
 extern "C" int rtpbr_set_camera(rtpbr_ctx* c, const rtpbr_camera* cam);
@@ -138,7 +141,19 @@ static void free_noise(rtpbr_ctx* c) {
     c->noise_map = c->noise_var = nullptr;
 }
 
-// the selection of rtpbr_select_mask / rtpbr_select_noisy (allocated on the first select call)
+// buffers of rtpbr_half_update / rtpbr_denoise_error (allocated on first use)
+static void free_half(rtpbr_ctx* c) {
+    (void)hipFree(c->half_a);
+    (void)hipFree(c->half_snapshot);
+    (void)hipFree(c->half_b);
+    (void)hipFree(c->half_da);
+    (void)hipFree(c->half_db);
+    (void)hipFree(c->denoised_error);
+    c->half_a = c->half_snapshot = c->half_b = nullptr;
+    c->half_da = c->half_db = c->denoised_error = nullptr;
+}
+
+// the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (allocated on the first select call)
 static void free_selection(rtpbr_ctx* c) {
     (void)hipFree(c->sel_mask);
     (void)hipFree(c->sel_list);
@@ -177,6 +192,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->march_out);
     free_features(c);
     free_noise(c);
+    free_half(c);
     free_selection(c);
     free_present(c);
     (void)hipFree(c->noise_stats);
@@ -279,6 +295,7 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
         c->diff_pixels = nullptr;
         free_features(c);
         free_noise(c);
+        free_half(c);
         free_selection(c);
         free_present(c);
         HIP_TRY(hipMalloc(&c->image_buffer, n * sizeof(float4)));
@@ -717,7 +734,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b <= RTPBR_BUF_PRESENT; b++)
+    for (int b = 0; b <= RTPBR_BUF_DENOISED_ERROR; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -745,6 +762,7 @@ extern "C" int rtpbr_refresh(rtpbr_ctx* c) {
         HIP_TRY(hipMemsetAsync(c->noise_moments, 0, n * sizeof(float4), c->stream));
         HIP_TRY(hipMemsetAsync(c->noise_snapshot, 0, n * sizeof(float4), c->stream));
     }
+    if (int r = half_restart(c, false)) return r;      // the halves start over with the image
     launch_refresh(c->image_buffer, c->ray_buffer, c->diff_buffer, c->diff_pixels, c->cfg.adaptive_sampling, n, c->stream);
     HIP_TRY(hipGetLastError());
     c->history_ok = true;
@@ -1521,16 +1539,20 @@ static int denoised_alloc(rtpbr_ctx* c, int iterations) {
 // The levels of either filter, after every refusal: level k reads half (k - 1) & 1 of denoise_scratch and writes half k & 1; the
 // first reads image_buffer, the last writes denoised.  g != nullptr: the guided kernel, whose variance goes the same way through
 // the two planes of noise_var behind the estimate's (plane 0).  No level: the tone-map-only pass, the same for both.
-static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g) {
-    if (int r = denoised_alloc(c, iterations)) return r;
+// in / out (rtpbr_denoise_error): the filter of another (sum r, sum g, sum b, count) buffer into another display buffer; the caller
+// has allocated the ping-pong.
+static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
+                          const float4* in = nullptr, float* out = nullptr) {
+    if (!out)
+        if (int r = denoised_alloc(c, iterations)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     DenoiseArgs A{};
     A.cfg = c->cfg;
-    A.image_buffer = c->image_buffer;
+    A.image_buffer = in ? in : c->image_buffer;
     A.guide_nz = c->feat_guides;
     A.albedo = c->feat_albedo;
     A.object = c->feat_object;
-    A.out = c->denoised;
+    A.out = out ? out : c->denoised;
     A.in = inv[1];
     A.iz = inv[2];
     A.demodulate = demodulate;
@@ -1559,9 +1581,8 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
     return RTPBR_OK;
 }
 
-extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
-    if (!c) return fail(RTPBR_EINVAL, "null ctx");
-    rtpbr_denoise_params d;
+// p (NULL: the defaults) -> d and inv[k] = 1 / sigma_k^2, after the parameter checks of rtpbr_denoise
+static int denoise_params(const rtpbr_denoise_params* p, rtpbr_denoise_params& d, float* inv) {
     if (p) {
         d = *p;
     } else {
@@ -1573,11 +1594,18 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
         d.sigma_albedo = RTPBR_DENOISE_DEFAULT_SIGMA_ALBEDO;
     }
     const float sig[4] = {d.sigma_color, d.sigma_normal, d.sigma_depth, d.sigma_albedo};
-    float inv[4];
     if (int r = denoise_params_check(d.iterations, d.demodulate, sig, inv, 4)) return r;
     // the colour weight alone grows, by 4 per level: it must stay finite up to the last level, 4^(iterations-1)
     if (d.iterations > 1 && !std::isfinite(inv[0] * (float)(1u << (2 * (d.iterations - 1)))))
         return fail(RTPBR_EINVAL, "denoise sigma_color too small for this many levels: 1/sigma^2 * 4^(iterations-1) overflows");
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_params d;
+    float inv[4];
+    if (int r = denoise_params(p, d, inv)) return r;
     if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
@@ -1675,6 +1703,7 @@ static int reproject_run(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_repr
     if (objs) launch_reproject_scene(A, c->scene_motion, n_objs, c->stream);
     else launch_reproject(A, c->stream);
     HIP_TRY(hipGetLastError());
+    if (int r = half_restart(c, true)) return r;      // the warped history is one body of samples: it lies in B
     c->history_ok = true;
     return RTPBR_OK;
 }
@@ -1810,6 +1839,11 @@ extern "C" int rtpbr_noise_estimate(rtpbr_ctx* c, float threshold, rtpbr_noise_s
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "noise threshold must be >= 0");
     if (int r = whole_frame_state(c, NOISE_TILES)) return r;
     if (int r = noise_estimate_enqueue(c, threshold)) return r;
+    return noise_stats_read(c, out);
+}
+
+// the statistics a kernel left in noise_stats come back and are folded (blocks)
+static int noise_stats_read(rtpbr_ctx* c, rtpbr_noise_stats* out) {
     static_assert(sizeof(NoiseStats) == 128, "one line per shard");
     std::vector<NoiseStats> sh(NOISE_SHARDS);
     HIP_TRY(hipMemcpyAsync(sh.data(), c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats), hipMemcpyDeviceToHost, c->stream));
@@ -1841,7 +1875,7 @@ static int selection_alloc(rtpbr_ctx* c) {
 }
 
 // mark, scan, scatter on the stream, then the list's length (4 bytes) comes back: blocks
-static int selection_build(rtpbr_ctx* c, SelectArgs& A, bool noisy, uint32_t* n_selected) {
+static int selection_build(rtpbr_ctx* c, SelectArgs& A, int rule, uint32_t* n_selected) {
     A.mask = c->sel_mask;
     A.blocks = c->sel_blocks;
     A.list = c->sel_list;
@@ -1849,7 +1883,7 @@ static int selection_build(rtpbr_ctx* c, SelectArgs& A, bool noisy, uint32_t* n_
     A.height = c->cfg.height;
     c->have_selection = false;      // (until the new list's length is known)
     c->sel_count = 0;
-    launch_select(A, noisy, c->stream);
+    launch_select(A, rule, c->stream);
     HIP_TRY(hipGetLastError());
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, c->sel_blocks + select_blocks(c->cfg.width, c->cfg.height), sizeof total, hipMemcpyDeviceToHost, c->stream));
@@ -1873,7 +1907,7 @@ extern "C" int rtpbr_select_mask(rtpbr_ctx* c, const uint8_t* mask, size_t nbyte
     HIP_TRY(hipMemcpyAsync(c->sel_mask, mask, nbytes, hipMemcpyHostToDevice, c->stream));
     SelectArgs A{};
     A.host_mask = c->sel_mask;
-    return selection_build(c, A, false, n_selected);
+    return selection_build(c, A, SELECT_MASK, n_selected);
 }
 
 extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
@@ -1890,7 +1924,7 @@ extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uin
     A.threshold = threshold;
     A.dilate = dilate;
     A.min_samples = (float)c->noise_estimator.min_samples;
-    return selection_build(c, A, true, n_selected);
+    return selection_build(c, A, SELECT_NOISY, n_selected);
 }
 
 extern "C" int rtpbr_sample_selected(rtpbr_ctx* c, int n) {
@@ -1933,6 +1967,120 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
         if (int r = rtpbr_render_features(c)) return r;
     }
     return denoise_levels(c, d.iterations, d.demodulate, inv, &d);
+}
+
+// ---- the two-half error estimate of the denoised frame (rt_half.hip)
+enum : unsigned { W_HALF = 1u << RTPBR_BUF_HALF_BUFFER, W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR };
+static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
+
+// What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
+// snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.
+static int half_restart(rtpbr_ctx* c, bool snapshot_image) {
+    if (!c->half_a) return RTPBR_OK;
+    if (int r = rt_order_after_reads(c, W_HALF)) return r;
+    const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
+    HIP_TRY(hipMemsetAsync(c->half_a, 0, bytes, c->stream));
+    if (snapshot_image) HIP_TRY(hipMemcpyAsync(c->half_snapshot, c->image_buffer, bytes, hipMemcpyDeviceToDevice, c->stream));
+    else HIP_TRY(hipMemsetAsync(c->half_snapshot, 0, bytes, c->stream));
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_half_update(rtpbr_ctx* c) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, HALF_TILES);
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->half_a) {
+        HIP_TRY(hipMalloc(&c->half_a, n * sizeof(float4)));
+        HIP_TRY(hipMemsetAsync(c->half_a, 0, n * sizeof(float4), c->stream));
+    }
+    if (!c->half_snapshot) {
+        HIP_TRY(hipMalloc(&c->half_snapshot, n * sizeof(float4)));
+        HIP_TRY(hipMemsetAsync(c->half_snapshot, 0, n * sizeof(float4), c->stream));
+    }
+    if (int r = rt_order_after_reads(c, W_HALF)) return r;
+    HalfArgs A{};
+    A.image_buffer = c->image_buffer;
+    A.snapshot = c->half_snapshot;
+    A.half_a = c->half_a;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    launch_half_update(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_error_params* e, float threshold,
+                                   rtpbr_noise_stats* out) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_params d;
+    float inv[4];
+    if (int r = denoise_params(p, d, inv)) return r;
+    const int radius = e ? e->radius : RTPBR_ERROR_DEFAULT_RADIUS;
+    if (radius < 1 || radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_error: radius must be 1..3");
+    if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
+    if (int r = whole_frame_state(c, HALF_TILES)) return r;
+    if (!c->half_a) return fail(RTPBR_ESTATE, "rtpbr_denoise_error: no half buffer yet (rtpbr_half_update first)");
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, n * sizeof(float4)));
+    if (!c->half_da) HIP_TRY(hipMalloc(&c->half_da, n * 3 * sizeof(float)));
+    if (!c->half_db) HIP_TRY(hipMalloc(&c->half_db, n * 3 * sizeof(float)));
+    if (!c->denoised_error) HIP_TRY(hipMalloc(&c->denoised_error, n * sizeof(float)));
+    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
+    if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
+    if (int r = rt_order_after_reads(c, W_ERROR)) return r;
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;
+    HalfArgs S{};
+    S.image_buffer = c->image_buffer;
+    S.half_a = c->half_a;
+    S.half_b = c->half_b;
+    S.width = c->cfg.width;
+    S.height = c->cfg.height;
+    launch_half_subtract(S, c->stream);
+    // the same filter on either half: "has samples" is the half's own count
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_a, c->half_da)) return r;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_b, c->half_db)) return r;
+    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    ErrorArgs A{};
+    A.da = c->half_da;
+    A.db = c->half_db;
+    A.half_a = c->half_a;
+    A.half_b = c->half_b;
+    A.object = c->feat_object;
+    A.error = c->denoised_error;
+    A.stats = c->noise_stats;
+    A.threshold = threshold;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    A.radius = radius;
+    launch_half_error(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    return noise_stats_read(c, out);
+}
+
+extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
+    if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
+    if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
+    if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_error: dilate must be 0..3");
+    if (int r = whole_frame_state(c, HALF_TILES)) return r;
+    if (!c->denoised_error || !c->half_a) return fail(RTPBR_ESTATE, "rtpbr_select_error: no error estimate yet (rtpbr_denoise_error first)");
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    if (int r = selection_alloc(c)) return r;
+    if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
+    SelectArgs A{};
+    A.image_buffer = c->image_buffer;
+    A.noise = c->denoised_error;
+    A.half_a = c->half_a;
+    A.threshold = threshold;
+    A.dilate = dilate;
+    A.min_samples = (float)c->noise_estimator.min_samples;
+    return selection_build(c, A, SELECT_ERROR, n_selected);
 }
 
 // ---- the present stage (rt_present.hip): a display buffer -> the packed 8-bit top-down frame, on the device
@@ -1996,12 +2144,15 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_NOISE: *p = c->noise_map; *n = np * 4; break;
         case RTPBR_BUF_SELECTION: *p = c->sel_mask; *n = np; break;
         case RTPBR_BUF_PRESENT: *p = c->present; *n = np * (size_t)c->present_channels; break;
+        case RTPBR_BUF_HALF_BUFFER: *p = c->half_a; *n = np * 16; break;
+        case RTPBR_BUF_DENOISED_ERROR: *p = c->denoised_error; *n = np * 4; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
     // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate,
-    // the packed frame from the first rtpbr_present)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present first");
+    // the packed frame from the first rtpbr_present, the half buffer from the first rtpbr_half_update, the error map from the first
+    // rtpbr_denoise_error)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error first");
     return 0;
 }
 
@@ -2102,8 +2253,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_PRESENT)
-        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection and present buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_DENOISED_ERROR)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half and error buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;
@@ -2112,6 +2263,8 @@ extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size
     HIP_TRY(hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, c->stream));
     if (which == RTPBR_BUF_IMAGE_BUFFER && c->noise_snapshot)      // written data is no batch of the noise estimate
         HIP_TRY(hipMemcpyAsync(c->noise_snapshot, c->image_buffer, n, hipMemcpyDeviceToDevice, c->stream));
+    if (which == RTPBR_BUF_IMAGE_BUFFER)                           // ... and none of the halves: it lies in B
+        if (int r = half_restart(c, true)) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RTPBR_OK;
 }

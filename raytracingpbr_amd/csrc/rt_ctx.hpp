@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "rt_device.hpp"
+#include "rt_half.hpp"
 #include "rt_noise.hpp"
 #include "rt_present.hpp"
 #include "rt_select.hpp"
@@ -178,7 +179,7 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[15] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[17] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
     float* feat_albedo = nullptr;      // (W,H,3)
@@ -206,7 +207,15 @@ struct rtpbr_ctx {
     int noise_tracking = RTPBR_NOISE_TRACK_OFF;      // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
     rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
                                           RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};      // rtpbr_set_noise_estimator: plain state, kept across refresh / set_config / set_scene / reproject
-    // the selection of rtpbr_select_mask / rtpbr_select_noisy (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
+    // the two halves and the error estimate of the denoised frame (rt_half.hip): half_a and half_snapshot from the first rtpbr_half_update
+    // on, the others from the first rtpbr_denoise_error on; freed with the context or a new resolution
+    float4* half_a = nullptr;          // (W,H): RTPBR_BUF_HALF_BUFFER
+    float4* half_snapshot = nullptr;   // (W,H): image_buffer at the last rtpbr_half_update
+    float4* half_b = nullptr;          // (W,H): image_buffer - half_a, materialised per rtpbr_denoise_error
+    float* half_da = nullptr;          // (W,H,3): the filter's display colour of half A
+    float* half_db = nullptr;          // (W,H,3): ... of half B
+    float* denoised_error = nullptr;   // (W,H): RTPBR_BUF_DENOISED_ERROR
+    // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
     uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
     uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)
     uint32_t* sel_blocks = nullptr;    // per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them

@@ -7,7 +7,6 @@
 
 namespace rt {
 
-RT_D float nz_lum(vec3 c) { return (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z; }
 // compressed luminance of the mean of a texel (sum r, sum g, sum b, count), count > 0
 RT_D float nz_lum_of_mean(float x, float y, float z, float cnt) { return nz_lum(tonemap_r(mk(x / cnt, y / cnt, z / cnt))); }
 
@@ -77,31 +76,6 @@ RT_D float nz_spatial(const NoiseArgs& A, int x, int y, int op) {
     return cn >= 2.0f ? fmax_((s2 - (s1 * s1) / cn) / (cn - 1.0f), 0.0f) : 0.0f;
 }
 
-// the statistics, by every lane of the block (blk: three zeroed LDS words, a barrier since): per wave a ballot and a butterfly
-// maximum, per block three LDS atomics per wave, then three global ones into the block's shard
-RT_D void nz_stats(const NoiseArgs& A, uint32_t* blk, bool estimated, float noise, uint32_t block) {
-    const bool above = estimated && noise > A.threshold;
-    const unsigned long long m_est = __ballot(estimated), m_abv = __ballot(above);
-    uint32_t mx = __float_as_uint(noise);       // >= +0: the bit patterns order like the values
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)mx, o, 64);
-        mx = other > mx ? other : mx;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&blk[0], (uint32_t)__popcll(m_est));
-        atomicAdd(&blk[1], (uint32_t)__popcll(m_abv));
-        atomicMax(&blk[2], mx);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        NoiseStats* s = A.stats + (block % NOISE_SHARDS);
-        if (blk[0]) atomicAdd(&s->estimated, blk[0]);
-        if (blk[1]) atomicAdd(&s->above, blk[1]);
-        if (blk[2]) atomicMax(&s->max_bits, blk[2]);
-    }
-}
-
 // One lane per pixel.  Pixels with two batches or more take the temporal estimate (16 bytes of moments); the others walk their
 // 7x7 neighbourhood (nz_spatial).
 __global__ void __launch_bounds__(256) noise_estimate(const NoiseArgs A) {
@@ -130,7 +104,7 @@ __global__ void __launch_bounds__(256) noise_estimate(const NoiseArgs A) {
         A.noise[i] = noise;
         A.var0[i] = estimated ? v : -1.0f;
     }
-    nz_stats(A, blk, estimated, noise, blockIdx.x);
+    nz_stats(A.stats, A.threshold, blk, estimated, noise, blockIdx.x);
 }
 
 // ---- the pooled estimate (rtpbr_set_noise_estimator with pool_batches > 0): noise_estimate with the young temporal pixels
@@ -236,7 +210,7 @@ __global__ void __launch_bounds__(256) noise_estimate_pooled(const NoiseArgs A) 
         A.noise[i] = noise;
         A.var0[i] = estimated ? v : -1.0f;
     }
-    nz_stats(A, blk, estimated, noise, blockIdx.y * gridDim.x + blockIdx.x);
+    nz_stats(A.stats, A.threshold, blk, estimated, noise, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 static unsigned grid_of(int w, int h) { return (unsigned)(((size_t)w * h + 255) / 256); }

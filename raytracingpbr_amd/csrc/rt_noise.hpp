@@ -30,6 +30,35 @@ struct NoiseStats {
     uint32_t estimated, above, max_bits, pad[29];
 };
 
+// lum(c) of include/rtpbr.h
+RT_D float nz_lum(vec3 c) { return (0.299f * c.x + 0.587f * c.y) + 0.114f * c.z; }
+
+// the statistics, by every lane of the block (blk: three zeroed LDS words, a barrier since): per wave a ballot and a butterfly
+// maximum, per block three LDS atomics per wave, then three global ones into the block's shard.  Shared by the estimate kernels
+// here and half_error<R> (rt_half.hip).
+RT_D void nz_stats(NoiseStats* stats, float threshold, uint32_t* blk, bool estimated, float noise, uint32_t block) {
+    const bool above = estimated && noise > threshold;
+    const unsigned long long m_est = __ballot(estimated), m_abv = __ballot(above);
+    uint32_t mx = __float_as_uint(noise);       // >= +0: the bit patterns order like the values
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)mx, o, 64);
+        mx = other > mx ? other : mx;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&blk[0], (uint32_t)__popcll(m_est));
+        atomicAdd(&blk[1], (uint32_t)__popcll(m_abv));
+        atomicMax(&blk[2], mx);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        NoiseStats* s = stats + (block % NOISE_SHARDS);
+        if (blk[0]) atomicAdd(&s->estimated, blk[0]);
+        if (blk[1]) atomicAdd(&s->above, blk[1]);
+        if (blk[2]) atomicMax(&s->max_bits, blk[2]);
+    }
+}
+
 struct NoiseArgs {
     const float4* image_buffer;
     float4* snapshot;             // noise_update: in / out

@@ -1,4 +1,4 @@
-// rt_select.hip — kernels of rtpbr_select_mask / rtpbr_select_noisy (see rt_select.hpp).
+// rt_select.hip — kernels of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (see rt_select.hpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_select.hpp"
@@ -10,9 +10,11 @@ RT_D uint32_t sel_rank(unsigned long long m) {      // set bits below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
 }
 
-// One lane per pixel, i = x * H + y.  NOISY: the rule of rtpbr_select_noisy (include/rtpbr.h) — comparisons only; the
+// One lane per pixel, i = x * H + y.  SELECT_NOISY: the rule of rtpbr_select_noisy (include/rtpbr.h) — comparisons only; the
 // neighbourhood is walked along y (the contiguous index) in the inner loop, at most 49 4-byte loads, and left at the first hit.
-template <bool NOISY>
+// SELECT_ERROR: the rule of rtpbr_select_error — the same on RTPBR_BUF_DENOISED_ERROR, and a pixel with an empty half is selected
+// as one without samples is (16 more bytes read per pixel: half A's texel).
+template <int RULE>
 __global__ void __launch_bounds__(256) select_mark(const SelectArgs A) {
     __shared__ uint32_t wcnt[4];
     const int H = A.height, W = A.width;
@@ -20,9 +22,13 @@ __global__ void __launch_bounds__(256) select_mark(const SelectArgs A) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool sel = false;
     if (i < n) {
-        if constexpr (NOISY) {
+        if constexpr (RULE != SELECT_MASK) {
             const float cnt = A.image_buffer[i].w;
             sel = !(cnt > 0.0f) || cnt < A.min_samples;
+            if constexpr (RULE == SELECT_ERROR) {
+                const float ca = A.half_a[i].w;
+                sel = sel || !(ca > 0.0f) || !(cnt - ca > 0.0f);
+            }
             if (!sel) {
                 const int x = (int)(i / (uint32_t)H), y = (int)(i - (uint32_t)x * (uint32_t)H);
                 const int d = A.dilate;
@@ -95,10 +101,11 @@ __global__ void __launch_bounds__(256) select_scatter(const SelectArgs A) {
     A.list[at + sel_rank(m)] = i;      // at + rank < the total <= n: the list has n entries of room
 }
 
-void launch_select(const SelectArgs& A, bool noisy, hipStream_t st) {
+void launch_select(const SelectArgs& A, int rule, hipStream_t st) {
     const uint32_t nb = select_blocks(A.width, A.height);
-    if (noisy) hipLaunchKernelGGL(select_mark<true>, dim3(nb), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(select_mark<false>, dim3(nb), dim3(256), 0, st, A);
+    if (rule == SELECT_NOISY) hipLaunchKernelGGL(select_mark<SELECT_NOISY>, dim3(nb), dim3(256), 0, st, A);
+    else if (rule == SELECT_ERROR) hipLaunchKernelGGL(select_mark<SELECT_ERROR>, dim3(nb), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(select_mark<SELECT_MASK>, dim3(nb), dim3(256), 0, st, A);
     hipLaunchKernelGGL(select_scan, dim3(1), dim3(256), 0, st, A.blocks, nb);
     hipLaunchKernelGGL(select_scatter, dim3(nb), dim3(256), 0, st, A);
 }

@@ -1,8 +1,8 @@
-// rt_select.hpp — the pixel selection of rtpbr_select_mask / rtpbr_select_noisy: RTPBR_BUF_SELECTION and the compacted,
+// rt_select.hpp — the pixel selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error: RTPBR_BUF_SELECTION and the compacted,
 // ordered list rtpbr_sample_selected traces.
 //
 //   select_mark_*       one lane per pixel along the contiguous index i = x * H + y: decide "selected" (the host mask's byte, or the
-//                       rule of rtpbr_select_noisy: comparisons only), write the byte of RTPBR_BUF_SELECTION, and count per block of
+//                       rule of rtpbr_select_noisy or rtpbr_select_error: comparisons only), write the byte of RTPBR_BUF_SELECTION, and count per block of
 //                       256 pixels — a wave64 ballot + popcount per wave, four LDS words, ONE plain store per block: no global atomics.
 //   select_scan         one block: the exclusive prefix sum of the block counts in place (tiles of 256 with a carry: 8100 counts at
 //                       1080p are 32 tiles), the total behind them.
@@ -14,20 +14,23 @@
 
 namespace rt {
 
+enum { SELECT_MASK = 0, SELECT_NOISY = 1, SELECT_ERROR = 2 };      // the rule of select_mark
+
 struct SelectArgs {
-    const float4* image_buffer;   // noisy: pixels without samples are selected
-    const float* noise;           // noisy: RTPBR_BUF_NOISE of the estimate just made
+    const float4* image_buffer;   // noisy, error: pixels without samples are selected
+    const float* noise;           // noisy: RTPBR_BUF_NOISE of the estimate just made; error: RTPBR_BUF_DENOISED_ERROR as it is
+    const float4* half_a;         // error: RTPBR_BUF_HALF_BUFFER — pixels with an empty half are selected
     const uint8_t* host_mask;     // mask: the caller's bytes, uploaded (nonzero = selected); may be `mask` itself
     uint8_t* mask;                // out: RTPBR_BUF_SELECTION, 0 / 1
     uint32_t* blocks;             // n_blocks counts -> starts, then the total
     uint32_t* list;               // out: the selected buffer indices, ascending
     float threshold;
     int32_t dilate;               // 0..3: Chebyshev radius
-    float min_samples;            // noisy: pixels with fewer samples are selected too (0 = off: no count is below it)
+    float min_samples;            // noisy, error: pixels with fewer samples are selected too (0 = off: no count is below it)
     int32_t width, height;
 };
 
-void launch_select(const SelectArgs& A, bool noisy, hipStream_t st);      // the three passes; A.blocks[n_blocks] = the list's length afterwards
+void launch_select(const SelectArgs& A, int rule, hipStream_t st);      // the three passes; A.blocks[n_blocks] = the list's length afterwards
 inline uint32_t select_blocks(int w, int h) { return (uint32_t)(((size_t)w * (size_t)h + 255) / 256); }
 
 }  // namespace rt

@@ -130,6 +130,14 @@ class NoiseEstimator(_Pod):
     DEFAULTS = {"pool_batches": 0, "pool_radius": 3, "min_samples": 0}
 
 
+class ErrorParams(_Pod):
+    """rtpbr_error_params (include/rtpbr.h): the window of rtpbr_denoise_error's two-half estimate."""
+    _fields_ = [("radius", C.c_int32)]
+
+    # include/rtpbr.h RTPBR_ERROR_DEFAULT_*, what rtpbr_denoise_error(ctx, p, NULL, ...) uses (tests/test_half_ref.py keeps the two equal)
+    DEFAULTS = {"radius": 2}
+
+
 class DenoiseGuidedParams(_Pod):
     """rtpbr_denoise_guided_params (include/rtpbr.h): the a-trous whose colour term is measured in standard deviations of the
     pixel's estimated noise."""

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -28,6 +28,8 @@ BUF_MOMENTS, BUF_NOISE = 11, 12
 BUF_SELECTION = 13
 # the packed 8-bit frame (present): (H,W,C) uint8, top-down, C = 3 or 4 as the last present() said; exists from the first present() on
 BUF_PRESENT = 14
+# half A of the two-half split (half_update) and the estimated noise of the denoised frame (denoise_error); each exists from the first such call on
+BUF_HALF_BUFFER, BUF_DENOISED_ERROR = 15, 16
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -42,6 +44,7 @@ class Renderer:
         self.noise_estimator = NoiseEstimator(**NoiseEstimator.DEFAULTS)      # what set_noise_estimator() last set
         self.track_noise = False             # True: every sample() call is one batch of the noise estimate (noise_update() after it)
         self.noise_per_sample = False        # what set_noise_tracking() last set: every SAMPLE is a batch, folded in by sample() itself
+        self.track_halves = False            # True: every sample() / sample_selected() call is one batch of the two halves (half_update() after it)
         self.set_config(config)
         self.set_scene(scene)
         self.set_camera(camera if camera is not None else scene.camera)
@@ -105,6 +108,8 @@ class Renderer:
         self.api.call("sample", self._ctx, int(n))
         if self.track_noise:
             self.noise_update()
+        if self.track_halves:
+            self.half_update()
 
     pathtrace = sample
 
@@ -295,6 +300,8 @@ class Renderer:
         self.api.call("sample_selected", self._ctx, int(n))
         if self.track_noise:
             self.noise_update()
+        if self.track_halves:
+            self.half_update()
 
     def render_adaptive(self, noise: float, max_spp: int, batch_spp: int = 16, dilate: int = 0, per_sample: bool = False):
         """``render_until`` that stops sampling a pixel once it is done: two full-frame batches of ``batch_spp`` (the temporal
@@ -355,6 +362,76 @@ class Renderer:
             self.track_noise = keep
             self.set_noise_tracking(mode)
 
+    # ------------------------------------------------------------ the error of the denoised frame (include/rtpbr.h rtpbr_half_update / rtpbr_denoise_error)
+    def half_update(self):
+        """Deal the samples deposited since the last call to one of two halves: per pixel the half with fewer samples takes the
+        batch (half A on a tie, so equal batches alternate).  ``half_buffer`` is half A; half B is ``image_buffer`` minus it.
+        The first call's batch is everything accumulated so far."""
+        self.api.call("half_update", self._ctx)
+
+    def denoise_error(self, threshold: float = 0.0, radius=None, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None,
+                      sigma_depth=None, sigma_albedo=None) -> NoiseStats:
+        """Write ``denoised_error``: the estimated standard deviation of the luminance of what ``denoise`` (with the same
+        parameters) shows, from the difference of the filter's results on the two halves, averaged over the (2 radius + 1)^2
+        window on each pixel's object.  Returns how many pixels have samples in both halves, how many of them are above
+        ``threshold``, and the largest value.  Blocks.  Variance only: the filter's bias (blur) is the same in both halves and is
+        not seen.  ``denoised_pixels`` is not written.  ``None`` = the library's default for that parameter."""
+        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
+                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
+        p = None
+        if any(v is not None for v in given.values()):
+            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
+        e = None if radius is None else C.byref(ErrorParams(int(radius)))
+        s = NoiseStats()
+        self.api.call("denoise_error", self._ctx, p, e, float(threshold), C.byref(s))
+        return s
+
+    def select_error(self, threshold: float, dilate: int = 0) -> int:
+        """select_noisy's counterpart on ``denoised_error`` as the last denoise_error() wrote it (not recomputed): the pixels
+        without samples, those with an empty half, those below the estimator's ``min_samples`` and those with a pixel above
+        ``threshold`` within ``dilate`` (0..3) pixels.  Returns how many.  Blocks."""
+        n = C.c_uint32()
+        self.api.call("select_error", self._ctx, float(threshold), int(dilate), C.byref(n))
+        return int(n.value)
+
+    def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, **denoise_params):
+        """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
+        half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
+        sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
+        would take a pixel past ``max_spp``; it ends with denoise(), so ``denoised_pixels`` is the filter of the whole buffer.
+        ``denoise_params`` go to both denoise_error and denoise.  Returns (pixel-samples traced, NoiseStats of the last
+        estimate).  Continues whatever is accumulated: refresh() first for a new frame.  The estimate is variance only: the
+        loop stops when the denoised picture has stopped moving, which the filter's bias does not prevent."""
+        if not (batch_spp >= 1 and max_spp >= 1):
+            raise ValueError("batch_spp and max_spp must be >= 1")
+        batch, budget = int(batch_spp), int(max_spp)
+        n_pix = self.config.width * self.config.height
+        keep_noise, self.track_noise = self.track_noise, False
+        keep_halves, self.track_halves = self.track_halves, False
+        try:
+            traced, used = 0, 0
+            for _ in range(2):
+                n = min(batch, budget - used)
+                if n <= 0:
+                    break
+                self.sample(n)
+                self.half_update()
+                traced, used = traced + n_pix * n, used + n
+            while True:
+                stats = self.denoise_error(error, **denoise_params)
+                if stats.pixels_above == 0 or used + batch > budget:
+                    break
+                n_sel = self.select_error(error, dilate)
+                self.sample_selected(batch)
+                self.half_update()
+                traced, used = traced + n_sel * batch, used + batch
+            self.denoise(**denoise_params)
+            return traced, stats
+        finally:
+            self.track_noise, self.track_halves = keep_noise, keep_halves
+
     # ------------------------------------------------------------ the present stage (include/rtpbr.h rtpbr_present)
     def present(self, source="pixels", format="rgba8", dither=False):
         """Enqueue the display frame: ``source`` ("pixels" = image_pixels, "denoised" = denoised_pixels, "accum" = the tone map of
@@ -390,7 +467,8 @@ class Renderer:
                 BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),
                 BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
                 BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
-                BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8)}[which]
+                BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8),
+                BUF_HALF_BUFFER: ((W, H, 4), np.float32), BUF_DENOISED_ERROR: ((W, H), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -538,6 +616,16 @@ class Renderer:
     def selection(self):
         """(W,H) uint8: 1 = selected by the last select_mask() / select_noisy()"""
         return self._read(BUF_SELECTION)
+
+    @property
+    def half_buffer(self):
+        """(W,H,4): half A's (sum r, sum g, sum b, count) as half_update() dealt it; half B is image_buffer minus this"""
+        return self._read(BUF_HALF_BUFFER)
+
+    @property
+    def denoised_error(self):
+        """(W,H): the last denoise_error()'s standard deviation of each pixel's denoised luminance, 0 where a half is empty"""
+        return self._read(BUF_DENOISED_ERROR)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

@@ -664,7 +664,8 @@ int rtpbr_sample_selected(rtpbr_ctx* ctx, int n);
  *   asynchronous reads of RTPBR_BUF_HALF_BUFFER, is asynchronous and writes nothing else; it is independent of the moments and
  *   their snapshot.  Once A exists: rtpbr_refresh zeroes A and sh; rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) zeroes A and sets
  *   sh to the written data (written data is no batch: it lies in B); rtpbr_reproject and rtpbr_reproject_scene zero A after the
- *   gather and set sh to the warped image_buffer (the history is one body of samples: it lies in B; A is not warped).  Until
+ *   gather and set sh to the warped image_buffer (the history is one body of samples: it lies in B; A is not warped unless
+ *   rtpbr_set_half_mode turned warp on, see below).  Until
  *   their next batch such pixels have an empty half and count as not estimated below.  rtpbr_set_config with a new resolution
  *   frees both buffers.  image_buffer, the motion buffer, the moments and the features are bit for bit what they are without.
  *   Errors: RTPBR_EINVAL for NULL; RTPBR_ESTATE before rtpbr_set_config and with tiles of world > 1.
@@ -705,6 +706,57 @@ typedef struct rtpbr_error_params {   /* 4-byte members, no padding */
 int rtpbr_half_update(rtpbr_ctx* ctx);
 int rtpbr_denoise_error(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_error_params* e, float threshold, rtpbr_noise_stats* out);
 int rtpbr_select_error(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
+
+/* ---- Halves dealt per sample and carried through reprojection.
+ *
+ * Two switches of the section above, both off by default; with the defaults every buffer, counter and timing path is bit for bit
+ * what it is without this call.  Every operation is f32, nothing fused.
+ *
+ * rtpbr_set_half_mode sets both; m == NULL restores the defaults.  The mode is plain context state: it survives rtpbr_refresh
+ *   (which zeroes A and sh as before), rtpbr_set_config (a new resolution frees A and sh; the next dealing call makes them
+ *   again), rtpbr_set_scene, rtpbr_reproject and rtpbr_reproject_scene.  Turning per_sample from 0 to 1 first does exactly what
+ *   rtpbr_half_update does (same refusals: everything deposited so far is one batch, sh = image_buffer), then sets the mode;
+ *   every other transition sets the mode, enqueues nothing and allocates nothing.  RTPBR_EINVAL for a NULL context or a field
+ *   that is not 0 or 1.  A refused call changes nothing.
+ *
+ * per_sample = 1: rtpbr_sample(n) and rtpbr_sample_selected(n) of the complete-path form deal every staged sample to a half inside
+ *   the pass that adds it to image_buffer.  For a pixel that receives samples, with b its image_buffer value, A its half and
+ *   c = (r, g, b) each of its records in sample order:
+ *     cB = b.w - A.w;                                                             (before the sample is added)
+ *     if (A.w <= cB) { A.x = A.x + c.x; A.y = A.y + c.y; A.z = A.z + c.z; A.w = A.w + 1; }
+ *     b.x += c.x; b.y += c.y; b.z += c.z; b.w += 1;                              (rtpbr_sample's own sum, unchanged)
+ *   and after the pixel's last record of a sub-launch sh = b.  This is rtpbr_half_update's rule for a batch of one sample: samples
+ *   alternate A, B, A, ... on a pixel whose halves are equal, and a pixel behind in one half catches up first; one rtpbr_sample(8)
+ *   gives halves of 4 + 4.  The pass overwrites sh without reading it.  Pixels that receive no samples (unselected ones) keep A
+ *   and sh bit for bit.  A dealing call allocates A and sh (zeroed) when they do not exist, is ordered behind asynchronous reads
+ *   of RTPBR_BUF_HALF_BUFFER, and keeps item-linear staging whatever option stage_dense says (same bits, as
+ *   rtpbr_sample_selected).  image_buffer, the work counters, sample_base, the timing and every other buffer are bit for bit those
+ *   of the call without the mode, and the result does not depend on how the staging budget splits the call into sub-launches (it
+ *   splits along samples).  An rtpbr_half_update after a dealing call finds d = 0 and changes nothing: the two may be mixed.  Noise
+ *   tracking (rtpbr_set_noise_tracking) may be on at the same time: the moments' arithmetic and store order are untouched.
+ *   While per_sample is on rtpbr_sample / rtpbr_sample_selected are refused with RTPBR_ESTATE, changing nothing, in the
+ *   persistent-ray form (no per-sample records), with option precision = 1 (its unstaged instance keeps no records) and with
+ *   tiles of world > 1.
+ *
+ * warp = 1: while A exists, rtpbr_reproject and rtpbr_reproject_scene carry half A with the image.  Before the gather A is copied
+ *   into an internal history buffer (ordered behind asynchronous reads of RTPBR_BUF_HALF_BUFFER).  Per new pixel, over exactly
+ *   the accepted taps q and weights w of the image (rtpbr_reproject), in tap order, with a_q the old A:
+ *     SA = SA + w * a_q per component;        then A' = SA / Wt per component;
+ *     when the cap applies (b.w > max_history before scaling): A' = A' * k per component, k = max_history / b.w the image's own;
+ *     with no accepted tap A' = 0.
+ *   sh becomes the warped image_buffer.  Because w >= 0, a_q.w <= b_q.w and every operation is monotone, 0 <= A'.w <= b'.w holds
+ *   exactly: B' = b' - A' stays a valid half, and a pixel with history in both halves stays estimated across the move.
+ *   image_buffer, RTPBR_BUF_MOTION, the moments and their snapshot and the features are bit for bit what they are without the
+ *   mode.  With warp off, or before A exists, the calls do what the section above says (A is zeroed, sh becomes the warped
+ *   image).  rtpbr_refresh and rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) keep their rules in both modes. */
+typedef struct rtpbr_half_mode {   /* 4-byte members, no padding */
+    int32_t per_sample;   /* 0 (default) / 1: rtpbr_sample and rtpbr_sample_selected deal every sample to a half themselves */
+    int32_t warp;         /* 0 (default) / 1: rtpbr_reproject and rtpbr_reproject_scene carry half A with the image          */
+} rtpbr_half_mode;
+/* Defaults (m == NULL): off.  raytracingpbr_amd.dataclass.HalfMode.DEFAULTS mirrors them (tests/test_half_mode_ref.py checks). */
+#define RTPBR_HALF_MODE_DEFAULT_PER_SAMPLE 0
+#define RTPBR_HALF_MODE_DEFAULT_WARP       0
+int rtpbr_set_half_mode(rtpbr_ctx* ctx, const rtpbr_half_mode* m);   /* NULL = the defaults */
 
 /* ---- The present stage: a display buffer becomes a packed 8-bit frame on the device, in one kernel.
  *

@@ -25,7 +25,8 @@ using namespace rt;
 
 static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_error);
 static int noise_alloc(rtpbr_ctx* c);
-static int half_restart(rtpbr_ctx* c, bool snapshot_image);
+static int half_restart(rtpbr_ctx* c, bool snapshot_image, bool keep_a = false);
+static int half_alloc(rtpbr_ctx* c);
 static int noise_stats_read(rtpbr_ctx* c, rtpbr_noise_stats* out);
 extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value);
 extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world);
@@ -145,11 +146,12 @@ static void free_noise(rtpbr_ctx* c) {
 static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->half_a);
     (void)hipFree(c->half_snapshot);
+    (void)hipFree(c->hist_half);
     (void)hipFree(c->half_b);
     (void)hipFree(c->half_da);
     (void)hipFree(c->half_db);
     (void)hipFree(c->denoised_error);
-    c->half_a = c->half_snapshot = c->half_b = nullptr;
+    c->half_a = c->half_snapshot = c->hist_half = c->half_b = nullptr;
     c->half_da = c->half_db = c->denoised_error = nullptr;
 }
 
@@ -896,7 +898,7 @@ static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_
         const bool aot_special = c->kind == KIND_BOXES && c->n_obj == 8 && P.box_sig != 0;
         if (c->jit >= 1 || !aot_special || c->precision) {
             *key = make_jit_key(c->kind, c->n_obj, c->objm, c->cfg, P, persistent, c->jit_bake, c->jit_waves, jit_bunny, c->precision);
-            key->dense = (c->stage_dense && !persistent && !c->precision && c->noise_tracking == RTPBR_NOISE_TRACK_OFF) ? 1 : 0;      // (a tracked launch keeps item-linear records)
+            key->dense = (c->stage_dense && !persistent && !c->precision && c->noise_tracking == RTPBR_NOISE_TRACK_OFF && !c->half_mode.per_sample) ? 1 : 0;      // (a tracked or dealing launch keeps item-linear records)
             *want = true;
         }
     } else if (c->jit == 2) {
@@ -1228,6 +1230,8 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
     // per-sample noise tracking (rtpbr_set_noise_tracking): the accumulate pass folds every record into the moments (the callers
     // have refused what keeps no records and have allocated the moments and the snapshot)
     const bool tracked = c->noise_tracking == RTPBR_NOISE_TRACK_SAMPLES;
+    // per-sample dealing to the halves (rtpbr_set_half_mode): likewise, into half A and its snapshot
+    const bool dealt = c->half_mode.per_sample != 0;
     while (left > 0) {
         const bool split_ok = !selected && c->primary_split && P.scheduler == 1 && c->kind != KIND_BUNNY && c->kind != KIND_MIXED;
         // the tolerance flavour accumulates in LDS and adds to image_buffer directly: no staging, no accumulate kernel
@@ -1268,7 +1272,7 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
         // dense staging (rt_trace.hpp stage_sample, accumulate_dense): the claim must be whole pixels or a whole fraction of one, and
         // fit the record's one-byte offset; a launch that has no such claim size near the one wanted keeps the item-linear records
         P.stage_dense = 0;
-        if (c->stage_dense && c->jit_mod != nullptr && !unstaged && P.scheduler == 1 && !tracked) {      // (compiled into run-time instances only: RtJitKey::dense)
+        if (c->stage_dense && c->jit_mod != nullptr && !unstaged && P.scheduler == 1 && !tracked && !dealt) {      // (compiled into run-time instances only: RtJitKey::dense)
             long long lo = DENSE_CHUNK_MIN, hi = chunk < 64 ? 64 : chunk > (long long)DENSE_CHUNK_MAX ? (long long)DENSE_CHUNK_MAX : chunk, cc = 0;
             if (c->chunk > 0) lo = hi = c->chunk;       // a claim size that was asked for is kept as it is (or the records stay item-linear)
             if (lo >= (long long)DENSE_CHUNK_MIN && hi <= (long long)DENSE_CHUNK_MAX)
@@ -1311,7 +1315,10 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
         } else
             launch_trace(P, c->kind, grid, c->stream);
         if (c->timed) HIP_TRY(hipEventRecord(b, c->stream));
-        if (tracked && selected) launch_accumulate_selected_tracked(P, c->noise_moments, c->noise_snapshot, c->stream);
+        float4* const mo = tracked ? c->noise_moments : nullptr;
+        if (dealt && selected) launch_accumulate_selected_dealt(P, mo, c->noise_snapshot, c->half_a, c->half_snapshot, c->stream);
+        else if (dealt) launch_accumulate_dealt(P, mo, c->noise_snapshot, c->half_a, c->half_snapshot, c->stream);
+        else if (tracked && selected) launch_accumulate_selected_tracked(P, c->noise_moments, c->noise_snapshot, c->stream);
         else if (tracked) launch_accumulate_tracked(P, c->noise_moments, c->noise_snapshot, c->stream);
         else if (selected) launch_accumulate_selected(P, c->stream);
         else if (!unstaged) launch_accumulate(P, c->n_cu, c->stream);
@@ -1326,7 +1333,9 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     if (int r = set_dev(c)) return r;
     // (diff_buffer: instrumented builds write their per-wave records over it; a tracked call — rtpbr_set_noise_tracking — writes the moments)
     const bool tracked = c->noise_tracking == RTPBR_NOISE_TRACK_SAMPLES;
-    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | (tracked ? 1u << RTPBR_BUF_MOMENTS : 0u))) return r;
+    const bool dealt = c->half_mode.per_sample != 0;      // ... and a dealing call — rtpbr_set_half_mode — half A
+    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | (tracked ? 1u << RTPBR_BUF_MOMENTS : 0u) |
+                                            (dealt ? 1u << RTPBR_BUF_HALF_BUFFER : 0u))) return r;
     // A shading the previous call left pending (lazy shading of one-step launches) rides along only if this call is again a launch of the
     // wavefront split; otherwise it is launched now, while the previous call's work counters are still the current ones
     {
@@ -1372,6 +1381,9 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     // a tracked call folds into the moments and re-takes the snapshot: both exist (zeroed) from here on, as after rtpbr_noise_update
     if (tracked)
         if (int r = noise_alloc(c)) return r;
+    // a dealing call deals into half A and re-takes its snapshot: both exist (zeroed) from here on, as after rtpbr_half_update
+    if (dealt)
+        if (int r = half_alloc(c)) return r;
     static_assert((sizeof(Counters) + 64) % 16 == 0, "zero_next_counters / launch_zero fill 16-byte words");
     // This call's work counters (+ the claim counters behind them): the buffer whose turn it is, zeroed by the previous call's kernels
     // (or here, if that call launched none); this call's kernels zero the other one.
@@ -1425,8 +1437,17 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     return RTPBR_OK;
 }
 
-// what a sample call with per-sample noise tracking on (rtpbr_set_noise_tracking) refuses: there must be a record per sample
+// what a sample call with per-sample noise tracking (rtpbr_set_noise_tracking) or per-sample dealing (rtpbr_set_half_mode) on refuses:
+// there must be a record per sample
 static int tracked_sample_check(rtpbr_ctx* c) {
+    if (c->half_mode.per_sample) {      // rtpbr_set_half_mode: the same three refusals
+        if (c->cfg.kernel_form != RTPBR_FORM_COMPLETE_PATH)
+            return fail(RTPBR_ESTATE, "per-sample dealing to the halves: the complete-path form only (the persistent-ray form has no per-sample records): "
+                                      "rtpbr_set_half_mode with per_sample = 0 first");
+        if (c->precision)
+            return fail(RTPBR_ESTATE, "per-sample dealing to the halves: not with option precision = 1 (the tolerance flavour's unstaged instance keeps no records)");
+        if (c->world > 1) return fail(RTPBR_ESTATE, "per-sample dealing to the halves works on the whole frame: not with tiles of world > 1");
+    }
     if (c->noise_tracking != RTPBR_NOISE_TRACK_SAMPLES) return RTPBR_OK;
     if (c->cfg.kernel_form != RTPBR_FORM_COMPLETE_PATH)
         return fail(RTPBR_ESTATE, "per-sample noise tracking: the complete-path form only (the persistent-ray form has no per-sample records): "
@@ -1613,7 +1634,7 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
 }
 
 // ---- temporal reuse (rt_reproject.hip): rtpbr_set_camera + rtpbr_refresh that keeps what the new view can reuse
-enum : unsigned { W_MOTION = 1u << RTPBR_BUF_MOTION };
+enum : unsigned { W_MOTION = 1u << RTPBR_BUF_MOTION, W_HALF = 1u << RTPBR_BUF_HALF_BUFFER };
 
 // p == NULL: the defaults; RTPBR_EINVAL for a parameter out of range
 static int reproject_params(const rtpbr_reproject_params* p, rtpbr_reproject_params& d) {
@@ -1660,6 +1681,12 @@ static int reproject_run(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_repr
         if (int r = rt_order_after_reads(c, 1u << RTPBR_BUF_MOMENTS)) return r;
         HIP_TRY(hipMemcpyAsync(c->hist_moments, c->noise_moments, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     }
+    const bool warp_half = c->half_mode.warp != 0 && c->half_a != nullptr;      // rtpbr_set_half_mode: half A moves with the image
+    if (warp_half) {
+        if (!c->hist_half) HIP_TRY(hipMalloc(&c->hist_half, n * sizeof(float4)));
+        if (int r = rt_order_after_reads(c, W_HALF)) return r;
+        HIP_TRY(hipMemcpyAsync(c->hist_half, c->half_a, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    }
     const CamFrame old_frame = c->P.cam;
     // copies, not pointer swaps: the public buffers keep the addresses rtpbr_buffer_device_ptr handed out
     HIP_TRY(hipMemcpyAsync(c->hist_image, c->image_buffer, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
@@ -1700,10 +1727,13 @@ static int reproject_run(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_repr
     A.hist_moments = c->noise_moments ? c->hist_moments : nullptr;
     A.moments = c->noise_moments;
     A.snapshot = c->noise_snapshot;
+    A.hist_half = warp_half ? c->hist_half : nullptr;
+    A.half_a = c->half_a;
     if (objs) launch_reproject_scene(A, c->scene_motion, n_objs, c->stream);
     else launch_reproject(A, c->stream);
     HIP_TRY(hipGetLastError());
-    if (int r = half_restart(c, true)) return r;      // the warped history is one body of samples: it lies in B
+    // the warped history is one body of samples: it lies in B — unless half A came along (the gather wrote it); sh = the warped image
+    if (int r = half_restart(c, true, warp_half)) return r;
     c->history_ok = true;
     return RTPBR_OK;
 }
@@ -1970,27 +2000,23 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
 }
 
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
-enum : unsigned { W_HALF = 1u << RTPBR_BUF_HALF_BUFFER, W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR };
+enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR };
 static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
 
 // What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
-// snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.
-static int half_restart(rtpbr_ctx* c, bool snapshot_image) {
+// snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.  keep_a: A has
+// been written by the caller (a reprojection that carries it, rtpbr_set_half_mode): the snapshot alone.
+static int half_restart(rtpbr_ctx* c, bool snapshot_image, bool keep_a) {
     if (!c->half_a) return RTPBR_OK;
     if (int r = rt_order_after_reads(c, W_HALF)) return r;
     const size_t bytes = (size_t)c->cfg.width * c->cfg.height * sizeof(float4);
-    HIP_TRY(hipMemsetAsync(c->half_a, 0, bytes, c->stream));
+    if (!keep_a) HIP_TRY(hipMemsetAsync(c->half_a, 0, bytes, c->stream));
     if (snapshot_image) HIP_TRY(hipMemcpyAsync(c->half_snapshot, c->image_buffer, bytes, hipMemcpyDeviceToDevice, c->stream));
     else HIP_TRY(hipMemsetAsync(c->half_snapshot, 0, bytes, c->stream));
     return RTPBR_OK;
 }
 
-extern "C" int rtpbr_half_update(rtpbr_ctx* c) {
-    if (!c) return fail(RTPBR_EINVAL, "null ctx");
-    if (!c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
-    if (c->world > 1) return fail(RTPBR_ESTATE, HALF_TILES);
-    if (int r = set_dev(c)) return r;
-    if (int r = flush_shade(c)) return r;
+static int half_alloc(rtpbr_ctx* c) {
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     if (!c->half_a) {
         HIP_TRY(hipMalloc(&c->half_a, n * sizeof(float4)));
@@ -2000,6 +2026,16 @@ extern "C" int rtpbr_half_update(rtpbr_ctx* c) {
         HIP_TRY(hipMalloc(&c->half_snapshot, n * sizeof(float4)));
         HIP_TRY(hipMemsetAsync(c->half_snapshot, 0, n * sizeof(float4), c->stream));
     }
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_half_update(rtpbr_ctx* c) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (!c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, HALF_TILES);
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    if (int r = half_alloc(c)) return r;
     if (int r = rt_order_after_reads(c, W_HALF)) return r;
     HalfArgs A{};
     A.image_buffer = c->image_buffer;
@@ -2009,6 +2045,18 @@ extern "C" int rtpbr_half_update(rtpbr_ctx* c) {
     A.height = c->cfg.height;
     launch_half_update(A, c->stream);
     HIP_TRY(hipGetLastError());
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_set_half_mode(rtpbr_ctx* c, const rtpbr_half_mode* m) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_half_mode d{RTPBR_HALF_MODE_DEFAULT_PER_SAMPLE, RTPBR_HALF_MODE_DEFAULT_WARP};
+    if (m) d = *m;
+    if ((d.per_sample != 0 && d.per_sample != 1) || (d.warp != 0 && d.warp != 1))
+        return fail(RTPBR_EINVAL, "rtpbr_set_half_mode: per_sample and warp must be 0 or 1");
+    if (d.per_sample && !c->half_mode.per_sample)      // everything deposited so far is one batch; the samples to come are batches of one
+        if (int r = rtpbr_half_update(c)) return r;
+    c->half_mode = d;
     return RTPBR_OK;
 }
 

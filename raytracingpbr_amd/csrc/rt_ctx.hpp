@@ -22,6 +22,10 @@ void launch_accumulate_selected(const Params& P, hipStream_t st);
 // per-sample noise tracking (rtpbr_set_noise_tracking): the accumulate pass also folds every sample into the moments and re-takes the snapshot
 void launch_accumulate_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st);
 void launch_accumulate_selected_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st);
+// per-sample dealing to the two halves (rtpbr_set_half_mode): the accumulate pass also deals every sample to half A or B and re-takes the
+// halves' snapshot; moments != nullptr: the noise moments are folded in the same pass
+void launch_accumulate_dealt(const Params& P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh, hipStream_t st);
+void launch_accumulate_selected_dealt(const Params& P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh, hipStream_t st);
 int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler);
 void launch_zero(void* p, size_t bytes, hipStream_t st);      // a small fill as a kernel of our own (bytes % 16 == 0)
 void launch_persistent(const Params& P, int kind, int steps, hipStream_t st);
@@ -211,6 +215,8 @@ struct rtpbr_ctx {
     // on, the others from the first rtpbr_denoise_error on; freed with the context or a new resolution
     float4* half_a = nullptr;          // (W,H): RTPBR_BUF_HALF_BUFFER
     float4* half_snapshot = nullptr;   // (W,H): image_buffer at the last rtpbr_half_update
+    float4* hist_half = nullptr;       // (W,H): half A before a reprojection that carries it (rtpbr_set_half_mode, warp)
+    rtpbr_half_mode half_mode{RTPBR_HALF_MODE_DEFAULT_PER_SAMPLE, RTPBR_HALF_MODE_DEFAULT_WARP};      // rtpbr_set_half_mode: plain state, kept across refresh / set_config / set_scene / reproject
     float4* half_b = nullptr;          // (W,H): image_buffer - half_a, materialised per rtpbr_denoise_error
     float* half_da = nullptr;          // (W,H,3): the filter's display colour of half A
     float* half_db = nullptr;          // (W,H,3): ... of half B

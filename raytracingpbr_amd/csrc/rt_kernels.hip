@@ -18,6 +18,8 @@
 //                            image_buffer (T7), exactly like "image_buffer[i,j] += vec4(color,1)".
 //   accumulate_*_tracked     the same pass with every sample folded into the noise moments as well
 //                            (rtpbr_set_noise_tracking).
+//   accumulate_*_dealt       the same pass with every sample dealt to one of the two halves as well
+//                            (rtpbr_set_half_mode, per_sample); *_tracked_dealt does both.
 //   persistent_steps<KIND>   src/ form (F1-F4,F6,F7: src/pathtracer.py:16-103, src/scene.py:59-84):
 //                            one lane per pixel, ray state in ray_buffer between launches.
 //   refresh, post_process, pack/unpack tiles, math_probe (test hook).
@@ -38,11 +40,26 @@ RT_D void fold_sample(float4& M, float r, float g, float b) {
     M.w = M.w + 1.0f;
 }
 
+// Per-sample dealing (rtpbr_set_half_mode, per_sample): every record is also a batch of one for the two halves (rt_half.hip
+// half_update with d = (c, 1)): half A takes it when it holds no more samples than B = image_buffer - A, counted BEFORE the record
+// is added to image_buffer.
+RT_D void deal_sample(float4& A, const float4& acc, float r, float g, float b) {
+    const float cB = acc.w - A.w;
+    if (A.w <= cB) {
+        A.x = A.x + r;
+        A.y = A.y + g;
+        A.z = A.z + b;
+        A.w = A.w + 1.0f;
+    }
+}
+
 // image_buffer[i,j] += vec4(color, 1) for k = 0..K-1 in order (renderer.py:36)
 // TRACK: moments / snapshot are RTPBR_BUF_MOMENTS and the noise snapshot, indexed like image_buffer (one 16-byte load and store of
 // M, one 16-byte store of s = the new image_buffer value per pixel); the untracked instance never looks at them.
-template <bool TRACK>
-RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snapshot) {
+// HALVES: half_a / half_sh are RTPBR_BUF_HALF_BUFFER and the halves' snapshot, indexed alike (one 16-byte load and store of A, one
+// 16-byte store of sh = the new image_buffer value per pixel); the instances without the flag never look at them.
+template <bool TRACK, bool HALVES>
+RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh) {
     uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     int x = 0, y = 0;
     const bool valid = q < (uint32_t)P.np && pixel_of(P, q, x, y);
@@ -57,6 +74,8 @@ RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snap
     const size_t px = (size_t)(dst - P.image_buffer);      // the buffer index x * H + y: the moments and the snapshot lie like image_buffer
     float4 M = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if constexpr (TRACK) M = moments[px];
+    float4 HA = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (HALVES) HA = half_a[px];
     // a pixel's K records (12 bytes each) are contiguous (item-linear staging): fetch them 8 at a time (96 B per lane as
     // six 16-byte loads when the pixel's run starts on a 16-byte boundary, i.e. K % 4 == 0) and add them strictly in
     // sample order
@@ -73,6 +92,7 @@ RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snap
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 if constexpr (TRACK) fold_sample(M, f[3 * i], f[3 * i + 1], f[3 * i + 2]);
+                if constexpr (HALVES) deal_sample(HA, acc, f[3 * i], f[3 * i + 1], f[3 * i + 2]);
                 acc.x += f[3 * i];
                 acc.y += f[3 * i + 1];
                 acc.z += f[3 * i + 2];
@@ -82,6 +102,7 @@ RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snap
     }
     for (; k < P.K; k++) {
         if constexpr (TRACK) fold_sample(M, src[3 * k], src[3 * k + 1], src[3 * k + 2]);
+        if constexpr (HALVES) deal_sample(HA, acc, src[3 * k], src[3 * k + 1], src[3 * k + 2]);
         acc.x += src[3 * k];
         acc.y += src[3 * k + 1];
         acc.z += src[3 * k + 2];
@@ -92,16 +113,27 @@ RT_D void accumulate_samples_body(const Params& P, float4* moments, float4* snap
         moments[px] = M;
         snapshot[px] = acc;
     }
+    if constexpr (HALVES) {
+        half_a[px] = HA;
+        half_sh[px] = acc;
+    }
 }
-__global__ void __launch_bounds__(256) accumulate_samples(const Params P) { accumulate_samples_body<false>(P, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) accumulate_samples(const Params P) { accumulate_samples_body<false, false>(P, nullptr, nullptr, nullptr, nullptr); }
 __global__ void __launch_bounds__(256) accumulate_samples_tracked(const Params P, float4* moments, float4* snapshot) {
-    accumulate_samples_body<true>(P, moments, snapshot);
+    accumulate_samples_body<true, false>(P, moments, snapshot, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) accumulate_samples_dealt(const Params P, float4* half_a, float4* half_sh) {
+    accumulate_samples_body<false, true>(P, nullptr, nullptr, half_a, half_sh);
+}
+__global__ void __launch_bounds__(256) accumulate_samples_tracked_dealt(const Params P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh) {
+    accumulate_samples_body<true, true>(P, moments, snapshot, half_a, half_sh);
 }
 
 // ... of a selected launch (rtpbr_sample_selected): local pixel q is entry q of the selection list, a buffer index; every
-// other pixel of image_buffer (and, TRACK, of the moments and the snapshot) is left alone.  Item-linear staging only.
-template <bool TRACK>
-RT_D void accumulate_selected_body(const Params& P, float4* moments, float4* snapshot) {
+// other pixel of image_buffer (and, TRACK, of the moments and the snapshot; HALVES, of half A and its snapshot) is left alone.
+// Item-linear staging only.
+template <bool TRACK, bool HALVES>
+RT_D void accumulate_selected_body(const Params& P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = q < (uint32_t)P.np;
     {
@@ -114,9 +146,12 @@ RT_D void accumulate_selected_body(const Params& P, float4* moments, float4* sna
     float4 acc = *dst;
     float4 M = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if constexpr (TRACK) M = moments[px];
+    float4 HA = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (HALVES) HA = half_a[px];
     const float* src = P.stage + (size_t)q * (size_t)P.K * 3u;
     for (int k = 0; k < P.K; k++) {      // strictly in sample order
         if constexpr (TRACK) fold_sample(M, src[3 * k], src[3 * k + 1], src[3 * k + 2]);
+        if constexpr (HALVES) deal_sample(HA, acc, src[3 * k], src[3 * k + 1], src[3 * k + 2]);
         acc.x += src[3 * k];
         acc.y += src[3 * k + 1];
         acc.z += src[3 * k + 2];
@@ -127,10 +162,20 @@ RT_D void accumulate_selected_body(const Params& P, float4* moments, float4* sna
         moments[px] = M;
         snapshot[px] = acc;
     }
+    if constexpr (HALVES) {
+        half_a[px] = HA;
+        half_sh[px] = acc;
+    }
 }
-__global__ void __launch_bounds__(256) accumulate_selected(const Params P) { accumulate_selected_body<false>(P, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) accumulate_selected(const Params P) { accumulate_selected_body<false, false>(P, nullptr, nullptr, nullptr, nullptr); }
 __global__ void __launch_bounds__(256) accumulate_selected_tracked(const Params P, float4* moments, float4* snapshot) {
-    accumulate_selected_body<true>(P, moments, snapshot);
+    accumulate_selected_body<true, false>(P, moments, snapshot, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) accumulate_selected_dealt(const Params P, float4* half_a, float4* half_sh) {
+    accumulate_selected_body<false, true>(P, nullptr, nullptr, half_a, half_sh);
+}
+__global__ void __launch_bounds__(256) accumulate_selected_tracked_dealt(const Params P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh) {
+    accumulate_selected_body<true, true>(P, moments, snapshot, half_a, half_sh);
 }
 
 // The same sum over the DENSE staging (rt_trace.hpp stage_sample): a block takes `acc_batch` consecutive items at a time (a multiple
@@ -511,6 +556,11 @@ void launch_accumulate_selected(const Params& P, hipStream_t st) {
 void launch_accumulate_selected_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st) {
     hipLaunchKernelGGL(accumulate_selected_tracked, dim3((unsigned)((P.np + 255) / 256)), dim3(256), 0, st, P, moments, snapshot);
 }
+void launch_accumulate_selected_dealt(const Params& P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh, hipStream_t st) {
+    const dim3 grid((unsigned)((P.np + 255) / 256));
+    if (moments) hipLaunchKernelGGL(accumulate_selected_tracked_dealt, grid, dim3(256), 0, st, P, moments, snapshot, half_a, half_sh);
+    else hipLaunchKernelGGL(accumulate_selected_dealt, grid, dim3(256), 0, st, P, half_a, half_sh);
+}
 int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler) {
     int per_cu = 0;
     hipError_t e = hipSuccess;
@@ -580,6 +630,12 @@ void launch_accumulate(const Params& P, int n_cu, hipStream_t st) {
 void launch_accumulate_tracked(const Params& P, float4* moments, float4* snapshot, hipStream_t st) {
     int grid = (P.np + 255) / 256;
     hipLaunchKernelGGL(accumulate_samples_tracked, dim3(grid), dim3(256), 0, st, P, moments, snapshot);
+}
+// per-sample dealing to the halves (moments != nullptr: with noise tracking as well): item-linear staging only, as above
+void launch_accumulate_dealt(const Params& P, float4* moments, float4* snapshot, float4* half_a, float4* half_sh, hipStream_t st) {
+    int grid = (P.np + 255) / 256;
+    if (moments) hipLaunchKernelGGL(accumulate_samples_tracked_dealt, dim3(grid), dim3(256), 0, st, P, moments, snapshot, half_a, half_sh);
+    else hipLaunchKernelGGL(accumulate_samples_dealt, dim3(grid), dim3(256), 0, st, P, half_a, half_sh);
 }
 void launch_persistent_pool(const Params& P, int kind, int steps, int grid, hipStream_t st) {
     if (kind == KIND_BOXES) hipLaunchKernelGGL((persistent_pool<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, steps);

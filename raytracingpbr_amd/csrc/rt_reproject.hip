@@ -38,7 +38,10 @@ RT_D vec3 centre_ray(const ReprojArgs& A, int x, int y) {
 // The gather of pixel i from D (the first hit as the old eye sees it; on a miss the direction) and nn (the normal the old
 // normals are compared with), and everything the pixel's lane writes: shared by reproject_gather and reproject_gather_scene.
 // A tap loads the 4-byte old object first, then the 16-byte history texel, then (hits only) the 16-byte (normal, depth) record.
-template <bool MOMENTS>
+// HALVES: half A (rt_half.hpp) rides along like the moments: one more 16-byte load per accepted tap, one more 16-byte store per
+// pixel.  Where the cap applies A is scaled by the image's own quotient k, so 0 <= A.w <= image_buffer.w stays exact (a_q.w <=
+// b_q.w per tap, w >= 0, and every operation is monotone).
+template <bool MOMENTS, bool HALVES>
 RT_D void gather_taps(const ReprojArgs& A, uint32_t i, int obj, vec3 D, vec3 nn) {
     const int H = A.height, W = A.width;
     const CamFrame& f0 = A.cam0;
@@ -51,6 +54,7 @@ RT_D void gather_taps(const ReprojArgs& A, uint32_t i, int obj, vec3 D, vec3 nn)
     const float s = dot(q, N) / dot(D, N);
     float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 SM = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 SA = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float Wt = 0.0f;
     float2 mv = make_float2(-1.0f, -1.0f);
     if (s > 0.0f) {
@@ -93,20 +97,30 @@ RT_D void gather_taps(const ReprojArgs& A, uint32_t i, int obj, vec3 D, vec3 nn)
                     SM.z = SM.z + w * m.z;
                     SM.w = SM.w + w * m.w;
                 }
+                if constexpr (HALVES) {
+                    const float4 a = A.hist_half[qi];
+                    SA.x = SA.x + w * a.x;
+                    SA.y = SA.y + w * a.y;
+                    SA.z = SA.z + w * a.z;
+                    SA.w = SA.w + w * a.w;
+                }
             }
             if (Wt > 0.0f) mv = make_float2((float)x0 + fx, (float)y0 + fy);
         }
     }
     float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 M = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 HA = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (Wt > 0.0f) {
         b = make_float4(S.x / Wt, S.y / Wt, S.z / Wt, S.w / Wt);
         if constexpr (MOMENTS) M = make_float4(SM.x / Wt, SM.y / Wt, SM.z / Wt, SM.w / Wt);
+        if constexpr (HALVES) HA = make_float4(SA.x / Wt, SA.y / Wt, SA.z / Wt, SA.w / Wt);
         if (b.w > A.max_history) {
             const float k = A.max_history / b.w;
             b = make_float4(b.x * k, b.y * k, b.z * k, b.w * k);
             // the history weighs max_history samples in the estimate as in the image; the per-sample variance stays
             if constexpr (MOMENTS) M = make_float4(M.x * k, M.y * k, M.z * k, M.w > 1.0f ? 1.0f + (M.w - 1.0f) * k : M.w);
+            if constexpr (HALVES) HA = make_float4(HA.x * k, HA.y * k, HA.z * k, HA.w * k);
         }
     }
     A.image_buffer[i] = b;
@@ -114,6 +128,7 @@ RT_D void gather_taps(const ReprojArgs& A, uint32_t i, int obj, vec3 D, vec3 nn)
         A.moments[i] = M;
         A.snapshot[i] = b;      // what is in image_buffer now is no batch
     }
+    if constexpr (HALVES) A.half_a[i] = HA;
     A.motion[i] = mv;
     // what rtpbr_refresh resets besides image_buffer (refresh_kernel, rt_kernels.hip)
     A.ray_buffer[i].depth = 0;
@@ -128,7 +143,8 @@ RT_D void gather_taps(const ReprojArgs& A, uint32_t i, int obj, vec3 D, vec3 nn)
 // the caches: for a small move a wave's taps cover about two columns' worth of old pixels).
 // MOMENTS: the luminance moments of the noise estimate (rt_noise.hpp) ride along — the same accepted taps and weights, 16 more
 // bytes per accepted tap; the image's arithmetic is untouched.
-template <bool MOMENTS>
+// HALVES: so does half A of the two-half error estimate (rtpbr_set_half_mode, warp).
+template <bool MOMENTS, bool HALVES>
 __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
@@ -144,7 +160,7 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
         D = fma3(nz.w, d, v3f(A.cam1.lf)) - v3f(A.cam0.lf);             // the first hit as the old eye sees it
         nn = mk(nz.x, nz.y, nz.z);
     }
-    gather_taps<MOMENTS>(A, i, obj, D, nn);
+    gather_taps<MOMENTS, HALVES>(A, i, obj, D, nn);
 }
 
 // reproject_gather with objects that moved rigidly between the old and the new frame (rtpbr_reproject_scene).  `table`: per
@@ -153,7 +169,7 @@ __global__ void __launch_bounds__(256) reproject_gather(const ReprojArgs A) {
 // LDS read costs a few cycles where a divergent global read costs a cache line per object.  Every thread of the block takes
 // part in the staging and reaches the barrier, whether it owns a pixel or not (the last block of a frame, or a frame with
 // fewer pixels than table words).  A hit on an object that did not move, and a miss, take reproject_gather's expressions.
-template <bool MOMENTS>
+template <bool MOMENTS, bool HALVES>
 __global__ void __launch_bounds__(256) reproject_gather_scene(const ReprojArgs A, const float* __restrict__ table, const int n_obj) {
     __shared__ float T[MAX_OBJ * SCENE_MOTION_WORDS];
     const int words = (n_obj < MAX_OBJ ? n_obj : MAX_OBJ) * SCENE_MOTION_WORDS;
@@ -190,19 +206,23 @@ __global__ void __launch_bounds__(256) reproject_gather_scene(const ReprojArgs A
             D = X1 - v3f(A.cam0.lf);
         }
     }
-    gather_taps<MOMENTS>(A, i, obj, D, nn);
+    gather_taps<MOMENTS, HALVES>(A, i, obj, D, nn);
 }
 
 void launch_reproject(const ReprojArgs& A, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (A.hist_moments) hipLaunchKernelGGL(reproject_gather<true>, dim3(grid), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(reproject_gather<false>, dim3(grid), dim3(256), 0, st, A);
+    if (A.hist_moments && A.hist_half) hipLaunchKernelGGL((reproject_gather<true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (A.hist_moments) hipLaunchKernelGGL((reproject_gather<true, false>), dim3(grid), dim3(256), 0, st, A);
+    else if (A.hist_half) hipLaunchKernelGGL((reproject_gather<false, true>), dim3(grid), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((reproject_gather<false, false>), dim3(grid), dim3(256), 0, st, A);
 }
 
 void launch_reproject_scene(const ReprojArgs& A, const float* table, int n_obj, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (A.hist_moments) hipLaunchKernelGGL(reproject_gather_scene<true>, dim3(grid), dim3(256), 0, st, A, table, n_obj);
-    else hipLaunchKernelGGL(reproject_gather_scene<false>, dim3(grid), dim3(256), 0, st, A, table, n_obj);
+    if (A.hist_moments && A.hist_half) hipLaunchKernelGGL((reproject_gather_scene<true, true>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
+    else if (A.hist_moments) hipLaunchKernelGGL((reproject_gather_scene<true, false>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
+    else if (A.hist_half) hipLaunchKernelGGL((reproject_gather_scene<false, true>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
+    else hipLaunchKernelGGL((reproject_gather_scene<false, false>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
 }
 
 }  // namespace rt

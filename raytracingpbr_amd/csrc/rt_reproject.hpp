@@ -6,7 +6,8 @@
 //                      (image_buffer before the move) is gathered bilinearly from the 2x2 old pixels around it, keeping only
 //                      taps on the same object with a matching depth and normal; the sum is renormalised and capped.
 //                      The same lane resets what rtpbr_refresh resets except image_buffer (ray_buffer.depth, the diff buffers).
-//                      reproject_gather<true> also warps the noise estimate's moments (rtpbr_noise_update) with the same taps.
+//                      reproject_gather<true, *> also warps the noise estimate's moments (rtpbr_noise_update) with the same taps,
+//                      reproject_gather<*, true> half A of the two-half error estimate (rtpbr_set_half_mode, warp).
 //   reproject_gather_scene   the same gather for rtpbr_reproject_scene: a first hit on an object that moved is carried through
 //                      the object's frame into the old world (and its world-space normal turned back) before it is projected;
 //                      the per-object table (old and new position and matrix) is staged in LDS by every block.
@@ -38,6 +39,9 @@ struct ReprojArgs {
     const float4* hist_moments;     // (W,H): the moments before the move
     float4* moments;                // out: warped with the image's taps and weights, capped with it
     float4* snapshot;               // out: the warped image_buffer
+    // half A of the two-half error estimate (rt_half.hpp), when the context carries it (rtpbr_set_half_mode, warp): nullptr otherwise
+    const float4* hist_half;        // (W,H): half A before the move
+    float4* half_a;                 // out: warped with the image's taps and weights, scaled with it where the cap applies
 };
 
 // rtpbr_reproject_scene's per-object record: the moved flag (0.0f / 1.0f), p0, p1, R0, R1 (0 = old, 1 = new; R row major)

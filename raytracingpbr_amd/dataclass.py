@@ -138,6 +138,14 @@ class ErrorParams(_Pod):
     DEFAULTS = {"radius": 2}
 
 
+class HalfMode(_Pod):
+    """rtpbr_half_mode (include/rtpbr.h): halves dealt per sample by the sample calls, half A carried through the reprojections."""
+    _fields_ = [("per_sample", C.c_int32), ("warp", C.c_int32)]
+
+    # include/rtpbr.h RTPBR_HALF_MODE_DEFAULT_*, what rtpbr_set_half_mode(ctx, NULL) sets: off (tests/test_half_mode_ref.py keeps the two equal)
+    DEFAULTS = {"per_sample": 0, "warp": 0}
+
+
 class DenoiseGuidedParams(_Pod):
     """rtpbr_denoise_guided_params (include/rtpbr.h): the a-trous whose colour term is measured in standard deviations of the
     pixel's estimated noise."""

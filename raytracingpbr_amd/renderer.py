@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
+from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -45,6 +45,7 @@ class Renderer:
         self.track_noise = False             # True: every sample() call is one batch of the noise estimate (noise_update() after it)
         self.noise_per_sample = False        # what set_noise_tracking() last set: every SAMPLE is a batch, folded in by sample() itself
         self.track_halves = False            # True: every sample() / sample_selected() call is one batch of the two halves (half_update() after it)
+        self.half_mode = HalfMode(**HalfMode.DEFAULTS)      # what set_half_mode() last set
         self.set_config(config)
         self.set_scene(scene)
         self.set_camera(camera if camera is not None else scene.camera)
@@ -369,6 +370,17 @@ class Renderer:
         The first call's batch is everything accumulated so far."""
         self.api.call("half_update", self._ctx)
 
+    def set_half_mode(self, per_sample: bool = False, warp: bool = False):
+        """``per_sample``: from now on sample() and sample_selected() of the complete-path form deal every sample to a half
+        themselves, in the pass that adds it to image_buffer: one sample(8) gives halves of 4 + 4, and no half_update() is needed
+        (what was deposited before is dealt as one batch by this call; a later half_update() finds nothing new).  Refused by
+        sample() in the persistent-ray form, with option precision = 1 and with tiles of world > 1.  ``warp``: reproject() and
+        reproject_scene() carry half A with the image instead of zeroing it, so pixels with history stay estimated across a
+        move.  Both are off by default and kept across refresh / set_config / set_scene / reproject."""
+        m = HalfMode(1 if per_sample else 0, 1 if warp else 0)
+        self.api.call("set_half_mode", self._ctx, C.byref(m))
+        self.half_mode = m
+
     def denoise_error(self, threshold: float = 0.0, radius=None, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None,
                       sigma_depth=None, sigma_albedo=None) -> NoiseStats:
         """Write ``denoised_error``: the estimated standard deviation of the luminance of what ``denoise`` (with the same
@@ -396,20 +408,25 @@ class Renderer:
         self.api.call("select_error", self._ctx, float(threshold), int(dilate), C.byref(n))
         return int(n.value)
 
-    def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, **denoise_params):
+    def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False, **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
         would take a pixel past ``max_spp``; it ends with denoise(), so ``denoised_pixels`` is the filter of the whole buffer.
         ``denoise_params`` go to both denoise_error and denoise.  Returns (pixel-samples traced, NoiseStats of the last
         estimate).  Continues whatever is accumulated: refresh() first for a new frame.  The estimate is variance only: the
-        loop stops when the denoised picture has stopped moving, which the filter's bias does not prevent."""
+        loop stops when the denoised picture has stopped moving, which the filter's bias does not prevent.
+        ``per_sample``: with set_half_mode(per_sample=True) for the duration of the call (``warp`` as it is; restored after):
+        every batch is split evenly over the halves by the sample calls themselves and the loop makes no half_update()."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
         n_pix = self.config.width * self.config.height
         keep_noise, self.track_noise = self.track_noise, False
         keep_halves, self.track_halves = self.track_halves, False
+        mode = self.half_mode
+        if per_sample:
+            self.set_half_mode(True, bool(mode.warp))
         try:
             traced, used = 0, 0
             for _ in range(2):
@@ -417,7 +434,8 @@ class Renderer:
                 if n <= 0:
                     break
                 self.sample(n)
-                self.half_update()
+                if not per_sample:
+                    self.half_update()
                 traced, used = traced + n_pix * n, used + n
             while True:
                 stats = self.denoise_error(error, **denoise_params)
@@ -425,12 +443,15 @@ class Renderer:
                     break
                 n_sel = self.select_error(error, dilate)
                 self.sample_selected(batch)
-                self.half_update()
+                if not per_sample:
+                    self.half_update()
                 traced, used = traced + n_sel * batch, used + batch
             self.denoise(**denoise_params)
             return traced, stats
         finally:
             self.track_noise, self.track_halves = keep_noise, keep_halves
+            if per_sample:
+                self.set_half_mode(bool(mode.per_sample), bool(mode.warp))
 
     # ------------------------------------------------------------ the present stage (include/rtpbr.h rtpbr_present)
     def present(self, source="pixels", format="rgba8", dither=False):

@@ -1,0 +1,514 @@
+"""rtpbr_set_half_mode on the GPU: halves dealt per sample inside the accumulate pass (per_sample) and half A carried through
+rtpbr_reproject / rtpbr_reproject_scene (warp).  Every comparison is ``==`` on bit patterns against the CPU restatement
+(tests/half_mode_ref/half_mode_ref.c) — the fold fed with the per-sample colours of the unchanged CPU oracle, the gather with the
+GPU's own buffers and features — and against a twin renderer with the mode off; plus the state, lifetime and error rules of
+include/rtpbr.h."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import half_mode_ref_lib as hm
+import half_ref_lib as hl
+import noise_ref_lib as nr
+import reproject_scene_ref_lib as rs
+import sample_moments_ref_lib as sm
+import test_gpu_features_denoise as fd
+import test_gpu_half as gh
+import test_gpu_reproject as rp
+from oracle_backend import OracleRenderer
+from raytracingpbr_amd import Config, Renderer, src_scene
+from raytracingpbr_amd.dataclass import HalfMode
+from raytracingpbr_amd.renderer import BUF_HALF_BUFFER, BUF_IMAGE_BUFFER, BUF_MOMENTS, BUF_MOTION
+
+pytestmark = pytest.mark.gpu
+
+ESTATE, EINVAL = -4, -1
+FRAMES = gh.FRAMES                       # (7, 5), (33, 17), (64, 48): less than a block; partial blocks both ways; whole blocks
+KS = (1, 3, 8, 12)                       # the scalar tail alone; scalar (K % 4 != 0); the 8-at-a-time path alone; both together
+N_REF = 2 * sum(KS)                      # a full-frame and a selected call of every K
+_scene, _same, _bits, _code, _counters, _stripe = gh._scene, gh._same, gh._bits, gh._code, gh._counters, gh._stripe
+_fid = lambda f: f"{f[0]}x{f[1]}"      # noqa: E731
+
+_colours = {}
+
+
+def _ref_colours(name, frame):
+    """per-sample colours 0 .. N_REF - 1 from the oracle, computed once per scene and frame and never modified"""
+    key = (name, frame)
+    if key not in _colours:
+        scene, cfg = _scene(name, *frame)
+        c = sm.oracle_colours(OracleRenderer(scene, cfg), 0, N_REF)
+        c.setflags(write=False)
+        _colours[key] = c
+    return _colours[key]
+
+
+def _check_dealt(r, twin, d, t, what):
+    """A and image_buffer against the CPU dealer and the mode-off twin; sh through a half_update, which must find nothing new"""
+    ib = r.image_buffer
+    _same(ib, twin.image_buffer, what + "image_buffer against the twin without the mode")
+    _same(ib, d.image_buffer, what + "image_buffer")
+    assert _counters(r) == _counters(twin), what
+    _same(r.half_buffer, d.a, what + "half A")
+    _same(d.snapshot, d.image_buffer, what + "restated sh")
+    r.half_update()
+    _same(r.half_buffer, d.a, what + "half A after a half_update (sh is image_buffer)")
+    if t is not None:
+        _same(r.moments, t.moments, what + "moments")
+        _same(twin.moments, t.moments, what + "the twin's moments")
+
+
+# ------------------------------------------------------------------ 1. dealing
+@pytest.mark.parametrize("tracked", [False, True], ids=["plain", "noise_tracked"])
+@pytest.mark.parametrize("frame", FRAMES, ids=_fid)
+@pytest.mark.parametrize("name", ["cornell_v3", "scene_demo"])
+def test_dealing_matches_the_restatement_and_the_twin(name, frame, tracked):
+    w, h = frame
+    scene, cfg = _scene(name, w, h)
+    c = _ref_colours(name, frame)
+    r, twin = Renderer(scene, cfg), Renderer(scene, cfg)
+    r.set_half_mode(per_sample=True)
+    assert (r.half_mode.per_sample, r.half_mode.warp) == (1, 0) and not r.half_buffer.any()
+    if tracked:
+        r.set_noise_tracking(True)
+        twin.set_noise_tracking(True)
+    d, t = hm.Dealer(w, h), (sm.Tracker(w, h) if tracked else None)
+    k = 0
+    for n in KS:
+        r.sample(n)
+        twin.sample(n)
+        d.sample(c[k:k + n])
+        if t:
+            t.sample(c[k:k + n])
+        k += n
+        _check_dealt(r, twin, d, t, f"sample({n}): ")
+        assert r.counters().deposits == w * h * n
+    assert (d.a[..., 3] == sum(KS) // 2).all()
+    mask = _stripe(w, h)
+    for x in (r, twin):
+        assert x.select_mask(mask) == int(mask.sum())
+    for n in KS:
+        before = r.half_buffer
+        r.sample_selected(n)
+        twin.sample_selected(n)
+        d.sample(c[k:k + n], mask)
+        if t:
+            t.sample(c[k:k + n], mask)
+        k += n
+        assert np.array_equal(_bits(r.half_buffer)[mask == 0], _bits(before)[mask == 0])
+        _check_dealt(r, twin, d, t, f"sample_selected({n}): ")
+    assert np.array_equal(d.a[..., 3], np.where(mask != 0, sum(KS), sum(KS) // 2).astype(np.float32))
+    # sh holds all four words: with the mode off, a batch of two samples goes to A (a tie) as image_buffer - sh
+    r.set_half_mode(per_sample=False)
+    r.sample(2)
+    ref = hl.Halves(w, h)
+    ref.a, ref.snapshot = d.a.copy(), d.snapshot.copy()
+    _same(r.half_buffer, d.a, "half A after a call without the mode")
+    r.half_update()
+    ref.update(r.image_buffer)
+    _same(r.half_buffer, ref.a, "half A after an undealt batch on the dealt sh")
+    assert (ref.a[..., 3] == d.a[..., 3] + 2).all()
+
+
+def test_sub_launches_give_the_same_bits():
+    """the smallest staging budget (1 MiB) holds 3 records of 12 bytes for each of 170 x 130 pixels and not 4 (no primary records):
+    12 samples run as four sub-launches, and a selected call over three quarters of the frame as three — every sample is dealt on
+    its own, so the split does not show"""
+    w, h = 170, 130
+    assert (1 << 20) // (w * h * 12) == 3
+    scene, cfg = _scene("cornell_v3", w, h)
+    mask = 1 - _stripe(w, h)
+    got = []
+    for budget in (1 << 20, 1 << 30):
+        r = Renderer(scene, cfg)
+        r.set_option("primary_split", 0)
+        r.set_option("staging_bytes", budget)
+        r.set_half_mode(per_sample=True)
+        r.set_noise_tracking(True)
+        r.sample(12)
+        assert r.last_sample_ms()[2] == (4 if budget == 1 << 20 else 1)
+        r.select_mask(mask)
+        r.sample_selected(12)
+        assert (r.last_sample_ms()[2] > 1) == (budget == 1 << 20)
+        got.append((r.half_buffer, r.image_buffer, r.moments))
+    for a, b, what in zip(got[0], got[1], ("half A", "image_buffer", "moments")):
+        _same(a, b, f"{what}, sub-launches against one launch")
+    c = sm.oracle_colours(OracleRenderer(scene, cfg), 0, 24)
+    d = hm.Dealer(w, h).sample(c[:12]).sample(c[12:], mask)
+    _same(got[0][0], d.a, "half A")
+    _same(got[0][1], d.image_buffer, "image_buffer")
+    assert np.array_equal(d.a[..., 3], np.where(mask != 0, 12, 6).astype(np.float32))
+
+
+@pytest.mark.parametrize("options", [{"scheduler": 0}, {"primary_split": 2}, {"jit": 1, "stage_dense": 1}],
+                         ids=lambda o: ",".join(f"{k}={v}" for k, v in o.items()))
+def test_options_do_not_change_the_bits(options, tmp_path, monkeypatch):
+    monkeypatch.setenv("RTPBR_JIT_CACHE", str(tmp_path))
+    w, h = frame = (33, 17)
+    scene, cfg = _scene("cornell_v3", w, h)
+    r = Renderer(scene, cfg)
+    for k, v in options.items():
+        r.set_option(k, v)
+    r.set_half_mode(per_sample=True)
+    r.sample(8)
+    if "stage_dense" in options:
+        assert r.counter("jit_active") == 1 and r.counter("dense_launches") == 0      # a run-time instance, item-linear records
+    d = hm.Dealer(w, h).sample(_ref_colours("cornell_v3", frame)[:8])
+    _same(r.image_buffer, d.image_buffer, f"{options}: image_buffer")
+    _same(r.half_buffer, d.a, f"{options}: half A")
+
+
+# ------------------------------------------------------------------ 2. the defaults change nothing
+def _dealt_by_calls(r, w, h):
+    """the sequence of test_gpu_half._dealt"""
+    r.sample(2)
+    r.half_update()
+    r.sample(3)
+    r.half_update()
+    r.select_mask(_stripe(w, h))
+    r.sample_selected(2)
+    r.half_update()
+    r.sample(1)
+
+
+@pytest.mark.parametrize("name", ["cornell_v3", "scene_demo"])
+def test_the_defaults_change_nothing(name):
+    w, h = 33, 17
+    scene, cfg = _scene(name, w, h)
+    c = scene.camera
+    plain, null, py = Renderer(scene, cfg), Renderer(scene, cfg), Renderer(scene, cfg)
+    null.api.call("set_half_mode", null._ctx, None)
+    py.set_half_mode()
+    for x in (plain, null, py):
+        x.refresh()
+        _dealt_by_calls(x, w, h)
+    cam = rp._translated(c, 0.02)
+    for r in (null, py):
+        _same(r.image_buffer, plain.image_buffer, "image_buffer")
+        _same(r.half_buffer, plain.half_buffer, "half A")
+        assert _counters(r) == _counters(plain)
+    a, b = plain.denoise_error(0.01), null.denoise_error(0.01)
+    assert (a.pixels_estimated, a.pixels_above, a.max_noise) == (b.pixels_estimated, b.pixels_above, b.max_noise)
+    _same(null.denoised_error, plain.denoised_error, "denoised_error")
+    for x in (plain, null):
+        x.reproject(cam)
+    _same(null.image_buffer, plain.image_buffer, "image_buffer after reproject")
+    _same(null._read(BUF_MOTION), plain._read(BUF_MOTION), "motion")
+    assert not null.half_buffer.any() and not plain.half_buffer.any()
+
+
+# ------------------------------------------------------------------ 3. warp
+def _built(scene, cfg, cam, moments, warp):
+    """halves of 4 + 4, and of 6 + 5 on the stripe (unequal: A'.w / b'.w differs from pixel to pixel)"""
+    w, h = cfg.width, cfg.height
+    r = Renderer(scene, cfg, cam)
+    r.refresh()
+    r.set_half_mode(per_sample=True, warp=warp)
+    r.sample(8)
+    if moments:
+        r.noise_update()
+    r.select_mask(_stripe(w, h))
+    r.sample_selected(3)
+    if moments:
+        r.noise_update()
+    r.render_features()
+    return r
+
+
+def _state(r, moments):
+    return r.image_buffer, r.half_buffer, (r.moments if moments else None), fd._gpu_features(r)
+
+
+def _check_warped(r, twin, want, moments, want_M, what):
+    want_b, want_mv, want_A = want
+    _same(r.image_buffer, want_b, what + "image_buffer")
+    _same(r._read(BUF_MOTION), want_mv, what + "motion")
+    _same(r.half_buffer, want_A, what + "half A")
+    _same(r.image_buffer, twin.image_buffer, what + "image_buffer against the twin without warp")
+    _same(r._read(BUF_MOTION), twin._read(BUF_MOTION), what + "motion against the twin")
+    assert not twin.half_buffer.any()
+    if moments:
+        _same(r.moments, want_M, what + "moments")
+        _same(r.moments, twin.moments, what + "moments against the twin")
+    else:
+        assert _code(lambda: r.moments) == ESTATE
+    none = want_mv[..., 0] == -1
+    assert not want_A[none].any() and np.all(want_A[..., 3] <= want_b[..., 3]) and np.all(want_A[..., 3] >= 0)
+    assert (want_A[..., 3] > 0).any() and (want_b[..., 3] - want_A[..., 3] > 0).any()
+
+
+def _check_sh(r, want_b, want_A, what):
+    """sh is the warped image_buffer in all four words: an undealt batch after the move is image_buffer - sh"""
+    w, h = want_b.shape[:2]
+    r.half_update()
+    _same(r.half_buffer, want_A, what + "half A after a half_update")
+    r.set_half_mode(per_sample=False, warp=True)
+    r.sample(2)
+    r.half_update()
+    ref = hl.Halves(w, h)
+    ref.a, ref.snapshot = want_A.copy(), want_b.copy()
+    ref.update(r.image_buffer)
+    _same(r.half_buffer, ref.a, what + "half A after an undealt batch on the warped sh")
+
+
+CASES = {"plain": (False, None), "moments": (True, None), "cap": (True, 4.0)}      # 8 to 11 spp of history: 4.0 caps every pixel
+
+
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("frame", FRAMES, ids=_fid)
+@pytest.mark.parametrize("name", ["cornell_v3", "scene_demo"])
+def test_reproject_carries_half_a(name, frame, case):
+    w, h = frame
+    moments, max_history = CASES[case]
+    scene, cfg = _scene(name, w, h)
+    old, new = rp.MOVES["translate"](scene.camera)
+    r, twin = _built(scene, cfg, old, moments, True), _built(scene, cfg, old, moments, False)
+    ib, A, M, f0 = _state(r, moments)
+    _same(twin.half_buffer, A, "half A before the move")
+    # an unchanged camera leaves A (and everything else) bit for bit
+    r.reproject(old, max_history=1e6)
+    _same(r.half_buffer, A, "half A under an unchanged camera")
+    _same(r.image_buffer, ib, "image_buffer under an unchanged camera")
+    for x in (r, twin):
+        x.reproject(new, max_history=max_history)
+    assert (r.half_mode.per_sample, r.half_mode.warp) == (1, 1)
+    f1 = fd._gpu_features(r)
+    want = hm.gather(cfg, scene, scene, old, new, ib, A, f0, f1, max_history=max_history)
+    want_M = nr.reproject(cfg, old, new, ib, M, f0, f1, max_history=max_history)[1] if moments else None
+    _check_warped(r, twin, want, moments, want_M, f"{case}: ")
+    if case == "cap":
+        hist = want[1][..., 0] != -1
+        assert np.all(want[0][hist][:, 3] <= 4.0) and np.all(ib[..., 3] >= 8)
+    _check_sh(r, want[0], want[2], f"{case}: ")
+
+
+@pytest.mark.parametrize("camera_moves", [False, True], ids=["camera_still", "camera_moved"])
+@pytest.mark.parametrize("frame", FRAMES, ids=_fid)
+def test_reproject_scene_carries_half_a(frame, camera_moves):
+    w, h = frame
+    scene, cfg = _scene("cornell_v3", w, h)
+    moved = rs.moved_scene(scene, {6: ((0.08, 0.0, 0.05), (0, 7, 0))})      # Cornell's small box
+    old = scene.camera
+    new = rp._translated(old, 0.02) if camera_moves else None
+    for moments, max_history in ((False, None), (True, 4.0)):
+        r, twin = _built(scene, cfg, old, moments, True), _built(scene, cfg, old, moments, False)
+        ib, A, M, f0 = _state(r, moments)
+        for x in (r, twin):
+            x.reproject_scene(moved, new, max_history=max_history)
+        f1 = fd._gpu_features(r)
+        want = hm.gather(cfg, scene, moved, old, new, ib, A, f0, f1, max_history=max_history)
+        want_M = rs.reproject_scene(cfg, scene, moved, old, new, ib, f0, f1, moments=M, max_history=max_history)[2] if moments else None
+        _check_warped(r, twin, want, moments, want_M, f"moments {moments}: ")
+        _check_sh(r, want[0], want[2], f"moments {moments}: ")
+
+
+@pytest.mark.parametrize("frame", FRAMES, ids=_fid)
+def test_error_and_selection_after_a_warped_move(frame):
+    w, h = frame
+    scene, cfg = _scene("cornell_v3", w, h)
+    old, new = rp.MOVES["translate"](scene.camera)
+    r, twin = _built(scene, cfg, old, False, True), _built(scene, cfg, old, False, False)
+    for x in (r, twin):
+        x.reproject(new)
+    model = hl.Halves(w, h)
+    model.a = r.half_buffer
+    ib = r.image_buffer
+    hist = ib[..., 3] > 0
+    both = (model.a[..., 3] > 0) & (ib[..., 3] - model.a[..., 3] > 0)
+    assert np.array_equal(both, hist)                                     # every pixel with history keeps both halves
+    err, stats = gh._check_error(r, cfg, model, 0.0, 2)
+    assert stats.pixels_estimated == int(hist.sum()) > 0
+    assert twin.denoise_error(0.0).pixels_estimated == 0                  # without warp every pixel has an empty half
+    # a threshold nothing exceeds: only the pixels without history are selected; without warp, the whole frame
+    sel = gh._check_select(r, model, err, 1e9, 0)
+    assert np.array_equal(sel != 0, ~hist) and int(sel.sum()) < w * h
+    assert twin.select_error(1e9, 0) == w * h
+    thr = float(np.median(err[err > 0]))
+    err, stats = gh._check_error(r, cfg, model, thr, 2)
+    sel = gh._check_select(r, model, err, thr, 1)
+    assert 0 < stats.pixels_above < stats.pixels_estimated
+
+
+# ------------------------------------------------------------------ 4. refusals and lifetime
+def test_refusals_change_nothing():
+    from raytracingpbr_amd import _capi
+    api = _capi.hip_api()
+    ctx = C.c_void_p()
+    api.call("create", 0, C.byref(ctx))
+    try:
+        on = HalfMode(1, 0)
+        assert api.fn["set_half_mode"](ctx, C.byref(on)) == ESTATE             # 0 -> 1 is rtpbr_half_update: before set_config
+        assert api.fn["set_half_mode"](ctx, C.byref(HalfMode(0, 1))) == 0      # every other transition only sets the mode
+        assert api.fn["set_half_mode"](ctx, None) == 0
+        assert api.fn["set_half_mode"](None, C.byref(on)) == EINVAL
+    finally:
+        api.call("destroy", ctx)
+    w, h = frame = (33, 17)
+    scene, cfg = _scene("cornell_v3", w, h)
+    r = Renderer(scene, cfg)
+    r.set_half_mode(per_sample=True, warp=True)
+    r.sample(3)
+    r.select_mask(_stripe(w, h))
+    keep = {b: r._read(b) for b in (BUF_IMAGE_BUFFER, BUF_HALF_BUFFER)}
+    counters = _counters(r)
+    for bad in ((2, 0), (-1, 0), (0, 2), (1, -1), (7, 7)):
+        assert r.api.fn["set_half_mode"](r._ctx, C.byref(HalfMode(*bad))) == EINVAL
+    r.set_tiles(16, 16, 0, 2)
+    assert _code(lambda: r.sample(1)) == ESTATE and _code(lambda: r.sample_selected(1)) == ESTATE
+    r.set_tiles(0, 0, 0, 1)
+    r.set_option("precision", 1)
+    assert _code(lambda: r.sample(1)) == ESTATE
+    r.set_option("precision", 0)
+    assert _counters(r) == counters
+    for b, a in keep.items():
+        _same(r._read(b), a, f"buffer {b} after refused calls")
+    # ... and neither the mode nor the sample index moved: the next dealing call deposits samples 3 and 4
+    r.sample(2)
+    d = hm.Dealer(w, h).sample(_ref_colours("cornell_v3", frame)[:5])
+    _same(r.half_buffer, d.a, "half A")
+    _same(r.image_buffer, d.image_buffer, "image_buffer")
+    # 0 -> 1 with tiles of world > 1 is refused as rtpbr_half_update is, and leaves the mode off
+    q = Renderer(scene, cfg)
+    q.sample(1)
+    q.set_tiles(16, 16, 0, 2)
+    assert _code(lambda: q.set_half_mode(per_sample=True)) == ESTATE
+    q.set_tiles(0, 0, 0, 1)
+    q.sample(1)
+    assert _code(lambda: q.half_buffer) == ESTATE                              # the mode stayed off: nothing was dealt or allocated
+    # the persistent-ray form has no per-sample records
+    pscene, pcfg = src_scene(aspect=20 / 13), Config.src(20, 13, 7, steps_per_launch=1)
+    p = fd._renderer(pscene, pcfg)
+    p.sample(2)
+    p.set_half_mode(per_sample=True)              # the set call itself is half_update: any form
+    before, A = p.image_buffer, p.half_buffer
+    _same(A, before, "everything deposited so far is one batch")
+    assert _code(lambda: p.sample(1)) == ESTATE
+    _same(p.image_buffer, before, "image_buffer")
+    _same(p.half_buffer, A, "half A")
+    p.set_half_mode(per_sample=False)
+    p.sample(1)
+
+
+def test_lifetime():
+    w, h = frame = (33, 17)
+    scene, cfg = _scene("cornell_v3", w, h)
+    c = _ref_colours("cornell_v3", frame)
+    r = Renderer(scene, cfg)
+    r.sample(2)                                   # undealt: the set call deals these as one batch, as half_update would
+    assert _code(lambda: r.half_buffer) == ESTATE
+    r.set_half_mode(per_sample=True)
+    d = hm.Dealer(w, h)
+    d.image_buffer = r.image_buffer
+    d.a, d.snapshot = d.image_buffer.copy(), d.image_buffer.copy()
+    _same(r.half_buffer, d.a, "half A after the set call")
+    r.sample(3)
+    _same(r.half_buffer, d.sample(c[2:5]).a, "half A after a batch and three samples")      # B catches up first: B, B, A
+    assert (d.a[..., 3] == 3).all()
+    # refresh zeroes A and sh, the mode stays on (the sample index goes on: samples 5 .. 7)
+    r.refresh()
+    assert not r.half_buffer.any() and r.half_mode.per_sample == 1
+    r.sample(3)
+    d = hm.Dealer(w, h).sample(c[5:8])
+    _same(r.half_buffer, d.a, "half A after refresh")
+    _same(r.image_buffer, d.image_buffer, "image_buffer after refresh")
+    # write_buffer(IMAGE_BUFFER): A = 0, sh = the written data, which lies in B; the next samples catch A up
+    ib = r.image_buffer
+    ib[3:6, 2:9] = 0.0
+    r.image_buffer = ib
+    assert not r.half_buffer.any()
+    r.half_update()
+    assert not r.half_buffer.any()
+    r.sample(2)
+    d.a[:], d.snapshot, d.image_buffer = 0.0, ib.copy(), ib.copy()
+    _same(r.half_buffer, d.sample(c[8:10]).a, "half A after a write")
+    _same(r.image_buffer, d.image_buffer, "image_buffer after a write")
+    # every other transition only sets the mode
+    A = r.half_buffer
+    r.set_half_mode(per_sample=False, warp=True)
+    r.set_half_mode(per_sample=False, warp=False)
+    _same(r.half_buffer, A, "half A after the mode changes")
+    r.sample(2)
+    _same(r.half_buffer, A, "half A after a call without the mode")
+    # a new resolution frees the buffers; the mode survives and the next dealing call makes them again, zeroed
+    r.set_half_mode(per_sample=True, warp=True)
+    w2, h2 = frame2 = (7, 5)
+    scene2, cfg2 = _scene("cornell_v3", w2, h2)
+    r.set_config(cfg2)
+    r.set_camera(scene2.camera)
+    assert _code(lambda: r.half_buffer) == ESTATE
+    r.refresh()
+    r.set_option("sample_base", 0)
+    r.sample(3)
+    d2 = hm.Dealer(w2, h2).sample(_ref_colours("cornell_v3", frame2)[:3])
+    _same(r.half_buffer, d2.a, "half A after a new resolution")
+    _same(r.image_buffer, d2.image_buffer, "image_buffer after a new resolution")
+    # set_scene keeps the mode
+    r.set_scene(scene2)
+    r.refresh()
+    r.sample(1)
+    assert (r.half_buffer[..., 3] == 1).all() and (r.half_mode.per_sample, r.half_mode.warp) == (1, 1)
+
+
+def test_async_read_of_half_a_lands_the_pre_call_contents():
+    scene, cfg = _scene("cornell_v3", 128, 128)
+    r = Renderer(scene, cfg)
+    r.set_half_mode(per_sample=True)
+    r.sample(2)
+    host = r.host_array(BUF_HALF_BUFFER)
+    before = r.half_buffer
+    t = r.read_async(BUF_HALF_BUFFER, host)       # the dealing launch that follows must not overtake this copy
+    r.sample(4)
+    r.read_wait(t)
+    _same(host, before, "asynchronously read half A")
+    assert (r.half_buffer[..., 3] == 3).all()
+
+
+# ------------------------------------------------------------------ 5. the loop
+def test_render_adaptive_denoised_per_sample_is_its_calls_one_by_one():
+    w = h = 32
+    scene, cfg = _scene("cornell_v3", w, h)
+    error, max_spp, batch, dilate = 0.02, 24, 4, 1
+    r = Renderer(scene, cfg)
+    r.set_half_mode(warp=True)
+    r.track_halves = True
+    traced, stats = r.render_adaptive_denoised(error, max_spp, batch, dilate, per_sample=True, iterations=3)
+    assert r.track_halves and (r.half_mode.per_sample, r.half_mode.warp) == (0, 1)      # restored
+    s = Renderer(scene, cfg)
+    s.set_half_mode(per_sample=True)
+    want_traced, used = 0, 0
+    for _ in range(2):
+        s.sample(batch)
+        want_traced, used = want_traced + w * h * batch, used + batch
+    while True:
+        st = s.denoise_error(error, iterations=3)
+        if st.pixels_above == 0 or used + batch > max_spp:
+            break
+        n_sel = s.select_error(error, dilate)
+        s.sample_selected(batch)
+        want_traced, used = want_traced + n_sel * batch, used + batch
+    assert traced == want_traced and used > 2 * batch
+    assert (stats.pixels_estimated, stats.pixels_above, stats.max_noise) == (st.pixels_estimated, st.pixels_above, st.max_noise)
+    _same(r.image_buffer, s.image_buffer, "image_buffer")
+    _same(r.half_buffer, s.half_buffer, "half A")
+    ib, A = r.image_buffer, r.half_buffer
+    assert np.array_equal(A[..., 3], np.ceil(ib[..., 3] / 2))                            # every pixel's halves differ by at most one sample
+
+
+# ------------------------------------------------------------------ 6. random call sequences against the state model
+@pytest.mark.parametrize("seed", range(10))
+def test_random_half_sequence_matches_model(seed):
+    """~40 random operations of tests/half_sequences.py on 33 x 17 / 20 x 13 frames, both kernel forms: half of them those of the
+    existing sequences, half rtpbr_set_half_mode, dealing sample calls, rtpbr_half_update, rtpbr_denoise_error / rtpbr_select_error
+    and reprojections that carry or zero half A — every call refused or accepted as include/rtpbr.h says, every value it returns
+    or leaves behind bit for bit the model's (tests/half_mode_model.py)"""
+    import call_sequences as cs
+    import half_sequences as hs
+    s = hs.half_script(seed)
+    a, b = cs.new_renderer(s, Renderer), hs.model(s)
+    try:
+        seen, _ = hs.run_half(s, a, b)
+    finally:
+        a.close()
+        b.close()
+    assert any(k == "image_buffer" for _, k, _ in seen) and any(k == "half_buffer" for _, k, _ in seen)

@@ -237,7 +237,9 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        /* the two halves and the error estimate of the denoised frame (rtpbr_half_update / rtpbr_denoise_error): each allocated on
         * the first such call, RTPBR_ESTATE before; outputs only */
        RTPBR_BUF_HALF_BUFFER  = 15,  /* (W,H,4) f32 half A's (sum r, sum g, sum b, count); half B = image_buffer - A per component */
-       RTPBR_BUF_DENOISED_ERROR = 16 }; /* (W,H) f32 estimated standard deviation of lum(rtpbr_denoise's display colour)         */
+       RTPBR_BUF_DENOISED_ERROR = 16, /* (W,H) f32 estimated standard deviation of lum(rtpbr_denoise's display colour)         */
+       /* the weight of rtpbr_denoise_blend: allocated by its first call, freed by rtpbr_set_config with a new resolution; output only */
+       RTPBR_BUF_BLEND_WEIGHT = 17 };   /* (W,H) f32 t in [0, 1]: 1 = the denoised colour, 0 = the raw average                    */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -706,6 +708,65 @@ typedef struct rtpbr_error_params {   /* 4-byte members, no padding */
 int rtpbr_half_update(rtpbr_ctx* ctx);
 int rtpbr_denoise_error(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_error_params* e, float threshold, rtpbr_noise_stats* out);
 int rtpbr_select_error(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
+
+/* ---- The bias-aware blend of the denoised and the raw frame, from the same two halves.
+ *
+ * rtpbr_denoise_error sees variance only.  What the a-trous filter leaves behind once the noise is gone is bias — blur inside one
+ * object — and a host that shows RTPBR_BUF_DENOISED_PIXELS never converges, while the raw average does.  The two halves hold what
+ * is needed to see that bias: for one half, filter(half) - raw(half) estimates bias - noise of that half, the two halves' noise is
+ * independent, so the PRODUCT of the two differences has expectation bias^2, and the covariance of the raw frame with
+ * (filtered - raw) gives the mean-square-optimal weight between the two frames.  rtpbr_denoise_blend is a member of the denoise
+ * family: it writes RTPBR_BUF_DENOISED_PIXELS as rtpbr_denoise_guided does (so rtpbr_present(RTPBR_PRESENT_DENOISED) and every
+ * read of that buffer serve the blended frame), and RTPBR_BUF_BLEND_WEIGHT, and nothing else: image_buffer, half A and its
+ * snapshot, the moments, RTPBR_BUF_NOISE, RTPBR_BUF_DENOISED_ERROR, the selection and the work counters keep their bits.  It
+ * blocks like rtpbr_denoise_error (the statistics come back), flushes lazy shading, is ordered behind asynchronous reads of the
+ * two buffers it writes and renders stale features first.  p == NULL: rtpbr_denoise's defaults; e == NULL: the defaults below.
+ *
+ * Every operation is f32, in the order written, nothing fused; lum is the noise section's.  The statistics are taken on LINEAR
+ * radiance, before the tone map (in display space the tone map saturates and the raw half is no longer unbiased).  With
+ * b = image_buffer and A = half A:
+ *   B = b - A per component (materialised as for rtpbr_denoise_error);
+ *   F(buf) = rtpbr_denoise's filter with p applied to buf, "has samples" meaning buf's own count > 0, stopped before the tone map:
+ *     the linear colour after remodulation, exactly the value the last level hands to the tone map;
+ *   FD = F(b), FA = F(A), FB = F(B);   Pb = (b.x / b.w, b.y / b.w, b.z / b.w), PA and PB alike from A and B;
+ *   m = (float)min_half_samples, z2 = z * z.
+ * Per pixel q, cA = A.w, cB = B.w (= b.w - A.w):
+ *   q is usable when cA >= m and cB >= m;
+ *   f  = (cA * cB) / ((cA + cB) * (cA + cB));
+ *   dA = lum(FA) - lum(PA);  dB = lum(FB) - lum(PB);  dp = lum(PA) - lum(PB);  dd = dA - dB;  dl = lum(FD) - lum(Pb);
+ *   a_q = (f * dp) * dd;     q_q = dl * dl;     x_q = dA * dB.
+ * Per usable pixel p, all sums from +0, over q = p + (dx, dy), dy = -R..R (outer), dx = -R..R (inner), inside the frame, on p's
+ * RTPBR_BUF_FEAT_OBJECT, usable:
+ *   n = n + 1;  SC = SC + a_q;  SQ = SQ + q_q;  SX = SX + x_q;  SXX = SXX + x_q * x_q;
+ *   m1 = SX / n;   v = fmaxf(SXX / n - m1 * m1, 0);
+ *   significant = m1 > 0 and (m1 * m1) * n > z2 * v;
+ *   t = 1 unless significant; otherwise t = -SC / SQ; if (!(t < 1)) t = 1; if (t < 0) t = 0          (a NaN gives 1).
+ * A pixel that is not usable has t = 1.  RTPBR_BUF_BLEND_WEIGHT = t.  For a pixel with b.w > 0:
+ *   t == 1: c = FD;   otherwise u = 1 - t; c.k = FD.k + u * (Pb.k - FD.k) per channel;   denoised = tone_map(cfg, (c, 1));
+ * a pixel without samples shows what rtpbr_post_process shows, and its weight is 1.
+ * Why this shape: with raw = truth + noise and filtered = truth + bias + noise', the weight t on the filtered colour that
+ * minimises E[(t filtered + (1 - t) raw - truth)^2] is -cov(raw, filtered - raw) / E[(filtered - raw)^2].  dp dd is the halves'
+ * sample of that covariance — (PA - PB) carries the raw noise, (dA - dB) the noise of filtered - raw, the truth and the bias
+ * cancel in both — and f scales a difference of halves to the full frame as in the error section: E[SC / n] = cov, SQ / n
+ * estimates E[(filtered - raw)^2].  SX / n estimates bias^2; its standard error is sqrt(v / n), from SXX; the gate "the squared
+ * bias exceeds z standard errors" is written without a root.  Without the gate the weight lets raw noise back in where the halves
+ * cannot see any bias yet.  With t = 1 everywhere — min_half_samples above every count, or no significant
+ * window — the call writes rtpbr_denoise(p)'s bytes exactly.
+ * Statistics: pixels_estimated = the usable pixels, pixels_above = those with t < 1, max_noise = the largest 1 - t.
+ * Errors, each before anything changes: RTPBR_EINVAL for a NULL context, parameters rtpbr_denoise refuses, a radius outside 1..3,
+ * a z that is not finite and >= 0, min_half_samples outside 1..16777216; RTPBR_ESTATE before set_config / set_scene / set_camera,
+ * with tiles of world > 1 and before half A exists (no rtpbr_half_update or dealing call yet). */
+typedef struct rtpbr_blend_params {   /* 4-byte members, no padding */
+    int32_t radius;             /* 1..3: window (2 radius + 1)^2 on the pixel's object      */
+    float   z;                  /* >= 0, finite: the bias must exceed z standard errors     */
+    int32_t min_half_samples;   /* 1..16777216: both halves need this many samples          */
+} rtpbr_blend_params;
+/* Defaults (e == NULL): the setting measured in DESIGN.md section 6l.
+ * raytracingpbr_amd.dataclass.BlendParams.DEFAULTS mirrors them (tests/test_blend_ref.py checks). */
+#define RTPBR_BLEND_DEFAULT_RADIUS 3
+#define RTPBR_BLEND_DEFAULT_Z 2.0f
+#define RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES 16
+int rtpbr_denoise_blend(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out);
 
 /* ---- Halves dealt per sample and carried through reprojection.
  *

@@ -12,7 +12,7 @@ import ctypes as C
 import os
 
 from .config import Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, ReprojectParams, SDFObject
+from .dataclass import BlendParams, Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, ReprojectParams, SDFObject
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPBR_HIP_LIB overrides the path (A/B of differently built HIP libraries); it must still be a HIP build
@@ -28,12 +28,12 @@ ENTRY_POINTS = [
     "rccl_unique_id", "rccl_init", "rccl_init_all", "gather_tiles", "gather_tiles_all", "rccl_info", "jit_prebuild",
     "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
     "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
-    "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode",
+    "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode", "denoise_blend",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
 ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
                    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
-                   "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode")
+                   "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode", "denoise_blend")
 
 
 class RtpbrError(RuntimeError):
@@ -108,6 +108,7 @@ class CApi:
             "denoise_error": (C.c_int, [p, C.POINTER(DenoiseParams), C.POINTER(ErrorParams), C.c_float, C.POINTER(NoiseStats)]),
             "select_error": (C.c_int, [p, C.c_float, C.c_int, C.POINTER(C.c_uint32)]),
             "set_half_mode": (C.c_int, [p, C.POINTER(HalfMode)]),
+            "denoise_blend": (C.c_int, [p, C.POINTER(DenoiseParams), C.POINTER(BlendParams), C.POINTER(NoiseStats)]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

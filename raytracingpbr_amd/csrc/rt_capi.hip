@@ -142,7 +142,7 @@ static void free_noise(rtpbr_ctx* c) {
     c->noise_map = c->noise_var = nullptr;
 }
 
-// buffers of rtpbr_half_update / rtpbr_denoise_error (allocated on first use)
+// buffers of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend (allocated on first use)
 static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->half_a);
     (void)hipFree(c->half_snapshot);
@@ -151,8 +151,10 @@ static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->half_da);
     (void)hipFree(c->half_db);
     (void)hipFree(c->denoised_error);
+    (void)hipFree(c->half_fd);
+    (void)hipFree(c->blend_weight);
     c->half_a = c->half_snapshot = c->hist_half = c->half_b = nullptr;
-    c->half_da = c->half_db = c->denoised_error = nullptr;
+    c->half_da = c->half_db = c->denoised_error = c->half_fd = c->blend_weight = nullptr;
 }
 
 // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (allocated on the first select call)
@@ -736,7 +738,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b <= RTPBR_BUF_DENOISED_ERROR; b++)
+    for (int b = 0; b <= RTPBR_BUF_BLEND_WEIGHT; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -1560,10 +1562,11 @@ static int denoised_alloc(rtpbr_ctx* c, int iterations) {
 // The levels of either filter, after every refusal: level k reads half (k - 1) & 1 of denoise_scratch and writes half k & 1; the
 // first reads image_buffer, the last writes denoised.  g != nullptr: the guided kernel, whose variance goes the same way through
 // the two planes of noise_var behind the estimate's (plane 0).  No level: the tone-map-only pass, the same for both.
-// in / out (rtpbr_denoise_error): the filter of another (sum r, sum g, sum b, count) buffer into another display buffer; the caller
-// has allocated the ping-pong.
+// in / out (rtpbr_denoise_error, rtpbr_denoise_blend): the filter of another (sum r, sum g, sum b, count) buffer into another
+// display buffer; the caller has allocated the ping-pong.  linear (plain filter, with out): the last level stops before the tone
+// map and out takes the linear colour after remodulation.
 static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
-                          const float4* in = nullptr, float* out = nullptr) {
+                          const float4* in = nullptr, float* out = nullptr, bool linear = false) {
     if (!out)
         if (int r = denoised_alloc(c, iterations)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
@@ -1584,7 +1587,7 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
         A.sc2 = g->sigma_color * g->sigma_color;
         A.floor = g->variance_floor;
     }
-    if (iterations == 0) launch_atrous_level(A, true, true, false, c->stream);      // (A.step = 0)
+    if (iterations == 0) launch_atrous_level(A, true, true, false, c->stream, linear);      // (A.step = 0)
     for (int k = 0; k < iterations; k++) {
         const bool first = k == 0, last = k + 1 == iterations;
         A.src = first ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
@@ -1596,7 +1599,7 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
             A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
         }
         A.step = 1 << k;
-        launch_atrous_level(A, first, last, g != nullptr, c->stream);
+        launch_atrous_level(A, first, last, g != nullptr, c->stream, linear && last);
     }
     HIP_TRY(hipGetLastError());
     return RTPBR_OK;
@@ -2000,8 +2003,8 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
 }
 
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
-enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR };
-static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
+enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT };
+static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
 
 // What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
 // snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.  keep_a: A has
@@ -2111,6 +2114,66 @@ extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     return noise_stats_read(c, out);
 }
 
+// ---- the bias-aware blend of the denoised and the raw frame (half_blend<R>, rt_half.hip)
+extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_params d;
+    float inv[4];
+    if (int r = denoise_params(p, d, inv)) return r;
+    rtpbr_blend_params b{RTPBR_BLEND_DEFAULT_RADIUS, RTPBR_BLEND_DEFAULT_Z, RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES};
+    if (e) b = *e;
+    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend: radius must be 1..3");
+    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend: z must be finite and >= 0");
+    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend: min_half_samples must be 1..16777216");
+    if (int r = whole_frame_state(c, HALF_TILES)) return r;
+    if (!c->half_a) return fail(RTPBR_ESTATE, "rtpbr_denoise_blend: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)");
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, n * sizeof(float4)));
+    if (!c->half_da) HIP_TRY(hipMalloc(&c->half_da, n * 3 * sizeof(float)));
+    if (!c->half_db) HIP_TRY(hipMalloc(&c->half_db, n * 3 * sizeof(float)));
+    if (!c->half_fd) HIP_TRY(hipMalloc(&c->half_fd, n * 3 * sizeof(float)));
+    if (!c->blend_weight) HIP_TRY(hipMalloc(&c->blend_weight, n * sizeof(float)));
+    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
+    if (int r = denoised_alloc(c, d.iterations)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
+    if (int r = rt_order_after_reads(c, W_BLEND)) return r;
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;
+    HalfArgs S{};
+    S.image_buffer = c->image_buffer;
+    S.half_a = c->half_a;
+    S.half_b = c->half_b;
+    S.width = c->cfg.width;
+    S.height = c->cfg.height;
+    launch_half_subtract(S, c->stream);
+    // three runs of the same filter, each stopping before the tone map
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->half_fd, true)) return r;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_a, c->half_da, true)) return r;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_b, c->half_db, true)) return r;
+    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    BlendArgs A{};
+    A.cfg = c->cfg;
+    A.image_buffer = c->image_buffer;
+    A.half_a = c->half_a;
+    A.half_b = c->half_b;
+    A.fd = c->half_fd;
+    A.fa = c->half_da;
+    A.fb = c->half_db;
+    A.object = c->feat_object;
+    A.weight = c->blend_weight;
+    A.out = c->denoised;
+    A.stats = c->noise_stats;
+    A.min_half = (float)b.min_half_samples;
+    A.z2 = b.z * b.z;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    A.radius = b.radius;
+    launch_half_blend(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    return noise_stats_read(c, out);
+}
+
 extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
     if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
@@ -2194,13 +2257,14 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_PRESENT: *p = c->present; *n = np * (size_t)c->present_channels; break;
         case RTPBR_BUF_HALF_BUFFER: *p = c->half_a; *n = np * 16; break;
         case RTPBR_BUF_DENOISED_ERROR: *p = c->denoised_error; *n = np * 4; break;
+        case RTPBR_BUF_BLEND_WEIGHT: *p = c->blend_weight; *n = np * 4; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
     // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate,
     // the packed frame from the first rtpbr_present, the half buffer from the first rtpbr_half_update, the error map from the first
-    // rtpbr_denoise_error)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error first");
+    // rtpbr_denoise_error, the blend weight from the first rtpbr_denoise_blend)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend first");
     return 0;
 }
 
@@ -2301,8 +2365,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_DENOISED_ERROR)
-        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half and error buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_BLEND_WEIGHT)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half, error and blend-weight buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

@@ -183,7 +183,7 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[17] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[18] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
     float* feat_albedo = nullptr;      // (W,H,3)
@@ -218,9 +218,12 @@ struct rtpbr_ctx {
     float4* hist_half = nullptr;       // (W,H): half A before a reprojection that carries it (rtpbr_set_half_mode, warp)
     rtpbr_half_mode half_mode{RTPBR_HALF_MODE_DEFAULT_PER_SAMPLE, RTPBR_HALF_MODE_DEFAULT_WARP};      // rtpbr_set_half_mode: plain state, kept across refresh / set_config / set_scene / reproject
     float4* half_b = nullptr;          // (W,H): image_buffer - half_a, materialised per rtpbr_denoise_error
-    float* half_da = nullptr;          // (W,H,3): the filter's display colour of half A
+    float* half_da = nullptr;          // (W,H,3): the filter's colour of half A (scratch of the call that fills it)
     float* half_db = nullptr;          // (W,H,3): ... of half B
     float* denoised_error = nullptr;   // (W,H): RTPBR_BUF_DENOISED_ERROR
+    // rtpbr_denoise_blend: from its first call on (it filters the halves into half_da / half_db too, in their linear form); freed with the halves
+    float* half_fd = nullptr;          // (W,H,3): the filter's linear colour of image_buffer
+    float* blend_weight = nullptr;     // (W,H): RTPBR_BUF_BLEND_WEIGHT
     // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
     uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
     uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)

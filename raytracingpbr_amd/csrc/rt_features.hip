@@ -103,8 +103,11 @@ constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pix
 // GUIDED: the colour term's ic is per pixel, 1 / (sigma_c^2 max(g, floor)), g the 3x3 Gaussian of the level's variance (nine
 // more taps of object word + variance, 8 bytes each), and the variance is filtered beside the colour with the squared weights:
 // 4 more bytes per tap taken (40 / 36), one more 4-byte record written.
-template <bool FIRST, bool LAST, bool GUIDED>
+// LINEAR (last level only; rtpbr_denoise_blend): out takes the linear colour after remodulation — exactly the value the other
+// form hands to tone_map — and +0 for a pixel without samples.
+template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false>
 __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
+    static_assert(LAST || !LINEAR, "the linear form is a last level");
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -124,7 +127,7 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     }
     if (!valid) {       // no samples: exactly what post_process shows, and nobody's neighbour
         if constexpr (LAST) {
-            const vec3 t = tone_map(A.cfg, A.image_buffer[i]);
+            const vec3 t = LINEAR ? mk(0.0f, 0.0f, 0.0f) : tone_map(A.cfg, A.image_buffer[i]);
             A.out[(size_t)i * 3 + 0] = t.x;
             A.out[(size_t)i * 3 + 1] = t.y;
             A.out[(size_t)i * 3 + 2] = t.z;
@@ -217,7 +220,7 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     vec3 c = mk(sx / sw, sy / sw, sz / sw);
     if constexpr (LAST) {
         if (A.demodulate) c = mk(c.x * ac.x, c.y * ac.y, c.z * ac.z);
-        const vec3 t = tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
+        const vec3 t = LINEAR ? c : tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
         A.out[(size_t)i * 3 + 0] = t.x;
         A.out[(size_t)i * 3 + 1] = t.y;
         A.out[(size_t)i * 3 + 2] = t.z;
@@ -228,6 +231,8 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
 }
 
 // iterations = 0: the average, demodulated and remodulated, tone-mapped (with demodulate = 0 bit for bit post_process's image_pixels)
+// LINEAR: as atrous_level's
+template <bool LINEAR>
 __global__ void __launch_bounds__(256) atrous_none(const DenoiseArgs A) {
     const uint32_t n = (uint32_t)A.width * (uint32_t)A.height;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -238,9 +243,9 @@ __global__ void __launch_bounds__(256) atrous_none(const DenoiseArgs A) {
         const vec3 ac = A.demodulate ? albedo_clamped(A, i) : mk(1.0f, 1.0f, 1.0f);
         vec3 c = start_colour(b, ac, A.demodulate);
         if (A.demodulate) c = mk(c.x * ac.x, c.y * ac.y, c.z * ac.z);
-        t = tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
+        t = LINEAR ? c : tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
     } else {
-        t = tone_map(A.cfg, b);
+        t = LINEAR ? mk(0.0f, 0.0f, 0.0f) : tone_map(A.cfg, b);
     }
     A.out[(size_t)i * 3 + 0] = t.x;
     A.out[(size_t)i * 3 + 1] = t.y;
@@ -263,10 +268,13 @@ static void launch_level(const DenoiseArgs& A, bool first, bool last, unsigned g
     else hipLaunchKernelGGL((atrous_level<false, false, GUIDED>), dim3(grid), dim3(256), 0, st, A);
 }
 
-// step 0 (no level) is the iterations = 0 pass of both calls
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st) {
+// step 0 (no level) is the iterations = 0 pass of both calls; linear: the plain filter's last level (or that pass) without the tone map
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (A.step == 0) hipLaunchKernelGGL(atrous_none, dim3(grid), dim3(256), 0, st, A);
+    if (A.step == 0 && linear) hipLaunchKernelGGL(atrous_none<true>, dim3(grid), dim3(256), 0, st, A);
+    else if (A.step == 0) hipLaunchKernelGGL(atrous_none<false>, dim3(grid), dim3(256), 0, st, A);
+    else if (linear && first) hipLaunchKernelGGL((atrous_level<true, true, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (linear) hipLaunchKernelGGL((atrous_level<false, true, false, true>), dim3(grid), dim3(256), 0, st, A);
     else if (guided) launch_level<true>(A, first, last, grid, st);
     else launch_level<false>(A, first, last, grid, st);
 }

@@ -15,6 +15,7 @@
 //                        variance (rt_noise.hip's estimate at level 0) is filtered along with the squared weights; it travels
 //                        in a record of its own, 4 bytes, loaded only on taps that pass the object test.
 //   atrous_none          iterations = 0 of either call: the average, tone-mapped.
+//   The last level and atrous_none have a LINEAR form (rtpbr_denoise_blend): the colour before the tone map goes to `out`.
 // The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_denoise / rtpbr_denoise_guided) so that the CPU
 // restatements match bit for bit (tests/feature_ref, tests/noise_ref).
 #pragma once
@@ -41,7 +42,7 @@ struct DenoiseArgs {
     const int32_t* object;        // (W,H): level 0's taps
     const float4* src;            // levels > 0: the previous level's (colour, object index as bits; -2 = pixel without samples)
     float4* dst;                  // every level but the last
-    float* out;                   // the last level: denoised display colour (W,H,3)
+    float* out;                   // the last level: denoised display colour (W,H,3); the linear form: the colour before the tone map
     float ic, in, iz;             // 1/sigma^2 of colour (already x 4^k; plain only), normal, depth (the albedo term is 0 on every tap taken)
     int32_t step;                 // 2^k
     int32_t demodulate;
@@ -58,6 +59,6 @@ struct DenoiseArgs {
 RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), c.z / (1.0f + c.z)); }
 
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st);
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear = false);      // linear: last && !guided
 
 }  // namespace rt

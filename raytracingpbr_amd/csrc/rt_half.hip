@@ -1,4 +1,4 @@
-// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error (see rt_half.hpp).
+// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend (see rt_half.hpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_half.hpp"
@@ -109,6 +109,111 @@ __global__ void __launch_bounds__(256) half_error(const ErrorArgs A) {
     nz_stats(A.stats, A.threshold, blk, estimated, err, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
+// ---- the blend kernel: half_error<R>'s tile, halo and pitch with four planes (a_q, q_q, x_q, object_q), 16 bytes per entry.  An
+// entry that is not usable or lies outside the frame holds +0 in all three and ERR_NOBODY.  The three sums are signed, but a sum
+// that starts at +0 never becomes -0 (x + (-x) = +0 in round-to-nearest, +0 + -0 = +0), so adding +0 for a skipped tap is still
+// the identity and the tap loop is the object compare alone.  The lane that summed the window makes t, the blend and the tone map.
+// Traffic per staged entry: the three 16-byte texels, 36 bytes of the three linear filtered colours, 4 bytes of object: 88 bytes
+// against half_error's 36 (the count words there cost a whole texel each on the bus); per pixel 28 more (b and FD of the centre
+// again, 16 written).
+template <int R>
+__global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
+    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
+    __shared__ float t_a[HX * PITCH];
+    __shared__ float t_q[HX * PITCH];
+    __shared__ float t_x[HX * PITCH];
+    __shared__ int t_obj[HX * PITCH];
+    __shared__ uint32_t blk[3];
+    if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
+    const int H = A.height, W = A.width;
+    const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
+    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
+        const int hx = t / HY, hy = t - hx * HY;
+        const int xq = x0 - R + hx, yq = y0 - R + hy;
+        float aq = 0.0f, qq = 0.0f, xx = 0.0f;
+        int oq = ERR_NOBODY;
+        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
+            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+            const float4 ha = A.half_a[q], hb = A.half_b[q];
+            const float cA = ha.w, cB = hb.w;
+            if (cA >= A.min_half && cB >= A.min_half) {
+                const float4 b = A.image_buffer[q];
+                const float f = (cA * cB) / ((cA + cB) * (cA + cB));
+                const float lPA = nz_lum(mk(ha.x / ha.w, ha.y / ha.w, ha.z / ha.w));
+                const float lPB = nz_lum(mk(hb.x / hb.w, hb.y / hb.w, hb.z / hb.w));
+                const float lPb = nz_lum(mk(b.x / b.w, b.y / b.w, b.z / b.w));
+                const float dA = nz_lum(mk(A.fa[q * 3 + 0], A.fa[q * 3 + 1], A.fa[q * 3 + 2])) - lPA;
+                const float dB = nz_lum(mk(A.fb[q * 3 + 0], A.fb[q * 3 + 1], A.fb[q * 3 + 2])) - lPB;
+                const float dp = lPA - lPB;
+                const float dd = dA - dB;
+                const float dl = nz_lum(mk(A.fd[q * 3 + 0], A.fd[q * 3 + 1], A.fd[q * 3 + 2])) - lPb;
+                aq = (f * dp) * dd;
+                qq = dl * dl;
+                xx = dA * dB;
+                oq = A.object[q];
+            }
+        }
+        t_a[hx * PITCH + hy] = aq;
+        t_q[hx * PITCH + hy] = qq;
+        t_x[hx * PITCH + hy] = xx;
+        t_obj[hx * PITCH + hy] = oq;
+    }
+    __syncthreads();
+    const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
+    const int x = x0 + lx, y = y0 + ly;
+    bool usable = false;
+    float t = 1.0f;
+    if (x < W && y < H) {
+        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        if (op != ERR_NOBODY) {
+            usable = true;
+            float n = 0.0f, SC = 0.0f, SQ = 0.0f, SX = 0.0f, SXX = 0.0f;
+            // (rows stay a loop: with all (2R+1)^2 x 4 LDS reads hoisted the kernel takes 103 / 199 VGPRs at R = 2 / 3 and runs at
+            // four / two waves per SIMD; a row at a time it takes 48 at every radius)
+#pragma unroll 1
+            for (int dy = -R; dy <= R; dy++) {
+#pragma unroll
+                for (int dx = -R; dx <= R; dx++) {
+                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
+                    const bool same = t_obj[q] == op;
+                    const float xq = same ? t_x[q] : 0.0f;
+                    n = n + (same ? 1.0f : 0.0f);
+                    SC = SC + (same ? t_a[q] : 0.0f);
+                    SQ = SQ + (same ? t_q[q] : 0.0f);
+                    SX = SX + xq;
+                    SXX = SXX + xq * xq;
+                }
+            }
+            const float m1 = SX / n;
+            const float v = fmax_(SXX / n - m1 * m1, 0.0f);
+            if (m1 > 0.0f && (m1 * m1) * n > A.z2 * v) {
+                t = -SC / SQ;
+                if (!(t < 1.0f)) t = 1.0f;      // (a NaN gives 1)
+                if (t < 0.0f) t = 0.0f;
+            }
+        }
+        const size_t p = (size_t)x * (size_t)H + (size_t)y;
+        const float4 b = A.image_buffer[p];
+        vec3 d;
+        if (b.w > 0.0f) {
+            vec3 c = mk(A.fd[p * 3 + 0], A.fd[p * 3 + 1], A.fd[p * 3 + 2]);
+            if (t != 1.0f) {
+                const float u = 1.0f - t;
+                c = mk(c.x + u * (b.x / b.w - c.x), c.y + u * (b.y / b.w - c.y), c.z + u * (b.z / b.w - c.z));
+            }
+            d = tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f));
+        } else {      // no samples: what post_process shows
+            d = tone_map(A.cfg, b);
+        }
+        A.weight[p] = t;
+        A.out[p * 3 + 0] = d.x;
+        A.out[p * 3 + 1] = d.y;
+        A.out[p * 3 + 2] = d.z;
+    }
+    // pixels_above = usable pixels with t < 1 (1 - t > 0 exactly then), max_noise = the largest 1 - t
+    nz_stats(A.stats, 0.0f, blk, usable, 1.0f - t, blockIdx.y * gridDim.x + blockIdx.x);
+}
+
 static unsigned grid_of(int w, int h) { return (unsigned)(((size_t)w * h + 255) / 256); }
 
 void launch_half_update(const HalfArgs& A, hipStream_t st) {
@@ -124,6 +229,13 @@ void launch_half_error(const ErrorArgs& A, hipStream_t st) {      // (rt_capi.hi
     if (A.radius == 1) hipLaunchKernelGGL(half_error<1>, grid, dim3(256), 0, st, A);
     else if (A.radius == 2) hipLaunchKernelGGL(half_error<2>, grid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL(half_error<3>, grid, dim3(256), 0, st, A);
+}
+
+void launch_half_blend(const BlendArgs& A, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
+    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
+    if (A.radius == 1) hipLaunchKernelGGL(half_blend<1>, grid, dim3(256), 0, st, A);
+    else if (A.radius == 2) hipLaunchKernelGGL(half_blend<2>, grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(half_blend<3>, grid, dim3(256), 0, st, A);
 }
 
 }  // namespace rt

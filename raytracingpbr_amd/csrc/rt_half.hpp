@@ -1,4 +1,5 @@
-// rt_half.hpp — the two-half error estimate of the denoised frame (rtpbr_half_update, rtpbr_denoise_error).
+// rt_half.hpp — the two-half error estimate of the denoised frame (rtpbr_half_update, rtpbr_denoise_error) and the bias-aware
+// blend of the denoised and the raw frame made from the same halves (rtpbr_denoise_blend).
 //
 // The samples of image_buffer are kept in two independent halves: A is stored (RTPBR_BUF_HALF_BUFFER), B = image_buffer - A is
 // not.  rtpbr_denoise's filter runs on each half (the existing atrous_level / atrous_none instances, rt_features.hip); the
@@ -13,8 +14,14 @@
 //                       statistics of rtpbr_noise_estimate.  The layout of noise_estimate_pooled<R> (rt_noise.hip): a 2-D tile
 //                       per block, (e_q, object) of the tile and an R-pixel halo staged in LDS once — e_q is computed while
 //                       staging and never goes to memory —, then every lane walks its window in LDS.
+//   half_blend<R>       rtpbr_denoise_blend's window kernel, in half_error<R>'s layout.  From the LINEAR filter results of the full
+//                       frame and of either half (atrous_level's LINEAR form, rt_features.hip) and the three raw averages it
+//                       stages (a_q, q_q, x_q, object) — the regression's cross term, (filtered - raw)^2 and the product of the
+//                       halves' (filtered - raw), whose expectation is bias^2 —, sums them over the window on the pixel's
+//                       object, makes the weight t (RTPBR_BUF_BLEND_WEIGHT), blends the filtered and the raw colour, tone-maps
+//                       and writes RTPBR_BUF_DENOISED_PIXELS; statistics through nz_stats.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that the CPU restatement matches bit for bit
-// (tests/half_ref/half_ref.c).
+// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c).
 #pragma once
 #include "rt_noise.hpp"
 
@@ -41,7 +48,26 @@ struct ErrorArgs {
     int32_t radius;               // 1..3
 };
 
+struct BlendArgs {
+    rtpbr_config cfg;             // tone map
+    const float4* image_buffer;   // b
+    const float4* half_a;         // A
+    const float4* half_b;         // B as half_subtract wrote it
+    const float* fd;              // (W,H,3): the filter's linear colour of image_buffer
+    const float* fa;              // ... of half A
+    const float* fb;              // ... of half B
+    const int32_t* object;        // RTPBR_BUF_FEAT_OBJECT
+    float* weight;                // out: RTPBR_BUF_BLEND_WEIGHT
+    float* out;                   // out: RTPBR_BUF_DENOISED_PIXELS
+    NoiseStats* stats;            // out (zeroed before the launch)
+    float min_half;               // (float)min_half_samples
+    float z2;                     // z * z
+    int32_t width, height;
+    int32_t radius;               // 1..3
+};
+
 void launch_half_update(const HalfArgs& A, hipStream_t st);
+void launch_half_blend(const BlendArgs& A, hipStream_t st);
 void launch_half_subtract(const HalfArgs& A, hipStream_t st);
 void launch_half_error(const ErrorArgs& A, hipStream_t st);
 

@@ -138,6 +138,14 @@ class ErrorParams(_Pod):
     DEFAULTS = {"radius": 2}
 
 
+class BlendParams(_Pod):
+    """rtpbr_blend_params (include/rtpbr.h): the window, the significance gate and the minimum half size of rtpbr_denoise_blend."""
+    _fields_ = [("radius", C.c_int32), ("z", C.c_float), ("min_half_samples", C.c_int32)]
+
+    # include/rtpbr.h RTPBR_BLEND_DEFAULT_*, what rtpbr_denoise_blend(ctx, p, NULL, ...) uses (tests/test_blend_ref.py keeps the two equal)
+    DEFAULTS = {"radius": 3, "z": 2.0, "min_half_samples": 16}
+
+
 class HalfMode(_Pod):
     """rtpbr_half_mode (include/rtpbr.h): halves dealt per sample by the sample calls, half A carried through the reprojections."""
     _fields_ = [("per_sample", C.c_int32), ("warp", C.c_int32)]

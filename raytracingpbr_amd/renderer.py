@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
+from .dataclass import BlendParams, Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -30,6 +30,8 @@ BUF_SELECTION = 13
 BUF_PRESENT = 14
 # half A of the two-half split (half_update) and the estimated noise of the denoised frame (denoise_error); each exists from the first such call on
 BUF_HALF_BUFFER, BUF_DENOISED_ERROR = 15, 16
+# the weight of the last denoise_blend(): 1 = the denoised colour, 0 = the raw average; exists from the first denoise_blend() on
+BUF_BLEND_WEIGHT = 17
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -408,7 +410,32 @@ class Renderer:
         self.api.call("select_error", self._ctx, float(threshold), int(dilate), C.byref(n))
         return int(n.value)
 
-    def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False, **denoise_params):
+    def denoise_blend(self, radius=None, z=None, min_half_samples=None, iterations=None, demodulate=None, sigma_color=None,
+                      sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
+        """Write ``denoised_pixels`` as ``denoise`` (with the same parameters) does, blended per pixel with the raw average where
+        the two halves show that the filter's bias outweighs the noise it removes, and ``blend_weight`` (1 = the denoised
+        colour, 0 = the raw one).  The statistics are sums over the (2 radius + 1)^2 window on each pixel's object, of pixels
+        whose halves both hold ``min_half_samples``; the weight leaves 1 only where the squared bias exceeds ``z`` standard
+        errors.  Returns how many pixels had usable halves, how many of them got a weight below 1, and the largest 1 - weight.
+        Blocks.  ``None`` = the library's default for that parameter."""
+        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
+                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
+        p = None
+        if any(v is not None for v in given.values()):
+            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
+        e = None
+        if radius is not None or z is not None or min_half_samples is not None:
+            d = BlendParams.DEFAULTS
+            e = C.byref(BlendParams(int(d["radius"] if radius is None else radius), float(d["z"] if z is None else z),
+                                    int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
+        s = NoiseStats()
+        self.api.call("denoise_blend", self._ctx, p, e, C.byref(s))
+        return s
+
+    def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
+                                 blend: bool = False, **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -417,7 +444,8 @@ class Renderer:
         estimate).  Continues whatever is accumulated: refresh() first for a new frame.  The estimate is variance only: the
         loop stops when the denoised picture has stopped moving, which the filter's bias does not prevent.
         ``per_sample``: with set_half_mode(per_sample=True) for the duration of the call (``warp`` as it is; restored after):
-        every batch is split evenly over the halves by the sample calls themselves and the loop makes no half_update()."""
+        every batch is split evenly over the halves by the sample calls themselves and the loop makes no half_update().
+        ``blend``: the loop ends with denoise_blend() (its defaults) instead of denoise(); the stop rule is unchanged."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
@@ -446,7 +474,10 @@ class Renderer:
                 if not per_sample:
                     self.half_update()
                 traced, used = traced + n_sel * batch, used + batch
-            self.denoise(**denoise_params)
+            if blend:
+                self.denoise_blend(**denoise_params)
+            else:
+                self.denoise(**denoise_params)
             return traced, stats
         finally:
             self.track_noise, self.track_halves = keep_noise, keep_halves
@@ -489,7 +520,8 @@ class Renderer:
                 BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
                 BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
                 BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8),
-                BUF_HALF_BUFFER: ((W, H, 4), np.float32), BUF_DENOISED_ERROR: ((W, H), np.float32)}[which]
+                BUF_HALF_BUFFER: ((W, H, 4), np.float32), BUF_DENOISED_ERROR: ((W, H), np.float32),
+                BUF_BLEND_WEIGHT: ((W, H), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -647,6 +679,11 @@ class Renderer:
     def denoised_error(self):
         """(W,H): the last denoise_error()'s standard deviation of each pixel's denoised luminance, 0 where a half is empty"""
         return self._read(BUF_DENOISED_ERROR)
+
+    @property
+    def blend_weight(self):
+        """(W,H): the last denoise_blend()'s weight of the denoised colour, 1 where the halves are not usable or see no bias"""
+        return self._read(BUF_BLEND_WEIGHT)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

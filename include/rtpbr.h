@@ -239,7 +239,10 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_HALF_BUFFER  = 15,  /* (W,H,4) f32 half A's (sum r, sum g, sum b, count); half B = image_buffer - A per component */
        RTPBR_BUF_DENOISED_ERROR = 16, /* (W,H) f32 estimated standard deviation of lum(rtpbr_denoise's display colour)         */
        /* the weight of rtpbr_denoise_blend: allocated by its first call, freed by rtpbr_set_config with a new resolution; output only */
-       RTPBR_BUF_BLEND_WEIGHT = 17 };   /* (W,H) f32 t in [0, 1]: 1 = the denoised colour, 0 = the raw average                    */
+       RTPBR_BUF_BLEND_WEIGHT = 17,  /* (W,H) f32 t in [0, 1]: 1 = the denoised colour, 0 = the raw average (rtpbr_denoise_blend_levels: T_K) */
+       /* the depth of rtpbr_denoise_blend_levels: allocated by its first call (which allocates the weight too), freed by
+        * rtpbr_set_config with a new resolution; output only */
+       RTPBR_BUF_BLEND_DEPTH  = 18 };   /* (W,H) f32 in 0..K: K = the whole filter was kept, 0 = the raw average                   */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -767,6 +770,45 @@ typedef struct rtpbr_blend_params {   /* 4-byte members, no padding */
 #define RTPBR_BLEND_DEFAULT_Z 2.0f
 #define RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES 16
 int rtpbr_denoise_blend(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out);
+
+/* ---- The same blend across the a-trous levels: narrow the filter where the halves see bias.
+ *
+ * rtpbr_denoise_blend repairs the filter's bias by giving way to the RAW average, so it hands back the noise reduction wherever it
+ * acts.  The a-trous filter already computes a ladder of narrower filters: level k's intermediate result is the filter with
+ * iterations = k, because the schedule ic_k = ic_0 4^k does not depend on the level count.  rtpbr_denoise_blend_levels judges every
+ * rung of that ladder with the blend's statistics, the finer level k - 1 standing where the blend has the raw average, and keeps
+ * of each level's increment the fraction the halves vouch for.  It is a member of the denoise family with the blend's state rules
+ * word for word: it writes RTPBR_BUF_DENOISED_PIXELS (rtpbr_present(RTPBR_PRESENT_DENOISED) and every read of that buffer serve
+ * its frame), RTPBR_BUF_BLEND_WEIGHT and RTPBR_BUF_BLEND_DEPTH, and nothing else; it blocks, flushes lazy shading, is ordered
+ * behind asynchronous reads of the three buffers it writes and renders stale features first.  p == NULL: rtpbr_denoise's defaults;
+ * e == NULL: RTPBR_BLEND_DEFAULT_* (the blend's struct, range checks and defaults).  rtpbr_denoise_blend keeps its behaviour and
+ * its bits.
+ *
+ * Every operation is f32, in the order written, nothing fused.  b, A, B, lum, m, z2, "usable" and f are the blend section's.
+ *   K = p->iterations;
+ *   F_k(buf), k = 0..K: rtpbr_denoise's filter with iterations = k and p's other fields applied to buf, "has samples" meaning buf's
+ *     own count > 0, stopped before the tone map — the blend section's F for iterations = k (+0 for a pixel without samples).
+ *     k = 0 is the average, demodulated and remodulated when p->demodulate is set; with demodulate the remodulation
+ *     c * max(albedo, 1e-3) is applied at every k, as the last level applies it;
+ *   FD_k = F_k(b), FA_k = F_k(A), FB_k = F_k(B).
+ * For each level k = 1..K, per usable pixel q (f from cA, cB as in the blend section):
+ *   dA = lum(FA_k) - lum(FA_{k-1});  dB = lum(FB_k) - lum(FB_{k-1});  dp = lum(FA_{k-1}) - lum(FB_{k-1});
+ *   dd = dA - dB;  dl = lum(FD_k) - lum(FD_{k-1});   a_q = (f * dp) * dd;  q_q = dl * dl;  x_q = dA * dB.
+ * Per usable pixel p: the blend's window and tap order, its sums n, SC, SQ, SX, SXX from +0, its m1, v, gate and clamp give t_k
+ * (1 unless significant; a NaN gives 1).  A pixel that is not usable has t_k = 1 for every k.  Then, for a pixel with b.w > 0:
+ *   T_0 = 1;  T_k = T_{k-1} * t_k;  depth = 0;  c = FD_0;
+ *   k = 1..K in order:  depth = depth + T_k;   c.ch = c.ch + T_k * (FD_k.ch - FD_{k-1}.ch)  per channel;
+ *   if T_K == 1: c = FD_K   (every t_k was 1: the bytes are then rtpbr_denoise(p)'s);
+ *   denoised = tone_map(cfg, (c, 1)).
+ * Once a fine level is refused every coarser increment is scaled down with it: a coarser level is not trusted past a finer one the
+ * halves have caught blurring.  RTPBR_BUF_BLEND_WEIGHT = T_K; RTPBR_BUF_BLEND_DEPTH = depth, in 0..K.  A pixel without samples
+ * shows what rtpbr_post_process shows; its weight is 1 and its depth K.  K = 0 writes rtpbr_denoise's bytes, weight 1, depth 0.
+ * Statistics: pixels_estimated = the usable pixels, pixels_above = those with T_K < 1, max_noise = the largest 1 - T_K.
+ * Memory: beside the two outputs the call keeps the records of levels k - 1 and k of all three filter runs, six (W,H) planes of
+ * 16 bytes (199 MB at 1920 x 1080), allocated by the first call and freed, like both outputs, by rtpbr_set_config with a new
+ * resolution.
+ * Errors, each before anything changes: exactly rtpbr_denoise_blend's. */
+int rtpbr_denoise_blend_levels(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out);
 
 /* ---- Halves dealt per sample and carried through reprojection.
  *

@@ -142,7 +142,7 @@ static void free_noise(rtpbr_ctx* c) {
     c->noise_map = c->noise_var = nullptr;
 }
 
-// buffers of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend (allocated on first use)
+// buffers of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels (allocated on first use)
 static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->half_a);
     (void)hipFree(c->half_snapshot);
@@ -153,8 +153,11 @@ static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->denoised_error);
     (void)hipFree(c->half_fd);
     (void)hipFree(c->blend_weight);
+    (void)hipFree(c->blend_depth);
+    (void)hipFree(c->levels_scratch);
     c->half_a = c->half_snapshot = c->hist_half = c->half_b = nullptr;
-    c->half_da = c->half_db = c->denoised_error = c->half_fd = c->blend_weight = nullptr;
+    c->half_da = c->half_db = c->denoised_error = c->half_fd = c->blend_weight = c->blend_depth = nullptr;
+    c->levels_scratch = nullptr;
 }
 
 // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (allocated on the first select call)
@@ -738,7 +741,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b <= RTPBR_BUF_BLEND_WEIGHT; b++)
+    for (int b = 0; b <= RTPBR_BUF_BLEND_DEPTH; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -2003,8 +2006,8 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
 }
 
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
-enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT };
-static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
+enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT, W_DEPTH = 1u << RTPBR_BUF_BLEND_DEPTH };
+static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
 
 // What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
 // snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.  keep_a: A has
@@ -2174,6 +2177,100 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     return noise_stats_read(c, out);
 }
 
+// ---- the same blend across the a-trous levels (level_blend<R, FIRST, LAST>, rt_half.hip)
+extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_params d;
+    float inv[4];
+    if (int r = denoise_params(p, d, inv)) return r;
+    rtpbr_blend_params b{RTPBR_BLEND_DEFAULT_RADIUS, RTPBR_BLEND_DEFAULT_Z, RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES};
+    if (e) b = *e;
+    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend_levels: radius must be 1..3");
+    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend_levels: z must be finite and >= 0");
+    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend_levels: min_half_samples must be 1..16777216");
+    if (int r = whole_frame_state(c, HALF_TILES)) return r;
+    if (!c->half_a) return fail(RTPBR_ESTATE, "rtpbr_denoise_blend_levels: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)");
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    const int K = d.iterations;
+    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, n * sizeof(float4)));
+    if (!c->blend_weight) HIP_TRY(hipMalloc(&c->blend_weight, n * sizeof(float)));
+    if (!c->blend_depth) HIP_TRY(hipMalloc(&c->blend_depth, n * sizeof(float)));
+    if (!c->levels_scratch) HIP_TRY(hipMalloc(&c->levels_scratch, 6 * n * sizeof(float4)));
+    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
+    if (int r = denoised_alloc(c, 0)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
+    if (int r = rt_order_after_reads(c, W_BLEND | W_DEPTH)) return r;
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;
+    HalfArgs S{};
+    S.image_buffer = c->image_buffer;
+    S.half_a = c->half_a;
+    S.half_b = c->half_b;
+    S.width = c->cfg.width;
+    S.height = c->cfg.height;
+    launch_half_subtract(S, c->stream);
+    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    LevelsArgs A{};
+    A.cfg = c->cfg;
+    A.image_buffer = c->image_buffer;
+    A.half_a = c->half_a;
+    A.half_b = c->half_b;
+    A.albedo = c->feat_albedo;
+    A.object = c->feat_object;
+    A.weight = c->blend_weight;
+    A.depth = c->blend_depth;
+    A.out = c->denoised;
+    A.stats = c->noise_stats;
+    A.min_half = (float)b.min_half_samples;
+    A.z2 = b.z * b.z;
+    A.demodulate = d.demodulate;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    A.radius = b.radius;
+    if (K == 0) {      // rtpbr_denoise's pass, weight 1, depth 0
+        if (int r = denoise_levels(c, 0, d.demodulate, inv, nullptr)) return r;
+        launch_level_blend(A, true, true, c->stream);
+    }
+    // the K levels of the three chains in lock step through the non-last instances: chain j keeps level k in plane 2 j + (k & 1),
+    // so level k - 1 is still there when the window kernel compares the two
+    DenoiseArgs F{};
+    F.cfg = c->cfg;
+    F.guide_nz = c->feat_guides;
+    F.albedo = c->feat_albedo;
+    F.object = c->feat_object;
+    F.in = inv[1];
+    F.iz = inv[2];
+    F.demodulate = d.demodulate;
+    F.width = c->cfg.width;
+    F.height = c->cfg.height;
+    const float4* const chain_in[3] = {c->image_buffer, c->half_a, c->half_b};
+    for (int k = 0; k < K; k++) {      // k + 1 is the level's number in include/rtpbr.h
+        const bool first = k == 0, last = k + 1 == K;
+        float4* now[3];
+        const float4* before[3];
+        F.ic = inv[0] * (float)(1u << (2 * k));
+        F.step = 1 << k;
+        for (int j = 0; j < 3; j++) {
+            now[j] = c->levels_scratch + (size_t)(2 * j + (k & 1)) * n;
+            before[j] = first ? nullptr : c->levels_scratch + (size_t)(2 * j + ((k - 1) & 1)) * n;
+            F.image_buffer = chain_in[j];
+            F.src = before[j];
+            F.dst = now[j];
+            launch_atrous_level(F, first, false, false, c->stream);
+        }
+        A.kd = now[0];
+        A.ka = now[1];
+        A.kb = now[2];
+        A.pd = before[0];
+        A.pa = before[1];
+        A.pb = before[2];
+        launch_level_blend(A, first, last, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return noise_stats_read(c, out);
+}
+
 extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
     if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
@@ -2258,13 +2355,15 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_HALF_BUFFER: *p = c->half_a; *n = np * 16; break;
         case RTPBR_BUF_DENOISED_ERROR: *p = c->denoised_error; *n = np * 4; break;
         case RTPBR_BUF_BLEND_WEIGHT: *p = c->blend_weight; *n = np * 4; break;
+        case RTPBR_BUF_BLEND_DEPTH: *p = c->blend_depth; *n = np * 4; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
     // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate,
     // the packed frame from the first rtpbr_present, the half buffer from the first rtpbr_half_update, the error map from the first
-    // rtpbr_denoise_error, the blend weight from the first rtpbr_denoise_blend)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend first");
+    // rtpbr_denoise_error, the blend weight from the first rtpbr_denoise_blend or rtpbr_denoise_blend_levels, the blend depth from
+    // the first rtpbr_denoise_blend_levels)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels first");
     return 0;
 }
 
@@ -2365,8 +2464,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_BLEND_WEIGHT)
-        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half, error and blend-weight buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_BLEND_DEPTH)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half, error, blend-weight and blend-depth buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

@@ -16,6 +16,8 @@
 //                        in a record of its own, 4 bytes, loaded only on taps that pass the object test.
 //   atrous_none          iterations = 0 of either call: the average, tone-mapped.
 //   The last level and atrous_none have a LINEAR form (rtpbr_denoise_blend): the colour before the tone map goes to `out`.
+//   rtpbr_denoise_blend_levels reads the non-last levels' records themselves: level k's (colour, object index) is the filter with
+//   iterations = k before remodulation (level_blend, rt_half.hip).
 // The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_denoise / rtpbr_denoise_guided) so that the CPU
 // restatements match bit for bit (tests/feature_ref, tests/noise_ref).
 #pragma once

@@ -1,4 +1,4 @@
-// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend (see rt_half.hpp).
+// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels (see rt_half.hpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_half.hpp"
@@ -214,6 +214,165 @@ __global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
     nz_stats(A.stats, 0.0f, blk, usable, 1.0f - t, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
+// ---- the level kernel of rtpbr_denoise_blend_levels: half_blend<R>'s tile, halo, pitch and four planes, once per a-trous level k
+// = 1..K, with the finer level k - 1 in the place of the raw average.  A level's record (colour, object word) is the filter with
+// iterations = k before remodulation; level 0 (FIRST) is made from the (sum, count) buffers with atrous_none<LINEAR>'s operations.
+// A usable entry has samples in all three buffers (cA >= m >= 1, cB >= m, b.w = cA + cB), so its six records are colours and not
+// the NO_SAMPLES record.  After the window the lane updates its own pixel's running T (in `weight`), depth and linear colour (in
+// `out`) in place: no other lane reads or writes them.  LAST tone-maps and makes the statistics.
+// Traffic per staged entry: six 16-byte records (FIRST: three and the three 16-byte texels), the two count words, 4 bytes of
+// object, 12 of albedo when demodulating: 108 to 120 bytes against half_blend's 88; per pixel two records and 20 bytes of running
+// state both ways.
+RT_D vec3 lv_albedo(const LevelsArgs& A, size_t i) {
+    if (!A.demodulate) return mk(1.0f, 1.0f, 1.0f);
+    return mk(fmax_(A.albedo[i * 3 + 0], 1e-3f), fmax_(A.albedo[i * 3 + 1], 1e-3f), fmax_(A.albedo[i * 3 + 2], 1e-3f));
+}
+// F_k of a record: remodulated as the last level does
+RT_D vec3 lv_record(float4 r, vec3 ac, int demod) { return demod ? mk(r.x * ac.x, r.y * ac.y, r.z * ac.z) : mk(r.x, r.y, r.z); }
+// F_0 of a (sum, count) texel: the average, demodulated and remodulated
+RT_D vec3 lv_average(float4 b, vec3 ac, int demod) {
+    vec3 c = mk(b.x / b.w, b.y / b.w, b.z / b.w);
+    if (demod) {
+        c = mk(c.x / ac.x, c.y / ac.y, c.z / ac.z);
+        c = mk(c.x * ac.x, c.y * ac.y, c.z * ac.z);
+    }
+    return c;
+}
+
+template <int R, bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
+    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
+    __shared__ float t_a[HX * PITCH];
+    __shared__ float t_q[HX * PITCH];
+    __shared__ float t_x[HX * PITCH];
+    __shared__ int t_obj[HX * PITCH];
+    __shared__ uint32_t blk[3];
+    if constexpr (LAST)
+        if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
+    const int H = A.height, W = A.width;
+    const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
+    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
+        const int hx = t / HY, hy = t - hx * HY;
+        const int xq = x0 - R + hx, yq = y0 - R + hy;
+        float aq = 0.0f, qq = 0.0f, xx = 0.0f;
+        int oq = ERR_NOBODY;
+        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
+            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+            const float cA = A.half_a[q].w, cB = A.half_b[q].w;
+            if (cA >= A.min_half && cB >= A.min_half) {
+                const vec3 ac = lv_albedo(A, q);
+                const float f = (cA * cB) / ((cA + cB) * (cA + cB));
+                float lA0, lB0, lD0;      // the finer level
+                if constexpr (FIRST) {
+                    lA0 = nz_lum(lv_average(A.half_a[q], ac, A.demodulate));
+                    lB0 = nz_lum(lv_average(A.half_b[q], ac, A.demodulate));
+                    lD0 = nz_lum(lv_average(A.image_buffer[q], ac, A.demodulate));
+                } else {
+                    lA0 = nz_lum(lv_record(A.pa[q], ac, A.demodulate));
+                    lB0 = nz_lum(lv_record(A.pb[q], ac, A.demodulate));
+                    lD0 = nz_lum(lv_record(A.pd[q], ac, A.demodulate));
+                }
+                const float dA = nz_lum(lv_record(A.ka[q], ac, A.demodulate)) - lA0;
+                const float dB = nz_lum(lv_record(A.kb[q], ac, A.demodulate)) - lB0;
+                const float dp = lA0 - lB0;
+                const float dd = dA - dB;
+                const float dl = nz_lum(lv_record(A.kd[q], ac, A.demodulate)) - lD0;
+                aq = (f * dp) * dd;
+                qq = dl * dl;
+                xx = dA * dB;
+                oq = A.object[q];
+            }
+        }
+        t_a[hx * PITCH + hy] = aq;
+        t_q[hx * PITCH + hy] = qq;
+        t_x[hx * PITCH + hy] = xx;
+        t_obj[hx * PITCH + hy] = oq;
+    }
+    __syncthreads();
+    const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
+    const int x = x0 + lx, y = y0 + ly;
+    bool usable = false;
+    float T = 1.0f;
+    if (x < W && y < H) {
+        float t = 1.0f;
+        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        if (op != ERR_NOBODY) {
+            usable = true;
+            float n = 0.0f, SC = 0.0f, SQ = 0.0f, SX = 0.0f, SXX = 0.0f;
+            // (rows stay a loop, as in half_blend<R>)
+#pragma unroll 1
+            for (int dy = -R; dy <= R; dy++) {
+#pragma unroll
+                for (int dx = -R; dx <= R; dx++) {
+                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
+                    const bool same = t_obj[q] == op;
+                    const float xq = same ? t_x[q] : 0.0f;
+                    n = n + (same ? 1.0f : 0.0f);
+                    SC = SC + (same ? t_a[q] : 0.0f);
+                    SQ = SQ + (same ? t_q[q] : 0.0f);
+                    SX = SX + xq;
+                    SXX = SXX + xq * xq;
+                }
+            }
+            const float m1 = SX / n;
+            const float v = fmax_(SXX / n - m1 * m1, 0.0f);
+            if (m1 > 0.0f && (m1 * m1) * n > A.z2 * v) {
+                t = -SC / SQ;
+                if (!(t < 1.0f)) t = 1.0f;      // (a NaN gives 1)
+                if (t < 0.0f) t = 0.0f;
+            }
+        }
+        const size_t p = (size_t)x * (size_t)H + (size_t)y;
+        const vec3 ac = lv_albedo(A, p);
+        const vec3 fk = lv_record(A.kd[p], ac, A.demodulate);
+        float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if constexpr (FIRST || LAST) b = A.image_buffer[p];
+        vec3 f0, c;
+        float depth;
+        if constexpr (FIRST) {      // T_0 = 1, depth = 0, c = FD_0
+            f0 = lv_average(b, ac, A.demodulate);
+            c = f0;
+            depth = 0.0f;
+        } else {
+            f0 = lv_record(A.pd[p], ac, A.demodulate);
+            c = mk(A.out[p * 3 + 0], A.out[p * 3 + 1], A.out[p * 3 + 2]);
+            depth = A.depth[p];
+            T = A.weight[p];
+        }
+        T = T * t;
+        depth = depth + T;
+        c = mk(c.x + T * (fk.x - f0.x), c.y + T * (fk.y - f0.y), c.z + T * (fk.z - f0.z));
+        if constexpr (LAST) {
+            if (T == 1.0f) c = fk;      // every t_k was 1: rtpbr_denoise's bytes
+            // (no samples: what post_process shows; T = 1 and depth = K by the sums above)
+            c = b.w > 0.0f ? tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)) : tone_map(A.cfg, b);
+        }
+        A.weight[p] = T;
+        A.depth[p] = depth;
+        A.out[p * 3 + 0] = c.x;
+        A.out[p * 3 + 1] = c.y;
+        A.out[p * 3 + 2] = c.z;
+    }
+    // pixels_above = usable pixels with T_K < 1 (1 - T_K > 0 exactly then), max_noise = the largest 1 - T_K
+    if constexpr (LAST) nz_stats(A.stats, 0.0f, blk, usable, 1.0f - T, blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+// K = 0 of rtpbr_denoise_blend_levels (the frame is atrous_none's): weight 1, depth 0, and the count of usable pixels
+__global__ void __launch_bounds__(256) level_blend_none(const LevelsArgs A) {
+    __shared__ uint32_t blk[3];
+    if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t n = (uint32_t)A.width * (uint32_t)A.height;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool usable = false;
+    if (i < n) {
+        usable = A.half_a[i].w >= A.min_half && A.half_b[i].w >= A.min_half;
+        A.weight[i] = 1.0f;
+        A.depth[i] = 0.0f;
+    }
+    nz_stats(A.stats, 0.0f, blk, usable, 0.0f, blockIdx.x);
+}
+
 static unsigned grid_of(int w, int h) { return (unsigned)(((size_t)w * h + 255) / 256); }
 
 void launch_half_update(const HalfArgs& A, hipStream_t st) {
@@ -236,6 +395,26 @@ void launch_half_blend(const BlendArgs& A, hipStream_t st) {      // (rt_capi.hi
     if (A.radius == 1) hipLaunchKernelGGL(half_blend<1>, grid, dim3(256), 0, st, A);
     else if (A.radius == 2) hipLaunchKernelGGL(half_blend<2>, grid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL(half_blend<3>, grid, dim3(256), 0, st, A);
+}
+
+template <int R>
+static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, dim3 grid, hipStream_t st) {
+    if (first && last) hipLaunchKernelGGL((level_blend<R, true, true>), grid, dim3(256), 0, st, A);
+    else if (first) hipLaunchKernelGGL((level_blend<R, true, false>), grid, dim3(256), 0, st, A);
+    else if (last) hipLaunchKernelGGL((level_blend<R, false, true>), grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((level_blend<R, false, false>), grid, dim3(256), 0, st, A);
+}
+
+// no level (first && last && no records): the K = 0 pass
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
+    if (!A.kd) {
+        hipLaunchKernelGGL(level_blend_none, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
+        return;
+    }
+    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
+    if (A.radius == 1) launch_level_blend_r<1>(A, first, last, grid, st);
+    else if (A.radius == 2) launch_level_blend_r<2>(A, first, last, grid, st);
+    else launch_level_blend_r<3>(A, first, last, grid, st);
 }
 
 }  // namespace rt

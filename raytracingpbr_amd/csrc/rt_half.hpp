@@ -1,5 +1,6 @@
-// rt_half.hpp — the two-half error estimate of the denoised frame (rtpbr_half_update, rtpbr_denoise_error) and the bias-aware
-// blend of the denoised and the raw frame made from the same halves (rtpbr_denoise_blend).
+// rt_half.hpp — the two-half error estimate of the denoised frame (rtpbr_half_update, rtpbr_denoise_error), the bias-aware
+// blend of the denoised and the raw frame made from the same halves (rtpbr_denoise_blend) and the same blend across the a-trous
+// levels (rtpbr_denoise_blend_levels).
 //
 // The samples of image_buffer are kept in two independent halves: A is stored (RTPBR_BUF_HALF_BUFFER), B = image_buffer - A is
 // not.  rtpbr_denoise's filter runs on each half (the existing atrous_level / atrous_none instances, rt_features.hip); the
@@ -20,8 +21,16 @@
 //                       halves' (filtered - raw), whose expectation is bias^2 —, sums them over the window on the pixel's
 //                       object, makes the weight t (RTPBR_BUF_BLEND_WEIGHT), blends the filtered and the raw colour, tone-maps
 //                       and writes RTPBR_BUF_DENOISED_PIXELS; statistics through nz_stats.
+//   level_blend<R,F,L>  rtpbr_denoise_blend_levels' window kernel, one launch per a-trous level k = 1..K, in half_blend<R>'s
+//                       layout.  The non-last atrous_level instances run all K levels of the full frame and of either half in lock
+//                       step, each chain in a ping-pong of its own, so the records of level k - 1 and k are both live (six float4
+//                       planes).  The kernel applies half_blend's rule with the finer level in the place of the raw average
+//                       (FIRST: level 0 from the (sum, count) buffers), makes t_k, and the lane updates its own pixel's running
+//                       product T_k = T_{k-1} t_k, the depth sum of T_k and the colour c = c + T_k (FD_k - FD_{k-1}) in place
+//                       (RTPBR_BUF_BLEND_WEIGHT, RTPBR_BUF_BLEND_DEPTH, RTPBR_BUF_DENOISED_PIXELS); LAST tone-maps and makes the
+//                       statistics.  level_blend_none: K = 0.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that the CPU restatement matches bit for bit
-// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c).
+// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c, tests/levels_ref/levels_ref.c).
 #pragma once
 #include "rt_noise.hpp"
 
@@ -66,7 +75,32 @@ struct BlendArgs {
     int32_t radius;               // 1..3
 };
 
+struct LevelsArgs {
+    rtpbr_config cfg;             // tone map (LAST)
+    const float4* image_buffer;   // b: level 0 (FIRST), pixels without samples (LAST)
+    const float4* half_a;         // A: the count words; level 0 (FIRST)
+    const float4* half_b;         // B as half_subtract wrote it
+    const float4* kd;             // level k's (colour, object word) of image_buffer; nullptr: K = 0
+    const float4* ka;             // ... of half A
+    const float4* kb;             // ... of half B
+    const float4* pd;             // level k - 1's, of image_buffer (not FIRST)
+    const float4* pa;             // ... of half A
+    const float4* pb;             // ... of half B
+    const float* albedo;          // (W,H,3): remodulation
+    const int32_t* object;        // RTPBR_BUF_FEAT_OBJECT
+    float* weight;                // in / out: the running T_k; RTPBR_BUF_BLEND_WEIGHT after LAST
+    float* depth;                 // in / out: the running sum of T_k; RTPBR_BUF_BLEND_DEPTH
+    float* out;                   // in / out: the running linear colour; LAST: RTPBR_BUF_DENOISED_PIXELS
+    NoiseStats* stats;            // out (zeroed before the launches; LAST adds to it)
+    float min_half;               // (float)min_half_samples
+    float z2;                     // z * z
+    int32_t demodulate;
+    int32_t width, height;
+    int32_t radius;               // 1..3
+};
+
 void launch_half_update(const HalfArgs& A, hipStream_t st);
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st);
 void launch_half_blend(const BlendArgs& A, hipStream_t st);
 void launch_half_subtract(const HalfArgs& A, hipStream_t st);
 void launch_half_error(const ErrorArgs& A, hipStream_t st);

@@ -32,6 +32,8 @@ BUF_PRESENT = 14
 BUF_HALF_BUFFER, BUF_DENOISED_ERROR = 15, 16
 # the weight of the last denoise_blend(): 1 = the denoised colour, 0 = the raw average; exists from the first denoise_blend() on
 BUF_BLEND_WEIGHT = 17
+# how many a-trous levels the last denoise_blend_levels() kept, 0..iterations; exists from the first denoise_blend_levels() on
+BUF_BLEND_DEPTH = 18
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -434,8 +436,32 @@ class Renderer:
         self.api.call("denoise_blend", self._ctx, p, e, C.byref(s))
         return s
 
+    def denoise_blend_levels(self, radius=None, z=None, min_half_samples=None, iterations=None, demodulate=None, sigma_color=None,
+                             sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
+        """denoise_blend's rule applied to every a-trous level against the next finer one instead of to the whole filter
+        against the raw average: where the halves see a level blurring, that level's increment and every coarser one are scaled
+        down, so the filter narrows per pixel and keeps the noise reduction of the levels that hold.  Writes
+        ``denoised_pixels``, ``blend_weight`` (the product of the levels' weights: 1 = exactly ``denoise``'s colour) and
+        ``blend_depth`` (the sum of the running products, 0..iterations: how many levels were kept).  Same parameters,
+        defaults and statistics as denoise_blend.  Blocks."""
+        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
+                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
+        p = None
+        if any(v is not None for v in given.values()):
+            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
+        e = None
+        if radius is not None or z is not None or min_half_samples is not None:
+            d = BlendParams.DEFAULTS
+            e = C.byref(BlendParams(int(d["radius"] if radius is None else radius), float(d["z"] if z is None else z),
+                                    int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
+        s = NoiseStats()
+        self.api.call("denoise_blend_levels", self._ctx, p, e, C.byref(s))
+        return s
+
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
-                                 blend: bool = False, **denoise_params):
+                                 blend=False, **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -445,7 +471,10 @@ class Renderer:
         loop stops when the denoised picture has stopped moving, which the filter's bias does not prevent.
         ``per_sample``: with set_half_mode(per_sample=True) for the duration of the call (``warp`` as it is; restored after):
         every batch is split evenly over the halves by the sample calls themselves and the loop makes no half_update().
-        ``blend``: the loop ends with denoise_blend() (its defaults) instead of denoise(); the stop rule is unchanged."""
+        ``blend``: True: the loop ends with denoise_blend() (its defaults) instead of denoise(); "levels": with
+        denoise_blend_levels(); the stop rule is unchanged."""
+        if isinstance(blend, str) and blend != "levels":
+            raise ValueError('blend must be True, False or "levels"')
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
@@ -474,7 +503,9 @@ class Renderer:
                 if not per_sample:
                     self.half_update()
                 traced, used = traced + n_sel * batch, used + batch
-            if blend:
+            if blend == "levels":
+                self.denoise_blend_levels(**denoise_params)
+            elif blend:
                 self.denoise_blend(**denoise_params)
             else:
                 self.denoise(**denoise_params)
@@ -521,7 +552,7 @@ class Renderer:
                 BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
                 BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8),
                 BUF_HALF_BUFFER: ((W, H, 4), np.float32), BUF_DENOISED_ERROR: ((W, H), np.float32),
-                BUF_BLEND_WEIGHT: ((W, H), np.float32)}[which]
+                BUF_BLEND_WEIGHT: ((W, H), np.float32), BUF_BLEND_DEPTH: ((W, H), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -684,6 +715,11 @@ class Renderer:
     def blend_weight(self):
         """(W,H): the last denoise_blend()'s weight of the denoised colour, 1 where the halves are not usable or see no bias"""
         return self._read(BUF_BLEND_WEIGHT)
+
+    @property
+    def blend_depth(self):
+        """(W,H): how many a-trous levels the last denoise_blend_levels() kept, 0 (the raw average) .. iterations (the whole filter)"""
+        return self._read(BUF_BLEND_DEPTH)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

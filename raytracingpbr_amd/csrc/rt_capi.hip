@@ -1265,6 +1265,7 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
         P.drain_lanes = c->drain_lanes;
         P.stage = c->stage;
         P.K = K;
+        P.k_shift = item_shift_of(K);       // (rt_item.hpp: a power-of-two K splits the work item by shift and mask)
         P.sample_base = c->sample_base;
         P.total_items = (uint32_t)((long long)P.np * K);
         int grid = trace_grid(c, P.total_items, selected);

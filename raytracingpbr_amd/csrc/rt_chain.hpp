@@ -23,7 +23,9 @@ template <int KIND, int NOBJ = 0, uint32_t SIG = 0>
 RT_D void chain_steps_impl(const Params& P, int steps) {
     __shared__ ObjFull lds_obj[MAX_OBJ];
     __shared__ float4 xch_all[4][8];      // per wave: the exchange buffer of the object-parallel evaluation (nearest_op3)
+    __shared__ float shade_tab[shade_tab_words(MAX_OBJ)];
     stage_objects(P, lds_obj);
+    stage_shade_tables<false>(P, lds_obj, shade_tab);
     const OpView OV = {lds_obj, ((P.src_op & 1) != 0 && P.n_obj <= 8) ? xch_all[threadIdx.x >> 6] : nullptr};
     const int lane = threadIdx.x & 63;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
@@ -140,7 +142,7 @@ RT_D void chain_steps_impl(const Params& P, int steps) {
                 depth += 1;
                 if (L.state == ST_HIT) {
                     const ObjFull ob = lds_obj[L.idx];
-                    surface_interaction<KIND>(P, ob, L.o, L.o, L.d, col, key, cnt);
+                    surface_interaction<KIND>(P, ob, L.o, L.o, L.d, col, key, cnt, vec3{0, 0, 0}, shade_tab, L.idx);
                     n_hits++;
                     float intensity = brightness(col);
                     col = col * mk(ob.emission[0], ob.emission[1], ob.emission[2]);

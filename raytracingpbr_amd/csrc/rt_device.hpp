@@ -971,12 +971,47 @@ RT_D vec3 hemispheric_sampling(vec3 n, uint32_t key, uint32_t& cnt) {
     return normalize(n + u);
 }
 
+// ---------------------------------------------------------------- shading tables (one per block, in LDS)
+// Two things every shaded hit computed per lane depend on nothing but the bounce number or the object hit:
+//   p(b) = 1 - 1 / exp(b / light_quality)         the roulette probability of bounce b: one of max_raytrace values
+//   eta, F0 of (object, side of the surface)       relative index of refraction and the Fresnel term at normal incidence: 2 n_obj values
+// — an exponential, an int -> float conversion and four IEEE divisions per hit (measured on the 1080p Cornell frame: 1.4 % of the
+// pool kernel's vector instructions, profiles/valu_trim.json).  The
+// first threads of the block compute them ONCE at kernel start (stage_shade_tables, next to stage_objects) and the hits read them
+// back.  The tables are filled ON THE DEVICE by the functions below, which are also what a hit without a table (and a bounce beyond
+// the table) evaluates inline: the same instructions on the same inputs, so the bits are equal by construction — a table filled
+// on the host would have to match the device's exp_ and its division to the last bit instead.
+// Layout (floats): [0, SHADE_RR) p(1) .. p(SHADE_RR), then per object {eta_outer, F0_outer, eta_inner, F0_inner}.
+// Exact kernels only: under RT_FAST_MATH contraction may fuse these products into their consumers differently per call site.
+constexpr int SHADE_RR = 64;
+constexpr bool SHADE_TABLES = !RT_FAST_MATH;
+constexpr int shade_tab_words(int n_obj) { return SHADE_TABLES ? SHADE_RR + 4 * n_obj : 1; }
+
+// cornell_box_v3/pathtracer.py:97-99: inv_pdf = exp(i / LIGHT_QUALITY); the path stops with probability 1 - 1 / inv_pdf
+RT_D float roulette_p(const Params& P, int bounce) {
+    float inv_pdf = exp_((float)bounce / P.cfg.light_quality);
+    return 1.0f - 1.0f / inv_pdf;
+}
+// src/pbr.py:36-41 / cornell_box_v3/pbr.py:44-48
+RT_D void eta_f0(const rtpbr_config& g, float ior, bool outer, float& eta, float& F0) {
+    eta = outer ? g.env_ior / ior : ior / g.env_ior;
+    if (g.fresnel_kind == RTPBR_FRESNEL_C2) {
+        F0 = (eta - 1.0f) / (eta + 1.0f);
+        F0 = F0 * (2.0f * F0);
+    } else {
+        F0 = 2.0f * (eta - 1.0f) / (eta + 1.0f);
+        F0 = F0 * F0;
+    }
+}
+
 // ---------------------------------------------------------------- F12/F22 surface interaction
 // src/pbr.py:22-62; cornell_box_v3/pbr.py:30-66; cornell_box_shortest.py:91-94.
 // `origin` is the ray origin (src form: already marched), `pos` the hit position.
+// shade_tab / obj: the block's shading tables and the index of `o` in the object table (nullptr: eta and F0 are computed here)
 template <int KIND, bool HAVE_NORMAL = false>
 RT_D void surface_interaction(const Params& P, const ObjFull& o, vec3 pos, vec3& origin, vec3& dir, vec3& col,
-                              uint32_t key, uint32_t& cnt, vec3 given_normal = vec3{0, 0, 0}) {
+                              uint32_t key, uint32_t& cnt, vec3 given_normal = vec3{0, 0, 0}, const float* shade_tab = nullptr,
+                              int obj = 0) {
     const rtpbr_config& g = P.cfg;
     vec3 n = HAVE_NORMAL ? given_normal : calc_normal<KIND>(P, o, pos);
     // The material is fetched from LDS only after the normal is done: without this compiler barrier the
@@ -998,16 +1033,14 @@ RT_D void surface_interaction(const Params& P, const ObjFull& o, vec3 pos, vec3&
     float alpha = o.roughness * o.roughness;
     vec3 N = normalize(mix(n, hemi, alpha));
     float NoI = dot(N, I);
-    float eta = outer ? g.env_ior / o.ior : o.ior / g.env_ior;
-    float k = 1.0f - eta * eta * (1.0f - NoI * NoI);
-    float F0;
-    if (g.fresnel_kind == RTPBR_FRESNEL_C2) {
-        F0 = (eta - 1.0f) / (eta + 1.0f);
-        F0 = F0 * (2.0f * F0);
+    float eta, F0;
+    if (SHADE_TABLES && shade_tab != nullptr) {
+        const float* e = shade_tab + SHADE_RR + 4 * obj + (outer ? 0 : 2);
+        eta = e[0], F0 = e[1];
     } else {
-        F0 = 2.0f * (eta - 1.0f) / (eta + 1.0f);
-        F0 = F0 * F0;
+        eta_f0(g, o.ior, outer, eta, F0);
     }
+    float k = 1.0f - eta * eta * (1.0f - NoI * NoI);
     float x1 = fabs_(1.0f + NoI), x2 = x1 * x1, x5 = x2 * x2 * x1;
     float F = mix(x5, 1.0f, F0);
     if (g.fresnel_roughness_mix) F = mix(F, F0, o.roughness);

@@ -13,8 +13,10 @@ namespace rt {
 template <int KIND, int NOBJ = 0, uint32_t SIG = 0>
 RT_D void persistent_steps_impl(const Params& P, int steps) {
     __shared__ ObjFull lds_obj[MAX_OBJ];
+    __shared__ float shade_tab[shade_tab_words(MAX_OBJ)];
     zero_next_counters(P);
     stage_objects(P, lds_obj);
+    stage_shade_tables<false>(P, lds_obj, shade_tab);
     uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     int px = 0, py = 0;
     bool valid = q < (uint32_t)P.np && pixel_of(P, q, px, py);
@@ -77,7 +79,7 @@ RT_D void persistent_steps_impl(const Params& P, int steps) {
                 // raytrace :16-36
                 if (hit) {
                     const ObjFull ob = lds_obj[idx];
-                    surface_interaction<KIND>(P, ob, o, o, d, col, key, cnt);
+                    surface_interaction<KIND>(P, ob, o, o, d, col, key, cnt, vec3{0, 0, 0}, shade_tab, idx);
                     n_hits++;
                     float intensity = brightness(col);
                     col = col * mk(ob.emission[0], ob.emission[1], ob.emission[2]);
@@ -760,8 +762,10 @@ RT_D void persistent_pool_impl(const Params& P, int steps) {
 #if RT_POOL_OP
     __shared__ float4 xch_all[4][8];
 #endif
+    __shared__ float shade_tab[shade_tab_words(MAX_OBJ)];
     zero_next_counters(P);
     stage_objects(P, lds_obj);
+    stage_shade_tables<false>(P, lds_obj, shade_tab);
 
     const unsigned long long t_wave0 = __builtin_readcyclecounter();
     const int lane = threadIdx.x & 63;
@@ -997,7 +1001,7 @@ RT_D void persistent_pool_impl(const Params& P, int steps) {
                     X.depth += 1;
                     if (st == SL_HIT) {
                         const ObjFull ob = lds_obj[X.idx];
-                        surface_interaction<KIND>(P, ob, X.o, X.o, X.d, X.col, X.key, X.cnt);
+                        surface_interaction<KIND>(P, ob, X.o, X.o, X.d, X.col, X.key, X.cnt, vec3{0, 0, 0}, shade_tab, X.idx);
                         L.n_hits++;
                         float intensity = brightness(X.col);
                         X.col = X.col * mk(ob.emission[0], ob.emission[1], ob.emission[2]);

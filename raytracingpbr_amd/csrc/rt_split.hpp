@@ -27,7 +27,7 @@ RT_D uint32_t mw_pack(uint32_t state, int idx, uint32_t cnt) { return state | ((
 // The rest of raytrace() (src/pathtracer.py:16-36) after the raycast of bounce-step `base` ended in `word` (MS_HIT / MS_MISS), on the
 // pixel's ray record in registers: surface interaction or environment lookup, stop tests — the state the next bounce-step starts from.
 template <int KIND>
-RT_D void src_shade_core(const Params& P, const ObjFull* lds_obj, int px, int py, uint32_t word, uint32_t base, rtpbr_ray& rb,
+RT_D void src_shade_core(const Params& P, const ObjFull* lds_obj, const float* shade_tab, int px, int py, uint32_t word, uint32_t base, rtpbr_ray& rb,
                          uint32_t& n_hits, uint32_t& n_sky, uint32_t& n_samples) {
     vec3 o = mk(rb.origin[0], rb.origin[1], rb.origin[2]);
     vec3 d = mk(rb.direction[0], rb.direction[1], rb.direction[2]);
@@ -37,8 +37,9 @@ RT_D void src_shade_core(const Params& P, const ObjFull* lds_obj, int px, int py
     // depth += 1 (scene.py:83)
     int depth = rb.depth + 1;
     if ((word & 3u) == MS_HIT) {
-        const ObjFull ob = lds_obj[(word >> 2) & 31u];
-        surface_interaction<KIND>(P, ob, o, o, d, col, key, cnt);
+        const int oi = (int)((word >> 2) & 31u);
+        const ObjFull ob = lds_obj[oi];
+        surface_interaction<KIND>(P, ob, o, o, d, col, key, cnt, vec3{0, 0, 0}, shade_tab, oi);
         n_hits = 1;
         float intensity = brightness(col);
         col = col * mk(ob.emission[0], ob.emission[1], ob.emission[2]);
@@ -67,8 +68,12 @@ RT_D void src_shade_core(const Params& P, const ObjFull* lds_obj, int px, int py
 template <int KIND, bool SHADE_FIRST = false, bool COUNT = false>
 RT_D void src_gen_impl(const Params& P) {
     __shared__ ObjFull lds_obj[SHADE_FIRST ? MAX_OBJ : 1];
+    __shared__ float shade_tab[SHADE_FIRST ? shade_tab_words(MAX_OBJ) : 1];
     zero_next_counters(P);
-    if constexpr (SHADE_FIRST) stage_objects(P, lds_obj);
+    if constexpr (SHADE_FIRST) {
+        stage_objects(P, lds_obj);
+        stage_shade_tables<false>(P, lds_obj, shade_tab);
+    }
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     int px = 0, py = 0;
     const bool in_frame = q < (uint32_t)P.np && pixel_of(P, q, px, py);
@@ -86,7 +91,7 @@ RT_D void src_gen_impl(const Params& P) {
         if constexpr (SHADE_FIRST) {
             if (shade) {
                 uint32_t h_ = 0, s_ = 0, n_ = 0;
-                src_shade_core<KIND>(P, lds_obj, px, py, old_word, P.shade_base, rb, h_, s_, n_);
+                src_shade_core<KIND>(P, lds_obj, shade_tab, px, py, old_word, P.shade_base, rb, h_, s_, n_);
                 if constexpr (COUNT) n_hits = h_, n_sky = s_, n_samples = n_;
             }
         }
@@ -439,7 +444,9 @@ RT_D void src_march_impl(const Params& P) {
 template <int KIND>
 RT_D void src_shade_impl(const Params& P) {
     __shared__ ObjFull lds_obj[MAX_OBJ];
+    __shared__ float shade_tab[shade_tab_words(MAX_OBJ)];
     stage_objects(P, lds_obj);
+    stage_shade_tables<false>(P, lds_obj, shade_tab);
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t n_hits = 0, n_sky = 0, n_samples = 0;
     const uint32_t word = q < (uint32_t)P.np ? P.march_out[q] : 0u;
@@ -449,7 +456,7 @@ RT_D void src_shade_impl(const Params& P) {
         pixel_of(P, q, px, py);
         const size_t pi = (size_t)px * P.cfg.height + py;
         rtpbr_ray rb = P.ray_buffer[pi];
-        src_shade_core<KIND>(P, lds_obj, px, py, word, P.sample_base, rb, n_hits, n_sky, n_samples);
+        src_shade_core<KIND>(P, lds_obj, shade_tab, px, py, word, P.sample_base, rb, n_hits, n_sky, n_samples);
         P.ray_buffer[pi] = rb;
     }
     flush_counters(P, 0, 0, n_hits, n_sky, n_samples, 0);

@@ -57,6 +57,27 @@ RT_D void stage_objects(const Params& P, ObjFull* lds_obj) {
     for (int i = threadIdx.x; i < nw; i += blockDim.x) dst[i] = src[i];
     __syncthreads();
 }
+// Fill the block's shading tables (rt_device.hpp: layout, and why on the device), after stage_objects: entry e < SHADE_RR is the
+// roulette probability of bounce e + 1, the entries behind it are (eta, F0) of object j seen from outside and from inside.
+// RR = false: a kernel that only calls surface_interaction (the src/ form has no roulette) leaves the first part unwritten.
+template <bool RR = true>
+RT_D void stage_shade_tables(const Params& P, const ObjFull* lds_obj, float* tab) {
+    if constexpr (SHADE_TABLES) {
+        const int n = SHADE_RR + 2 * P.n_obj;
+        for (int e = threadIdx.x; e < n; e += blockDim.x) {
+            if (e < SHADE_RR) {
+                if (RR) tab[e] = roulette_p(P, e + 1);
+            } else {
+                const int j = (e - SHADE_RR) >> 1;
+                float eta, F0;
+                eta_f0(P.cfg, lds_obj[j].ior, ((e - SHADE_RR) & 1) == 0, eta, F0);
+                tab[SHADE_RR + 2 * (e - SHADE_RR)] = eta;
+                tab[SHADE_RR + 2 * (e - SHADE_RR) + 1] = F0;
+            }
+        }
+        __syncthreads();
+    }
+}
 
 // -------------------------------------------------------------------------------------------
 // Pieces of the bounce loop shared by both schedulers (cornell_box_v3/pathtracer.py:81-106).
@@ -72,10 +93,10 @@ struct PathRay {
 // after a hit: surface interaction, emission / stop test, next-bounce roulette (:84-89,:97-104).
 // returns true if the path continues with another raycast.
 template <int KIND, bool HAVE_NORMAL = false>
-RT_D bool shade_hit(const Params& P, const ObjFull* lds_obj, PathRay& R, vec3 given_normal = vec3{0, 0, 0}) {
+RT_D bool shade_hit(const Params& P, const ObjFull* lds_obj, const float* shade_tab, PathRay& R, vec3 given_normal = vec3{0, 0, 0}) {
     const ObjFull& o = lds_obj[R.idx];   // read field by field where it is used (see surface_interaction)
     vec3 pos = fma3(R.t_eval, R.d, R.o);
-    surface_interaction<KIND, HAVE_NORMAL>(P, o, pos, R.o, R.d, R.col, R.key, R.cnt, given_normal);
+    surface_interaction<KIND, HAVE_NORMAL>(P, o, pos, R.o, R.d, R.col, R.key, R.cnt, given_normal, shade_tab, R.idx);
     float intensity = brightness(R.col);
     R.col = R.col * mk(o.emission[0], o.emission[1], o.emission[2]);
     float visible = brightness(R.col);
@@ -83,8 +104,10 @@ RT_D bool shade_hit(const Params& P, const ObjFull* lds_obj, PathRay& R, vec3 gi
     if (stop) return false;
     R.bounce++;
     if (R.bounce >= P.cfg.max_raytrace) return false;  // falls out of the loop keeping the throughput (G4)
-    float inv_pdf = exp_((float)R.bounce / P.cfg.light_quality);
-    float p = 1.0f - 1.0f / inv_pdf;
+    // (bounce >= 1 here; the table holds bounces 1 .. SHADE_RR, a deeper one computes the same expression inline)
+    float p;
+    if (SHADE_TABLES && R.bounce <= SHADE_RR) p = shade_tab[R.bounce - 1];
+    else p = roulette_p(P, R.bounce);
     if (rng_next(R.key, R.cnt) < p) {
         R.col = R.col * p;
         return false;
@@ -216,8 +239,8 @@ RT_D void acc_flush_all(const Params& P, const AccView& A, int lane, uint32_t& n
 // x * H + y, whole frame, no padding pixels) — a compile-time choice, the unlisted instances do not know about it
 template <bool LIST = false>
 RT_D int start_item(const Params& P, PathRay& R) {
-    uint32_t q = R.item / (uint32_t)P.K;
-    uint32_t k = R.item - q * (uint32_t)P.K;
+    uint32_t q, k;
+    item_split(R.item, (uint32_t)P.K, P.k_shift, q, k);      // (a power-of-two K: shift and mask, rt_item.hpp)
     int px, py;
     if constexpr (LIST) {
         const uint32_t i = P.order[q];
@@ -287,7 +310,9 @@ RT_D bool claim_items(const Params& P, WorkRange& wr, bool want, int lane, uint3
 template <int KIND, int NOBJ, uint32_t SIG = 0, bool LIST = false>
 __global__ void __launch_bounds__(256) trace_paths(const Params P) {
     __shared__ ObjFull lds_obj[MAX_OBJ];
+    __shared__ float shade_tab[shade_tab_words(MAX_OBJ)];
     stage_objects(P, lds_obj);
+    stage_shade_tables(P, lds_obj, shade_tab);
 
     const int lane = threadIdx.x & 63;
     Lane L;
@@ -311,7 +336,7 @@ __global__ void __launch_bounds__(256) trace_paths(const Params P) {
         bool alive = false;
         if (L.state == ST_HIT) {
             R.o = L.o; R.d = L.d; R.t_eval = L.t_eval; R.idx = L.idx;
-            alive = shade_hit<KIND>(P, lds_obj, R);
+            alive = shade_hit<KIND>(P, lds_obj, shade_tab, R);
             L.n_hits++;
             finished = !alive;
         } else if (L.state == ST_MISS) {
@@ -676,7 +701,10 @@ RT_D void trace_paths_pool_impl(const Params& P) {
     __shared__ float acc_all[4][ACC_SLOTS][4];
     __shared__ uint32_t acc_tag_all[4][ACC_SLOTS];
 #endif
+    // (+ 384 bytes for eight boxes: 22 912 in all, a seventh block per CU still fits — 160 KB / 7 = 23 405)
+    __shared__ float shade_tab[shade_tab_words(NOBJ > 0 ? NOBJ : (KIND == KIND_BUNNY ? 1 : MAX_OBJ))];
     stage_objects(P, lds_obj);
+    stage_shade_tables(P, lds_obj, shade_tab);
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -775,7 +803,7 @@ RT_D void trace_paths_pool_impl(const Params& P) {
                     R.item = pool[F_ITEM][lane];
                     if (KIND != KIND_BUNNY) {
                         if (st == SL_HIT) {
-                            alive = shade_hit<KIND>(P, lds_obj, R);
+                            alive = shade_hit<KIND>(P, lds_obj, shade_tab, R);
                         } else {
                             shade_miss(P, R, sky1);
                         }
@@ -792,14 +820,14 @@ RT_D void trace_paths_pool_impl(const Params& P) {
                         else if (st == SL_HIT) nrm = calc_normal<KIND_BUNNY>(P, lds_obj[0], hp);
                     }
                     if (st == SL_HIT) {
-                        alive = shade_hit<KIND, true>(P, lds_obj, R, nrm);
+                        alive = shade_hit<KIND, true>(P, lds_obj, shade_tab, R, nrm);
                     } else if (st == SL_MISS) {
                         shade_miss(P, R, sky1);
                     }
                 }
                 w_sky += (uint32_t)__popcll(__ballot(sky1 != 0));
 #if RT_FAST_MATH
-                acc_add(P, A, (st == SL_HIT || st == SL_MISS) && !alive, R.item / (uint32_t)P.K, R.col, lane, n_dep);
+                acc_add(P, A, (st == SL_HIT || st == SL_MISS) && !alive, item_pixel(R.item, (uint32_t)P.K, P.k_shift), R.col, lane, n_dep);
 #else
                 stage_sample(P, (st == SL_HIT || st == SL_MISS) && !alive, R.item, R.col, lane);
 #endif
@@ -843,7 +871,7 @@ RT_D void trace_paths_pool_impl(const Params& P) {
                     roulette0 = r == 0;
                 }
 #if RT_FAST_MATH
-                acc_add(P, A, roulette0, R.item / (uint32_t)P.K, R.col, lane, n_dep);
+                acc_add(P, A, roulette0, item_pixel(R.item, (uint32_t)P.K, P.k_shift), R.col, lane, n_dep);
 #else
 #if RT_STAGE_DENSE
                 if (__any(roulette0)) stage_sample(P, roulette0, R.item, R.col, lane);

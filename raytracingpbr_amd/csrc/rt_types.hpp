@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/rtpbr.h"
+#include "rt_item.hpp"
 #include "rt_math.hpp"
 
 namespace rt {
@@ -236,6 +237,8 @@ struct Params {
     uint32_t* march_out;    // wavefront split of the src/ form (rt_split.hpp): one word per local pixel between its three kernels
     const uint32_t* order;
     struct PlanBuf* plan;
+    int32_t k_shift;        // log2(K) when K is a power of two, else -1: item -> (pixel, sample) by shift and mask (rt_item.hpp).  Behind
+                            // every field the kernels read by offset, in front of the march table only: nothing else moves
     ObjM objm[MAX_OBJ];
 };
 static_assert(sizeof(Params) < 3900, "Params must fit the 4 KB kernarg segment");

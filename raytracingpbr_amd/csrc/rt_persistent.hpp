@@ -763,6 +763,9 @@ RT_D void persistent_pool_impl(const Params& P, int steps) {
     __shared__ float4 xch_all[4][8];
 #endif
     __shared__ float shade_tab[shade_tab_words(MAX_OBJ)];
+    // pool_swap hands a free slot's old words to the lane that parks there (dead as they are): defined ones from the start.  By the
+    // whole block, ahead of stage_objects' barrier: zeroed per wave beside `sstate` below, the fused kernel spilled 30 registers instead of 18
+    for (int i = threadIdx.x; i < 4 * G_COUNT * 64; i += 256) (&pool_all[0][0][0])[i] = 0u;
     zero_next_counters(P);
     stage_objects(P, lds_obj);
     stage_shade_tables<false>(P, lds_obj, shade_tab);
@@ -1086,26 +1089,13 @@ RT_D void persistent_pool_impl(const Params& P, int steps) {
         // ================================================================ dispatch (pool_swap, as in trace_paths_pool)
         {
             const bool is_done = L.state == ST_HIT || L.state == ST_MISS;
-            uint32_t rec[POOL_WORDS];
-            rec[G_OX] = f2u(L.o.x); rec[G_OY] = f2u(L.o.y); rec[G_OZ] = f2u(L.o.z);
-            rec[G_DX] = f2u(L.d.x); rec[G_DY] = f2u(L.d.y); rec[G_DZ] = f2u(L.d.z);
-            rec[G_CR] = f2u(a_col.x); rec[G_CG] = f2u(a_col.y); rec[G_CB] = f2u(a_col.z);
-            rec[G_DEPTH] = (uint32_t)a_depth;
-            rec[G_META] = (uint32_t)L.idx | (a_meta + (L.n_steps << 14));
-            rec[G_K] = a_k;
-            rec[G_Q] = a_q;
-            rec[G_KEY] = a_key; rec[G_CNT] = a_cnt;
-            const int r = pool_swap(V, lane, is_done, L.state == ST_IDLE, L.state == ST_HIT ? SL_HIT : SL_MISS, rec, m_ready, m_shade);
+            // the record is the lane's own variables in G_* order, exchanged in place; only the meta word is composed
+            uint32_t meta_w = (uint32_t)L.idx | (a_meta + (L.n_steps << 14));
+            const int r = pool_swap<G_COUNT>(V, lane, is_done, L.state == ST_IDLE, L.state == ST_HIT ? SL_HIT : SL_MISS, m_ready, m_shade,
+                                             L.o.x, L.o.y, L.o.z, L.d.x, L.d.y, L.d.z, a_col.x, a_col.y, a_col.z, a_depth, meta_w, a_k, a_q, a_key, a_cnt);
             if (r & 2) L.state = ST_IDLE;
             if (r & 1) {
-                L.o = mk(u2f(rec[G_OX]), u2f(rec[G_OY]), u2f(rec[G_OZ]));
-                L.d = mk(u2f(rec[G_DX]), u2f(rec[G_DY]), u2f(rec[G_DZ]));
-                a_col = mk(u2f(rec[G_CR]), u2f(rec[G_CG]), u2f(rec[G_CB]));
-                a_depth = (int)rec[G_DEPTH];
-                a_meta = (rec[G_META] & ~31u) - (L.n_steps << 14);
-                a_k = rec[G_K];
-                a_q = rec[G_Q];
-                a_key = rec[G_KEY]; a_cnt = rec[G_CNT];
+                a_meta = (meta_w & ~31u) - (L.n_steps << 14);
                 src_march_init(L);
                 Tk.lb2 = Tk.lb3 = -1.0f;
             }

@@ -588,28 +588,41 @@ RT_D void lds_wave_fence() {
 RT_D int wave_rank(unsigned long long m) {   // number of set bits below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
 }
-template <int W>
-RT_D void pool_load(const PoolView& V, uint32_t slot, uint32_t (&rec)[W]) {
-#pragma unroll
-    for (int w = 0; w < W; w++) rec[w] = V.pool[w][slot];
+// One record word changes places with its word in the slot: a single LDS exchange whose source and destination are the
+// caller's register (relaxed, wave scope: no fence and no wait of its own; pool_swap's fences order it against the other lanes).
+RT_D void pool_xchg(uint32_t* p, uint32_t& x) {
+    x = __hip_atomic_exchange(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
-template <int W>
-RT_D void pool_store(const PoolView& V, uint32_t slot, const uint32_t (&rec)[W]) {
-#pragma unroll
-    for (int w = 0; w < W; w++) V.pool[w][slot] = rec[w];
+RT_D void pool_xchg(uint32_t* p, int& x) {
+    x = (int)__hip_atomic_exchange(p, (uint32_t)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+RT_D void pool_xchg(uint32_t* p, float& x) {
+    x = __builtin_bit_cast(float, __hip_atomic_exchange(p, __builtin_bit_cast(uint32_t, x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+}
+template <int I = 0, typename T, typename... Ts>
+RT_D void pool_xchg_words(const PoolView& V, uint32_t slot, T& x, Ts&... xs) {
+    pool_xchg(&V.pool[I][slot], x);
+    if constexpr (sizeof...(Ts) > 0) pool_xchg_words<I + 1>(V, slot, xs...);
 }
 
 // Swap finished lanes with parked READY records (wave-uniform control flow; all lanes call it).
-//   is_done: this lane holds a finished record in rec[] that must be parked as `done_state`;
+//   is_done: this lane holds a finished record in words... that must be parked as `done_state`;
 //   is_idle: this lane holds nothing and wants a READY record.
 // Finished lanes are served first (they need ANY non-occupied slot: READY ones are swapped, free
 // ones just receive the record), then idle lanes take the remaining READY records.  The j-th
 // requester gets the j-th listed slot: both sides are ranked with ballot + mbcnt prefix counts and
-// matched through the 64-entry table.  Returns bit 0 = rec[] now holds a taken READY record,
+// matched through the 64-entry table.  Returns bit 0 = words... now hold a taken READY record,
 // bit 1 = this lane's record was parked.  m_ready / m_shade are refreshed from the slot states.
-template <int W>
+// words... are the W dwords of the record, in record order, and they are THE CALLER'S OWN variables (float, int or
+// uint32_t): every served lane exchanges each of them with its slot's word in place, one exec-masked group of W LDS
+// exchanges for all three cases — finished lane + READY slot: a swap; finished lane + free slot: what comes back is the
+// slot's stale content and dead (bit 0 clear, the caller goes idle); idle lane + READY slot: what is written is dead (the
+// slot becomes SL_EMPTY).  A lane that is not served keeps its variables.  The matching is one-to-one, so no two lanes
+// touch the same slot and the exchanges need no order among themselves.
+template <int W, typename... Ts>
 RT_D int pool_swap(const PoolView& V, int lane, bool is_done, bool is_idle, uint32_t done_state,
-                   uint32_t (&rec)[W], unsigned long long& m_ready, unsigned long long& m_shade) {
+                   unsigned long long& m_ready, unsigned long long& m_shade, Ts&... words) {
+    static_assert(sizeof...(Ts) == W, "one variable per record word");
     const unsigned long long done = __ballot(is_done);
     const unsigned long long idle = __ballot(is_idle);
     const int n_done = __popcll(done);
@@ -628,19 +641,10 @@ RT_D int pool_swap(const PoolView& V, int lane, bool is_done, bool is_idle, uint
     const bool parks = served && is_done;
     uint32_t slot = 0;
     if (served) slot = V.tbl[req];
-    uint32_t got[W];
-#pragma unroll
-    for (int w = 0; w < W; w++) got[w] = rec[w];
-    if (takes) pool_load(V, slot, got);          // read the READY record before overwriting its slot
-    lds_wave_fence();
-    if (parks) {
-        pool_store(V, slot, rec);
-        V.sstate[slot] = done_state;
-    } else if (takes) {
-        V.sstate[slot] = SL_EMPTY;
+    if (parks || takes) {   // (an idle lane matched with a free slot has nothing to move)
+        pool_xchg_words(V, slot, words...);
+        V.sstate[slot] = parks ? done_state : (uint32_t)SL_EMPTY;
     }
-#pragma unroll
-    for (int w = 0; w < W; w++) rec[w] = got[w];
     lds_wave_fence();   // slot states written by the lanes that parked / took
     const uint32_t st = V.sstate[lane];
     m_ready = __ballot(st == SL_READY);
@@ -719,6 +723,9 @@ RT_D void trace_paths_pool_impl(const Params& P) {
     uint32_t* const tbl_w = PARK ? reinterpret_cast<uint32_t*>(&save_all[PARK ? wave : 0][0][0]) : tbl_all[PARK ? 0 : wave];
     const PoolView V = {pool_all[wave], sstate_all[wave], tbl_w};
     sstate[lane] = SL_EMPTY;
+    // (a lane that parks into a free slot gets the slot's old words back, dead as they are: let them be defined from the start)
+#pragma unroll
+    for (int w = 0; w < F_COUNT; w++) pool[w][lane] = 0u;
 
     Lane L;
     L.state = ST_IDLE;   // ST_IDLE = no ray, ST_MARCH, ST_HIT / ST_MISS = raycast done, ray still in registers
@@ -732,8 +739,12 @@ RT_D void trace_paths_pool_impl(const Params& P) {
     uint32_t a_meta = 0, a_key = 0, a_item = 0;   // a_meta: bounce and draw count, packed like F_META
     // work counters kept wave-uniform (scalar registers, scalar adds of ballot popcounts) where the
     // control flow allows it: the per-lane v_add per march step and 3 VGPRs go away
-    uint32_t w_steps = 0, w_raycasts = 0, w_hits = 0, w_samples = 0, w_sky = 0;
+    uint32_t w_raycasts = 0, w_hits = 0, w_samples = 0, w_sky = 0;
     uint32_t w_mlp_wave = 0, w_mlp_lane = 0;
+    // march steps: a raycast that is parked has taken max_raymarch - steps_left of them (march_update counts both together), so the
+    // lane adds that up at the swap — nothing is counted per step, neither per lane nor per wave (the wave count sat in a VGPR: the
+    // scalar registers are full), and the drain needs no count of its own.  (The neural-SDF march keeps Lane::n_steps.)
+    uint32_t l_steps = 0;
     WorkRange wr = {0, 0, false};
     unsigned long long m_ready = 0, m_shade = 0;   // slot masks (wave-uniform)
     __shared__ __attribute__((aligned(16))) float b_lds_all[(KIND == KIND_BUNNY) ? 4 * BUNNY_LDS_WORDS : 4];
@@ -760,7 +771,7 @@ RT_D void trace_paths_pool_impl(const Params& P) {
 #endif
 #ifdef RT_DEBUG_PHASE
     unsigned long long tB = 0, tD = 0, tA = 0, tc = __builtin_readcyclecounter();
-    unsigned long long dbg_march_lanes = 0, dbg_march_steps = 0, dbg_shade_lanes = 0, dbg_shade_passes = 0;
+    unsigned long long dbg_march_lanes = 0, dbg_march_steps = 0, dbg_shade_lanes = 0, dbg_shade_passes = 0, dbg_outer = 0, dbg_swaps = 0;
 #define RT_PHASE(acc) { unsigned long long tn = __builtin_readcyclecounter(); acc += tn - tc; tc = tn; }
 #else
 #define RT_PHASE(acc)
@@ -916,24 +927,19 @@ RT_D void trace_paths_pool_impl(const Params& P) {
         // ================================================================ dispatch: swap finished lanes with parked rays
         {
             const bool is_done = L.state == ST_HIT || L.state == ST_MISS;
-            uint32_t rec[F_COUNT];
-            rec[F_OX] = f2u(L.o.x); rec[F_OY] = f2u(L.o.y); rec[F_OZ] = f2u(L.o.z);
-            rec[F_DX] = f2u(L.d.x); rec[F_DY] = f2u(L.d.y); rec[F_DZ] = f2u(L.d.z);
-            rec[F_CR] = f2u(a_col.x); rec[F_CG] = f2u(a_col.y); rec[F_CB] = f2u(a_col.z);
-            rec[F_TEVAL] = f2u(L.t_eval);
-            rec[F_META] = (a_meta & ~31u) | (uint32_t)L.idx;
-            rec[F_KEY] = a_key; rec[F_ITEM] = a_item;
-            const int r = pool_swap(V, lane, is_done, L.state == ST_IDLE, L.state == ST_HIT ? SL_HIT : SL_MISS, rec, m_ready, m_shade);
+            // the record IS the lane's registers, in F_* order; a_meta carries the nearest-object index in its low bits from here on
+            // (nobody reads them there: they are replaced at the next dispatch, and a READY record has them zero)
+            a_meta = (a_meta & ~31u) | (uint32_t)L.idx;
+            const int r = pool_swap<F_COUNT>(V, lane, is_done, L.state == ST_IDLE, L.state == ST_HIT ? SL_HIT : SL_MISS, m_ready, m_shade,
+                                             L.o.x, L.o.y, L.o.z, L.d.x, L.d.y, L.d.z, a_col.x, a_col.y, a_col.z, L.t_eval, a_meta, a_key, a_item);
             if (r & 2) L.state = ST_IDLE;
+            if (KIND != KIND_BUNNY && (r & 2)) l_steps += (uint32_t)(P.cfg.max_raymarch - L.steps_left);
             w_raycasts += (uint32_t)__popcll(__ballot((r & 1) != 0));
-            if (r & 1) {
-                L.o = mk(u2f(rec[F_OX]), u2f(rec[F_OY]), u2f(rec[F_OZ]));
-                L.d = mk(u2f(rec[F_DX]), u2f(rec[F_DY]), u2f(rec[F_DZ]));
-                a_col = mk(u2f(rec[F_CR]), u2f(rec[F_CG]), u2f(rec[F_CB]));
-                a_meta = rec[F_META];
-                a_key = rec[F_KEY]; a_item = rec[F_ITEM];
-                march_init(P, L);
-            }
+            if (r & 1) march_init(P, L);
+#ifdef RT_DEBUG_PHASE
+            dbg_outer++;
+            dbg_swaps += __ballot(r != 0) != 0 ? 1u : 0u;      // dispatches that moved at least one record
+#endif
         }
 
         RT_PHASE(tD)
@@ -952,9 +958,7 @@ RT_D void trace_paths_pool_impl(const Params& P) {
             // ray runs its object's lean loop.
             if constexpr (NOBJ > 0 && (KIND == KIND_BOXES || KIND == KIND_GENERIC)) {
                 if (wr.drained && n_ready == 0 && n_march <= P.drain_lanes && P.cull_ok) {
-                    const uint32_t s0 = L.n_steps;
-                    culled_march_wave<KIND, NOBJ, SIG>(P, L, nullptr);
-                    w_steps += wave_sum(L.n_steps - s0);
+                    culled_march_wave<KIND, NOBJ, SIG>(P, L, nullptr);      // (its steps are counted like all others: at the swap)
                     continue;
                 }
             }
@@ -1004,7 +1008,6 @@ RT_D void trace_paths_pool_impl(const Params& P) {
                         }
                     }
                 } else {
-                    w_steps += (uint32_t)n_march;
 #ifdef RT_DEBUG_PHASE
                     dbg_march_lanes += (unsigned)n_march;
                     dbg_march_steps += 1;
@@ -1057,6 +1060,8 @@ RT_D void trace_paths_pool_impl(const Params& P) {
         atomicAdd(&P.counters->mlp_lane_evals, tA >> 10);
         atomicAdd(&P.counters->hits, dbg_march_lanes);          // (replaces the hit count in this build)
         atomicAdd(&P.counters->deposits, dbg_march_steps);
+        atomicAdd(&P.counters->dbg[2], dbg_outer);              // outer iterations (= dispatches), and those that moved a record
+        atomicAdd(&P.counters->dbg[3], dbg_swaps);
     }
 #endif
 #ifdef RT_DEBUG_CULL
@@ -1075,8 +1080,8 @@ RT_D void trace_paths_pool_impl(const Params& P) {
 #else
     const uint32_t dep_out = 0;
 #endif
-    // (the neural-SDF march counts its steps per lane: run-ahead lanes step at different times)
-    flush_counters(P, KIND == KIND_BUNNY ? L.n_steps : (lane == 0 ? w_steps : 0u), lane == 0 ? w_raycasts : 0u,
+    // (the neural-SDF march counts its steps per lane and step: run-ahead lanes step at different times)
+    flush_counters(P, KIND == KIND_BUNNY ? L.n_steps : l_steps, lane == 0 ? w_raycasts : 0u,
 #ifdef RT_DEBUG_PHASE
                    0u,
 #else

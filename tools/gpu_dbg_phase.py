@@ -14,3 +14,4 @@ ml, ms = c.hits, c.deposits - W * H * 64      # marching lanes summed over wave-
 print("march lane utilisation %.4f (lanes marching per wave-step / 64), wave-steps per sample %.4f" % (ml / max(ms, 1) / 64, ms / (W * H * 64)))
 t = B + D + A
 print("trace ms", tr, "phase shares (cycle sums >> 10): shade/refill B %.3f  dispatch %.3f  march A %.3f" % (B / t, D / t, A / t), B, D, A)
+print("outer iterations per launch %d, of which %d moved a record (summed over waves); wave-steps %d" % (r.counter("dbg2"), r.counter("dbg3"), ms))

@@ -242,7 +242,11 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_BLEND_WEIGHT = 17,  /* (W,H) f32 t in [0, 1]: 1 = the denoised colour, 0 = the raw average (rtpbr_denoise_blend_levels: T_K) */
        /* the depth of rtpbr_denoise_blend_levels: allocated by its first call (which allocates the weight too), freed by
         * rtpbr_set_config with a new resolution; output only */
-       RTPBR_BUF_BLEND_DEPTH  = 18 };   /* (W,H) f32 in 0..K: K = the whole filter was kept, 0 = the raw average                   */
+       RTPBR_BUF_BLEND_DEPTH  = 18,  /* (W,H) f32 in 0..K: K = the whole filter was kept, 0 = the raw average                   */
+       /* the error estimate of the level-blended frame (rtpbr_blend_error): allocated by its first call, freed by rtpbr_set_config
+        * with a new resolution; output only */
+       RTPBR_BUF_BLEND_ERROR  = 19 };   /* (W,H) f32 estimated root-mean-square error of lum(rtpbr_denoise_blend_levels' display
+                                         *           colour): variance and the bias the halves can see                         */
 
 enum { RTPBR_ENV_RGB8 = 0,           /* uint8 (W_e,H_e,3), [x][y], y=0 bottom: what ti.tools.imread gives */
        RTPBR_ENV_RGB32F = 1 };       /* float32 (W_e,H_e,3) already preprocessed (T9 as is)               */
@@ -809,6 +813,60 @@ int rtpbr_denoise_blend(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtp
  * resolution.
  * Errors, each before anything changes: exactly rtpbr_denoise_blend's. */
 int rtpbr_denoise_blend_levels(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out);
+
+/* ---- The error of the LEVEL-BLENDED frame, and sampling driven by it.
+ *
+ * rtpbr_denoise_error measures the variance of the unblended filter and is blind to bias; a host that shows
+ * rtpbr_denoise_blend_levels' frame wants to know how wrong THAT frame still is.  The two halves answer as they do for
+ * rtpbr_denoise_error, but on the blended frame itself: the full frame's weights T_k applied to each half's own ladder give XA and
+ * XB, the blended frame of either half; their difference measures the variance, correlations between neighbours included; the
+ * product of the halves' (blended - raw) has expectation bias^2, because the halves' noise is independent (the argument
+ * rtpbr_denoise_blend rests on); variance plus squared bias is the mean-square error of the picture on the screen.  THE BIAS IS
+ * ONLY WHAT THE HALVES CAN SEE: averaged over the window, on the pixel's object, where both halves hold min_half_samples.
+ *
+ * rtpbr_blend_error does everything rtpbr_denoise_blend_levels(p, e) does — RTPBR_BUF_DENOISED_PIXELS, RTPBR_BUF_BLEND_WEIGHT and
+ *   RTPBR_BUF_BLEND_DEPTH come out with the same bytes, under the same state rules (it blocks, flushes lazy shading, is ordered
+ *   behind asynchronous reads of the buffers it writes, renders stale features first) — and writes RTPBR_BUF_BLEND_ERROR besides.
+ *   Nothing else changes: image_buffer, half A and its snapshot, the moments, RTPBR_BUF_NOISE, RTPBR_BUF_DENOISED_ERROR, the
+ *   selection and the work counters keep their bits.  NULL p, e, w: the defaults of rtpbr_denoise, rtpbr_denoise_blend and
+ *   rtpbr_denoise_error.  out (if not NULL) receives the statistics of the ERROR plane, not the blend's: pixels_estimated = the
+ *   valid pixels, pixels_above = those with error > threshold, max_noise = the largest error.
+ *   Every operation is f32, in the order written, nothing fused.  b, A, B, cA, cB, f, lum, m, "usable", FD_k, FA_k, FB_k, T_k and K
+ *   are those of the blend-levels section; PA, PB the blend section's raw averages of the halves.
+ *   Per pixel (only pixels with samples in the half are ever read), alongside the ladder sum for c:
+ *     XA = FA_0;  XB = FB_0;
+ *     k = 1..K in order:  XA.ch = XA.ch + T_k * (FA_k.ch - FA_{k-1}.ch)  per channel;  XB likewise from FB;
+ *     if T_K == 1: XA = FA_K, XB = FB_K.
+ *   Variance, in display space as in rtpbr_denoise_error.  q is valid when cA > 0 and cB > 0:
+ *     dl = lum(tone_map(cfg, (XA, 1))) - lum(tone_map(cfg, (XB, 1)));   e_q = fmaxf((dl * dl) * f, 0)        (a NaN gives 0).
+ *   Squared bias, in linear radiance (the raw half is unbiased only there), for usable q (cA >= m and cB >= m):
+ *     x_q = (lum(XA) - lum(PA)) * (lum(XB) - lum(PB));
+ *   a valid pixel that is not usable has x_q = +0 and does not count in nb.
+ *   Slope of the display luminance at the blended colour: c is the linear colour the call tone-maps (a pixel with b.w > 0),
+ *     Y = lum(c);   c1 = (1.0625f * c.x, 1.0625f * c.y, 1.0625f * c.z);
+ *     s = (lum(tone_map(cfg, (c1, 1))) - lum(tone_map(cfg, (c, 1)))) / (0.0625f * Y)  when Y > 0;   s = 0 otherwise.
+ *   Per valid pixel p, over rtpbr_denoise_error's window with its tap order — q = p + (dx, dy), dy = -R..R (outer), dx = -R..R
+ *   (inner), R = w->radius, inside the frame, on p's RTPBR_BUF_FEAT_OBJECT, valid — all sums from +0:
+ *     S = S + e_q;  n = n + 1;  and for usable q:  SX = SX + x_q;  nb = nb + 1;
+ *     bias2 = nb > 0 ? fmaxf(SX / nb, 0) : 0                                                      (a NaN gives 0);
+ *     error_p = sqrt(S / n + (s * s) * bias2), correctly rounded.
+ *   A pixel that is not valid has error 0 and is not estimated.
+ *   With min_half_samples above every count every T_k is 1, no pixel is usable, XA = FA_K and XB = FB_K: the plane is then
+ *   rtpbr_denoise_error(p, w)'s bit for bit.  K = 0 is allowed: the frame is the raw average, the variance is the raw halves' and
+ *   bias2 is exactly 0 without demodulate (XA = PA; with it XA differs from PA by the rounding of c / albedo * albedo, and bias2
+ *   is of that order squared).  NOT CALIBRATED: against the empirical error on Cornell v3 the mean of error^2 is 6.6 to 7.4 times
+ *   too large (the bias term; the variance term alone is about half the empirical variance): DESIGN.md section 6n.
+ *   Memory: beside what rtpbr_denoise_blend_levels keeps, two (W,H) planes of 16 bytes (XA, XB) and the 4-byte output plane (75 MB
+ *   at 1920 x 1080), allocated by the first call and freed by rtpbr_set_config with a new resolution.
+ *   Errors, each before anything changes: rtpbr_denoise_blend_levels', and rtpbr_denoise_error's for w and threshold (RTPBR_EINVAL
+ *   for a window radius outside 1..3 and a threshold that is not >= 0).
+ *
+ * rtpbr_select_blend_error is rtpbr_select_error's rule word for word, reading RTPBR_BUF_BLEND_ERROR as the last rtpbr_blend_error
+ *   wrote it in the place of RTPBR_BUF_DENOISED_ERROR.  Errors as rtpbr_select_error, and RTPBR_ESTATE before the first
+ *   rtpbr_blend_error. */
+int rtpbr_blend_error(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, const rtpbr_error_params* w,
+                      float threshold, rtpbr_noise_stats* out);
+int rtpbr_select_blend_error(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 
 /* ---- Halves dealt per sample and carried through reprojection.
  *

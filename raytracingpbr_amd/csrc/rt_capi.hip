@@ -142,7 +142,7 @@ static void free_noise(rtpbr_ctx* c) {
     c->noise_map = c->noise_var = nullptr;
 }
 
-// buffers of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels (allocated on first use)
+// buffers of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error (allocated on first use)
 static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->half_a);
     (void)hipFree(c->half_snapshot);
@@ -155,9 +155,12 @@ static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->blend_weight);
     (void)hipFree(c->blend_depth);
     (void)hipFree(c->levels_scratch);
+    (void)hipFree(c->blend_error);
+    (void)hipFree(c->blend_x);
     c->half_a = c->half_snapshot = c->hist_half = c->half_b = nullptr;
     c->half_da = c->half_db = c->denoised_error = c->half_fd = c->blend_weight = c->blend_depth = nullptr;
-    c->levels_scratch = nullptr;
+    c->levels_scratch = c->blend_x = nullptr;
+    c->blend_error = nullptr;
 }
 
 // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (allocated on the first select call)
@@ -741,7 +744,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b <= RTPBR_BUF_BLEND_DEPTH; b++)
+    for (int b = 0; b <= RTPBR_BUF_BLEND_ERROR; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -2007,8 +2010,9 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
 }
 
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
-enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT, W_DEPTH = 1u << RTPBR_BUF_BLEND_DEPTH };
-static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_select_error work on the whole frame: not with tiles of world > 1";
+enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT, W_DEPTH = 1u << RTPBR_BUF_BLEND_DEPTH,
+                  W_BLEND_ERROR = 1u << RTPBR_BUF_BLEND_ERROR };
+static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_select_error / rtpbr_select_blend_error work on the whole frame: not with tiles of world > 1";
 
 // What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
 // snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.  keep_a: A has
@@ -2178,19 +2182,26 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     return noise_stats_read(c, out);
 }
 
-// ---- the same blend across the a-trous levels (level_blend<R, FIRST, LAST>, rt_half.hip)
-extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out) {
+// ---- the same blend across the a-trous levels (level_blend<R, FIRST, LAST>, rt_half.hip), and with `window` the error estimate of
+// its frame (rtpbr_blend_error: the ERR instances and blend_error<R>)
+static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_params* p, const rtpbr_blend_params* e,
+                        const rtpbr_error_params* w, bool with_error, float threshold, rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     rtpbr_denoise_params d;
     float inv[4];
     if (int r = denoise_params(p, d, inv)) return r;
     rtpbr_blend_params b{RTPBR_BLEND_DEFAULT_RADIUS, RTPBR_BLEND_DEFAULT_Z, RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES};
     if (e) b = *e;
-    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend_levels: radius must be 1..3");
-    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend_levels: z must be finite and >= 0");
-    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend_levels: min_half_samples must be 1..16777216");
+    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "%s: radius must be 1..3", who);
+    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "%s: z must be finite and >= 0", who);
+    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "%s: min_half_samples must be 1..16777216", who);
+    const int window = w ? w->radius : RTPBR_ERROR_DEFAULT_RADIUS;
+    if (with_error) {
+        if (window < 1 || window > 3) return fail(RTPBR_EINVAL, "%s: the window's radius must be 1..3", who);
+        if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
+    }
     if (int r = whole_frame_state(c, HALF_TILES)) return r;
-    if (!c->half_a) return fail(RTPBR_ESTATE, "rtpbr_denoise_blend_levels: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)");
+    if (!c->half_a) return fail(RTPBR_ESTATE, "%s: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)", who);
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
@@ -2200,8 +2211,10 @@ extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_para
     if (!c->blend_depth) HIP_TRY(hipMalloc(&c->blend_depth, n * sizeof(float)));
     if (!c->levels_scratch) HIP_TRY(hipMalloc(&c->levels_scratch, 6 * n * sizeof(float4)));
     if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
+    if (with_error && !c->blend_error) HIP_TRY(hipMalloc(&c->blend_error, n * sizeof(float)));
+    if (with_error && !c->blend_x) HIP_TRY(hipMalloc(&c->blend_x, 2 * n * sizeof(float4)));
     if (int r = denoised_alloc(c, 0)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
-    if (int r = rt_order_after_reads(c, W_BLEND | W_DEPTH)) return r;
+    if (int r = rt_order_after_reads(c, W_BLEND | W_DEPTH | (with_error ? W_BLEND_ERROR : 0u))) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
     HalfArgs S{};
@@ -2213,6 +2226,11 @@ extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_para
     launch_half_subtract(S, c->stream);
     HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
     LevelsArgs A{};
+    if (with_error) {      // the ERR instances: XA and XB beside the frame, the slope into the error plane
+        A.xa = c->blend_x;
+        A.xb = c->blend_x + n;
+        A.slope = c->blend_error;
+    }
     A.cfg = c->cfg;
     A.image_buffer = c->image_buffer;
     A.half_a = c->half_a;
@@ -2269,7 +2287,33 @@ extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_para
         launch_level_blend(A, first, last, c->stream);
     }
     HIP_TRY(hipGetLastError());
+    if (!with_error) return noise_stats_read(c, out);
+    // the statistics are the error plane's: the blend's own are not handed out by this call
+    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    BlendErrorArgs E{};
+    E.lx = c->blend_x;
+    E.half_a = c->half_a;
+    E.half_b = c->half_b;
+    E.object = c->feat_object;
+    E.error = c->blend_error;
+    E.stats = c->noise_stats;
+    E.threshold = threshold;
+    E.min_half = (float)b.min_half_samples;
+    E.width = c->cfg.width;
+    E.height = c->cfg.height;
+    E.radius = window;
+    launch_blend_error(E, c->stream);
+    HIP_TRY(hipGetLastError());
     return noise_stats_read(c, out);
+}
+
+extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out) {
+    return blend_levels(c, "rtpbr_denoise_blend_levels", p, e, nullptr, false, 0.0f, out);
+}
+
+extern "C" int rtpbr_blend_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, const rtpbr_error_params* w,
+                                 float threshold, rtpbr_noise_stats* out) {
+    return blend_levels(c, "rtpbr_blend_error", p, e, w, true, threshold, out);
 }
 
 extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
@@ -2285,6 +2329,27 @@ extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uin
     SelectArgs A{};
     A.image_buffer = c->image_buffer;
     A.noise = c->denoised_error;
+    A.half_a = c->half_a;
+    A.threshold = threshold;
+    A.dilate = dilate;
+    A.min_samples = (float)c->noise_estimator.min_samples;
+    return selection_build(c, A, SELECT_ERROR, n_selected);
+}
+
+// rtpbr_select_error's rule and kernels on RTPBR_BUF_BLEND_ERROR
+extern "C" int rtpbr_select_blend_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
+    if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
+    if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
+    if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_blend_error: dilate must be 0..3");
+    if (int r = whole_frame_state(c, HALF_TILES)) return r;
+    if (!c->blend_error || !c->half_a) return fail(RTPBR_ESTATE, "rtpbr_select_blend_error: no error estimate yet (rtpbr_blend_error first)");
+    if (int r = set_dev(c)) return r;
+    if (int r = flush_shade(c)) return r;
+    if (int r = selection_alloc(c)) return r;
+    if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
+    SelectArgs A{};
+    A.image_buffer = c->image_buffer;
+    A.noise = c->blend_error;
     A.half_a = c->half_a;
     A.threshold = threshold;
     A.dilate = dilate;
@@ -2357,14 +2422,15 @@ static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
         case RTPBR_BUF_DENOISED_ERROR: *p = c->denoised_error; *n = np * 4; break;
         case RTPBR_BUF_BLEND_WEIGHT: *p = c->blend_weight; *n = np * 4; break;
         case RTPBR_BUF_BLEND_DEPTH: *p = c->blend_depth; *n = np * 4; break;
+        case RTPBR_BUF_BLEND_ERROR: *p = c->blend_error; *n = np * 4; break;
         default: return fail(RTPBR_EINVAL, "unknown buffer id");
     }
     // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
     // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate,
     // the packed frame from the first rtpbr_present, the half buffer from the first rtpbr_half_update, the error map from the first
     // rtpbr_denoise_error, the blend weight from the first rtpbr_denoise_blend or rtpbr_denoise_blend_levels, the blend depth from
-    // the first rtpbr_denoise_blend_levels)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels first");
+    // the first rtpbr_denoise_blend_levels or rtpbr_blend_error, the blend error from the first rtpbr_blend_error)
+    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error first");
     return 0;
 }
 
@@ -2465,8 +2531,8 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_BLEND_DEPTH)
-        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half, error, blend-weight and blend-depth buffers are outputs only");
+    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_BLEND_ERROR)
+        return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half, error, blend-weight, blend-depth and blend-error buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
     if (int r = set_dev(c)) return r;

@@ -183,7 +183,7 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[19] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[20] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
     float* feat_albedo = nullptr;      // (W,H,3)
@@ -227,6 +227,9 @@ struct rtpbr_ctx {
     // rtpbr_denoise_blend_levels: from its first call on (it makes half_b and blend_weight too); freed with the halves
     float* blend_depth = nullptr;      // (W,H): RTPBR_BUF_BLEND_DEPTH
     float4* levels_scratch = nullptr;  // 6 x (W,H): a two-plane ping-pong of the levels' records for image_buffer, half A and half B each
+    // rtpbr_blend_error: from its first call on (it makes what rtpbr_denoise_blend_levels makes too); freed with the halves
+    float* blend_error = nullptr;      // (W,H): RTPBR_BUF_BLEND_ERROR
+    float4* blend_x = nullptr;         // 2 x (W,H): the running XA and XB of the levels (scratch of the call)
     // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
     uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
     uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)

@@ -1,4 +1,4 @@
-// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels (see rt_half.hpp).
+// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error (see rt_half.hpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_half.hpp"
@@ -223,6 +223,11 @@ __global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
 // Traffic per staged entry: six 16-byte records (FIRST: three and the three 16-byte texels), the two count words, 4 bytes of
 // object, 12 of albedo when demodulating: 108 to 120 bytes against half_blend's 88; per pixel two records and 20 bytes of running
 // state both ways.
+// ERR (rtpbr_blend_error): the lane also carries XA and XB, its T_k applied to either half's own ladder, in two float4 planes: the
+// centre pixel's four half records are the only new loads (64 bytes, 32 of running state both ways; FIRST takes level 0 from the
+// two texels).  LAST hands blend_error<R> what it stages — (lum XA, display lum XA, lum XB, display lum XB) in the first plane —
+// and the slope s of the display luminance at the blended colour in the error plane, so the tone map runs per pixel and never per
+// staged entry.  The instances without ERR keep their code.
 RT_D vec3 lv_albedo(const LevelsArgs& A, size_t i) {
     if (!A.demodulate) return mk(1.0f, 1.0f, 1.0f);
     return mk(fmax_(A.albedo[i * 3 + 0], 1e-3f), fmax_(A.albedo[i * 3 + 1], 1e-3f), fmax_(A.albedo[i * 3 + 2], 1e-3f));
@@ -239,7 +244,20 @@ RT_D vec3 lv_average(float4 b, vec3 ac, int demod) {
     return c;
 }
 
-template <int R, bool FIRST, bool LAST>
+// s of include/rtpbr.h: the slope of the display luminance at the linear colour c, whose display colour is d
+RT_D float lv_slope(const rtpbr_config& cfg, vec3 c, vec3 d) {
+    const float Y = nz_lum(c);
+    if (!(Y > 0.0f)) return 0.0f;
+    const vec3 d1 = tone_map(cfg, make_float4(1.0625f * c.x, 1.0625f * c.y, 1.0625f * c.z, 1.0f));
+    return (nz_lum(d1) - nz_lum(d)) / (0.0625f * Y);
+}
+// what LAST leaves of XA and XB: (lum XA, display lum XA, lum XB, display lum XB)
+RT_D float4 lv_lums(const rtpbr_config& cfg, vec3 xa, vec3 xb) {
+    return make_float4(nz_lum(xa), nz_lum(tone_map(cfg, make_float4(xa.x, xa.y, xa.z, 1.0f))), nz_lum(xb),
+                       nz_lum(tone_map(cfg, make_float4(xb.x, xb.y, xb.z, 1.0f))));
+}
+
+template <int R, bool FIRST, bool LAST, bool ERR = false>
 __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
     constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
     __shared__ float t_a[HX * PITCH];
@@ -342,10 +360,43 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
         T = T * t;
         depth = depth + T;
         c = mk(c.x + T * (fk.x - f0.x), c.y + T * (fk.y - f0.y), c.z + T * (fk.z - f0.z));
+        vec3 xa, xb;
+        if constexpr (ERR) {      // the same T_k on either half's own ladder (a half without samples: its values are never read)
+            const vec3 ak = lv_record(A.ka[p], ac, A.demodulate), bk = lv_record(A.kb[p], ac, A.demodulate);
+            vec3 a0, b0;
+            if constexpr (FIRST) {
+                a0 = lv_average(A.half_a[p], ac, A.demodulate);
+                b0 = lv_average(A.half_b[p], ac, A.demodulate);
+                xa = a0;
+                xb = b0;
+            } else {
+                a0 = lv_record(A.pa[p], ac, A.demodulate);
+                b0 = lv_record(A.pb[p], ac, A.demodulate);
+                const float4 va = A.xa[p], vb = A.xb[p];
+                xa = mk(va.x, va.y, va.z);
+                xb = mk(vb.x, vb.y, vb.z);
+            }
+            xa = mk(xa.x + T * (ak.x - a0.x), xa.y + T * (ak.y - a0.y), xa.z + T * (ak.z - a0.z));
+            xb = mk(xb.x + T * (bk.x - b0.x), xb.y + T * (bk.y - b0.y), xb.z + T * (bk.z - b0.z));
+            if constexpr (LAST) {
+                if (T == 1.0f) {
+                    xa = ak;
+                    xb = bk;
+                }
+            } else {
+                A.xa[p] = make_float4(xa.x, xa.y, xa.z, 0.0f);
+                A.xb[p] = make_float4(xb.x, xb.y, xb.z, 0.0f);
+            }
+        }
         if constexpr (LAST) {
             if (T == 1.0f) c = fk;      // every t_k was 1: rtpbr_denoise's bytes
             // (no samples: what post_process shows; T = 1 and depth = K by the sums above)
+            const vec3 lin = c;
             c = b.w > 0.0f ? tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)) : tone_map(A.cfg, b);
+            if constexpr (ERR) {
+                A.xa[p] = lv_lums(A.cfg, xa, xb);
+                A.slope[p] = b.w > 0.0f ? lv_slope(A.cfg, lin, c) : 0.0f;
+            }
         }
         A.weight[p] = T;
         A.depth[p] = depth;
@@ -357,7 +408,9 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
     if constexpr (LAST) nz_stats(A.stats, 0.0f, blk, usable, 1.0f - T, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
-// K = 0 of rtpbr_denoise_blend_levels (the frame is atrous_none's): weight 1, depth 0, and the count of usable pixels
+// K = 0 of rtpbr_denoise_blend_levels (the frame is atrous_none's): weight 1, depth 0, and the count of usable pixels.  ERR: XA,
+// XB and the blended colour are level 0 of the three buffers.
+template <bool ERR = false>
 __global__ void __launch_bounds__(256) level_blend_none(const LevelsArgs A) {
     __shared__ uint32_t blk[3];
     if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
@@ -369,8 +422,100 @@ __global__ void __launch_bounds__(256) level_blend_none(const LevelsArgs A) {
         usable = A.half_a[i].w >= A.min_half && A.half_b[i].w >= A.min_half;
         A.weight[i] = 1.0f;
         A.depth[i] = 0.0f;
+        if constexpr (ERR) {
+            const vec3 ac = lv_albedo(A, i);
+            const float4 b = A.image_buffer[i];
+            A.xa[i] = lv_lums(A.cfg, lv_average(A.half_a[i], ac, A.demodulate), lv_average(A.half_b[i], ac, A.demodulate));
+            float s = 0.0f;
+            if (b.w > 0.0f) {
+                const vec3 c = lv_average(b, ac, A.demodulate);
+                s = lv_slope(A.cfg, c, tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)));
+            }
+            A.slope[i] = s;
+        }
     }
     nz_stats(A.stats, 0.0f, blk, usable, 0.0f, blockIdx.x);
+}
+
+// ---- the window kernel of rtpbr_blend_error: half_error<R>'s tile, halo, pitch and ERR_NOBODY convention with four planes (e_q,
+// x_q, usable_q, object_q), 16 bytes per entry.  An entry that is not valid or lies outside the frame holds +0 in the three and
+// ERR_NOBODY; a valid entry that is not usable holds x = +0 and usable = 0.  SX is signed, but a sum that starts at +0 never becomes
+// -0 (half_blend<R>'s argument), so adding +0 for a skipped or an unusable tap is the identity and the tap loop is the object
+// compare alone.  The centre lane reads its slope s from the error plane (level_blend's LAST ERR instance wrote it) and overwrites
+// it with the error: no other lane reads or writes that word.
+// LDS: 4 x HX x PITCH words = 13.8 / 15.4 / 16.9 KB at R = 1 / 2 / 3 (the pitch is 48 words at every radius; half_blend<R>'s
+// footprint: eight blocks of four waves still fit a CU's 160 KB), rows a loop as there.
+// Traffic per staged entry: the 16-byte texel of luminances, the two 16-byte texels of the halves (count words and, where usable,
+// the raw averages), 4 bytes of object: 52 bytes against half_error's 36 + its two filtered colours; per pixel 4 read, 4 written.
+template <int R>
+__global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
+    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
+    __shared__ float t_e[HX * PITCH];
+    __shared__ float t_x[HX * PITCH];
+    __shared__ float t_u[HX * PITCH];
+    __shared__ int t_obj[HX * PITCH];
+    __shared__ uint32_t blk[3];
+    if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
+    const int H = A.height, W = A.width;
+    const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
+    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
+        const int hx = t / HY, hy = t - hx * HY;
+        const int xq = x0 - R + hx, yq = y0 - R + hy;
+        float e = 0.0f, xx = 0.0f, u = 0.0f;
+        int oq = ERR_NOBODY;
+        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
+            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+            const float4 ha = A.half_a[q], hb = A.half_b[q];
+            const float cA = ha.w, cB = hb.w;
+            if (cA > 0.0f && cB > 0.0f) {
+                const float4 l = A.lx[q];
+                const float dl = l.y - l.w;
+                e = fmax_((dl * dl) * ((cA * cB) / ((cA + cB) * (cA + cB))), 0.0f);      // (a NaN gives 0)
+                if (cA >= A.min_half && cB >= A.min_half) {
+                    const float lPA = nz_lum(mk(ha.x / ha.w, ha.y / ha.w, ha.z / ha.w));
+                    const float lPB = nz_lum(mk(hb.x / hb.w, hb.y / hb.w, hb.z / hb.w));
+                    xx = (l.x - lPA) * (l.z - lPB);
+                    u = 1.0f;
+                }
+                oq = A.object[q];
+            }
+        }
+        t_e[hx * PITCH + hy] = e;
+        t_x[hx * PITCH + hy] = xx;
+        t_u[hx * PITCH + hy] = u;
+        t_obj[hx * PITCH + hy] = oq;
+    }
+    __syncthreads();
+    const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
+    const int x = x0 + lx, y = y0 + ly;
+    bool estimated = false;
+    float err = 0.0f;
+    if (x < W && y < H) {
+        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        const size_t p = (size_t)x * (size_t)H + (size_t)y;
+        if (op != ERR_NOBODY) {
+            estimated = true;
+            float S = 0.0f, cn = 0.0f, SX = 0.0f, nb = 0.0f;
+            // (rows stay a loop, as in half_blend<R>)
+#pragma unroll 1
+            for (int dy = -R; dy <= R; dy++) {
+#pragma unroll
+                for (int dx = -R; dx <= R; dx++) {
+                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
+                    const bool same = t_obj[q] == op;
+                    S = S + (same ? t_e[q] : 0.0f);
+                    cn = cn + (same ? 1.0f : 0.0f);
+                    SX = SX + (same ? t_x[q] : 0.0f);
+                    nb = nb + (same ? t_u[q] : 0.0f);
+                }
+            }
+            const float bias2 = nb > 0.0f ? fmax_(SX / nb, 0.0f) : 0.0f;      // (a NaN gives 0)
+            const float s = A.error[p];
+            err = sqrt_ieee_(S / cn + (s * s) * bias2);
+        }
+        A.error[p] = err;
+    }
+    nz_stats(A.stats, A.threshold, blk, estimated, err, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 static unsigned grid_of(int w, int h) { return (unsigned)(((size_t)w * h + 255) / 256); }
@@ -397,24 +542,38 @@ void launch_half_blend(const BlendArgs& A, hipStream_t st) {      // (rt_capi.hi
     else hipLaunchKernelGGL(half_blend<3>, grid, dim3(256), 0, st, A);
 }
 
-template <int R>
+template <int R, bool ERR>
 static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, dim3 grid, hipStream_t st) {
-    if (first && last) hipLaunchKernelGGL((level_blend<R, true, true>), grid, dim3(256), 0, st, A);
-    else if (first) hipLaunchKernelGGL((level_blend<R, true, false>), grid, dim3(256), 0, st, A);
-    else if (last) hipLaunchKernelGGL((level_blend<R, false, true>), grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((level_blend<R, false, false>), grid, dim3(256), 0, st, A);
+    if (first && last) hipLaunchKernelGGL((level_blend<R, true, true, ERR>), grid, dim3(256), 0, st, A);
+    else if (first) hipLaunchKernelGGL((level_blend<R, true, false, ERR>), grid, dim3(256), 0, st, A);
+    else if (last) hipLaunchKernelGGL((level_blend<R, false, true, ERR>), grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((level_blend<R, false, false, ERR>), grid, dim3(256), 0, st, A);
 }
 
 // no level (first && last && no records): the K = 0 pass
 void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
     if (!A.kd) {
-        hipLaunchKernelGGL(level_blend_none, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
+        if (A.xa) hipLaunchKernelGGL(level_blend_none<true>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL(level_blend_none<false>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         return;
     }
     const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
-    if (A.radius == 1) launch_level_blend_r<1>(A, first, last, grid, st);
-    else if (A.radius == 2) launch_level_blend_r<2>(A, first, last, grid, st);
-    else launch_level_blend_r<3>(A, first, last, grid, st);
+    if (A.xa) {      // rtpbr_blend_error
+        if (A.radius == 1) launch_level_blend_r<1, true>(A, first, last, grid, st);
+        else if (A.radius == 2) launch_level_blend_r<2, true>(A, first, last, grid, st);
+        else launch_level_blend_r<3, true>(A, first, last, grid, st);
+        return;
+    }
+    if (A.radius == 1) launch_level_blend_r<1, false>(A, first, last, grid, st);
+    else if (A.radius == 2) launch_level_blend_r<2, false>(A, first, last, grid, st);
+    else launch_level_blend_r<3, false>(A, first, last, grid, st);
+}
+
+void launch_blend_error(const BlendErrorArgs& A, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
+    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
+    if (A.radius == 1) hipLaunchKernelGGL(blend_error<1>, grid, dim3(256), 0, st, A);
+    else if (A.radius == 2) hipLaunchKernelGGL(blend_error<2>, grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(blend_error<3>, grid, dim3(256), 0, st, A);
 }
 
 }  // namespace rt

@@ -1,6 +1,6 @@
 // rt_half.hpp — the two-half error estimate of the denoised frame (rtpbr_half_update, rtpbr_denoise_error), the bias-aware
-// blend of the denoised and the raw frame made from the same halves (rtpbr_denoise_blend) and the same blend across the a-trous
-// levels (rtpbr_denoise_blend_levels).
+// blend of the denoised and the raw frame made from the same halves (rtpbr_denoise_blend), the same blend across the a-trous
+// levels (rtpbr_denoise_blend_levels) and the error estimate of that level-blended frame (rtpbr_blend_error).
 //
 // The samples of image_buffer are kept in two independent halves: A is stored (RTPBR_BUF_HALF_BUFFER), B = image_buffer - A is
 // not.  rtpbr_denoise's filter runs on each half (the existing atrous_level / atrous_none instances, rt_features.hip); the
@@ -29,8 +29,19 @@
 //                       product T_k = T_{k-1} t_k, the depth sum of T_k and the colour c = c + T_k (FD_k - FD_{k-1}) in place
 //                       (RTPBR_BUF_BLEND_WEIGHT, RTPBR_BUF_BLEND_DEPTH, RTPBR_BUF_DENOISED_PIXELS); LAST tone-maps and makes the
 //                       statistics.  level_blend_none: K = 0.
+//   level_blend<.., ERR> rtpbr_blend_error's instances of the same kernel: the lane also applies its T_k to either half's own ladder
+//                       (XA, XB: two more float4 planes of running state, the centre pixel's four half records the only new
+//                       loads: 64 bytes read and 32 read and written per pixel and level, where a kernel of its own per level
+//                       would read T_k and the records again and launch K more times).  LAST leaves in the first plane what the
+//                       window kernel stages — (lum XA, display lum XA, lum XB, display lum XB) — and in the error plane the
+//                       slope s of the display luminance at the blended colour: the tone map runs four times per pixel here and
+//                       never per staged entry.
+//   blend_error<R>      rtpbr_blend_error's window kernel, in half_error<R>'s layout with four planes (e_q, x_q, usable_q, object):
+//                       e_q is half_error's with the blended halves' display luminances, x_q the product of the halves' (blended -
+//                       raw) in linear luminance; the lane sums both over the window on its object and writes the root of
+//                       variance + s^2 bias^2 into RTPBR_BUF_BLEND_ERROR; statistics through nz_stats.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that the CPU restatement matches bit for bit
-// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c, tests/levels_ref/levels_ref.c).
+// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c, tests/levels_ref/levels_ref.c, tests/blend_error_ref/blend_error_ref.c).
 #pragma once
 #include "rt_noise.hpp"
 
@@ -92,6 +103,9 @@ struct LevelsArgs {
     float* depth;                 // in / out: the running sum of T_k; RTPBR_BUF_BLEND_DEPTH
     float* out;                   // in / out: the running linear colour; LAST: RTPBR_BUF_DENOISED_PIXELS
     NoiseStats* stats;            // out (zeroed before the launches; LAST adds to it)
+    float4* xa;                   // ERR instances, in / out: the running XA; after LAST (lum XA, display lum XA, lum XB, display lum XB)
+    float4* xb;                   // ... the running XB
+    float* slope;                 // ERR instances, LAST: out, s (the plane of RTPBR_BUF_BLEND_ERROR, which blend_error<R> then overwrites)
     float min_half;               // (float)min_half_samples
     float z2;                     // z * z
     int32_t demodulate;
@@ -99,8 +113,22 @@ struct LevelsArgs {
     int32_t radius;               // 1..3
 };
 
+struct BlendErrorArgs {
+    const float4* lx;             // (W,H): (lum XA, display lum XA, lum XB, display lum XB) as level_blend's LAST ERR instance left it
+    const float4* half_a;         // A: the count word cA, PA
+    const float4* half_b;         // B as half_subtract wrote it
+    const int32_t* object;        // RTPBR_BUF_FEAT_OBJECT
+    float* error;                 // in: s per pixel; out: RTPBR_BUF_BLEND_ERROR
+    NoiseStats* stats;            // out (zeroed before the launch)
+    float threshold;
+    float min_half;               // (float)min_half_samples
+    int32_t width, height;
+    int32_t radius;               // 1..3
+};
+
 void launch_half_update(const HalfArgs& A, hipStream_t st);
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st);
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st);      // A.xa != nullptr: the ERR instances
+void launch_blend_error(const BlendErrorArgs& A, hipStream_t st);
 void launch_half_blend(const BlendArgs& A, hipStream_t st);
 void launch_half_subtract(const HalfArgs& A, hipStream_t st);
 void launch_half_error(const ErrorArgs& A, hipStream_t st);

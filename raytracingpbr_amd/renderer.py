@@ -34,6 +34,8 @@ BUF_HALF_BUFFER, BUF_DENOISED_ERROR = 15, 16
 BUF_BLEND_WEIGHT = 17
 # how many a-trous levels the last denoise_blend_levels() kept, 0..iterations; exists from the first denoise_blend_levels() on
 BUF_BLEND_DEPTH = 18
+# the estimated root-mean-square error of the level-blended frame's luminance (blend_error); exists from the first blend_error() on
+BUF_BLEND_ERROR = 19
 ENV_RGB8, ENV_RGB32F = 0, 1
 
 
@@ -460,8 +462,40 @@ class Renderer:
         self.api.call("denoise_blend_levels", self._ctx, p, e, C.byref(s))
         return s
 
+    def blend_error(self, threshold: float = 0.0, radius=None, z=None, min_half_samples=None, window=None, iterations=None,
+                    demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
+        """denoise_blend_levels (same parameters, same ``denoised_pixels``, ``blend_weight`` and ``blend_depth``) and besides
+        ``blend_error_map``: the estimated root-mean-square error of the luminance of the frame it shows.  The levels' weights
+        are applied to each half's own ladder; the difference of the two blended halves gives the variance, the product of their
+        (blended - raw) the squared bias the halves can see, both averaged over the (2 ``window`` + 1)^2 window on each pixel's
+        object (``window`` = denoise_error's radius).  Returns how many pixels have samples in both halves, how many of them are
+        above ``threshold``, and the largest value.  Blocks.  ``None`` = the library's default for that parameter."""
+        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
+                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
+        p = None
+        if any(v is not None for v in given.values()):
+            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
+            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
+        e = None
+        if radius is not None or z is not None or min_half_samples is not None:
+            d = BlendParams.DEFAULTS
+            e = C.byref(BlendParams(int(d["radius"] if radius is None else radius), float(d["z"] if z is None else z),
+                                    int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
+        w = None if window is None else C.byref(ErrorParams(int(window)))
+        s = NoiseStats()
+        self.api.call("blend_error", self._ctx, p, e, w, float(threshold), C.byref(s))
+        return s
+
+    def select_blend_error(self, threshold: float, dilate: int = 0) -> int:
+        """select_error's rule on ``blend_error_map`` as the last blend_error() wrote it (not recomputed).  Returns how many
+        pixels are selected.  Blocks."""
+        n = C.c_uint32()
+        self.api.call("select_blend_error", self._ctx, float(threshold), int(dilate), C.byref(n))
+        return int(n.value)
+
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
-                                 blend=False, **denoise_params):
+                                 blend=False, *, stop="filter", **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -472,9 +506,16 @@ class Renderer:
         ``per_sample``: with set_half_mode(per_sample=True) for the duration of the call (``warp`` as it is; restored after):
         every batch is split evenly over the halves by the sample calls themselves and the loop makes no half_update().
         ``blend``: True: the loop ends with denoise_blend() (its defaults) instead of denoise(); "levels": with
-        denoise_blend_levels(); the stop rule is unchanged."""
+        denoise_blend_levels(); the stop rule is unchanged.
+        ``stop``: "filter" (the default) is the rule above.  "blend" (with ``blend="levels"`` only) loops on blend_error(error)
+        -> select_blend_error(error, dilate) instead: the estimate is the error of the level-blended frame, variance and the
+        bias the halves can see, and the call ends with the frame the last blend_error() wrote."""
         if isinstance(blend, str) and blend != "levels":
             raise ValueError('blend must be True, False or "levels"')
+        if stop not in ("filter", "blend"):
+            raise ValueError('stop must be "filter" or "blend"')
+        if stop == "blend" and blend != "levels":
+            raise ValueError('stop="blend" estimates the level-blended frame: blend must be "levels"')
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
@@ -495,15 +536,17 @@ class Renderer:
                     self.half_update()
                 traced, used = traced + n_pix * n, used + n
             while True:
-                stats = self.denoise_error(error, **denoise_params)
+                stats = self.blend_error(error, **denoise_params) if stop == "blend" else self.denoise_error(error, **denoise_params)
                 if stats.pixels_above == 0 or used + batch > budget:
                     break
-                n_sel = self.select_error(error, dilate)
+                n_sel = self.select_blend_error(error, dilate) if stop == "blend" else self.select_error(error, dilate)
                 self.sample_selected(batch)
                 if not per_sample:
                     self.half_update()
                 traced, used = traced + n_sel * batch, used + batch
-            if blend == "levels":
+            if stop == "blend":
+                pass      # (the last blend_error() wrote the frame of the whole buffer)
+            elif blend == "levels":
                 self.denoise_blend_levels(**denoise_params)
             elif blend:
                 self.denoise_blend(**denoise_params)
@@ -552,7 +595,8 @@ class Renderer:
                 BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
                 BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8),
                 BUF_HALF_BUFFER: ((W, H, 4), np.float32), BUF_DENOISED_ERROR: ((W, H), np.float32),
-                BUF_BLEND_WEIGHT: ((W, H), np.float32), BUF_BLEND_DEPTH: ((W, H), np.float32)}[which]
+                BUF_BLEND_WEIGHT: ((W, H), np.float32), BUF_BLEND_DEPTH: ((W, H), np.float32),
+                BUF_BLEND_ERROR: ((W, H), np.float32)}[which]
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -720,6 +764,11 @@ class Renderer:
     def blend_depth(self):
         """(W,H): how many a-trous levels the last denoise_blend_levels() kept, 0 (the raw average) .. iterations (the whole filter)"""
         return self._read(BUF_BLEND_DEPTH)
+
+    @property
+    def blend_error_map(self):
+        """(W,H): the last blend_error()'s root-mean-square error of each pixel's level-blended luminance, 0 where a half is empty"""
+        return self._read(BUF_BLEND_ERROR)
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

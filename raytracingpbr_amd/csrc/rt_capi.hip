@@ -1566,6 +1566,21 @@ static int denoised_alloc(rtpbr_ctx* c, int iterations) {
     return rt_order_after_reads(c, W_DENOISED);
 }
 
+// what every a-trous launch of a call shares; the level's buffers, step and colour weight are the caller's
+static DenoiseArgs denoise_args(rtpbr_ctx* c, int demodulate, const float* inv) {
+    DenoiseArgs A{};
+    A.cfg = c->cfg;
+    A.guide_nz = c->feat_guides;
+    A.albedo = c->feat_albedo;
+    A.object = c->feat_object;
+    A.in = inv[1];
+    A.iz = inv[2];
+    A.demodulate = demodulate;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    return A;
+}
+
 // The levels of either filter, after every refusal: level k reads half (k - 1) & 1 of denoise_scratch and writes half k & 1; the
 // first reads image_buffer, the last writes denoised.  g != nullptr: the guided kernel, whose variance goes the same way through
 // the two planes of noise_var behind the estimate's (plane 0).  No level: the tone-map-only pass, the same for both.
@@ -1577,18 +1592,9 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
     if (!out)
         if (int r = denoised_alloc(c, iterations)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    DenoiseArgs A{};
-    A.cfg = c->cfg;
+    DenoiseArgs A = denoise_args(c, demodulate, inv);
     A.image_buffer = in ? in : c->image_buffer;
-    A.guide_nz = c->feat_guides;
-    A.albedo = c->feat_albedo;
-    A.object = c->feat_object;
     A.out = out ? out : c->denoised;
-    A.in = inv[1];
-    A.iz = inv[2];
-    A.demodulate = demodulate;
-    A.width = c->cfg.width;
-    A.height = c->cfg.height;
     if (g) {
         A.var0 = c->noise_var;
         A.sc2 = g->sigma_color * g->sigma_color;
@@ -1831,6 +1837,13 @@ extern "C" int rtpbr_set_noise_tracking(rtpbr_ctx* c, int mode) {
     return RTPBR_OK;
 }
 
+// the statistics' shards, zeroed on the stream for the kernel that is enqueued next (noise_stats_read brings them back)
+static int noise_stats_zero(rtpbr_ctx* c) {
+    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
+    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    return RTPBR_OK;
+}
+
 // the estimate pass on the stream (no read-back): RTPBR_BUF_NOISE, the guided filter's level-0 variance and the statistics
 static int noise_estimate_enqueue(rtpbr_ctx* c, float threshold) {
     if (!c->feat_valid)
@@ -1841,9 +1854,8 @@ static int noise_estimate_enqueue(rtpbr_ctx* c, float threshold) {
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     if (!c->noise_map) HIP_TRY(hipMalloc(&c->noise_map, n * sizeof(float)));
     if (!c->noise_var) HIP_TRY(hipMalloc(&c->noise_var, 3 * n * sizeof(float)));
-    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
     if (int r = rt_order_after_reads(c, W_NOISE)) return r;
-    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    if (int r = noise_stats_zero(c)) return r;
     NoiseArgs A{};
     A.image_buffer = c->image_buffer;
     A.moments = c->noise_moments;
@@ -2071,6 +2083,38 @@ extern "C" int rtpbr_set_half_mode(rtpbr_ctx* c, const rtpbr_half_mode* m) {
     return RTPBR_OK;
 }
 
+// What rtpbr_denoise_error and the blend calls do between their parameter checks and their allocations: the states they refuse
+// (no_half: the call's "no half buffer yet" message, `who` fills its %s), the device, the pending shade
+static int half_call_begin(rtpbr_ctx* c, const char* no_half, const char* who) {
+    if (int r = whole_frame_state(c, HALF_TILES)) return r;
+    if (!c->half_a) return fail(RTPBR_ESTATE, no_half, who);
+    if (int r = set_dev(c)) return r;
+    return flush_shade(c);
+}
+
+// B = image_buffer - A into its own buffer, enqueued here
+static int half_b_enqueue(rtpbr_ctx* c) {
+    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, (size_t)c->cfg.width * c->cfg.height * sizeof(float4)));
+    HalfArgs S{};
+    S.image_buffer = c->image_buffer;
+    S.half_a = c->half_a;
+    S.half_b = c->half_b;
+    S.width = c->cfg.width;
+    S.height = c->cfg.height;
+    launch_half_subtract(S, c->stream);
+    return RTPBR_OK;
+}
+
+// e (NULL: the defaults) -> b, after the parameter checks of the blend calls
+static int blend_params(const rtpbr_blend_params* e, const char* who, rtpbr_blend_params& b) {
+    b = rtpbr_blend_params{RTPBR_BLEND_DEFAULT_RADIUS, RTPBR_BLEND_DEFAULT_Z, RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES};
+    if (e) b = *e;
+    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "%s: radius must be 1..3", who);
+    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "%s: z must be finite and >= 0", who);
+    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "%s: min_half_samples must be 1..16777216", who);
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_error_params* e, float threshold,
                                    rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
@@ -2080,31 +2124,20 @@ extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     const int radius = e ? e->radius : RTPBR_ERROR_DEFAULT_RADIUS;
     if (radius < 1 || radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_error: radius must be 1..3");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
-    if (int r = whole_frame_state(c, HALF_TILES)) return r;
-    if (!c->half_a) return fail(RTPBR_ESTATE, "rtpbr_denoise_error: no half buffer yet (rtpbr_half_update first)");
-    if (int r = set_dev(c)) return r;
-    if (int r = flush_shade(c)) return r;
+    if (int r = half_call_begin(c, "%s: no half buffer yet (rtpbr_half_update first)", "rtpbr_denoise_error")) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, n * sizeof(float4)));
     if (!c->half_da) HIP_TRY(hipMalloc(&c->half_da, n * 3 * sizeof(float)));
     if (!c->half_db) HIP_TRY(hipMalloc(&c->half_db, n * 3 * sizeof(float)));
     if (!c->denoised_error) HIP_TRY(hipMalloc(&c->denoised_error, n * sizeof(float)));
-    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
     if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
     if (int r = rt_order_after_reads(c, W_ERROR)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
-    HalfArgs S{};
-    S.image_buffer = c->image_buffer;
-    S.half_a = c->half_a;
-    S.half_b = c->half_b;
-    S.width = c->cfg.width;
-    S.height = c->cfg.height;
-    launch_half_subtract(S, c->stream);
+    if (int r = half_b_enqueue(c)) return r;
     // the same filter on either half: "has samples" is the half's own count
     if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_a, c->half_da)) return r;
     if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_b, c->half_db)) return r;
-    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    if (int r = noise_stats_zero(c)) return r;
     ErrorArgs A{};
     A.da = c->half_da;
     A.db = c->half_db;
@@ -2123,43 +2156,31 @@ extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
 }
 
 // ---- the bias-aware blend of the denoised and the raw frame (half_blend<R>, rt_half.hip)
+static const char* const BLEND_NO_HALF = "%s: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)";
+
 extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     rtpbr_denoise_params d;
     float inv[4];
     if (int r = denoise_params(p, d, inv)) return r;
-    rtpbr_blend_params b{RTPBR_BLEND_DEFAULT_RADIUS, RTPBR_BLEND_DEFAULT_Z, RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES};
-    if (e) b = *e;
-    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend: radius must be 1..3");
-    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend: z must be finite and >= 0");
-    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "rtpbr_denoise_blend: min_half_samples must be 1..16777216");
-    if (int r = whole_frame_state(c, HALF_TILES)) return r;
-    if (!c->half_a) return fail(RTPBR_ESTATE, "rtpbr_denoise_blend: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)");
-    if (int r = set_dev(c)) return r;
-    if (int r = flush_shade(c)) return r;
+    rtpbr_blend_params b;
+    if (int r = blend_params(e, "rtpbr_denoise_blend", b)) return r;
+    if (int r = half_call_begin(c, BLEND_NO_HALF, "rtpbr_denoise_blend")) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, n * sizeof(float4)));
     if (!c->half_da) HIP_TRY(hipMalloc(&c->half_da, n * 3 * sizeof(float)));
     if (!c->half_db) HIP_TRY(hipMalloc(&c->half_db, n * 3 * sizeof(float)));
     if (!c->half_fd) HIP_TRY(hipMalloc(&c->half_fd, n * 3 * sizeof(float)));
     if (!c->blend_weight) HIP_TRY(hipMalloc(&c->blend_weight, n * sizeof(float)));
-    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
     if (int r = denoised_alloc(c, d.iterations)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
     if (int r = rt_order_after_reads(c, W_BLEND)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
-    HalfArgs S{};
-    S.image_buffer = c->image_buffer;
-    S.half_a = c->half_a;
-    S.half_b = c->half_b;
-    S.width = c->cfg.width;
-    S.height = c->cfg.height;
-    launch_half_subtract(S, c->stream);
+    if (int r = half_b_enqueue(c)) return r;
     // three runs of the same filter, each stopping before the tone map
     if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->half_fd, true)) return r;
     if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_a, c->half_da, true)) return r;
     if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_b, c->half_db, true)) return r;
-    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    if (int r = noise_stats_zero(c)) return r;
     BlendArgs A{};
     A.cfg = c->cfg;
     A.image_buffer = c->image_buffer;
@@ -2190,41 +2211,27 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     rtpbr_denoise_params d;
     float inv[4];
     if (int r = denoise_params(p, d, inv)) return r;
-    rtpbr_blend_params b{RTPBR_BLEND_DEFAULT_RADIUS, RTPBR_BLEND_DEFAULT_Z, RTPBR_BLEND_DEFAULT_MIN_HALF_SAMPLES};
-    if (e) b = *e;
-    if (b.radius < 1 || b.radius > 3) return fail(RTPBR_EINVAL, "%s: radius must be 1..3", who);
-    if (!(b.z >= 0.0f) || !std::isfinite(b.z)) return fail(RTPBR_EINVAL, "%s: z must be finite and >= 0", who);
-    if (b.min_half_samples < 1 || b.min_half_samples > 16777216) return fail(RTPBR_EINVAL, "%s: min_half_samples must be 1..16777216", who);
+    rtpbr_blend_params b;
+    if (int r = blend_params(e, who, b)) return r;
     const int window = w ? w->radius : RTPBR_ERROR_DEFAULT_RADIUS;
     if (with_error) {
         if (window < 1 || window > 3) return fail(RTPBR_EINVAL, "%s: the window's radius must be 1..3", who);
         if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
     }
-    if (int r = whole_frame_state(c, HALF_TILES)) return r;
-    if (!c->half_a) return fail(RTPBR_ESTATE, "%s: no half buffer yet (rtpbr_half_update or a dealing rtpbr_sample first)", who);
-    if (int r = set_dev(c)) return r;
-    if (int r = flush_shade(c)) return r;
+    if (int r = half_call_begin(c, BLEND_NO_HALF, who)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     const int K = d.iterations;
-    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, n * sizeof(float4)));
     if (!c->blend_weight) HIP_TRY(hipMalloc(&c->blend_weight, n * sizeof(float)));
     if (!c->blend_depth) HIP_TRY(hipMalloc(&c->blend_depth, n * sizeof(float)));
     if (!c->levels_scratch) HIP_TRY(hipMalloc(&c->levels_scratch, 6 * n * sizeof(float4)));
-    if (!c->noise_stats) HIP_TRY(hipMalloc(&c->noise_stats, NOISE_SHARDS * sizeof(NoiseStats)));
     if (with_error && !c->blend_error) HIP_TRY(hipMalloc(&c->blend_error, n * sizeof(float)));
     if (with_error && !c->blend_x) HIP_TRY(hipMalloc(&c->blend_x, 2 * n * sizeof(float4)));
     if (int r = denoised_alloc(c, 0)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
     if (int r = rt_order_after_reads(c, W_BLEND | W_DEPTH | (with_error ? W_BLEND_ERROR : 0u))) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
-    HalfArgs S{};
-    S.image_buffer = c->image_buffer;
-    S.half_a = c->half_a;
-    S.half_b = c->half_b;
-    S.width = c->cfg.width;
-    S.height = c->cfg.height;
-    launch_half_subtract(S, c->stream);
-    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    if (int r = half_b_enqueue(c)) return r;
+    if (int r = noise_stats_zero(c)) return r;
     LevelsArgs A{};
     if (with_error) {      // the ERR instances: XA and XB beside the frame, the slope into the error plane
         A.xa = c->blend_x;
@@ -2253,16 +2260,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     }
     // the K levels of the three chains in lock step through the non-last instances: chain j keeps level k in plane 2 j + (k & 1),
     // so level k - 1 is still there when the window kernel compares the two
-    DenoiseArgs F{};
-    F.cfg = c->cfg;
-    F.guide_nz = c->feat_guides;
-    F.albedo = c->feat_albedo;
-    F.object = c->feat_object;
-    F.in = inv[1];
-    F.iz = inv[2];
-    F.demodulate = d.demodulate;
-    F.width = c->cfg.width;
-    F.height = c->cfg.height;
+    DenoiseArgs F = denoise_args(c, d.demodulate, inv);
     const float4* const chain_in[3] = {c->image_buffer, c->half_a, c->half_b};
     for (int k = 0; k < K; k++) {      // k + 1 is the level's number in include/rtpbr.h
         const bool first = k == 0, last = k + 1 == K;
@@ -2289,7 +2287,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     HIP_TRY(hipGetLastError());
     if (!with_error) return noise_stats_read(c, out);
     // the statistics are the error plane's: the blend's own are not handed out by this call
-    HIP_TRY(hipMemsetAsync(c->noise_stats, 0, NOISE_SHARDS * sizeof(NoiseStats), c->stream));
+    if (int r = noise_stats_zero(c)) return r;
     BlendErrorArgs E{};
     E.lx = c->blend_x;
     E.half_a = c->half_a;
@@ -2316,19 +2314,22 @@ extern "C" int rtpbr_blend_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, co
     return blend_levels(c, "rtpbr_blend_error", p, e, w, true, threshold, out);
 }
 
-extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
+// The selection by an error estimate: `plane` is the estimate's, `who` the call (it fills the %s of its messages), no_estimate
+// what it says while the plane has not been made
+static int select_by_error(rtpbr_ctx* c, float* rtpbr_ctx::*plane, const char* who, const char* no_estimate, float threshold, int dilate,
+                           uint32_t* n_selected) {
     if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
-    if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_error: dilate must be 0..3");
+    if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "%s: dilate must be 0..3", who);
     if (int r = whole_frame_state(c, HALF_TILES)) return r;
-    if (!c->denoised_error || !c->half_a) return fail(RTPBR_ESTATE, "rtpbr_select_error: no error estimate yet (rtpbr_denoise_error first)");
+    if (!(c->*plane) || !c->half_a) return fail(RTPBR_ESTATE, no_estimate, who);
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
     if (int r = selection_alloc(c)) return r;
     if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
     SelectArgs A{};
     A.image_buffer = c->image_buffer;
-    A.noise = c->denoised_error;
+    A.noise = c->*plane;
     A.half_a = c->half_a;
     A.threshold = threshold;
     A.dilate = dilate;
@@ -2336,25 +2337,15 @@ extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uin
     return selection_build(c, A, SELECT_ERROR, n_selected);
 }
 
+extern "C" int rtpbr_select_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
+    return select_by_error(c, &rtpbr_ctx::denoised_error, "rtpbr_select_error", "%s: no error estimate yet (rtpbr_denoise_error first)", threshold,
+                           dilate, n_selected);
+}
+
 // rtpbr_select_error's rule and kernels on RTPBR_BUF_BLEND_ERROR
 extern "C" int rtpbr_select_blend_error(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
-    if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
-    if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
-    if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_blend_error: dilate must be 0..3");
-    if (int r = whole_frame_state(c, HALF_TILES)) return r;
-    if (!c->blend_error || !c->half_a) return fail(RTPBR_ESTATE, "rtpbr_select_blend_error: no error estimate yet (rtpbr_blend_error first)");
-    if (int r = set_dev(c)) return r;
-    if (int r = flush_shade(c)) return r;
-    if (int r = selection_alloc(c)) return r;
-    if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
-    SelectArgs A{};
-    A.image_buffer = c->image_buffer;
-    A.noise = c->blend_error;
-    A.half_a = c->half_a;
-    A.threshold = threshold;
-    A.dilate = dilate;
-    A.min_samples = (float)c->noise_estimator.min_samples;
-    return selection_build(c, A, SELECT_ERROR, n_selected);
+    return select_by_error(c, &rtpbr_ctx::blend_error, "rtpbr_select_blend_error", "%s: no error estimate yet (rtpbr_blend_error first)", threshold,
+                           dilate, n_selected);
 }
 
 // ---- the present stage (rt_present.hip): a display buffer -> the packed 8-bit top-down frame, on the device

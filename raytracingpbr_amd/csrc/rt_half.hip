@@ -37,14 +37,14 @@ __global__ void __launch_bounds__(256) half_subtract(const HalfArgs A) {
     A.half_b[i] = make_float4(b.x - a.x, b.y - a.y, b.z - a.z, b.w - a.w);
 }
 
-// ---- the window kernel.  A block owns a tile of ERR_TX x ERR_TY pixels (x by y, y contiguous; thread t: ly = t % ERR_TY, so a
-// wave runs along y) and stages (e_q, object_q) of the tile and an R-pixel halo into LDS once: 8 bytes per entry in two planes of
-// one pitch.  An entry that is not valid (a half without samples) or lies outside the frame holds e = +0 and an object word no
-// pixel has (ERR_NOBODY; first hits are >= -1): the object compare of the tap loop is then the whole test, the loop has one fixed
-// trip count per radius, and adding +0 to a non-negative sum is the identity.  The tile is noise_estimate_pooled<R>'s (16 x 16:
-// the shape measured best there) and so is the planes' pitch.
-// Traffic per staged entry: 24 bytes of the two filtered colours, the two count words of 16-byte texels, 4 bytes of object;
-// entries per pixel: (TX + 2R)(TY + 2R) / (TX TY) = 1.27 / 1.56 / 1.89.
+// ---- the window kernels' shared pieces.  A block owns a tile of ERR_TX x ERR_TY pixels (x by y, y contiguous; thread t: ly = t %
+// ERR_TY, so a wave runs along y) and stages what it sums of the tile and an R-pixel halo into LDS once: 4-byte planes of one pitch,
+// the last of them the entry's object word.  An entry that is not valid (what "valid" asks is the kernel's) or lies outside the
+// frame holds +0 in every value plane and an object word no pixel has (ERR_NOBODY; first hits are >= -1): the object compare of
+// the tap loop is then the whole test, the loop has one fixed trip count per radius, and adding +0 for a skipped tap is the
+// identity: to a non-negative sum, and to a signed one as well, since a sum that starts at +0 never becomes -0 (x + (-x) = +0 in
+// round-to-nearest, +0 + -0 = +0).  The tile is noise_estimate_pooled<R>'s (16 x 16: the shape measured best there, DESIGN.md
+// section 6f) and so is the planes' pitch.  Entries per pixel: (TX + 2R)(TY + 2R) / (TX TY) = 1.27 / 1.56 / 1.89.
 constexpr int ERR_TX = 16, ERR_TY = 16;
 constexpr int ERR_NOBODY = (int)0x80000000;
 // the pitch in words: the four column runs a wave reads at once start 16 banks apart (ds_read_b32 serves two runs per group of 32 lanes over 32 banks)
@@ -53,55 +53,129 @@ constexpr int err_pitch(int hy) {
     while (p % 32 != 16) p++;
     return p;
 }
+template <int R>
+struct Win {
+    static constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY), WORDS = HX * PITCH;      // (WORDS: one plane)
+};
 
+// staging: entry(slot, at) for every entry of the block's tile and halo, hy fastest (contiguous in memory); slot is the entry's
+// word in a plane, at() its pixel index where at.inside() says that it lies in the frame (computed there, not per entry)
+struct WinPixel {
+    int xq, yq, W, H;
+    RT_D bool inside() const { return xq >= 0 && xq < W && yq >= 0 && yq < H; }
+    RT_D size_t operator()() const { return (size_t)xq * (size_t)H + (size_t)yq; }
+};
+template <int R, class F>
+RT_D void win_for_each_entry(int x0, int y0, int W, int H, F entry) {
+    constexpr int HY = Win<R>::HY;
+    for (int t = (int)threadIdx.x; t < Win<R>::HX * HY; t += 256) {
+        const int hx = t / HY, hy = t - hx * HY;
+        const int xq = x0 - R + hx, yq = y0 - R + hy;
+        entry(hx * Win<R>::PITCH + hy, WinPixel{xq, yq, W, H});
+    }
+}
+
+// the lane's own entry, and tap(q, same) over its (2R+1)^2 window: same = the tap lies on the centre's object op.  ROWS_UNROLLED is
+// the kernel's choice: with the rows a loop only one row's LDS reads are in flight
+template <int R>
+RT_D int win_centre(int lx, int ly) { return (lx + R) * Win<R>::PITCH + (ly + R); }
+template <int R, bool ROWS_UNROLLED, class F>
+RT_D void win_for_each_tap(int lx, int ly, const int* t_obj, int op, F tap) {
+    constexpr int ROWS = ROWS_UNROLLED ? 2 * R + 1 : 1;
+#pragma unroll ROWS
+    for (int dy = -R; dy <= R; dy++) {
+#pragma unroll
+        for (int dx = -R; dx <= R; dx++) {
+            const int q = (lx + R + dx) * Win<R>::PITCH + (ly + R + dy);
+            tap(q, t_obj[q] == op);
+        }
+    }
+}
+
+// f of include/rtpbr.h, and e_q of half_error<R> and blend_error<R> from the two halves' luminance difference dl
+RT_D float win_f(float cA, float cB) { return (cA * cB) / ((cA + cB) * (cA + cB)); }
+RT_D float win_e(float dl, float cA, float cB) { return fmax_((dl * dl) * win_f(cA, cB), 0.0f); }      // (a NaN gives 0)
+
+// The blend rule of half_blend<R> and level_blend.  An entry's three values from the luminances of the finer (l.0: the raw
+// average, or level k - 1) and the coarser (l.k: the filter result, or level k) frame of either half and of the full frame: the
+// regression's cross term a_q, q_q = (coarser - finer)^2 and x_q, the product of the halves' (coarser - finer), whose expectation
+// is bias^2.
+RT_D void blend_stage(float f, float lA0, float lB0, float lD0, float lAk, float lBk, float lDk, float& aq, float& qq, float& xx) {
+    const float dA = lAk - lA0;
+    const float dB = lBk - lB0;
+    const float dp = lA0 - lB0;
+    const float dd = dA - dB;
+    const float dl = lDk - lD0;
+    aq = (f * dp) * dd;
+    qq = dl * dl;
+    xx = dA * dB;
+}
+// ... and the weight t of the lane whose object is op, from the sums over its window.  (Rows stay a loop: with all (2R+1)^2 x 4
+// LDS reads hoisted half_blend takes 103 / 199 VGPRs at R = 2 / 3 and runs at four / two waves per SIMD; a row at a time it takes
+// 48 at every radius.)
+template <int R>
+RT_D float blend_weight(int lx, int ly, const float* t_a, const float* t_q, const float* t_x, const int* t_obj, int op, float z2) {
+    float n = 0.0f, SC = 0.0f, SQ = 0.0f, SX = 0.0f, SXX = 0.0f;
+    win_for_each_tap<R, false>(lx, ly, t_obj, op, [&](int q, bool same) {
+        const float xq = same ? t_x[q] : 0.0f;
+        n = n + (same ? 1.0f : 0.0f);
+        SC = SC + (same ? t_a[q] : 0.0f);
+        SQ = SQ + (same ? t_q[q] : 0.0f);
+        SX = SX + xq;
+        SXX = SXX + xq * xq;
+    });
+    float t = 1.0f;
+    const float m1 = SX / n;
+    const float v = fmax_(SXX / n - m1 * m1, 0.0f);
+    if (m1 > 0.0f && (m1 * m1) * n > z2 * v) {
+        t = -SC / SQ;
+        if (!(t < 1.0f)) t = 1.0f;      // (a NaN gives 1)
+        if (t < 0.0f) t = 0.0f;
+    }
+    return t;
+}
+
+// ---- the error kernel: two planes (e_q, object_q), 8 bytes per entry; valid = both halves have samples.  Both tap loops are
+// unrolled (102 VGPRs and four waves per SIMD at R = 3).
+// Traffic per staged entry: 24 bytes of the two filtered colours, the two count words of 16-byte texels, 4 bytes of object.
 template <int R>
 __global__ void __launch_bounds__(256) half_error(const ErrorArgs A) {
-    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
-    __shared__ float t_e[HX * PITCH];
-    __shared__ int t_obj[HX * PITCH];
+    __shared__ float t_e[Win<R>::WORDS];
+    __shared__ int t_obj[Win<R>::WORDS];
     __shared__ uint32_t blk[3];
     if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
     const int H = A.height, W = A.width;
     const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
-    // the tile and its halo, hy fastest (contiguous in memory)
-    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
-        const int hx = t / HY, hy = t - hx * HY;
-        const int xq = x0 - R + hx, yq = y0 - R + hy;
+    win_for_each_entry<R>(x0, y0, W, H, [&](int slot, WinPixel at) {
         float e = 0.0f;
         int oq = ERR_NOBODY;
-        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
-            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+        if (at.inside()) {
+            const size_t q = at();
             const float cA = A.half_a[q].w, cB = A.half_b[q].w;
             if (cA > 0.0f && cB > 0.0f) {
                 const float dl = nz_lum(mk(A.da[q * 3 + 0], A.da[q * 3 + 1], A.da[q * 3 + 2])) -
                                  nz_lum(mk(A.db[q * 3 + 0], A.db[q * 3 + 1], A.db[q * 3 + 2]));
-                e = fmax_((dl * dl) * ((cA * cB) / ((cA + cB) * (cA + cB))), 0.0f);      // (a NaN gives 0)
+                e = win_e(dl, cA, cB);
                 oq = A.object[q];
             }
         }
-        t_e[hx * PITCH + hy] = e;
-        t_obj[hx * PITCH + hy] = oq;
-    }
+        t_e[slot] = e;
+        t_obj[slot] = oq;
+    });
     __syncthreads();
     const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
     const int x = x0 + lx, y = y0 + ly;
     bool estimated = false;
     float err = 0.0f;
     if (x < W && y < H) {
-        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        const int op = t_obj[win_centre<R>(lx, ly)];
         if (op != ERR_NOBODY) {
             estimated = true;
             float S = 0.0f, cn = 0.0f;
-#pragma unroll
-            for (int dy = -R; dy <= R; dy++) {
-#pragma unroll
-                for (int dx = -R; dx <= R; dx++) {
-                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
-                    const bool same = t_obj[q] == op;
-                    S = S + (same ? t_e[q] : 0.0f);
-                    cn = cn + (same ? 1.0f : 0.0f);
-                }
-            }
+            win_for_each_tap<R, true>(lx, ly, t_obj, op, [&](int q, bool same) {
+                S = S + (same ? t_e[q] : 0.0f);
+                cn = cn + (same ? 1.0f : 0.0f);
+            });
             err = sqrt_ieee_(S / cn);
         }
         A.error[(size_t)x * (size_t)H + (size_t)y] = err;
@@ -109,88 +183,55 @@ __global__ void __launch_bounds__(256) half_error(const ErrorArgs A) {
     nz_stats(A.stats, A.threshold, blk, estimated, err, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
-// ---- the blend kernel: half_error<R>'s tile, halo and pitch with four planes (a_q, q_q, x_q, object_q), 16 bytes per entry.  An
-// entry that is not usable or lies outside the frame holds +0 in all three and ERR_NOBODY.  The three sums are signed, but a sum
-// that starts at +0 never becomes -0 (x + (-x) = +0 in round-to-nearest, +0 + -0 = +0), so adding +0 for a skipped tap is still
-// the identity and the tap loop is the object compare alone.  The lane that summed the window makes t, the blend and the tone map.
+// ---- the blend kernel: four planes (a_q, q_q, x_q, object_q), 16 bytes per entry; valid = usable, both halves have min_half
+// samples.  The lane that summed the window makes t, the blend and the tone map.
 // Traffic per staged entry: the three 16-byte texels, 36 bytes of the three linear filtered colours, 4 bytes of object: 88 bytes
 // against half_error's 36 (the count words there cost a whole texel each on the bus); per pixel 28 more (b and FD of the centre
 // again, 16 written).
 template <int R>
 __global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
-    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
-    __shared__ float t_a[HX * PITCH];
-    __shared__ float t_q[HX * PITCH];
-    __shared__ float t_x[HX * PITCH];
-    __shared__ int t_obj[HX * PITCH];
+    __shared__ float t_a[Win<R>::WORDS];
+    __shared__ float t_q[Win<R>::WORDS];
+    __shared__ float t_x[Win<R>::WORDS];
+    __shared__ int t_obj[Win<R>::WORDS];
     __shared__ uint32_t blk[3];
     if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
     const int H = A.height, W = A.width;
     const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
-    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
-        const int hx = t / HY, hy = t - hx * HY;
-        const int xq = x0 - R + hx, yq = y0 - R + hy;
+    win_for_each_entry<R>(x0, y0, W, H, [&](int slot, WinPixel at) {
         float aq = 0.0f, qq = 0.0f, xx = 0.0f;
         int oq = ERR_NOBODY;
-        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
-            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+        if (at.inside()) {
+            const size_t q = at();
             const float4 ha = A.half_a[q], hb = A.half_b[q];
             const float cA = ha.w, cB = hb.w;
             if (cA >= A.min_half && cB >= A.min_half) {
                 const float4 b = A.image_buffer[q];
-                const float f = (cA * cB) / ((cA + cB) * (cA + cB));
+                const float f = win_f(cA, cB);
                 const float lPA = nz_lum(mk(ha.x / ha.w, ha.y / ha.w, ha.z / ha.w));
                 const float lPB = nz_lum(mk(hb.x / hb.w, hb.y / hb.w, hb.z / hb.w));
                 const float lPb = nz_lum(mk(b.x / b.w, b.y / b.w, b.z / b.w));
-                const float dA = nz_lum(mk(A.fa[q * 3 + 0], A.fa[q * 3 + 1], A.fa[q * 3 + 2])) - lPA;
-                const float dB = nz_lum(mk(A.fb[q * 3 + 0], A.fb[q * 3 + 1], A.fb[q * 3 + 2])) - lPB;
-                const float dp = lPA - lPB;
-                const float dd = dA - dB;
-                const float dl = nz_lum(mk(A.fd[q * 3 + 0], A.fd[q * 3 + 1], A.fd[q * 3 + 2])) - lPb;
-                aq = (f * dp) * dd;
-                qq = dl * dl;
-                xx = dA * dB;
+                blend_stage(f, lPA, lPB, lPb, nz_lum(mk(A.fa[q * 3 + 0], A.fa[q * 3 + 1], A.fa[q * 3 + 2])),
+                            nz_lum(mk(A.fb[q * 3 + 0], A.fb[q * 3 + 1], A.fb[q * 3 + 2])),
+                            nz_lum(mk(A.fd[q * 3 + 0], A.fd[q * 3 + 1], A.fd[q * 3 + 2])), aq, qq, xx);
                 oq = A.object[q];
             }
         }
-        t_a[hx * PITCH + hy] = aq;
-        t_q[hx * PITCH + hy] = qq;
-        t_x[hx * PITCH + hy] = xx;
-        t_obj[hx * PITCH + hy] = oq;
-    }
+        t_a[slot] = aq;
+        t_q[slot] = qq;
+        t_x[slot] = xx;
+        t_obj[slot] = oq;
+    });
     __syncthreads();
     const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
     const int x = x0 + lx, y = y0 + ly;
     bool usable = false;
     float t = 1.0f;
     if (x < W && y < H) {
-        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        const int op = t_obj[win_centre<R>(lx, ly)];
         if (op != ERR_NOBODY) {
             usable = true;
-            float n = 0.0f, SC = 0.0f, SQ = 0.0f, SX = 0.0f, SXX = 0.0f;
-            // (rows stay a loop: with all (2R+1)^2 x 4 LDS reads hoisted the kernel takes 103 / 199 VGPRs at R = 2 / 3 and runs at
-            // four / two waves per SIMD; a row at a time it takes 48 at every radius)
-#pragma unroll 1
-            for (int dy = -R; dy <= R; dy++) {
-#pragma unroll
-                for (int dx = -R; dx <= R; dx++) {
-                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
-                    const bool same = t_obj[q] == op;
-                    const float xq = same ? t_x[q] : 0.0f;
-                    n = n + (same ? 1.0f : 0.0f);
-                    SC = SC + (same ? t_a[q] : 0.0f);
-                    SQ = SQ + (same ? t_q[q] : 0.0f);
-                    SX = SX + xq;
-                    SXX = SXX + xq * xq;
-                }
-            }
-            const float m1 = SX / n;
-            const float v = fmax_(SXX / n - m1 * m1, 0.0f);
-            if (m1 > 0.0f && (m1 * m1) * n > A.z2 * v) {
-                t = -SC / SQ;
-                if (!(t < 1.0f)) t = 1.0f;      // (a NaN gives 1)
-                if (t < 0.0f) t = 0.0f;
-            }
+            t = blend_weight<R>(lx, ly, t_a, t_q, t_x, t_obj, op, A.z2);
         }
         const size_t p = (size_t)x * (size_t)H + (size_t)y;
         const float4 b = A.image_buffer[p];
@@ -214,8 +255,8 @@ __global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
     nz_stats(A.stats, 0.0f, blk, usable, 1.0f - t, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
-// ---- the level kernel of rtpbr_denoise_blend_levels: half_blend<R>'s tile, halo, pitch and four planes, once per a-trous level k
-// = 1..K, with the finer level k - 1 in the place of the raw average.  A level's record (colour, object word) is the filter with
+// ---- the level kernel of rtpbr_denoise_blend_levels: half_blend<R>'s four planes and rule, once per a-trous level k = 1..K, with
+// the finer level k - 1 in the place of the raw average.  A level's record (colour, object word) is the filter with
 // iterations = k before remodulation; level 0 (FIRST) is made from the (sum, count) buffers with atrous_none<LINEAR>'s operations.
 // A usable entry has samples in all three buffers (cA >= m >= 1, cB >= m, b.w = cA + cB), so its six records are colours and not
 // the NO_SAMPLES record.  After the window the lane updates its own pixel's running T (in `weight`), depth and linear colour (in
@@ -259,27 +300,24 @@ RT_D float4 lv_lums(const rtpbr_config& cfg, vec3 xa, vec3 xb) {
 
 template <int R, bool FIRST, bool LAST, bool ERR = false>
 __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
-    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
-    __shared__ float t_a[HX * PITCH];
-    __shared__ float t_q[HX * PITCH];
-    __shared__ float t_x[HX * PITCH];
-    __shared__ int t_obj[HX * PITCH];
+    __shared__ float t_a[Win<R>::WORDS];
+    __shared__ float t_q[Win<R>::WORDS];
+    __shared__ float t_x[Win<R>::WORDS];
+    __shared__ int t_obj[Win<R>::WORDS];
     __shared__ uint32_t blk[3];
     if constexpr (LAST)
         if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
     const int H = A.height, W = A.width;
     const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
-    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
-        const int hx = t / HY, hy = t - hx * HY;
-        const int xq = x0 - R + hx, yq = y0 - R + hy;
+    win_for_each_entry<R>(x0, y0, W, H, [&](int slot, WinPixel at) {
         float aq = 0.0f, qq = 0.0f, xx = 0.0f;
         int oq = ERR_NOBODY;
-        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
-            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+        if (at.inside()) {
+            const size_t q = at();
             const float cA = A.half_a[q].w, cB = A.half_b[q].w;
             if (cA >= A.min_half && cB >= A.min_half) {
                 const vec3 ac = lv_albedo(A, q);
-                const float f = (cA * cB) / ((cA + cB) * (cA + cB));
+                const float f = win_f(cA, cB);
                 float lA0, lB0, lD0;      // the finer level
                 if constexpr (FIRST) {
                     lA0 = nz_lum(lv_average(A.half_a[q], ac, A.demodulate));
@@ -290,22 +328,16 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
                     lB0 = nz_lum(lv_record(A.pb[q], ac, A.demodulate));
                     lD0 = nz_lum(lv_record(A.pd[q], ac, A.demodulate));
                 }
-                const float dA = nz_lum(lv_record(A.ka[q], ac, A.demodulate)) - lA0;
-                const float dB = nz_lum(lv_record(A.kb[q], ac, A.demodulate)) - lB0;
-                const float dp = lA0 - lB0;
-                const float dd = dA - dB;
-                const float dl = nz_lum(lv_record(A.kd[q], ac, A.demodulate)) - lD0;
-                aq = (f * dp) * dd;
-                qq = dl * dl;
-                xx = dA * dB;
+                blend_stage(f, lA0, lB0, lD0, nz_lum(lv_record(A.ka[q], ac, A.demodulate)), nz_lum(lv_record(A.kb[q], ac, A.demodulate)),
+                            nz_lum(lv_record(A.kd[q], ac, A.demodulate)), aq, qq, xx);
                 oq = A.object[q];
             }
         }
-        t_a[hx * PITCH + hy] = aq;
-        t_q[hx * PITCH + hy] = qq;
-        t_x[hx * PITCH + hy] = xx;
-        t_obj[hx * PITCH + hy] = oq;
-    }
+        t_a[slot] = aq;
+        t_q[slot] = qq;
+        t_x[slot] = xx;
+        t_obj[slot] = oq;
+    });
     __syncthreads();
     const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
     const int x = x0 + lx, y = y0 + ly;
@@ -313,32 +345,10 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
     float T = 1.0f;
     if (x < W && y < H) {
         float t = 1.0f;
-        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        const int op = t_obj[win_centre<R>(lx, ly)];
         if (op != ERR_NOBODY) {
             usable = true;
-            float n = 0.0f, SC = 0.0f, SQ = 0.0f, SX = 0.0f, SXX = 0.0f;
-            // (rows stay a loop, as in half_blend<R>)
-#pragma unroll 1
-            for (int dy = -R; dy <= R; dy++) {
-#pragma unroll
-                for (int dx = -R; dx <= R; dx++) {
-                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
-                    const bool same = t_obj[q] == op;
-                    const float xq = same ? t_x[q] : 0.0f;
-                    n = n + (same ? 1.0f : 0.0f);
-                    SC = SC + (same ? t_a[q] : 0.0f);
-                    SQ = SQ + (same ? t_q[q] : 0.0f);
-                    SX = SX + xq;
-                    SXX = SXX + xq * xq;
-                }
-            }
-            const float m1 = SX / n;
-            const float v = fmax_(SXX / n - m1 * m1, 0.0f);
-            if (m1 > 0.0f && (m1 * m1) * n > A.z2 * v) {
-                t = -SC / SQ;
-                if (!(t < 1.0f)) t = 1.0f;      // (a NaN gives 1)
-                if (t < 0.0f) t = 0.0f;
-            }
+            t = blend_weight<R>(lx, ly, t_a, t_q, t_x, t_obj, op, A.z2);
         }
         const size_t p = (size_t)x * (size_t)H + (size_t)y;
         const vec3 ac = lv_albedo(A, p);
@@ -437,40 +447,34 @@ __global__ void __launch_bounds__(256) level_blend_none(const LevelsArgs A) {
     nz_stats(A.stats, 0.0f, blk, usable, 0.0f, blockIdx.x);
 }
 
-// ---- the window kernel of rtpbr_blend_error: half_error<R>'s tile, halo, pitch and ERR_NOBODY convention with four planes (e_q,
-// x_q, usable_q, object_q), 16 bytes per entry.  An entry that is not valid or lies outside the frame holds +0 in the three and
-// ERR_NOBODY; a valid entry that is not usable holds x = +0 and usable = 0.  SX is signed, but a sum that starts at +0 never becomes
-// -0 (half_blend<R>'s argument), so adding +0 for a skipped or an unusable tap is the identity and the tap loop is the object
-// compare alone.  The centre lane reads its slope s from the error plane (level_blend's LAST ERR instance wrote it) and overwrites
-// it with the error: no other lane reads or writes that word.
-// LDS: 4 x HX x PITCH words = 13.8 / 15.4 / 16.9 KB at R = 1 / 2 / 3 (the pitch is 48 words at every radius; half_blend<R>'s
-// footprint: eight blocks of four waves still fit a CU's 160 KB), rows a loop as there.
+// ---- the window kernel of rtpbr_blend_error: four planes (e_q, x_q, usable_q, object_q), 16 bytes per entry; valid as in
+// half_error<R>, and a valid entry that is not usable (half_blend<R>'s test) holds x = +0 and usable = 0, so adding +0 covers an
+// unusable tap too.  The centre lane reads its slope s from the error plane (level_blend's LAST ERR instance wrote it) and
+// overwrites it with the error: no other lane reads or writes that word.
+// LDS: 4 planes = 13.8 / 15.4 / 16.9 KB at R = 1 / 2 / 3 (the pitch is 48 words at every radius; half_blend<R>'s footprint: eight
+// blocks of four waves still fit a CU's 160 KB), rows a loop as there.
 // Traffic per staged entry: the 16-byte texel of luminances, the two 16-byte texels of the halves (count words and, where usable,
 // the raw averages), 4 bytes of object: 52 bytes against half_error's 36 + its two filtered colours; per pixel 4 read, 4 written.
 template <int R>
 __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
-    constexpr int HX = ERR_TX + 2 * R, HY = ERR_TY + 2 * R, PITCH = err_pitch(HY);
-    __shared__ float t_e[HX * PITCH];
-    __shared__ float t_x[HX * PITCH];
-    __shared__ float t_u[HX * PITCH];
-    __shared__ int t_obj[HX * PITCH];
+    __shared__ float t_e[Win<R>::WORDS];
+    __shared__ float t_x[Win<R>::WORDS];
+    __shared__ float t_u[Win<R>::WORDS];
+    __shared__ int t_obj[Win<R>::WORDS];
     __shared__ uint32_t blk[3];
     if (threadIdx.x < 3) blk[threadIdx.x] = 0u;
     const int H = A.height, W = A.width;
     const int x0 = (int)blockIdx.x * ERR_TX, y0 = (int)blockIdx.y * ERR_TY;
-    for (int t = (int)threadIdx.x; t < HX * HY; t += 256) {
-        const int hx = t / HY, hy = t - hx * HY;
-        const int xq = x0 - R + hx, yq = y0 - R + hy;
+    win_for_each_entry<R>(x0, y0, W, H, [&](int slot, WinPixel at) {
         float e = 0.0f, xx = 0.0f, u = 0.0f;
         int oq = ERR_NOBODY;
-        if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
-            const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
+        if (at.inside()) {
+            const size_t q = at();
             const float4 ha = A.half_a[q], hb = A.half_b[q];
             const float cA = ha.w, cB = hb.w;
             if (cA > 0.0f && cB > 0.0f) {
                 const float4 l = A.lx[q];
-                const float dl = l.y - l.w;
-                e = fmax_((dl * dl) * ((cA * cB) / ((cA + cB) * (cA + cB))), 0.0f);      // (a NaN gives 0)
+                e = win_e(l.y - l.w, cA, cB);
                 if (cA >= A.min_half && cB >= A.min_half) {
                     const float lPA = nz_lum(mk(ha.x / ha.w, ha.y / ha.w, ha.z / ha.w));
                     const float lPB = nz_lum(mk(hb.x / hb.w, hb.y / hb.w, hb.z / hb.w));
@@ -480,35 +484,28 @@ __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
                 oq = A.object[q];
             }
         }
-        t_e[hx * PITCH + hy] = e;
-        t_x[hx * PITCH + hy] = xx;
-        t_u[hx * PITCH + hy] = u;
-        t_obj[hx * PITCH + hy] = oq;
-    }
+        t_e[slot] = e;
+        t_x[slot] = xx;
+        t_u[slot] = u;
+        t_obj[slot] = oq;
+    });
     __syncthreads();
     const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
     const int x = x0 + lx, y = y0 + ly;
     bool estimated = false;
     float err = 0.0f;
     if (x < W && y < H) {
-        const int op = t_obj[(lx + R) * PITCH + (ly + R)];
+        const int op = t_obj[win_centre<R>(lx, ly)];
         const size_t p = (size_t)x * (size_t)H + (size_t)y;
         if (op != ERR_NOBODY) {
             estimated = true;
             float S = 0.0f, cn = 0.0f, SX = 0.0f, nb = 0.0f;
-            // (rows stay a loop, as in half_blend<R>)
-#pragma unroll 1
-            for (int dy = -R; dy <= R; dy++) {
-#pragma unroll
-                for (int dx = -R; dx <= R; dx++) {
-                    const int q = (lx + R + dx) * PITCH + (ly + R + dy);
-                    const bool same = t_obj[q] == op;
-                    S = S + (same ? t_e[q] : 0.0f);
-                    cn = cn + (same ? 1.0f : 0.0f);
-                    SX = SX + (same ? t_x[q] : 0.0f);
-                    nb = nb + (same ? t_u[q] : 0.0f);
-                }
-            }
+            win_for_each_tap<R, false>(lx, ly, t_obj, op, [&](int q, bool same) {
+                S = S + (same ? t_e[q] : 0.0f);
+                cn = cn + (same ? 1.0f : 0.0f);
+                SX = SX + (same ? t_x[q] : 0.0f);
+                nb = nb + (same ? t_u[q] : 0.0f);
+            });
             const float bias2 = nb > 0.0f ? fmax_(SX / nb, 0.0f) : 0.0f;      // (a NaN gives 0)
             const float s = A.error[p];
             err = sqrt_ieee_(S / cn + (s * s) * bias2);
@@ -519,6 +516,14 @@ __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
 }
 
 static unsigned grid_of(int w, int h) { return (unsigned)(((size_t)w * h + 255) / 256); }
+static dim3 tile_grid(int w, int h) { return dim3((unsigned)((w + ERR_TX - 1) / ERR_TX), (unsigned)((h + ERR_TY - 1) / ERR_TY)); }
+// f(integral_constant<int, R>) for the window kernels' R = radius (rt_capi.hip admits radius 1..3 only)
+template <class F>
+static void with_radius(int radius, F f) {
+    if (radius == 1) f(std::integral_constant<int, 1>{});
+    else if (radius == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
 
 void launch_half_update(const HalfArgs& A, hipStream_t st) {
     hipLaunchKernelGGL(half_update, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
@@ -528,52 +533,38 @@ void launch_half_subtract(const HalfArgs& A, hipStream_t st) {
     hipLaunchKernelGGL(half_subtract, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
 }
 
-void launch_half_error(const ErrorArgs& A, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
-    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
-    if (A.radius == 1) hipLaunchKernelGGL(half_error<1>, grid, dim3(256), 0, st, A);
-    else if (A.radius == 2) hipLaunchKernelGGL(half_error<2>, grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(half_error<3>, grid, dim3(256), 0, st, A);
+void launch_half_error(const ErrorArgs& A, hipStream_t st) {
+    with_radius(A.radius, [&](auto r) { hipLaunchKernelGGL(half_error<decltype(r)::value>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
 }
 
-void launch_half_blend(const BlendArgs& A, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
-    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
-    if (A.radius == 1) hipLaunchKernelGGL(half_blend<1>, grid, dim3(256), 0, st, A);
-    else if (A.radius == 2) hipLaunchKernelGGL(half_blend<2>, grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(half_blend<3>, grid, dim3(256), 0, st, A);
+void launch_half_blend(const BlendArgs& A, hipStream_t st) {
+    with_radius(A.radius, [&](auto r) { hipLaunchKernelGGL(half_blend<decltype(r)::value>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
 }
 
 template <int R, bool ERR>
-static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, dim3 grid, hipStream_t st) {
+static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hipStream_t st) {
+    const dim3 grid = tile_grid(A.width, A.height);
     if (first && last) hipLaunchKernelGGL((level_blend<R, true, true, ERR>), grid, dim3(256), 0, st, A);
     else if (first) hipLaunchKernelGGL((level_blend<R, true, false, ERR>), grid, dim3(256), 0, st, A);
     else if (last) hipLaunchKernelGGL((level_blend<R, false, true, ERR>), grid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL((level_blend<R, false, false, ERR>), grid, dim3(256), 0, st, A);
 }
 
-// no level (first && last && no records): the K = 0 pass
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
+// no level (first && last && no records): the K = 0 pass.  A.xa (rtpbr_blend_error): the ERR instances
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st) {
     if (!A.kd) {
         if (A.xa) hipLaunchKernelGGL(level_blend_none<true>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         else hipLaunchKernelGGL(level_blend_none<false>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         return;
     }
-    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
-    if (A.xa) {      // rtpbr_blend_error
-        if (A.radius == 1) launch_level_blend_r<1, true>(A, first, last, grid, st);
-        else if (A.radius == 2) launch_level_blend_r<2, true>(A, first, last, grid, st);
-        else launch_level_blend_r<3, true>(A, first, last, grid, st);
-        return;
-    }
-    if (A.radius == 1) launch_level_blend_r<1, false>(A, first, last, grid, st);
-    else if (A.radius == 2) launch_level_blend_r<2, false>(A, first, last, grid, st);
-    else launch_level_blend_r<3, false>(A, first, last, grid, st);
+    with_radius(A.radius, [&](auto r) {
+        if (A.xa) launch_level_blend_r<decltype(r)::value, true>(A, first, last, st);
+        else launch_level_blend_r<decltype(r)::value, false>(A, first, last, st);
+    });
 }
 
-void launch_blend_error(const BlendErrorArgs& A, hipStream_t st) {      // (rt_capi.hip admits radius 1..3 only)
-    const dim3 grid((unsigned)((A.width + ERR_TX - 1) / ERR_TX), (unsigned)((A.height + ERR_TY - 1) / ERR_TY));
-    if (A.radius == 1) hipLaunchKernelGGL(blend_error<1>, grid, dim3(256), 0, st, A);
-    else if (A.radius == 2) hipLaunchKernelGGL(blend_error<2>, grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(blend_error<3>, grid, dim3(256), 0, st, A);
+void launch_blend_error(const BlendErrorArgs& A, hipStream_t st) {
+    with_radius(A.radius, [&](auto r) { hipLaunchKernelGGL(blend_error<decltype(r)::value>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
 }
 
 }  // namespace rt

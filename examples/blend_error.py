@@ -5,12 +5,14 @@ gives the variance, the product of their (blended - raw) the squared bias the ha
 
     python examples/blend_error.py --size 256 256                         # the estimate next to the true error, per sample count
     python examples/blend_error.py --size 64 64 --spp 32 128 --ref-spp 512  # a run of seconds
-    python examples/blend_error.py --bench                                # blend_error beside denoise_blend_levels, wall times
+    python examples/blend_error.py --size 256 256 --bias display          # the bias in display space per tap (rtpbr_blend_error_display)
+    python examples/blend_error.py --bench                                # both estimates beside denoise_blend_levels, wall times
 
 Prints, per sample count, the estimated root-mean-square error of the display luminance (the root of the mean of the plane's
 squares) and the true error of the blended frame against a longer render (another seed); saves the blended frame and the error
 map of the last row (white = --map-white or more).  On this scene the estimate overstates the error
-several times — the bias term, beside the light: DESIGN.md section 6n.  Headless; runs on the HIP library only.
+several times — the bias term, beside the light: DESIGN.md section 6n — and with --bias display it does not (section 6o).
+Headless; runs on the HIP library only.
 """
 import argparse
 import os
@@ -34,6 +36,7 @@ ap.add_argument("--iterations", type=int, default=None)
 ap.add_argument("--out", default="out/blend_error_frame.png")
 ap.add_argument("--error-map", default="out/blend_error_map.png")
 ap.add_argument("--map-white", type=float, default=0.25, help="the error shown as white in the map")
+ap.add_argument("--bias", choices=("linear", "display"), default="linear", help="blend_error's bias rule")
 ap.add_argument("--bench", action="store_true")
 a = ap.parse_args()
 
@@ -46,6 +49,7 @@ if a.bench:
             r.half_update()
         r.denoise_blend_levels(3, 2.0, 1)
         r.blend_error(0.0, 3, 2.0, 1)
+        r.blend_error(0.0, 3, 2.0, 1, bias="display")
         wall = {}
 
         def timed(what, call):
@@ -61,7 +65,8 @@ if a.bench:
             timed("denoise_blend_levels, radius 3", lambda: r.denoise_blend_levels(3, 2.0, 1))
             for window in (1, 2, 3):
                 timed(f"blend_error, radius 3, window {window}", lambda: r.blend_error(0.0, 3, 2.0, 1, window))
-        print(f"{W}x{H}, Cornell v3, 12 rounds of sample(1), half_update, denoise_blend_levels and blend_error")
+                timed(f"blend_error, radius 3, window {window}, bias display", lambda: r.blend_error(0.0, 3, 2.0, 1, window, bias="display"))
+        print(f"{W}x{H}, Cornell v3, 12 rounds of sample(1), half_update, denoise_blend_levels and blend_error with either bias")
         for what, ms in wall.items():
             print(f"    {what}: wall {np.mean(ms):.3f} ms (min {min(ms):.3f}, max {max(ms):.3f}), blocking, with the launches' host time")
         del r
@@ -84,7 +89,7 @@ ref = lum(ref_r.image_pixels)
 
 r = Renderer(scene, cfg)
 done = 0
-print(f"Cornell v3 {W}x{H}, root-mean-square error of the blended frame's display luminance: estimated, and true against {a.ref_spp} spp")
+print(f"Cornell v3 {W}x{H}, root-mean-square error of the blended frame's display luminance: estimated ({a.bias} bias), and true against {a.ref_spp} spp")
 print("  halves      estimated   true    estimated / true   median estimate   largest estimate")
 for spp in sorted(a.spp):
     half = spp // 2
@@ -95,7 +100,7 @@ for spp in sorted(a.spp):
         r.sample(half)
         r.half_update()
     done = 2 * half
-    st = r.blend_error(0.0, a.radius, a.z, a.min_half_samples, a.window, **denoise)
+    st = r.blend_error(0.0, a.radius, a.z, a.min_half_samples, a.window, bias=a.bias, **denoise)
     err = r.blend_error_map.astype(np.float64)
     est = float(np.sqrt(np.mean(err ** 2)))
     true = float(np.sqrt(np.mean((lum(r.denoised_pixels) - ref) ** 2)))

@@ -868,6 +868,40 @@ int rtpbr_blend_error(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr
                       float threshold, rtpbr_noise_stats* out);
 int rtpbr_select_blend_error(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 
+/* ---- The same estimate with the bias in display space per tap (rtpbr_blend_error_display).
+ *
+ * rtpbr_blend_error averages the squared bias over the window in linear radiance and converts the mean with the slope of the tone
+ * map at the centre pixel.  Where the window holds a pixel whose tone map is saturated — linear luminance of tens, a slope of
+ * nearly 0, a linear bias^2 of 16 to 20 on the ceiling beside Cornell's light — every neighbour inherits that bias^2 at its own
+ * slope, and the estimate overstates the mean-square error about seven times.  This call converts each tap's
+ * product with the TAP's own slope before it is summed.  THE NUMBER IS: the variance of the level-blended frame's display
+ * luminance plus the squared DISPLAY-SPACE bias the halves can see, as a root.  The variance term is rtpbr_blend_error's and is
+ * still about half the empirical variance (the halves share the weights T_k; DESIGN.md sections 6n (2), 6o and 8).
+ *
+ * rtpbr_blend_error_display is rtpbr_blend_error(p, e, w, threshold, out) in everything but the bias term: the same
+ *   RTPBR_BUF_DENOISED_PIXELS, RTPBR_BUF_BLEND_WEIGHT and RTPBR_BUF_BLEND_DEPTH byte for byte, the same state rules, errors, NULL
+ *   defaults and statistics, and the same output plane: RTPBR_BUF_BLEND_ERROR holds what the LAST of the two calls wrote, and
+ *   rtpbr_select_blend_error, rtpbr_present and every read work on it unchanged.  Nothing else changes.
+ *   Every operation is f32, in the order written, nothing fused.  XA, XB, PA, PB, "valid", "usable", e_q, x_q, s, the window, its tap
+ *   order, S, n and nb are those of the section above.
+ *   s_q is s of pixel q: defined for every pixel, 0 where b.w > 0 is false or Y > 0 is false.
+ *   For usable q:
+ *     xd_q = (s_q * s_q) * x_q;
+ *   a valid pixel that is not usable has xd_q = +0 and does not count in nb.
+ *   Per valid pixel p, all sums from +0:
+ *     S = S + e_q;  n = n + 1;  and for usable q:  SX = SX + xd_q;  nb = nb + 1;
+ *     bias2 = nb > 0 ? fmaxf(SX / nb, 0) : 0                                                      (a NaN gives 0);
+ *     error_p = sqrt(S / n + bias2), correctly rounded.
+ *   A pixel that is not valid has error 0 and is not estimated.
+ *   With min_half_samples above every count the plane is rtpbr_denoise_error(p, w)'s bit for bit, and with K = 0 without demodulate
+ *   it is rtpbr_blend_error's (both are then the variance alone).  Calibration on Cornell v3: DESIGN.md section 6o.
+ *   Memory: beside what rtpbr_blend_error keeps, one (W,H) plane of 4 bytes for s (8 MB at 1920 x 1080): a tap's s_q cannot live in
+ *   the output plane, whose words the neighbouring pixels' estimates overwrite.  Allocated by the first call and freed by
+ *   rtpbr_set_config with a new resolution.
+ *   Errors, each before anything changes: rtpbr_blend_error's. */
+int rtpbr_blend_error_display(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, const rtpbr_error_params* w,
+                              float threshold, rtpbr_noise_stats* out);
+
 /* ---- Halves dealt per sample and carried through reprojection.
  *
  * Two switches of the section above, both off by default; with the defaults every buffer, counter and timing path is bit for bit

@@ -29,13 +29,13 @@ ENTRY_POINTS = [
     "render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
     "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
     "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode", "denoise_blend",
-    "denoise_blend_levels", "blend_error", "select_blend_error",
+    "denoise_blend_levels", "blend_error", "select_blend_error", "blend_error_display",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
 ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
                    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
                    "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode", "denoise_blend",
-                   "denoise_blend_levels", "blend_error", "select_blend_error")
+                   "denoise_blend_levels", "blend_error", "select_blend_error", "blend_error_display")
 
 
 class RtpbrError(RuntimeError):
@@ -115,6 +115,8 @@ class CApi:
             "blend_error": (C.c_int, [p, C.POINTER(DenoiseParams), C.POINTER(BlendParams), C.POINTER(ErrorParams), C.c_float,
                                       C.POINTER(NoiseStats)]),
             "select_blend_error": (C.c_int, [p, C.c_float, C.c_int, C.POINTER(C.c_uint32)]),
+            "blend_error_display": (C.c_int, [p, C.POINTER(DenoiseParams), C.POINTER(BlendParams), C.POINTER(ErrorParams), C.c_float,
+                                              C.POINTER(NoiseStats)]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

@@ -157,10 +157,11 @@ static void free_half(rtpbr_ctx* c) {
     (void)hipFree(c->levels_scratch);
     (void)hipFree(c->blend_error);
     (void)hipFree(c->blend_x);
+    (void)hipFree(c->blend_slope);
     c->half_a = c->half_snapshot = c->hist_half = c->half_b = nullptr;
     c->half_da = c->half_db = c->denoised_error = c->half_fd = c->blend_weight = c->blend_depth = nullptr;
     c->levels_scratch = c->blend_x = nullptr;
-    c->blend_error = nullptr;
+    c->blend_error = c->blend_slope = nullptr;
 }
 
 // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (allocated on the first select call)
@@ -2024,7 +2025,7 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
 enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT, W_DEPTH = 1u << RTPBR_BUF_BLEND_DEPTH,
                   W_BLEND_ERROR = 1u << RTPBR_BUF_BLEND_ERROR };
-static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_select_error / rtpbr_select_blend_error work on the whole frame: not with tiles of world > 1";
+static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_blend_error_display / rtpbr_select_error / rtpbr_select_blend_error work on the whole frame: not with tiles of world > 1";
 
 // What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
 // snapshot = 0 (snapshot_image false: the image is being zeroed too) or = image_buffer as the stream has it by now.  keep_a: A has
@@ -2204,9 +2205,10 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
 }
 
 // ---- the same blend across the a-trous levels (level_blend<R, FIRST, LAST>, rt_half.hip), and with `window` the error estimate of
-// its frame (rtpbr_blend_error: the ERR instances and blend_error<R>)
+// its frame (rtpbr_blend_error: the ERR instances and blend_error<R>; `display`, rtpbr_blend_error_display: the slope goes to a
+// plane of its own and the DISPLAY instances read it per tap)
 static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_params* p, const rtpbr_blend_params* e,
-                        const rtpbr_error_params* w, bool with_error, float threshold, rtpbr_noise_stats* out) {
+                        const rtpbr_error_params* w, bool with_error, bool display, float threshold, rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     rtpbr_denoise_params d;
     float inv[4];
@@ -2226,6 +2228,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     if (!c->levels_scratch) HIP_TRY(hipMalloc(&c->levels_scratch, 6 * n * sizeof(float4)));
     if (with_error && !c->blend_error) HIP_TRY(hipMalloc(&c->blend_error, n * sizeof(float)));
     if (with_error && !c->blend_x) HIP_TRY(hipMalloc(&c->blend_x, 2 * n * sizeof(float4)));
+    if (display && !c->blend_slope) HIP_TRY(hipMalloc(&c->blend_slope, n * sizeof(float)));
     if (int r = denoised_alloc(c, 0)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
     if (int r = rt_order_after_reads(c, W_BLEND | W_DEPTH | (with_error ? W_BLEND_ERROR : 0u))) return r;
     if (!c->feat_valid)
@@ -2233,10 +2236,10 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     if (int r = half_b_enqueue(c)) return r;
     if (int r = noise_stats_zero(c)) return r;
     LevelsArgs A{};
-    if (with_error) {      // the ERR instances: XA and XB beside the frame, the slope into the error plane
+    if (with_error) {      // the ERR instances: XA and XB beside the frame, the slope into the error plane (display: into its own)
         A.xa = c->blend_x;
         A.xb = c->blend_x + n;
-        A.slope = c->blend_error;
+        A.slope = display ? c->blend_slope : c->blend_error;
     }
     A.cfg = c->cfg;
     A.image_buffer = c->image_buffer;
@@ -2294,6 +2297,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     E.half_b = c->half_b;
     E.object = c->feat_object;
     E.error = c->blend_error;
+    E.slope = display ? c->blend_slope : nullptr;
     E.stats = c->noise_stats;
     E.threshold = threshold;
     E.min_half = (float)b.min_half_samples;
@@ -2306,12 +2310,17 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
 }
 
 extern "C" int rtpbr_denoise_blend_levels(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, rtpbr_noise_stats* out) {
-    return blend_levels(c, "rtpbr_denoise_blend_levels", p, e, nullptr, false, 0.0f, out);
+    return blend_levels(c, "rtpbr_denoise_blend_levels", p, e, nullptr, false, false, 0.0f, out);
 }
 
 extern "C" int rtpbr_blend_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, const rtpbr_error_params* w,
                                  float threshold, rtpbr_noise_stats* out) {
-    return blend_levels(c, "rtpbr_blend_error", p, e, w, true, threshold, out);
+    return blend_levels(c, "rtpbr_blend_error", p, e, w, true, false, threshold, out);
+}
+
+extern "C" int rtpbr_blend_error_display(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_blend_params* e,
+                                         const rtpbr_error_params* w, float threshold, rtpbr_noise_stats* out) {
+    return blend_levels(c, "rtpbr_blend_error_display", p, e, w, true, true, threshold, out);
 }
 
 // The selection by an error estimate: `plane` is the estimate's, `who` the call (it fills the %s of its messages), no_estimate

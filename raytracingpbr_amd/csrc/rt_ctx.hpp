@@ -230,6 +230,8 @@ struct rtpbr_ctx {
     // rtpbr_blend_error: from its first call on (it makes what rtpbr_denoise_blend_levels makes too); freed with the halves
     float* blend_error = nullptr;      // (W,H): RTPBR_BUF_BLEND_ERROR
     float4* blend_x = nullptr;         // 2 x (W,H): the running XA and XB of the levels (scratch of the call)
+    // rtpbr_blend_error_display: from its first call on (it makes what rtpbr_blend_error makes too); freed with the halves
+    float* blend_slope = nullptr;      // (W,H): the slope s of every pixel (scratch of the call)
     // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
     uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
     uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)

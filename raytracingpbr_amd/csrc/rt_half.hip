@@ -1,4 +1,4 @@
-// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error (see rt_half.hpp).
+// rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_blend_error_display (see rt_half.hpp).
 #include <hip/hip_runtime.h>
 
 #include "rt_half.hpp"
@@ -455,7 +455,12 @@ __global__ void __launch_bounds__(256) level_blend_none(const LevelsArgs A) {
 // blocks of four waves still fit a CU's 160 KB), rows a loop as there.
 // Traffic per staged entry: the 16-byte texel of luminances, the two 16-byte texels of the halves (count words and, where usable,
 // the raw averages), 4 bytes of object: 52 bytes against half_error's 36 + its two filtered colours; per pixel 4 read, 4 written.
-template <int R>
+// DISPLAY (rtpbr_blend_error_display): the bias in display space per tap.  A usable entry stages xd_q = (s_q * s_q) * x_q with its
+// own slope — s * s once per staged entry, never per tap — and the centre adds the window's mean as it is.  A halo entry's s_q is
+// the slope of a pixel that another block owns and may already have overwritten with its error, so for this call level_blend's
+// LAST ERR instance (the same code, another pointer) leaves s in a plane of its own that no window kernel writes.  Traffic: +4
+// bytes per usable staged entry (56 against 52), and the centre's 4-byte read goes.  LDS, the tap loop and the rows are the same.
+template <int R, bool DISPLAY = false>
 __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
     __shared__ float t_e[Win<R>::WORDS];
     __shared__ float t_x[Win<R>::WORDS];
@@ -479,6 +484,10 @@ __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
                     const float lPA = nz_lum(mk(ha.x / ha.w, ha.y / ha.w, ha.z / ha.w));
                     const float lPB = nz_lum(mk(hb.x / hb.w, hb.y / hb.w, hb.z / hb.w));
                     xx = (l.x - lPA) * (l.z - lPB);
+                    if constexpr (DISPLAY) {
+                        const float s = A.slope[q];
+                        xx = (s * s) * xx;
+                    }
                     u = 1.0f;
                 }
                 oq = A.object[q];
@@ -507,8 +516,12 @@ __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
                 nb = nb + (same ? t_u[q] : 0.0f);
             });
             const float bias2 = nb > 0.0f ? fmax_(SX / nb, 0.0f) : 0.0f;      // (a NaN gives 0)
-            const float s = A.error[p];
-            err = sqrt_ieee_(S / cn + (s * s) * bias2);
+            if constexpr (DISPLAY) {
+                err = sqrt_ieee_(S / cn + bias2);
+            } else {
+                const float s = A.error[p];
+                err = sqrt_ieee_(S / cn + (s * s) * bias2);
+            }
         }
         A.error[p] = err;
     }
@@ -563,8 +576,13 @@ void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t 
     });
 }
 
+// A.slope != nullptr (rtpbr_blend_error_display): the DISPLAY instances
 void launch_blend_error(const BlendErrorArgs& A, hipStream_t st) {
-    with_radius(A.radius, [&](auto r) { hipLaunchKernelGGL(blend_error<decltype(r)::value>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
+    with_radius(A.radius, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (A.slope) hipLaunchKernelGGL((blend_error<R, true>), tile_grid(A.width, A.height), dim3(256), 0, st, A);
+        else hipLaunchKernelGGL((blend_error<R, false>), tile_grid(A.width, A.height), dim3(256), 0, st, A);
+    });
 }
 
 }  // namespace rt

@@ -40,8 +40,13 @@
 //                       e_q is half_error's with the blended halves' display luminances, x_q the product of the halves' (blended -
 //                       raw) in linear luminance; the lane sums both over the window on its object and writes the root of
 //                       variance + s^2 bias^2 into RTPBR_BUF_BLEND_ERROR; statistics through nz_stats.
+//   blend_error<R, DISPLAY>  rtpbr_blend_error_display's instances: the staged x_q is (s_q s_q) x_q with the entry's own slope, read
+//                       from a (W,H) plane of its own that the LAST ERR instance fills in the place of the error plane (a halo
+//                       entry's slope belongs to a pixel whose error word another block may already have written), and the
+//                       lane writes the root of variance + the window's mean of that.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that the CPU restatement matches bit for bit
-// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c, tests/levels_ref/levels_ref.c, tests/blend_error_ref/blend_error_ref.c).
+// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c, tests/levels_ref/levels_ref.c, tests/blend_error_ref/blend_error_ref.c,
+// tests/blend_display_ref/blend_display_ref.c).
 #pragma once
 #include "rt_noise.hpp"
 
@@ -105,7 +110,8 @@ struct LevelsArgs {
     NoiseStats* stats;            // out (zeroed before the launches; LAST adds to it)
     float4* xa;                   // ERR instances, in / out: the running XA; after LAST (lum XA, display lum XA, lum XB, display lum XB)
     float4* xb;                   // ... the running XB
-    float* slope;                 // ERR instances, LAST: out, s (the plane of RTPBR_BUF_BLEND_ERROR, which blend_error<R> then overwrites)
+    float* slope;                 // ERR instances, LAST: out, s (the plane of RTPBR_BUF_BLEND_ERROR, which blend_error<R> then overwrites;
+                                  // rtpbr_blend_error_display: a plane of its own)
     float min_half;               // (float)min_half_samples
     float z2;                     // z * z
     int32_t demodulate;
@@ -124,6 +130,8 @@ struct BlendErrorArgs {
     float min_half;               // (float)min_half_samples
     int32_t width, height;
     int32_t radius;               // 1..3
+    // (behind the others: the instances of rtpbr_blend_error keep their argument offsets)
+    const float* slope;           // nullptr, or (rtpbr_blend_error_display) s per pixel in a plane of its own: `error` is then out only
 };
 
 void launch_half_update(const HalfArgs& A, hipStream_t st);

@@ -463,13 +463,23 @@ class Renderer:
         return s
 
     def blend_error(self, threshold: float = 0.0, radius=None, z=None, min_half_samples=None, window=None, iterations=None,
-                    demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
+                    demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None,
+                    bias="linear") -> NoiseStats:
         """denoise_blend_levels (same parameters, same ``denoised_pixels``, ``blend_weight`` and ``blend_depth``) and besides
         ``blend_error_map``: the estimated root-mean-square error of the luminance of the frame it shows.  The levels' weights
         are applied to each half's own ladder; the difference of the two blended halves gives the variance, the product of their
         (blended - raw) the squared bias the halves can see, both averaged over the (2 ``window`` + 1)^2 window on each pixel's
         object (``window`` = denoise_error's radius).  Returns how many pixels have samples in both halves, how many of them are
-        above ``threshold``, and the largest value.  Blocks.  ``None`` = the library's default for that parameter."""
+        above ``threshold``, and the largest value.  Blocks.  ``None`` = the library's default for that parameter.
+        ``bias``: "linear" (the default) averages the squared bias in linear radiance and converts the mean with the slope of the
+        tone map at the centre pixel; "display" (rtpbr_blend_error_display) converts each tap's product with the tap's own slope
+        before summing, so a saturated pixel in the window no longer lends its linear bias to its neighbours.  Both write
+        ``blend_error_map``: the last call wins."""
+        if bias not in ("linear", "display"):
+            raise ValueError('bias must be "linear" or "display"')
+        entry = "blend_error_display" if bias == "display" else "blend_error"
+        if not self.api.has(entry):
+            raise NotImplementedError(f"this library has no rtpbr_{entry}")
         given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
                  "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
         p = None
@@ -484,7 +494,7 @@ class Renderer:
                                     int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
         w = None if window is None else C.byref(ErrorParams(int(window)))
         s = NoiseStats()
-        self.api.call("blend_error", self._ctx, p, e, w, float(threshold), C.byref(s))
+        self.api.call(entry, self._ctx, p, e, w, float(threshold), C.byref(s))
         return s
 
     def select_blend_error(self, threshold: float, dilate: int = 0) -> int:
@@ -495,7 +505,7 @@ class Renderer:
         return int(n.value)
 
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
-                                 blend=False, *, stop="filter", **denoise_params):
+                                 blend=False, *, stop="filter", bias="linear", **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -509,13 +519,18 @@ class Renderer:
         denoise_blend_levels(); the stop rule is unchanged.
         ``stop``: "filter" (the default) is the rule above.  "blend" (with ``blend="levels"`` only) loops on blend_error(error)
         -> select_blend_error(error, dilate) instead: the estimate is the error of the level-blended frame, variance and the
-        bias the halves can see, and the call ends with the frame the last blend_error() wrote."""
+        bias the halves can see, and the call ends with the frame the last blend_error() wrote.
+        ``bias`` (with ``stop="blend"`` only): blend_error's ``bias``, "linear" (the default) or "display"."""
         if isinstance(blend, str) and blend != "levels":
             raise ValueError('blend must be True, False or "levels"')
         if stop not in ("filter", "blend"):
             raise ValueError('stop must be "filter" or "blend"')
         if stop == "blend" and blend != "levels":
             raise ValueError('stop="blend" estimates the level-blended frame: blend must be "levels"')
+        if bias not in ("linear", "display"):
+            raise ValueError('bias must be "linear" or "display"')
+        if bias != "linear" and stop != "blend":
+            raise ValueError('bias selects the rule of blend_error(): stop must be "blend"')
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
@@ -536,7 +551,10 @@ class Renderer:
                     self.half_update()
                 traced, used = traced + n_pix * n, used + n
             while True:
-                stats = self.blend_error(error, **denoise_params) if stop == "blend" else self.denoise_error(error, **denoise_params)
+                if stop == "blend":
+                    stats = self.blend_error(error, bias=bias, **denoise_params)
+                else:
+                    stats = self.denoise_error(error, **denoise_params)
                 if stats.pixels_above == 0 or used + batch > budget:
                     break
                 n_sel = self.select_blend_error(error, dilate) if stop == "blend" else self.select_error(error, dilate)

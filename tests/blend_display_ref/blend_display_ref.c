@@ -1,0 +1,190 @@
+/*
+ * blend_display_ref.c — CPU restatement of rtpbr_blend_error_display (TEST INFRASTRUCTURE ONLY).
+ *
+ * tests/blend_error_ref/blend_error_ref.c with the bias term of the display section of include/rtpbr.h: every usable pixel's
+ * product is scaled by the square of its OWN slope before the window sums it, and the centre adds the mean as it is.  Built on
+ * demand by tests/blend_display_ref_lib.py the same way (the oracle's source is included for its tone map: hidden visibility,
+ * -Bsymbolic, only bdr_* is exported); the ladders come from tests/levels_ref_lib.py.  tests/test_blend_display_ref.py holds the
+ * frame, the weight and the depth this file makes equal to levels_ref's, and the plane equal to blend_error_ref's where the two
+ * rules agree.  The HIP kernels are the ERR instances of level_blend<R, FIRST, LAST> and blend_error<R, DISPLAY>
+ * (raytracingpbr_amd/csrc/rt_half.hip).
+ */
+#include "../../oracle/rt_oracle.c"
+
+#define BDR_API __attribute__((visibility("default")))
+
+static inline float bdr_lum(const float* c) { return (0.299f * c[0] + 0.587f * c[1]) + 0.114f * c[2]; }
+static inline float bdr_display_lum(const rtpbr_config* cfg, const float* c3) {
+    const float c[4] = {c3[0], c3[1], c3[2], 1.0f};
+    const v3 d = tone_map(cfg, c);
+    const float d3[3] = {d.x, d.y, d.z};
+    return bdr_lum(d3);
+}
+
+/* image, half_a, half_b (W,H,4); fd, fa, fb (K + 1, W, H, 3): F_0 .. F_K of the three; m = (float)min_half_samples, z2 = z * z as
+ * the host computes it; radius: the blend's window; window: the error's.
+ * out (W,H,3), weight, depth (W,H): what rtpbr_denoise_blend_levels writes; error (W,H): RTPBR_BUF_BLEND_ERROR;
+ * parts (3, W, H): S / n, bias2 (the display-space mean) and the centre's s of every pixel (0 where p is not valid);
+ * stats = {pixels_estimated, pixels_above, bits of the largest error} */
+BDR_API int bdr_blend_error(const rtpbr_config* cfg, const float* image, const float* half_a, const float* half_b, const float* fd,
+                            const float* fa, const float* fb, const int32_t* object, int K, int radius, float z2, float m, int window,
+                            float threshold, float* out, float* weight, float* depth, float* error, float* parts, uint32_t* stats) {
+    if (radius < 1 || radius > 3 || window < 1 || window > 3 || K < 0) return -1;
+    const int W = cfg->width, H = cfg->height;
+    const size_t n = (size_t)W * H;
+    float* buf = (float*)malloc(n * 15 * sizeof(float));
+    unsigned char* flag = (unsigned char*)malloc(n * 2);
+    if (!buf || !flag) { free(buf); free(flag); return RTPBR_ENOMEM; }
+    float *aq = buf, *qq = buf + n, *xq = buf + 2 * n, *run = buf + 3 * n, *xa = buf + 6 * n, *xb = buf + 9 * n;
+    float *eq = buf + 12 * n, *bq = buf + 13 * n, *sl = buf + 14 * n;
+    unsigned char *usable = flag, *valid = flag + n;
+    for (size_t q = 0; q < n; q++) {
+        const float cA = half_a[q * 4 + 3], cB = half_b[q * 4 + 3];
+        usable[q] = cA >= m && cB >= m;
+        valid[q] = cA > 0.0f && cB > 0.0f;
+        weight[q] = 1.0f;      /* T_0 */
+        depth[q] = 0.0f;
+        for (int ch = 0; ch < 3; ch++) {
+            run[q * 3 + ch] = fd[q * 3 + ch];      /* c = FD_0 */
+            xa[q * 3 + ch] = fa[q * 3 + ch];       /* XA = FA_0 */
+            xb[q * 3 + ch] = fb[q * 3 + ch];       /* XB = FB_0 */
+        }
+    }
+    for (int k = 1; k <= K; k++) {
+        const float *fdk = fd + (size_t)k * n * 3, *fak = fa + (size_t)k * n * 3, *fbk = fb + (size_t)k * n * 3;
+        const float *fd0 = fdk - n * 3, *fa0 = fak - n * 3, *fb0 = fbk - n * 3;      /* the finer level */
+        for (size_t q = 0; q < n; q++) {
+            aq[q] = qq[q] = xq[q] = 0.0f;
+            if (!usable[q]) continue;
+            const float cA = half_a[q * 4 + 3], cB = half_b[q * 4 + 3];
+            const float f = (cA * cB) / ((cA + cB) * (cA + cB));
+            const float lA0 = bdr_lum(fa0 + q * 3), lB0 = bdr_lum(fb0 + q * 3), lD0 = bdr_lum(fd0 + q * 3);
+            const float dA = bdr_lum(fak + q * 3) - lA0;
+            const float dB = bdr_lum(fbk + q * 3) - lB0;
+            const float dp = lA0 - lB0;
+            const float dd = dA - dB;
+            const float dl = bdr_lum(fdk + q * 3) - lD0;
+            aq[q] = (f * dp) * dd;
+            qq[q] = dl * dl;
+            xq[q] = dA * dB;
+        }
+        for (int x = 0; x < W; x++)
+            for (int y = 0; y < H; y++) {
+                const size_t p = (size_t)x * H + y;
+                float t = 1.0f;
+                if (usable[p]) {
+                    float cn = 0.0f, SC = 0.0f, SQ = 0.0f, SX = 0.0f, SXX = 0.0f;
+                    for (int dy = -radius; dy <= radius; dy++) {
+                        const int yq = y + dy;
+                        if (yq < 0 || yq >= H) continue;
+                        for (int dx = -radius; dx <= radius; dx++) {
+                            const int xx = x + dx;
+                            if (xx < 0 || xx >= W) continue;
+                            const size_t q = (size_t)xx * H + yq;
+                            if (object[q] != object[p] || !usable[q]) continue;
+                            cn = cn + 1.0f;
+                            SC = SC + aq[q];
+                            SQ = SQ + qq[q];
+                            SX = SX + xq[q];
+                            SXX = SXX + xq[q] * xq[q];
+                        }
+                    }
+                    const float m1 = SX / cn;
+                    const float v = fmaxf(SXX / cn - m1 * m1, 0.0f);
+                    if (m1 > 0.0f && (m1 * m1) * cn > z2 * v) {
+                        t = -SC / SQ;
+                        if (!(t < 1.0f)) t = 1.0f;
+                        if (t < 0.0f) t = 0.0f;
+                    }
+                }
+                const float T = weight[p] * t;
+                weight[p] = T;
+                depth[p] = depth[p] + T;
+                for (int ch = 0; ch < 3; ch++) {
+                    run[p * 3 + ch] = run[p * 3 + ch] + T * (fdk[p * 3 + ch] - fd0[p * 3 + ch]);
+                    xa[p * 3 + ch] = xa[p * 3 + ch] + T * (fak[p * 3 + ch] - fa0[p * 3 + ch]);
+                    xb[p * 3 + ch] = xb[p * 3 + ch] + T * (fbk[p * 3 + ch] - fb0[p * 3 + ch]);
+                }
+            }
+    }
+    const float *fdK = fd + (size_t)K * n * 3, *faK = fa + (size_t)K * n * 3, *fbK = fb + (size_t)K * n * 3;
+    for (size_t p = 0; p < n; p++) {
+        const float* b = image + p * 4;
+        const float T = weight[p];
+        const float* A3 = T == 1.0f ? faK + p * 3 : xa + p * 3;      /* if T_K == 1: XA = FA_K, XB = FB_K */
+        const float* B3 = T == 1.0f ? fbK + p * 3 : xb + p * 3;
+        eq[p] = bq[p] = sl[p] = 0.0f;
+        if (valid[p]) {
+            const float cA = half_a[p * 4 + 3], cB = half_b[p * 4 + 3];
+            const float dl = bdr_display_lum(cfg, A3) - bdr_display_lum(cfg, B3);
+            eq[p] = fmaxf((dl * dl) * ((cA * cB) / ((cA + cB) * (cA + cB))), 0.0f);
+        }
+        if (usable[p]) {
+            const float* a = half_a + p * 4;
+            const float* hb = half_b + p * 4;
+            const float pa[3] = {a[0] / a[3], a[1] / a[3], a[2] / a[3]};
+            const float pb[3] = {hb[0] / hb[3], hb[1] / hb[3], hb[2] / hb[3]};
+            bq[p] = (bdr_lum(A3) - bdr_lum(pa)) * (bdr_lum(B3) - bdr_lum(pb));      /* x_q */
+        }
+        v3 d;
+        if (b[3] > 0.0f) {
+            const float* c3 = T == 1.0f ? fdK + p * 3 : run + p * 3;
+            const float c[4] = {c3[0], c3[1], c3[2], 1.0f};
+            d = tone_map(cfg, c);
+            const float Y = bdr_lum(c3);
+            if (Y > 0.0f) {
+                const float c1[3] = {1.0625f * c3[0], 1.0625f * c3[1], 1.0625f * c3[2]};
+                const float d3[3] = {d.x, d.y, d.z};
+                sl[p] = (bdr_display_lum(cfg, c1) - bdr_lum(d3)) / (0.0625f * Y);
+            }
+        } else {      /* no samples: what post_process shows; weight 1, depth K */
+            d = tone_map(cfg, b);
+            weight[p] = 1.0f;
+            depth[p] = (float)K;
+        }
+        out[p * 3 + 0] = d.x; out[p * 3 + 1] = d.y; out[p * 3 + 2] = d.z;
+        if (usable[p]) bq[p] = (sl[p] * sl[p]) * bq[p];      /* xd_q */
+    }
+    uint32_t est = 0, above = 0, mx = 0;
+    for (int x = 0; x < W; x++)
+        for (int y = 0; y < H; y++) {
+            const size_t p = (size_t)x * H + y;
+            error[p] = parts[p] = parts[n + p] = parts[2 * n + p] = 0.0f;
+            if (!valid[p]) continue;
+            float S = 0.0f, cn = 0.0f, SX = 0.0f, nb = 0.0f;
+            for (int dy = -window; dy <= window; dy++) {
+                const int yq = y + dy;
+                if (yq < 0 || yq >= H) continue;
+                for (int dx = -window; dx <= window; dx++) {
+                    const int xx = x + dx;
+                    if (xx < 0 || xx >= W) continue;
+                    const size_t q = (size_t)xx * H + yq;
+                    if (object[q] != object[p] || !valid[q]) continue;
+                    S = S + eq[q];
+                    cn = cn + 1.0f;
+                    if (usable[q]) {
+                        SX = SX + bq[q];
+                        nb = nb + 1.0f;
+                    }
+                }
+            }
+            const float bias2 = nb > 0.0f ? fmaxf(SX / nb, 0.0f) : 0.0f;
+            const float s = sl[p];
+            const float er = sqrtf(S / cn + bias2);
+            error[p] = er;
+            parts[p] = S / cn;
+            parts[n + p] = bias2;
+            parts[2 * n + p] = s;
+            est++;
+            if (er > threshold) above++;
+            uint32_t bits;
+            memcpy(&bits, &er, 4);
+            if (bits > mx) mx = bits;
+        }
+    stats[0] = est;
+    stats[1] = above;
+    stats[2] = mx;
+    free(buf);
+    free(flag);
+    return 0;
+}

@@ -4,6 +4,7 @@ sweep behind DESIGN.md section 6n, longer than tests/test_blend_error_ref.py can
 
     python tools/blend_error_calibration.py                  # Cornell v3 64x64, halves 16 / 64 / 256, 6 groups
     python tools/blend_error_calibration.py --halves 16 64 --groups 4
+    python tools/blend_error_calibration.py --bias display   # rtpbr_blend_error_display's rule
 
 Per row: the estimated and the empirical mean-square error of the blended display luminance (the reference's own variance,
 a quarter of the mean square of the difference of its two independent halves, taken off), the variance term against the
@@ -19,6 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import blend_display_ref_lib as bd    # noqa: E402
 import blend_error_ref_lib as be      # noqa: E402
 import feature_ref_lib as fr          # noqa: E402
 import half_ref_lib as hl             # noqa: E402
@@ -31,6 +33,7 @@ ap.add_argument("--halves", type=int, nargs="+", default=[16, 64, 256])
 ap.add_argument("--groups", type=int, default=6)
 ap.add_argument("--ref-spp", type=int, default=2048, help="samples per pixel of each of the reference's two halves")
 ap.add_argument("--window", type=int, default=None)
+ap.add_argument("--bias", choices=("linear", "display"), default="linear", help="rtpbr_blend_error's rule, or rtpbr_blend_error_display's")
 a = ap.parse_args()
 
 
@@ -51,7 +54,7 @@ for base in (1 << 20, 1 << 21):
     o.sample(a.ref_spp)
     tr.append(shown(o.image_buffer))
 truth, tv = 0.5 * (tr[0] + tr[1]), float(np.mean((tr[0] - tr[1]) ** 2)) / 4
-print(f"Cornell v3 {W}x{H}, {a.groups} groups, reference 2 x {a.ref_spp} spp (its own variance {tv:.3e}), window {a.window or 2}")
+print(f"Cornell v3 {W}x{H}, {a.groups} groups, reference 2 x {a.ref_spp} spp (its own variance {tv:.3e}), window {a.window or 2}, {a.bias} bias")
 print("  halves    estimated mse   empirical mse   ratio | variance term / empirical variance | bias term / empirical bias^2 | "
       "top 1 % of the pixels carry | ratio without them")
 G = a.groups
@@ -64,7 +67,7 @@ for h in a.halves:
         for _ in range(2):
             o.sample(h)
             hv.update(o.image_buffer)
-        got = be.blend_error(cfg, o.image_buffer, hv.a, feats, window=a.window)
+        got = (bd if a.bias == "display" else be).blend_error(cfg, o.image_buffer, hv.a, feats, window=a.window)
         outs.append(lum(got.denoised))
         ests.append(got)
     outs = np.array(outs)
@@ -73,7 +76,8 @@ for h in a.halves:
     mse_emp = float(np.mean((outs - truth) ** 2)) - tv
     e2 = np.array([e.error.astype(np.float64) ** 2 for e in ests])
     v = float(np.mean([e.variance.mean() for e in ests]))
-    b = float(np.mean([(e.slope.astype(np.float64) ** 2 * e.bias2).mean() for e in ests]))
+    # (the display rule's bias2 is in display space already)
+    b = float(np.mean([(e.bias2 if a.bias == "display" else e.slope.astype(np.float64) ** 2 * e.bias2).mean() for e in ests]))
     per_pixel = e2.mean(0)
     top = per_pixel >= np.quantile(per_pixel, 0.99)
     rest = float(per_pixel[~top].mean()) / (float(np.mean(((outs - truth) ** 2).mean(0)[~top])) - tv)

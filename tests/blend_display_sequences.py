@@ -7,7 +7,6 @@ the same refusals, the same frame, weight and depth —; the plane holds what th
 either and goes with a new resolution; rtpbr_select_blend_error reads it whichever call left it."""
 import numpy as np
 
-import blend_display_ref_lib as bd
 import blend_error_ref_lib as be
 import blend_error_sequences as bs
 import call_sequences as cs
@@ -49,11 +48,11 @@ class BlendDisplayState(bs.BlendErrorState):
 class BlendDisplayModel(bs.BlendErrorModel):
     STATE = BlendDisplayState
 
-    def _do_blend_error(self, op, rule=be):
+    def _do_blend_error(self, op, display=False):
         a = op.args
         r, z, m = a["blend"] or (None, None, None)
-        b = rule.blend_error(self.st.cfg, self.o.image_buffer, self.halves.a, self._features(), a["threshold"], r, z, m, a["window"],
-                             **a["params"])
+        b = be.blend_error(self.st.cfg, self.o.image_buffer, self.halves.a, self._features(), a["threshold"], r, z, m, a["window"],
+                           display=display, **a["params"])
         self.blend = b
         self.last["denoised_pixels"] = b.denoised
         self.events.append((op.kind, b.stats[0], b.error.size, int((b.weight < 1).sum()), bool((b.bias2 > 0).any())))
@@ -61,7 +60,7 @@ class BlendDisplayModel(bs.BlendErrorModel):
                 "stats": (b.stats[0], b.stats[1], int(np.float32(b.stats[2]).view(np.uint32)))}
 
     def _do_blend_error_display(self, op):
-        return self._do_blend_error(op, bd)
+        return self._do_blend_error(op, display=True)
 
 
 class _Grammar(bs._Grammar):

@@ -1,12 +1,19 @@
 /*
- * blend_error_ref.c — CPU restatement of rtpbr_blend_error (TEST INFRASTRUCTURE ONLY).
+ * blend_error_ref.c — CPU restatement of rtpbr_blend_error and rtpbr_blend_error_display (TEST INFRASTRUCTURE ONLY).
  *
  * Built on demand by tests/blend_error_ref_lib.py the way tests/levels_ref_lib.py builds the levels' restatement: the oracle's
  * source is included for its tone map (hidden visibility, -Bsymbolic: only ber_* is exported).  The three ladders F_0 .. F_K come
  * from tests/levels_ref_lib.py, the subtract pass from tests/half_ref_lib.py; the weights T_k are restated here from the
  * blend-levels section so that XA and XB can follow them level by level (tests/test_blend_error_ref.py holds the frame, the
  * weight and the depth this file makes equal to levels_ref's).  The arithmetic follows include/rtpbr.h operation by operation; the
- * HIP kernels are the ERR instances of level_blend<R, FIRST, LAST> and blend_error<R> (raytracingpbr_amd/csrc/rt_half.hip).
+ * HIP kernels are the ERR instances of level_blend<R, FIRST, LAST> and blend_error<R, DISPLAY>
+ * (raytracingpbr_amd/csrc/rt_half.hip).
+ *
+ * The two rules differ in the bias term alone, and `display` selects nothing else.  rtpbr_blend_error (display = 0): the window
+ * averages the products x_q of its usable pixels in linear space and the centre scales the mean by the square of its own slope,
+ * sqrt(S / n + s * s * bias2).  rtpbr_blend_error_display (display != 0, the display section of include/rtpbr.h): every usable
+ * pixel's product is scaled by the square of its OWN slope before the window sums it, xd_q = s_q * s_q * x_q, and the centre adds
+ * the mean as it is, sqrt(S / n + bias2).  tests/test_blend_display_ref.py holds the two planes equal where the rules agree.
  */
 #include "../../oracle/rt_oracle.c"
 
@@ -23,11 +30,14 @@ static inline float ber_display_lum(const rtpbr_config* cfg, const float* c3) {
 /* image, half_a, half_b (W,H,4); fd, fa, fb (K + 1, W, H, 3): F_0 .. F_K of the three; m = (float)min_half_samples, z2 = z * z as
  * the host computes it; radius: the blend's window; window: the error's.
  * out (W,H,3), weight, depth (W,H): what rtpbr_denoise_blend_levels writes; error (W,H): RTPBR_BUF_BLEND_ERROR;
- * parts (3, W, H): S / n, bias2 and s of every pixel (0 where p is not valid);
+ * parts (3, W, H): S / n, bias2 and s of every pixel (0 where p is not valid).  display = 0: bias2 is the linear-space mean, which
+ * the error multiplies by s * s; display != 0: bias2 is the display-space mean, which the error adds as it is, and s, the centre's
+ * slope, is not in the error at all;
  * stats = {pixels_estimated, pixels_above, bits of the largest error} */
 BER_API int ber_blend_error(const rtpbr_config* cfg, const float* image, const float* half_a, const float* half_b, const float* fd,
                             const float* fa, const float* fb, const int32_t* object, int K, int radius, float z2, float m, int window,
-                            float threshold, float* out, float* weight, float* depth, float* error, float* parts, uint32_t* stats) {
+                            float threshold, int display, float* out, float* weight, float* depth, float* error, float* parts,
+                            uint32_t* stats) {
     if (radius < 1 || radius > 3 || window < 1 || window > 3 || K < 0) return -1;
     const int W = cfg->width, H = cfg->height;
     const size_t n = (size_t)W * H;
@@ -123,7 +133,7 @@ BER_API int ber_blend_error(const rtpbr_config* cfg, const float* image, const f
             const float* hb = half_b + p * 4;
             const float pa[3] = {a[0] / a[3], a[1] / a[3], a[2] / a[3]};
             const float pb[3] = {hb[0] / hb[3], hb[1] / hb[3], hb[2] / hb[3]};
-            bq[p] = (ber_lum(A3) - ber_lum(pa)) * (ber_lum(B3) - ber_lum(pb));
+            bq[p] = (ber_lum(A3) - ber_lum(pa)) * (ber_lum(B3) - ber_lum(pb));      /* x_q */
         }
         v3 d;
         if (b[3] > 0.0f) {
@@ -142,6 +152,7 @@ BER_API int ber_blend_error(const rtpbr_config* cfg, const float* image, const f
             depth[p] = (float)K;
         }
         out[p * 3 + 0] = d.x; out[p * 3 + 1] = d.y; out[p * 3 + 2] = d.z;
+        if (display && usable[p]) bq[p] = (sl[p] * sl[p]) * bq[p];      /* xd_q */
     }
     uint32_t est = 0, above = 0, mx = 0;
     for (int x = 0; x < W; x++)
@@ -168,7 +179,7 @@ BER_API int ber_blend_error(const rtpbr_config* cfg, const float* image, const f
             }
             const float bias2 = nb > 0.0f ? fmaxf(SX / nb, 0.0f) : 0.0f;
             const float s = sl[p];
-            const float er = sqrtf(S / cn + (s * s) * bias2);
+            const float er = display ? sqrtf(S / cn + bias2) : sqrtf(S / cn + (s * s) * bias2);
             error[p] = er;
             parts[p] = S / cn;
             parts[n + p] = bias2;

@@ -5,53 +5,18 @@ exported).
 The subtract pass goes through half_ref_lib; features come from feature_ref_lib.features() or from the renderer under test
 (dicts albedo / normal / depth / object)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import feature_ref_lib as fr
 import half_ref_lib as hl
 from raytracingpbr_amd.dataclass import BlendParams, DenoiseParams
+from ref_build import F, I, Library, P, ROOT, f32, ptr      # noqa: F401 (ROOT: for the tests)
 
-ROOT = fr.ROOT
-DIR = os.path.join(ROOT, "tests", "blend_ref")
-SRC = os.path.join(DIR, "blend_ref.c")
-LIB = os.path.join(DIR, "libblend_ref.so")
-DEPS = [SRC] + fr.DEPS[1:]
-FLAGS = fr.FLAGS
-
-_lib = None
-
-
-def build():
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CC", "gcc")] + FLAGS + [SRC, "-o", tmp, "-lm"], check=True)
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        l = C.CDLL(build())
-        p, i, f = C.c_void_p, C.c_int, C.c_float
-        l.br_filter.restype = i
-        l.br_filter.argtypes = [p, p, p, p, p, p, i, i, f, f, f, f, i, p]
-        l.br_blend.restype = i
-        l.br_blend.argtypes = [p, p, p, p, p, p, p, p, i, f, f, p, p, p]
-        _lib = l
-    return _lib
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32)
+_ref = Library("blend_ref", {
+    "br_filter": [P, P, P, P, P, P, I, I, F, F, F, F, I, P],
+    "br_blend": [P, P, P, P, P, P, P, P, I, F, F, P, P, P],
+})
+build, lib = _ref.build, _ref.lib
 
 
 def filter(cfg, image_buffer, feats, linear=True, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None,
@@ -59,14 +24,14 @@ def filter(cfg, image_buffer, feats, linear=True, iterations=None, demodulate=No
     """(W,H,3) — rtpbr_denoise's filter of this buffer; linear: stopped before the tone map (+0 for a pixel without samples)."""
     d = DenoiseParams.DEFAULTS
     pick = lambda v, k: d[k] if v is None else v      # noqa: E731
-    ib = _f32(image_buffer)
+    ib = f32(image_buffer)
     f = {k: np.ascontiguousarray(feats[k]) for k in ("albedo", "normal", "depth", "object")}
     assert f["object"].dtype == np.int32 and ib.shape == (cfg.width, cfg.height, 4)
     out = np.empty((cfg.width, cfg.height, 3), np.float32)
-    rc = lib().br_filter(C.cast(C.pointer(cfg), C.c_void_p), _ptr(ib), _ptr(f["albedo"]), _ptr(f["normal"]), _ptr(f["depth"]), _ptr(f["object"]),
+    rc = lib().br_filter(C.cast(C.pointer(cfg), C.c_void_p), ptr(ib), ptr(f["albedo"]), ptr(f["normal"]), ptr(f["depth"]), ptr(f["object"]),
                          int(pick(iterations, "iterations")), int(pick(demodulate, "demodulate")), float(pick(sigma_color, "sigma_color")),
                          float(pick(sigma_normal, "sigma_normal")), float(pick(sigma_depth, "sigma_depth")),
-                         float(pick(sigma_albedo, "sigma_albedo")), 1 if linear else 0, _ptr(out))
+                         float(pick(sigma_albedo, "sigma_albedo")), 1 if linear else 0, ptr(out))
     assert rc == 0, rc
     return out
 
@@ -76,7 +41,7 @@ class Filtered:
 
     def __init__(self, cfg, image_buffer, half_a, feats, **denoise):
         self.cfg = cfg
-        self.b, self.a = _f32(image_buffer), _f32(half_a)
+        self.b, self.a = f32(image_buffer), f32(half_a)
         self.hb = hl.subtract(self.b, self.a)
         self.obj = np.ascontiguousarray(feats["object"])
         self.fd = filter(cfg, self.b, feats, True, **denoise)
@@ -92,8 +57,8 @@ class Filtered:
         W, H = self.cfg.width, self.cfg.height
         weight, out = np.empty((W, H), np.float32), np.empty((W, H, 3), np.float32)
         st = np.zeros(3, np.uint32)
-        rc = lib().br_blend(C.cast(C.pointer(self.cfg), C.c_void_p), _ptr(self.b), _ptr(self.a), _ptr(self.hb), _ptr(self.fd), _ptr(self.fa),
-                            _ptr(self.fb), _ptr(self.obj), r, float(zz * zz), float(np.float32(m)), _ptr(weight), _ptr(out), _ptr(st))
+        rc = lib().br_blend(C.cast(C.pointer(self.cfg), C.c_void_p), ptr(self.b), ptr(self.a), ptr(self.hb), ptr(self.fd), ptr(self.fa),
+                            ptr(self.fb), ptr(self.obj), r, float(zz * zz), float(np.float32(m)), ptr(weight), ptr(out), ptr(st))
         assert rc == 0, rc
         return out, weight, (int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0]))
 

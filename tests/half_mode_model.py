@@ -18,6 +18,7 @@ the error map with them.  A bad argument and a bad state together have no code i
 import numpy as np
 
 import call_sequences as cs
+import checks as ck
 import half_mode_ref_lib as hm
 import half_ref_lib as hl
 import post_model as pm
@@ -25,10 +26,6 @@ import post_model as pm
 EINVAL, ESTATE, MISSING = cs.EINVAL, cs.ESTATE, pm.MISSING
 HALF_KINDS = ("set_half_mode", "half_update", "denoise_error", "select_error")
 DEALT = ("dealt:persistent", "dealt:tiles")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def mode_of(op):
@@ -147,7 +144,7 @@ class HalfModel(pm.MotionModel):
         h = self._halves()
         if len(colours):
             A, s, b = hm.fold(colours, h.a, h.snapshot, before, mask)
-            assert np.array_equal(_bits(b), _bits(self.o.image_buffer)), "the fold's image_buffer is not the call's without the mode"
+            assert np.array_equal(ck.bits(b), ck.bits(self.o.image_buffer)), "the fold's image_buffer is not the call's without the mode"
             h.a[:], h.snapshot[:] = A, s
             n_sel = before.shape[0] * before.shape[1] if mask is None else int((np.asarray(mask) != 0).sum())
             self.events.append(("dealt", "sample" if mask is None else "sample_selected", len(colours), n_sel, self.st.tracking))
@@ -228,7 +225,7 @@ class HalfModel(pm.MotionModel):
         if w is False:
             self.halves.restart(ib)
         else:
-            assert np.array_equal(_bits(w[0]), _bits(ib)) and np.array_equal(_bits(w[1]), _bits(out["motion"])), \
+            assert np.array_equal(ck.bits(w[0]), ck.bits(ib)) and np.array_equal(ck.bits(w[1]), ck.bits(out["motion"])), \
                 "the gather of half A and the model's own gather disagree on the image"
             self.halves.a[:], self.halves.snapshot[:] = w[2], ib
             both = (w[2][..., 3] > 0) & (ib[..., 3] - w[2][..., 3] > 0)

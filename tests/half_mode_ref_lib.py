@@ -7,49 +7,19 @@ fold() is the per-sample dealing of a sample call with per_sample on, fed with p
 rtpbr_reproject / rtpbr_reproject_scene leave with warp on."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-import feature_ref_lib as fr
 from raytracingpbr_amd.dataclass import Camera, ReprojectParams, SDFObject
+from ref_build import F, I, Library, ORACLE_DEPS, ORACLE_FLAGS, P, ROOT, ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIR = os.path.join(ROOT, "tests", "half_mode_ref")
-SRC = os.path.join(DIR, "half_mode_ref.c")
-MAP = os.path.join(DIR, "half_mode_ref.map")
-LIB = os.path.join(DIR, "libhalf_mode_ref.so")
-DEPS = [SRC, MAP, os.path.join(ROOT, "tests", "reproject_scene_ref", "reproject_scene_ref.c")] + \
-       [os.path.join(ROOT, "oracle", f) for f in ("rt_oracle.c", "rt_oracle.h", "rt_oracle_math.h")] + [os.path.join(ROOT, "include", "rtpbr.h")]
-FLAGS = fr.FLAGS + ["-Wl,--version-script=" + MAP]
-
-_lib = None
-
-
-def build():
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CC", "gcc")] + FLAGS + [SRC, "-o", tmp, "-lm"], check=True)
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        l = C.CDLL(build())
-        p, i, f = C.c_void_p, C.c_int, C.c_float
-        l.hm_fold.restype = i
-        l.hm_fold.argtypes = [i, i, i, p, p, p, p, p]
-        l.hm_gather.restype = i
-        l.hm_gather.argtypes = [p, p, p, p, i, p, i, i] + [p] * 8 + [f, f, f, p, p, p]
-        _lib = l
-    return _lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+MAP = os.path.join(ROOT, "tests", "half_mode_ref", "half_mode_ref.map")
+_ref = Library("half_mode_ref", {
+    "hm_fold": [I, I, I, P, P, P, P, P],
+    "hm_gather": [P, P, P, P, I, P, I, I] + [P] * 8 + [F, F, F, P, P, P],
+}, flags=ORACLE_FLAGS + ["-Wl,--version-script=" + MAP],
+   deps=ORACLE_DEPS + [MAP, os.path.join(ROOT, "tests", "reproject_scene_ref", "reproject_scene_ref.c")])
+build, lib = _ref.build, _ref.lib
 
 
 def _cam(c):
@@ -72,7 +42,7 @@ def fold(colours, half_a, half_sh, image_buffer, mask=None):
     if mask is not None:
         m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
         assert m.shape == (W, H)
-    rc = lib().hm_fold(n, W, H, _ptr(c), _ptr(m), _ptr(A), _ptr(s), _ptr(b))
+    rc = lib().hm_fold(n, W, H, ptr(c), ptr(m), ptr(A), ptr(s), ptr(b))
     assert rc == 0, rc
     return A, s, b
 
@@ -110,9 +80,9 @@ def gather(cfg, old_scene, new_scene, old_camera, new_camera, image_buffer, half
     c1 = c0 if new_camera is None else _cam(new_camera)
     rc = lib().hm_gather(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(c0), C.c_void_p), C.cast(C.pointer(c1), C.c_void_p),
                          C.cast(_objs(old_scene), C.c_void_p), 1 if old_scene.scale10 else 0, C.cast(_objs(new_scene), C.c_void_p),
-                         1 if new_scene.scale10 else 0, len(old_scene.objects), _ptr(ib), _ptr(a), _ptr(o["normal"]), _ptr(o["depth"]),
-                         _ptr(o["object"]), _ptr(n["normal"]), _ptr(n["depth"]), _ptr(n["object"]),
+                         1 if new_scene.scale10 else 0, len(old_scene.objects), ptr(ib), ptr(a), ptr(o["normal"]), ptr(o["depth"]),
+                         ptr(o["object"]), ptr(n["normal"]), ptr(n["depth"]), ptr(n["object"]),
                          float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
-                         float(pick(normal_cos, "normal_cos")), _ptr(out), _ptr(motion), _ptr(half))
+                         float(pick(normal_cos, "normal_cos")), ptr(out), ptr(motion), ptr(half))
     assert rc == 0, rc
     return out, motion, half

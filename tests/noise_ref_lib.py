@@ -4,56 +4,19 @@ of rtpbr_reproject (tests/noise_ref/noise_ref.c), built on demand the way tests/
 
 Features come from feature_ref_lib.features() or from the renderer under test (dicts albedo / normal / depth / object)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import feature_ref_lib as fr
 from raytracingpbr_amd.dataclass import Camera, DenoiseGuidedParams, ReprojectParams
+from ref_build import F, I, Library, P, ROOT, f32, ptr      # noqa: F401 (ROOT: for the tests)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIR = os.path.join(ROOT, "tests", "noise_ref")
-SRC = os.path.join(DIR, "noise_ref.c")
-LIB = os.path.join(DIR, "libnoise_ref.so")
-DEPS = [SRC] + [os.path.join(ROOT, "oracle", f) for f in ("rt_oracle.c", "rt_oracle.h", "rt_oracle_math.h")] + [os.path.join(ROOT, "include", "rtpbr.h")]
-FLAGS = fr.FLAGS
-
-_lib = None
-
-
-def build():
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CC", "gcc")] + FLAGS + [SRC, "-o", tmp, "-lm"], check=True)
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        l = C.CDLL(build())
-        p, i, f = C.c_void_p, C.c_int, C.c_float
-        l.nr_update.restype = i
-        l.nr_update.argtypes = [i, i, p, p, p]
-        l.nr_estimate.restype = i
-        l.nr_estimate.argtypes = [i, i, p, p, p, f, p, p, p]
-        l.nr_guided.restype = i
-        l.nr_guided.argtypes = [p, p, p, p, p, p, p, i, i, f, f, f, f, p]
-        l.nr_reproject.restype = i
-        l.nr_reproject.argtypes = [p] * 11 + [f, f, f, p, p]
-        _lib = l
-    return _lib
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32)
+_ref = Library("noise_ref", {
+    "nr_update": [I, I, P, P, P],
+    "nr_estimate": [I, I, P, P, P, F, P, P, P],
+    "nr_guided": [P, P, P, P, P, P, P, I, I, F, F, F, F, P],
+    "nr_reproject": [P] * 11 + [F, F, F, P, P],
+})
+build, lib = _ref.build, _ref.lib
 
 
 class Tracker:
@@ -65,9 +28,9 @@ class Tracker:
         self.snapshot = np.zeros((W, H, 4), np.float32)
 
     def update(self, image_buffer):
-        ib = _f32(image_buffer)
+        ib = f32(image_buffer)
         assert ib.shape == (self.W, self.H, 4)
-        rc = lib().nr_update(self.W, self.H, _ptr(ib), _ptr(self.snapshot), _ptr(self.moments))
+        rc = lib().nr_update(self.W, self.H, ptr(ib), ptr(self.snapshot), ptr(self.moments))
         assert rc == 0, rc
         return self.moments
 
@@ -77,18 +40,18 @@ class Tracker:
 
     def written(self, image_buffer):
         """rtpbr_write_buffer(IMAGE_BUFFER): the snapshot is re-taken"""
-        self.snapshot[:] = _f32(image_buffer)
+        self.snapshot[:] = f32(image_buffer)
 
 
 def estimate(image_buffer, moments, obj, threshold=0.0):
     """(noise (W,H), var0 (W,H), (pixels_estimated, pixels_above, max_noise)) — what rtpbr_noise_estimate computes."""
-    ib, M = _f32(image_buffer), _f32(moments)
+    ib, M = f32(image_buffer), f32(moments)
     W, H = ib.shape[:2]
     o = np.ascontiguousarray(obj)
     assert o.dtype == np.int32 and o.shape == (W, H) and M.shape == (W, H, 4)
     noise, var0 = np.empty((W, H), np.float32), np.empty((W, H), np.float32)
     st = np.zeros(3, np.uint32)
-    rc = lib().nr_estimate(W, H, _ptr(ib), _ptr(M), _ptr(o), float(threshold), _ptr(noise), _ptr(var0), _ptr(st))
+    rc = lib().nr_estimate(W, H, ptr(ib), ptr(M), ptr(o), float(threshold), ptr(noise), ptr(var0), ptr(st))
     assert rc == 0, rc
     return noise, var0, (int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0]))
 
@@ -98,15 +61,15 @@ def guided(cfg, image_buffer, feats, var0, iterations=None, demodulate=None, sig
     """(W,H,3) — what rtpbr_denoise_guided writes from this image_buffer, these features and this level-0 variance."""
     d = DenoiseGuidedParams.DEFAULTS
     pick = lambda v, k: d[k] if v is None else v      # noqa: E731
-    ib = _f32(image_buffer)
+    ib = f32(image_buffer)
     f = {k: np.ascontiguousarray(feats[k]) for k in ("albedo", "normal", "depth", "object")}
     assert f["object"].dtype == np.int32
-    v0 = _f32(var0)
+    v0 = f32(var0)
     out = np.empty((cfg.width, cfg.height, 3), np.float32)
-    rc = lib().nr_guided(C.cast(C.pointer(cfg), C.c_void_p), _ptr(ib), _ptr(f["albedo"]), _ptr(f["normal"]), _ptr(f["depth"]), _ptr(f["object"]),
-                         _ptr(v0), int(pick(iterations, "iterations")), int(pick(demodulate, "demodulate")), float(pick(sigma_color, "sigma_color")),
+    rc = lib().nr_guided(C.cast(C.pointer(cfg), C.c_void_p), ptr(ib), ptr(f["albedo"]), ptr(f["normal"]), ptr(f["depth"]), ptr(f["object"]),
+                         ptr(v0), int(pick(iterations, "iterations")), int(pick(demodulate, "demodulate")), float(pick(sigma_color, "sigma_color")),
                          float(pick(sigma_normal, "sigma_normal")), float(pick(sigma_depth, "sigma_depth")),
-                         float(pick(variance_floor, "variance_floor")), _ptr(out))
+                         float(pick(variance_floor, "variance_floor")), ptr(out))
     assert rc == 0, rc
     return out
 
@@ -121,14 +84,14 @@ def reproject(cfg, old_camera, new_camera, image_buffer, moments, old_feats, new
     d = ReprojectParams.DEFAULTS
     pick = lambda v, k: d[k] if v is None else v      # noqa: E731
     W, H = cfg.width, cfg.height
-    ib, M = _f32(image_buffer), _f32(moments)
+    ib, M = f32(image_buffer), f32(moments)
     o = {k: np.ascontiguousarray(old_feats[k]) for k in ("normal", "depth", "object")}
     n = {k: np.ascontiguousarray(new_feats[k]) for k in ("normal", "depth", "object")}
     out, mo = np.empty((W, H, 4), np.float32), np.empty((W, H, 4), np.float32)
     c0, c1 = _cam(old_camera), _cam(new_camera)
     rc = lib().nr_reproject(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(c0), C.c_void_p), C.cast(C.pointer(c1), C.c_void_p),
-                            _ptr(ib), _ptr(M), _ptr(o["normal"]), _ptr(o["depth"]), _ptr(o["object"]), _ptr(n["normal"]), _ptr(n["depth"]),
-                            _ptr(n["object"]), float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
-                            float(pick(normal_cos, "normal_cos")), _ptr(out), _ptr(mo))
+                            ptr(ib), ptr(M), ptr(o["normal"]), ptr(o["depth"]), ptr(o["object"]), ptr(n["normal"]), ptr(n["depth"]),
+                            ptr(n["object"]), float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
+                            float(pick(normal_cos, "normal_cos")), ptr(out), ptr(mo))
     assert rc == 0, rc
     return out, mo

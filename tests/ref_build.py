@@ -1,0 +1,59 @@
+"""Test helper: builds and loads a C restatement (tests/<stem>/<stem>.c -> tests/<stem>/lib<stem>.so) on demand.
+
+A restatement that includes the oracle's source carries its own copy of every rto_* symbol: the oracle's flags come with hidden
+visibility and -Bsymbolic (only the functions marked in the source are exported) so that it never interposes with
+oracle/librt_oracle.so, which the other tests load RTLD_GLOBAL into the same process.  Results are compared bit for bit, so the
+flags are part of what a restatement computes."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P, I, F = C.c_void_p, C.c_int, C.c_float      # for the argtypes tables
+# the oracle's flags (oracle/Makefile) + hidden symbols
+ORACLE_FLAGS = ["-O2", "-std=gnu11", "-fPIC", "-shared", "-march=x86-64-v3", "-ffp-contract=off", "-fno-fast-math", "-fopenmp",
+                "-fvisibility=hidden", "-Wl,-Bsymbolic", "-Wno-unused-function", "-Wno-misleading-indentation"]
+# what a restatement that includes oracle/rt_oracle.c is made of, besides its own source
+ORACLE_DEPS = [os.path.join(ROOT, "oracle", f) for f in ("rt_oracle.c", "rt_oracle.h", "rt_oracle_math.h")] + \
+              [os.path.join(ROOT, "include", "rtpbr.h")]
+
+
+class Library:
+    """One restatement: ``functions`` maps every exported name to its argtypes (all return int); ``flags`` is the whole compiler
+    flag set, ``deps`` what the library is made of besides its source (paths)."""
+
+    def __init__(self, stem, functions, flags=ORACLE_FLAGS, deps=ORACLE_DEPS):
+        self.dir = os.path.join(ROOT, "tests", stem)
+        self.src = os.path.join(self.dir, stem + ".c")
+        self.path = os.path.join(self.dir, f"lib{stem}.so")
+        self.functions, self.flags, self.deps = functions, list(flags), [self.src] + list(deps)
+        self._lib = None
+
+    def build(self):
+        """the library's path; compiled when it is missing or older than a dependency (into a file of this process, then
+        renamed: several pytest processes may get here at once)"""
+        if os.path.exists(self.path) and all(os.path.getmtime(self.path) >= os.path.getmtime(d) for d in self.deps):
+            return self.path
+        tmp = f"{self.path}.{os.getpid()}.tmp"
+        subprocess.run([os.environ.get("CC", "gcc")] + self.flags + [self.src, "-o", tmp, "-lm"], check=True)
+        os.replace(tmp, self.path)
+        return self.path
+
+    def lib(self):
+        if self._lib is None:
+            l = C.CDLL(self.build())
+            for name, argtypes in self.functions.items():
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = C.c_int, argtypes
+            self._lib = l
+        return self._lib
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)

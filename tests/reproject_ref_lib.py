@@ -3,46 +3,16 @@ tests/feature_ref_lib.py builds the feature reference (the oracle's flags, hidde
 
 The old and new features come from feature_ref_lib.features()."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import feature_ref_lib as fr
 from raytracingpbr_amd.dataclass import Camera, ReprojectParams
+from ref_build import F, Library, P, ROOT, ptr      # noqa: F401 (ROOT: for the tests)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIR = os.path.join(ROOT, "tests", "reproject_ref")
-SRC = os.path.join(DIR, "reproject_ref.c")
-LIB = os.path.join(DIR, "libreproject_ref.so")
-DEPS = [SRC] + [os.path.join(ROOT, "oracle", f) for f in ("rt_oracle.c", "rt_oracle.h", "rt_oracle_math.h")] + [os.path.join(ROOT, "include", "rtpbr.h")]
-FLAGS = fr.FLAGS
-
-_lib = None
-
-
-def build():
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in DEPS):
-        return LIB
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CC", "gcc")] + FLAGS + [SRC, "-o", tmp, "-lm"], check=True)
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        l = C.CDLL(build())
-        p = C.c_void_p
-        l.rr_reproject.restype = C.c_int
-        l.rr_reproject.argtypes = [p, p, p, p, p, p, p, p, p, p, C.c_float, C.c_float, C.c_float, p, p]
-        _lib = l
-    return _lib
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+_ref = Library("reproject_ref", {
+    "rr_reproject": [P, P, P, P, P, P, P, P, P, P, F, F, F, P, P],
+})
+build, lib = _ref.build, _ref.lib
 
 
 def _cam(c):
@@ -64,8 +34,8 @@ def reproject(cfg, old_camera, new_camera, image_buffer, old_feats, new_feats, m
     motion = np.empty((W, H, 2), np.float32)
     c0, c1 = _cam(old_camera), _cam(new_camera)
     rc = lib().rr_reproject(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(c0), C.c_void_p), C.cast(C.pointer(c1), C.c_void_p),
-                            _ptr(ib), _ptr(o["normal"]), _ptr(o["depth"]), _ptr(o["object"]), _ptr(n["normal"]), _ptr(n["depth"]),
-                            _ptr(n["object"]), float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
-                            float(pick(normal_cos, "normal_cos")), _ptr(out), _ptr(motion))
+                            ptr(ib), ptr(o["normal"]), ptr(o["depth"]), ptr(o["object"]), ptr(n["normal"]), ptr(n["depth"]),
+                            ptr(n["object"]), float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
+                            float(pick(normal_cos, "normal_cos")), ptr(out), ptr(motion))
     assert rc == 0, rc
     return out, motion

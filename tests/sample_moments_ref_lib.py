@@ -1,45 +1,14 @@
 """Test helper: the CPU restatement of the per-sample fold of rtpbr_set_noise_tracking (tests/sample_moments_ref/
 sample_moments_ref.c), built on demand the way tests/noise_ref_lib.py builds the noise reference (the oracle's flags, hidden
 visibility: only smr_* exported), and the per-sample colours it is fed with, taken from the unchanged CPU oracle."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
-import feature_ref_lib as fr
+from ref_build import I, Library, P, ROOT, ptr      # noqa: F401 (ROOT: for the tests)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIR = os.path.join(ROOT, "tests", "sample_moments_ref")
-SRC = os.path.join(DIR, "sample_moments_ref.c")
-LIB = os.path.join(DIR, "libsample_moments_ref.so")
-FLAGS = fr.FLAGS
-
-_lib = None
-
-
-def build():
-    if os.path.exists(LIB) and os.path.getmtime(LIB) >= os.path.getmtime(SRC):
-        return LIB
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CC", "gcc")] + FLAGS + [SRC, "-o", tmp, "-lm"], check=True)
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        l = C.CDLL(build())
-        p, i = C.c_void_p, C.c_int
-        l.smr_fold.restype = i
-        l.smr_fold.argtypes = [i, i, i, p, p, p, p, p]
-        _lib = l
-    return _lib
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+_ref = Library("sample_moments_ref", {
+    "smr_fold": [I, I, I, P, P, P, P, P],
+}, deps=[])
+build, lib = _ref.build, _ref.lib
 
 
 def fold(colours, moments, snapshot, image_buffer, mask=None):
@@ -54,7 +23,7 @@ def fold(colours, moments, snapshot, image_buffer, mask=None):
     if mask is not None:
         m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
         assert m.shape == (W, H)
-    rc = lib().smr_fold(n, W, H, _ptr(c), None if m is None else _ptr(m), _ptr(M), _ptr(s), _ptr(b))
+    rc = lib().smr_fold(n, W, H, ptr(c), None if m is None else ptr(m), ptr(M), ptr(s), ptr(b))
     assert rc == 0, rc
     return M, s, b
 

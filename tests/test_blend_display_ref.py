@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_blend_error_display (tests/blend_display_ref/blend_display_ref.c) that the GPU tests hold
+"""CPU tier: the restatement of rtpbr_blend_error_display (tests/blend_error_ref/blend_error_ref.c with display set) that the GPU tests hold
 the kernels to — the header's mirrors, the identities with rtpbr_denoise_error's and rtpbr_blend_error's restatements, known
 answers of the per-tap rule, the defect of the per-window rule it repairs, and the calibration of the estimate against the
 empirical error on the oracle."""
@@ -8,8 +8,8 @@ import re
 import numpy as np
 import pytest
 
-import blend_display_ref_lib as bd
 import blend_error_ref_lib as be
+import checks as ck
 import feature_ref_lib as fr
 import half_ref_lib as hl
 import hostile as hz
@@ -29,10 +29,6 @@ def _lum(c):
 def _lum64(c):
     c = np.asarray(c, np.float64)
     return 0.299 * c[..., 0] + 0.587 * c[..., 1] + 0.114 * c[..., 2]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _window(v, ok, obj, R, how):
@@ -117,14 +113,14 @@ def test_frame_weight_and_depth_are_the_levels_restatements(K):
         f = lv.Filtered(cfg, ib, a, feats, iterations=K, demodulate=demodulate)
         for radius, z, m in ((1, 0.0, 1), (3, 2.0, 4), (2, 0.0, 4)):
             out, t, depth, _ = f.blend(radius, z, m)
-            got = bd.from_ladders(f, 0.0, radius, z, m, 2)
-            assert np.array_equal(_bits(got.denoised), _bits(out)) and np.array_equal(_bits(got.weight), _bits(t))
-            assert np.array_equal(_bits(got.depth), _bits(depth))
+            got = be.from_ladders(f, 0.0, radius, z, m, 2, display=True)
+            assert np.array_equal(ck.bits(got.denoised), ck.bits(out)) and np.array_equal(ck.bits(got.weight), ck.bits(t))
+            assert np.array_equal(ck.bits(got.depth), ck.bits(depth))
             # variance and slope are the old rule's; the bias term is not, once there are levels
             old = be.from_ladders(f, 0.0, radius, z, m, 2)
-            assert np.array_equal(_bits(got.variance), _bits(old.variance)) and np.array_equal(_bits(got.slope), _bits(old.slope))
+            assert np.array_equal(ck.bits(got.variance), ck.bits(old.variance)) and np.array_equal(ck.bits(got.slope), ck.bits(old.slope))
             if K > 0:
-                assert (got.bias2 > 0).any() and not np.array_equal(_bits(got.error), _bits(old.error))
+                assert (got.bias2 > 0).any() and not np.array_equal(ck.bits(got.error), ck.bits(old.error))
 
 
 # ------------------------------------------------------------------ the identities
@@ -138,8 +134,8 @@ def test_with_nothing_usable_the_plane_is_rtpbr_denoise_errors_bit_for_bit(K):
         for window in (1, 2, 3):
             thr = float(np.median(hl.denoise_error(cfg, ib, a, feats, window, 0.0, **p)[0][valid]))      # some above, some below
             want, st, _ = hl.denoise_error(cfg, ib, a, feats, window, thr, **p)
-            got = bd.from_ladders(f, thr, 3, 0.0, NEVER, window)
-            assert np.array_equal(_bits(got.error), _bits(want)), (K, demodulate, window)
+            got = be.from_ladders(f, thr, 3, 0.0, NEVER, window, display=True)
+            assert np.array_equal(ck.bits(got.error), ck.bits(want)), (K, demodulate, window)
             assert got.stats[:2] == st[:2] and np.float32(got.stats[2]).view(np.uint32) == np.float32(st[2]).view(np.uint32)
             assert got.stats[0] == int(valid.sum()) and 0 < got.stats[1] < got.stats[0]
             assert np.all(got.weight == 1) and not got.bias2.any() and np.all(got.error[~valid] == 0)
@@ -150,13 +146,13 @@ def test_no_levels_without_demodulation_give_the_old_rules_plane_bit_for_bit():
     cfg, feats, ib, a = _cornell_state()
     f = lv.Filtered(cfg, ib, a, feats, iterations=0, demodulate=0)
     for window in (1, 2, 3):
-        got, old = bd.from_ladders(f, 0.01, 2, 0.0, 1, window), be.from_ladders(f, 0.01, 2, 0.0, 1, window)
+        got, old = be.from_ladders(f, 0.01, 2, 0.0, 1, window, display=True), be.from_ladders(f, 0.01, 2, 0.0, 1, window)
         assert got.stats[0] > 0 and got.stats == old.stats and not got.bias2.any()
-        assert np.array_equal(_bits(got.error), _bits(old.error))
+        assert np.array_equal(ck.bits(got.error), ck.bits(old.error))
     # with demodulation XA differs from PA by the rounding of c / albedo * albedo (2 ulp of values below 4: 5e-7): bias2 is a mean
     # of products of two such differences times a squared slope (below 16 on this frame)
     f = lv.Filtered(cfg, ib, a, feats, iterations=0, demodulate=1)
-    got = bd.from_ladders(f, 0.0, 2, 0.0, 1, 2)
+    got = be.from_ladders(f, 0.0, 2, 0.0, 1, 2, display=True)
     assert got.slope.max() < 4 and got.bias2.max() < 16e-12
 
 
@@ -185,8 +181,8 @@ def test_identical_halves_blurred_across_a_ramp_give_the_root_of_the_windows_mea
     a = ib * np.float32(0.5)
     window = 2
     f = lv.Filtered(cfg, ib, a, feats, iterations=1, demodulate=0)
-    assert np.array_equal(_bits(f.fa), _bits(f.fb))
-    got = bd.from_ladders(f, 0.0, 1, 1e6, 8, window)
+    assert np.array_equal(ck.bits(f.fa), ck.bits(f.fb))
+    got = be.from_ladders(f, 0.0, 1, 1e6, 8, window, display=True)
     assert got.stats[0] == W * H and not got.variance.any()
     T = lv.denoise_blend_levels(cfg, ib, a, feats, 1, 1e6, 8, iterations=1, demodulate=0)[1].astype(np.float64)
     xa = f.fa[0] + T[..., None] * (f.fa[1].astype(np.float64) - f.fa[0])
@@ -240,7 +236,7 @@ def test_a_saturated_neighbour_no_longer_lends_its_linear_bias():
     a = ib * np.float32(0.5)
     p = dict(iterations=1, demodulate=0, sigma_color=1e3)
     f = lv.Filtered(cfg, ib, a, feats, **p)
-    got, old = bd.from_ladders(f, 0.0, 1, 1e6, 8, window), be.from_ladders(f, 0.0, 1, 1e6, 8, window)
+    got, old = be.from_ladders(f, 0.0, 1, 1e6, 8, window, display=True), be.from_ladders(f, 0.0, 1, 1e6, 8, window)
     assert got.stats[0] == W * H and not got.variance.any() and not old.variance.any()
     T = lv.denoise_blend_levels(cfg, ib, a, feats, 1, 1e6, 8, **p)[1].astype(np.float64)
     xa = f.fa[0] + T[..., None] * (f.fa[1].astype(np.float64) - f.fa[0])
@@ -318,8 +314,8 @@ def test_the_estimate_is_calibrated_against_the_empirical_error_on_cornell():
             hv.update(snap[2 * h])
             assert np.all(hv.a[..., 3] == h)
             f = lv.Filtered(cfg, snap[2 * h], hv.a, feats)
-            got, old = bd.from_ladders(f), be.from_ladders(f)
-            assert got.stats[0] == W * H and np.array_equal(_bits(got.denoised), _bits(old.denoised))
+            got, old = be.from_ladders(f, display=True), be.from_ladders(f)
+            assert got.stats[0] == W * H and np.array_equal(ck.bits(got.denoised), ck.bits(old.denoised))
             est[h].append(float(np.mean(got.error.astype(np.float64) ** 2)))
             est_old[h].append(float(np.mean(old.error.astype(np.float64) ** 2)))
             emp[h].append(float(np.mean((_lum(got.denoised).astype(np.float64) - truth) ** 2)) - truth_var)

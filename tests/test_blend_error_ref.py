@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import blend_error_ref_lib as be
+import checks as ck
 import feature_ref_lib as fr
 import half_ref_lib as hl
 import hostile as hz
@@ -27,10 +28,6 @@ def _lum(c):
 def _lum64(c):
     c = np.asarray(c, np.float64)
     return 0.299 * c[..., 0] + 0.587 * c[..., 1] + 0.114 * c[..., 2]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _window_mean(v, ok, obj, R):
@@ -80,7 +77,7 @@ def test_header_enum_entry_points_and_defaults_are_mirrored():
     b2, _ = hz.base_buffer(W, H, seed=1)
     f = lv.Filtered(cfg, (a + b2) * 8, a * 8, feats, iterations=2)      # 32 + 32
     for x, y in zip(be.from_ladders(f), be.from_ladders(f, 0.0, 3, 2.0, 16, 2)):
-        assert np.array_equal(_bits(np.asarray(x, np.float32)), _bits(np.asarray(y, np.float32)))
+        assert np.array_equal(ck.bits(np.asarray(x, np.float32)), ck.bits(np.asarray(y, np.float32)))
     assert not np.array_equal(be.from_ladders(f).error, be.from_ladders(f, window=3).error)
 
 
@@ -93,8 +90,8 @@ def test_frame_weight_and_depth_are_the_levels_restatements(K):
         for radius, z, m in ((1, 0.0, 1), (3, 2.0, 4), (2, 0.0, 4)):
             out, t, depth, _ = f.blend(radius, z, m)
             got = be.from_ladders(f, 0.0, radius, z, m, 2)
-            assert np.array_equal(_bits(got.denoised), _bits(out)) and np.array_equal(_bits(got.weight), _bits(t))
-            assert np.array_equal(_bits(got.depth), _bits(depth))
+            assert np.array_equal(ck.bits(got.denoised), ck.bits(out)) and np.array_equal(ck.bits(got.weight), ck.bits(t))
+            assert np.array_equal(ck.bits(got.depth), ck.bits(depth))
 
 
 # ------------------------------------------------------------------ the identity with rtpbr_denoise_error
@@ -109,7 +106,7 @@ def test_with_nothing_usable_the_plane_is_rtpbr_denoise_errors_bit_for_bit(K):
             thr = float(np.median(hl.denoise_error(cfg, ib, a, feats, window, 0.0, **p)[0][valid]))      # some above, some below
             want, st, _ = hl.denoise_error(cfg, ib, a, feats, window, thr, **p)
             got = be.from_ladders(f, thr, 3, 0.0, NEVER, window)
-            assert np.array_equal(_bits(got.error), _bits(want)), (K, demodulate, window)
+            assert np.array_equal(ck.bits(got.error), ck.bits(want)), (K, demodulate, window)
             assert got.stats[:2] == st[:2] and np.float32(got.stats[2]).view(np.uint32) == np.float32(st[2]).view(np.uint32)
             assert got.stats[0] == int(valid.sum()) and 0 < got.stats[1] < got.stats[0]
             assert np.all(got.weight == 1) and not got.bias2.any() and np.all(got.error[~valid] == 0) and np.all(got.error[valid] > 0)
@@ -127,7 +124,7 @@ def test_no_levels_give_the_raw_halves_variance_and_no_bias():
         if demodulate == 0:
             assert not got.bias2.any()
             want = hl.denoise_error(cfg, ib, a, feats, 2, 0.0, iterations=0, demodulate=0)[0]
-            assert np.array_equal(_bits(got.error), _bits(want))
+            assert np.array_equal(ck.bits(got.error), ck.bits(want))
         else:
             assert got.bias2.max() < 1e-12
 
@@ -156,7 +153,7 @@ def test_identical_halves_blurred_across_a_ramp_give_slope_times_bias():
     a = ib * np.float32(0.5)
     window = 2
     f = lv.Filtered(cfg, ib, a, feats, iterations=1, demodulate=0)
-    assert np.array_equal(_bits(f.fa), _bits(f.fb))
+    assert np.array_equal(ck.bits(f.fa), ck.bits(f.fb))
     got = be.from_ladders(f, 0.0, 1, 1e6, 8, window)
     assert got.stats[0] == W * H and not got.variance.any()
     T = lv.denoise_blend_levels(cfg, ib, a, feats, 1, 1e6, 8, iterations=1, demodulate=0)[1].astype(np.float64)
@@ -197,7 +194,7 @@ def test_a_valid_pixel_that_is_not_usable_adds_variance_but_no_bias():
     inner[12:18, 12:18] = True                         # the whole window is unusable
     assert (valid & ~usable)[inner].all() and got.stats[0] == int(valid.sum())
     assert not got.bias2[inner].any() and np.all(got.variance[inner] > 0)
-    assert np.array_equal(_bits(got.error[inner]), _bits(np.sqrt(got.variance[inner] + np.float32(0))))
+    assert np.array_equal(ck.bits(got.error[inner]), ck.bits(np.sqrt(got.variance[inner] + np.float32(0))))
     assert (got.bias2[usable] > 0).any()
 
 

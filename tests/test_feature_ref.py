@@ -60,6 +60,6 @@ def test_cornell_v3_centre_hits_the_back_wall():
 
 def test_python_denoise_defaults_match_the_header():
     """Renderer.denoise() with some parameters given takes the others from DenoiseParams.DEFAULTS: the header's values"""
-    hdr = open(os.path.join(os.path.dirname(fr.DIR), "..", "include", "rtpbr.h")).read()
+    hdr = open(os.path.join(fr.ROOT, "include", "rtpbr.h")).read()
     found = {m.group(1).lower(): float(m.group(2)) for m in re.finditer(r"#define RTPBR_DENOISE_DEFAULT_([A-Z_]+)\s+([0-9.]+)f?", hdr)}
     assert found == {k: float(v) for k, v in DenoiseParams.DEFAULTS.items()}

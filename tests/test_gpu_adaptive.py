@@ -5,10 +5,12 @@ the numpy restatement of the rule (tests/select_ref_lib.py) on the GPU's own noi
 import numpy as np
 import pytest
 
+import checks as ck
 import select_ref_lib as sr
 import test_gpu_features_denoise as fd
 import test_gpu_reproject as rp
 from cases import all_cases
+from checks import EINVAL, ESTATE
 from oracle_backend import OracleRenderer
 from raytracingpbr_amd import Config, Renderer, cornell_box, src_scene
 from raytracingpbr_amd._capi import RtpbrError
@@ -16,24 +18,6 @@ from raytracingpbr_amd.renderer import (BUF_DIFF_BUFFER, BUF_DIFF_PIXELS, BUF_IM
                                         BUF_RAY_BUFFER, BUF_SELECTION)
 
 pytestmark = pytest.mark.gpu
-
-ESTATE, EINVAL = -4, -1
-COUNTERS = ("samples", "raycasts", "march_steps", "hits", "sky_lookups", "deposits")
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a
-
-
-def _same(got, want, what):
-    bad = _bits(got) != _bits(want)
-    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _counters(r):
-    c = r.counters()
-    return [getattr(c, k) for k in COUNTERS]
 
 
 def _small_cases():
@@ -97,7 +81,7 @@ def test_host_masks_bit_identical_to_composed_oracle(name):
     case, cfg = _small_cases()[name]
     steps = _sequence(cfg.width, cfg.height)
     got = _run(case.setup(Renderer(case.scene, cfg)), steps, False)
-    _same(got, _oracle_image(name, "seq", steps), "image_buffer")
+    ck.same(got, _oracle_image(name, "seq", steps), "image_buffer")
     assert len(np.unique(got[..., 3])) >= 3      # pixels with 6, 9, 11 and 14 samples
 
 
@@ -122,22 +106,22 @@ def test_special_masks(which):
     steps = [("sample", 4), ("select", mask), ("selected", 3), ("sample", 2)]       # (the last step: sample_base advanced for everybody)
     r = case.setup(Renderer(case.scene, cfg))
     got = _run(r, steps[:3], False)
-    sel_counters = _counters(r)
-    _same(got, _oracle_image(CORNELL, which + "/3", steps[:3]), "image_buffer after the selected launch")
+    sel_counters = ck.counters(r)
+    ck.same(got, _oracle_image(CORNELL, which + "/3", steps[:3]), "image_buffer after the selected launch")
     r.sample(2)
-    _same(r.image_buffer, _oracle_image(CORNELL, which + "/4", steps), "image_buffer after the next full-frame launch")
+    ck.same(r.image_buffer, _oracle_image(CORNELL, which + "/4", steps), "image_buffer after the next full-frame launch")
     if which == "empty":
         assert sel_counters == [0] * 6
     if which == "full":           # rtpbr_sample itself, counters included (HIP and oracle)
         plain = case.setup(Renderer(case.scene, cfg))
         plain.sample(4)
         plain.sample(3)
-        _same(got, plain.image_buffer, "image_buffer against rtpbr_sample")
-        assert sel_counters == _counters(plain)
+        ck.same(got, plain.image_buffer, "image_buffer against rtpbr_sample")
+        assert sel_counters == ck.counters(plain)
         o = case.setup(OracleRenderer(case.scene, cfg))
         o.sample(4)
         o.sample(3)
-        assert sel_counters == _counters(o)
+        assert sel_counters == ck.counters(o)
 
 
 def test_a_selection_survives_full_frame_calls_and_is_replaced_by_the_next():
@@ -145,7 +129,7 @@ def test_a_selection_survives_full_frame_calls_and_is_replaced_by_the_next():
     a, b = _random_mask(cfg.width, cfg.height, 5), _random_mask(cfg.width, cfg.height, 6)
     steps = [("select", a), ("selected", 2), ("sample", 1), ("selected", 2), ("select", b), ("selected", 1)]
     got = _run(case.setup(Renderer(case.scene, cfg)), steps, False)
-    _same(got, _oracle_image(CORNELL, "survives", steps), "image_buffer")
+    ck.same(got, _oracle_image(CORNELL, "survives", steps), "image_buffer")
 
 
 # ------------------------------------------------------------------ 2. options that must neither fail a selected launch nor change its bits
@@ -160,7 +144,7 @@ def test_options_do_not_change_the_bits(options):
     r = case.setup(Renderer(case.scene, cfg))
     for k, v in options.items():
         r.set_option(k, v)
-    _same(_run(r, steps, False), _oracle_image(CORNELL, "seq", steps), f"image_buffer with {options}")
+    ck.same(_run(r, steps, False), _oracle_image(CORNELL, "seq", steps), f"image_buffer with {options}")
 
 
 def test_many_sub_launches_of_a_selected_call():
@@ -178,7 +162,7 @@ def test_many_sub_launches_of_a_selected_call():
         assert c.samples == c.deposits == int(mask.sum()) * 200
         r.sample(1)                       # the context's own geometry is back: the full frame, sample 201
         got.append(r.image_buffer)
-    _same(got[0], got[1], "image_buffer, four sub-launches against one")
+    ck.same(got[0], got[1], "image_buffer, four sub-launches against one")
     assert np.array_equal(got[0][..., 3], np.where(mask != 0, 202, 2))
 
 
@@ -189,7 +173,7 @@ def _check_noisy(r, quantile, dilate, trace):
     thr = float(np.quantile(noise[noise > 0], quantile)) if (noise > 0).any() else 0.0
     n = r.select_noisy(thr, dilate)
     ib = r.image_buffer
-    _same(r.noise, noise, "noise written by select_noisy")
+    ck.same(r.noise, noise, "noise written by select_noisy")
     want = sr.select(r.noise, ib[..., 3], thr, dilate)
     got = r.selection
     assert got.dtype == np.uint8 and np.array_equal(got, want), f"{int((got != want).sum())} pixels differ"
@@ -200,7 +184,7 @@ def _check_noisy(r, quantile, dilate, trace):
         after = r.image_buffer
         assert np.array_equal(after[..., 3] - ib[..., 3], want.astype(np.float32))
         keep = want == 0
-        assert np.array_equal(_bits(after)[keep], _bits(ib)[keep])
+        assert np.array_equal(ck.bits(after)[keep], ck.bits(ib)[keep])
         c = r.counters()
         assert c.samples == c.deposits == n
     return want
@@ -280,7 +264,7 @@ def test_render_adaptive_holds_a_prefix_of_every_pixels_samples():
             o.sample(batch)
             done += batch
         group = count == c
-        bad = _bits(ib)[group] != _bits(o.image_buffer)[group]
+        bad = ck.bits(ib)[group] != ck.bits(o.image_buffer)[group]
         assert not bad.any(), f"pixels with {int(c)} samples: {int(bad.any(axis=-1).sum())} of {int(group.sum())} differ from the oracle"
 
 
@@ -351,7 +335,7 @@ def test_errors_and_a_refused_call_changes_nothing():
     r.post_process()
     buffers = (BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS, BUF_MOMENTS, BUF_NOISE, BUF_SELECTION)
     keep = {b: r._read(b) for b in buffers}
-    counters = _counters(r)
+    counters = ck.counters(r)
     nan = float("nan")
     n = C.c_uint32(77)
     m = np.ascontiguousarray(mask)
@@ -381,9 +365,9 @@ def test_errors_and_a_refused_call_changes_nothing():
     r.set_option("precision", 1)
     assert _code(r.sample_selected, 1) == ESTATE
     r.set_option("precision", 0)
-    assert _counters(r) == counters
+    assert ck.counters(r) == counters
     for b, a in keep.items():
-        _same(r._read(b), a, f"buffer {b} after refused calls")
+        ck.same(r._read(b), a, f"buffer {b} after refused calls")
     # ... and the sample index did not move: the next selected launch gives what it gives on a context that made the accepted calls only
     twin = Renderer(scene, cfg)
     for _ in range(2):
@@ -392,7 +376,7 @@ def test_errors_and_a_refused_call_changes_nothing():
     twin.sample_selected(1)
     for x in (r, twin):
         x.sample_selected(1)
-    _same(r.image_buffer, twin.image_buffer, "image_buffer one selected launch after the refused calls")
+    ck.same(r.image_buffer, twin.image_buffer, "image_buffer one selected launch after the refused calls")
 
 
 def test_refused_before_the_context_is_set_up():
@@ -422,7 +406,7 @@ def test_persistent_form_is_refused():
     assert r.select_mask(np.ones((40, 24), np.uint8)) == 40 * 24
     before = r.image_buffer
     assert _code(r.sample_selected, 1) == ESTATE
-    _same(r.image_buffer, before, "image_buffer")
+    ck.same(r.image_buffer, before, "image_buffer")
 
 
 def test_selected_launches_are_timed_and_asynchronous_reads_are_respected():
@@ -436,7 +420,7 @@ def test_selected_launches_are_timed_and_asynchronous_reads_are_respected():
     t = r.read_async(BUF_IMAGE_BUFFER, host)       # the selected launch that follows must not overtake this copy
     r.sample_selected(4)
     r.read_wait(t)
-    _same(host, before, "asynchronously read image_buffer")
+    ck.same(host, before, "asynchronously read image_buffer")
     trace_ms, total_ms, launches = r.last_sample_ms()
     assert launches == 1 and 0 < trace_ms <= total_ms
     r.select_mask(np.zeros((128, 128), np.uint8))

@@ -7,56 +7,24 @@ import numpy as np
 import pytest
 
 import blend_ref_lib as bl
+import checks as ck
 import hostile as hz
 import present_ref_lib as pr
-from raytracingpbr_amd import Camera, Config, Renderer, cornell_box, src_scene
-from raytracingpbr_amd._capi import RtpbrError
+from checks import EINVAL, ESTATE
+from raytracingpbr_amd import Camera, Renderer
 from raytracingpbr_amd.dataclass import BlendParams, NoiseStats
 from raytracingpbr_amd.renderer import (BUF_BLEND_WEIGHT, BUF_DENOISED_ERROR, BUF_DENOISED_PIXELS, BUF_HALF_BUFFER, BUF_IMAGE_BUFFER,
                                         BUF_IMAGE_PIXELS, BUF_MOMENTS, BUF_NOISE, BUF_SELECTION)
 
 pytestmark = pytest.mark.gpu
 
-ESTATE, EINVAL = -4, -1
-COUNTERS = ("samples", "raycasts", "march_steps", "hits", "sky_lookups", "deposits")
 FRAMES = [(7, 5), (33, 17), (64, 48)]      # smaller than a tile and than the radius-3 window; partial tiles both ways; whole tiles
 NEVER = 16777216                           # min_half_samples above every count: t = 1 everywhere
 
 
-def _scene(name, w, h):
-    if name == "cornell_v3":                  # a closed room: no misses
-        return cornell_box("v3", aspect=w / h), Config.cornell_v3(w, h, 0, 3)
-    return src_scene(aspect=w / h, tokyo=True), Config.scene_demo(w, h, 5, 8)      # 7 objects under the gradient sky: misses, object -1
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a
-
-
-def _same(got, want, what):
-    bad = _bits(got) != _bits(want)
-    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _feats(r):
-    return {"albedo": r.feature_albedo, "normal": r.feature_normal, "depth": r.feature_depth, "object": r.feature_object}
-
-
-def _counters(r):
-    c = r.counters()
-    return [getattr(c, k) for k in COUNTERS]
-
-
-def _code(fn):
-    with pytest.raises(RtpbrError) as e:
-        fn()
-    return e.value.code
-
-
 def _dealt(name, w, h, per_sample=False):
     """three unequal batches (2, 2, 3 spp: A, B, A), or the same 7 samples dealt one by one by the sample calls (4 + 3)"""
-    scene, cfg = _scene(name, w, h)
+    scene, cfg = ck.scene(name, w, h)
     r = Renderer(scene, cfg)
     if per_sample:
         r.set_half_mode(per_sample=True)
@@ -70,7 +38,7 @@ def _dealt(name, w, h, per_sample=False):
 
 
 def _want(r, cfg, radius, z, m, **denoise):
-    return bl.denoise_blend(cfg, r.image_buffer, r.half_buffer, _feats(r), radius, z, m, **denoise)
+    return bl.denoise_blend(cfg, r.image_buffer, r.half_buffer, ck.feats(r), radius, z, m, **denoise)
 
 
 def _check(r, cfg, radius=None, z=None, m=None, what="", **denoise):
@@ -78,8 +46,8 @@ def _check(r, cfg, radius=None, z=None, m=None, what="", **denoise):
     stats = r.denoise_blend(radius, z, m, **denoise)
     out, t, st = _want(r, cfg, radius, z, m, **denoise)
     what = f"{what} radius {radius} z {z} min_half_samples {m} {denoise}"
-    _same(r.blend_weight, t, "blend_weight " + what)
-    _same(r.denoised_pixels, out, "denoised_pixels " + what)
+    ck.same(r.blend_weight, t, "blend_weight " + what)
+    ck.same(r.denoised_pixels, out, "denoised_pixels " + what)
     assert (stats.pixels_estimated, stats.pixels_above) == st[:2], (what, stats, st)
     assert np.float32(stats.max_noise).view(np.uint32) == np.float32(st[2]).view(np.uint32), (what, stats, st)
     return out, t, st
@@ -142,10 +110,10 @@ def test_with_every_half_too_small_the_call_writes_rtpbr_denoises_bytes(name):
             r.denoise(**p)
             want = r.denoised_pixels
             stats = r.denoise_blend(2, 0.0, NEVER, **p)
-            _same(r.denoised_pixels, want, f"denoised_pixels {p}")
+            ck.same(r.denoised_pixels, want, f"denoised_pixels {p}")
             assert np.all(r.blend_weight == 1) and (stats.pixels_estimated, stats.pixels_above, stats.max_noise) == (0, 0, 0.0)
     r.post_process()
-    _same(r.denoised_pixels[:, 3], r.image_pixels[:, 3], "pixels without samples show what post_process shows")
+    ck.same(r.denoised_pixels[:, 3], r.image_pixels[:, 3], "pixels without samples show what post_process shows")
 
 
 def test_denoise_blend_writes_nothing_else():
@@ -157,17 +125,17 @@ def test_denoise_blend_writes_nothing_else():
     r.post_process()
     others = (BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_HALF_BUFFER, BUF_MOMENTS, BUF_NOISE, BUF_DENOISED_ERROR, BUF_SELECTION)
     before = {b: r._read(b) for b in others}
-    counters = _counters(r)
+    counters = ck.counters(r)
     for iterations in (0, 1, 4):
         r.denoise_blend(3, 0.0, 1, iterations=iterations, demodulate=1)
         for b, a in before.items():
-            _same(r._read(b), a, f"buffer {b} after denoise_blend")
-        assert _counters(r) == counters
+            ck.same(r._read(b), a, f"buffer {b} after denoise_blend")
+        assert ck.counters(r) == counters
     # the snapshot: the next half_update deals exactly what came since the last one
     r.sample(2)
     r.half_update()
     assert np.all(r.half_buffer[..., 3] == 5) and np.all(r.image_buffer[..., 3] == 9)      # A 5 > B 2: the batch went to B
-    assert _code(lambda: r._write(BUF_BLEND_WEIGHT, before[BUF_NOISE])) == EINVAL      # output only
+    assert ck.code(lambda: r._write(BUF_BLEND_WEIGHT, before[BUF_NOISE])) == EINVAL      # output only
 
 
 def test_present_serves_the_blended_frame():
@@ -186,8 +154,8 @@ def test_present_serves_the_blended_frame():
     r.denoise_blend(2, 0.0, NEVER)
     r.read_wait(tw)
     r.read_wait(td)
-    _same(hw, t, "the asynchronous read holds the earlier weight")
-    _same(hd, out, "the asynchronous read holds the earlier frame")
+    ck.same(hw, t, "the asynchronous read holds the earlier weight")
+    ck.same(hd, out, "the asynchronous read holds the earlier frame")
     assert np.all(r.blend_weight == 1)
 
 
@@ -196,7 +164,7 @@ def test_refusals_change_nothing():
     cfg, r = _dealt("cornell_v3", 33, 17)
     api, ctx = r.api, r._ctx
     nan, inf = float("nan"), float("inf")
-    assert _code(lambda: r.blend_weight) == ESTATE               # before the first call
+    assert ck.code(lambda: r.blend_weight) == ESTATE               # before the first call
     r.denoise_blend(2, 0.0, 1)
     watched = (BUF_BLEND_WEIGHT, BUF_DENOISED_PIXELS, BUF_HALF_BUFFER, BUF_IMAGE_BUFFER)
     before = {b: r._read(b) for b in watched}
@@ -204,28 +172,28 @@ def test_refusals_change_nothing():
     assert api.fn["denoise_blend"](None, None, None, C.byref(s)) == EINVAL
     for bad in ({"iterations": 9}, {"iterations": -1}, {"demodulate": 2}, {"sigma_color": 0.0}, {"sigma_normal": nan}, {"sigma_depth": -1.0},
                 {"sigma_albedo": inf}, {"iterations": 8, "sigma_color": 1e-18}):
-        assert _code(lambda: r.denoise_blend(**bad)) == EINVAL, bad
-        assert _code(lambda: r.denoise(**bad)) == EINVAL, bad      # exactly rtpbr_denoise's checks
+        assert ck.code(lambda: r.denoise_blend(**bad)) == EINVAL, bad
+        assert ck.code(lambda: r.denoise(**bad)) == EINVAL, bad      # exactly rtpbr_denoise's checks
     for radius in (0, 4, -1):
-        assert _code(lambda: r.denoise_blend(radius)) == EINVAL
+        assert ck.code(lambda: r.denoise_blend(radius)) == EINVAL
     for z in (-1.0, nan, inf, float("-inf"), -1e-30):
-        assert _code(lambda: r.denoise_blend(z=z)) == EINVAL
+        assert ck.code(lambda: r.denoise_blend(z=z)) == EINVAL
     for m in (0, -1, NEVER + 1):
-        assert _code(lambda: r.denoise_blend(min_half_samples=m)) == EINVAL
+        assert ck.code(lambda: r.denoise_blend(min_half_samples=m)) == EINVAL
     r.set_tiles(16, 16, 0, 2)
-    assert _code(lambda: r.denoise_blend()) == ESTATE
+    assert ck.code(lambda: r.denoise_blend()) == ESTATE
     r.set_tiles(0, 0, 0, 1)
     for b, a in before.items():
-        _same(r._read(b), a, f"buffer {b} after the refused calls")
+        ck.same(r._read(b), a, f"buffer {b} after the refused calls")
     # a NULL statistics pointer is allowed, as in rtpbr_denoise_error; -0 is a z >= 0
     e = BlendParams(2, -0.0, 1)
     assert api.fn["denoise_blend"](ctx, None, C.byref(e), None) == 0
     for b, a in before.items():
-        _same(r._read(b), a, f"buffer {b} after the same call again")
+        ck.same(r._read(b), a, f"buffer {b} after the same call again")
 
 
 def test_refusals_before_the_context_is_set_up_and_before_half_a_exists():
-    scene, cfg = _scene("cornell_v3", 16, 12)
+    scene, cfg = ck.scene("cornell_v3", 16, 12)
     api = Renderer(scene, cfg).api
     ctx = C.c_void_p()
     api.call("create", 0, C.byref(ctx))
@@ -239,9 +207,9 @@ def test_refusals_before_the_context_is_set_up_and_before_half_a_exists():
         api.call("destroy", ctx)
     r = Renderer(scene, cfg)
     r.sample(2)
-    assert _code(lambda: r.denoise_blend()) == ESTATE and _code(lambda: r.blend_weight) == ESTATE      # before half A exists
-    assert _code(lambda: r.denoise_blend(iterations=9)) == EINVAL and _code(lambda: r.denoise_blend(radius=4)) == EINVAL      # parameters come first
-    assert _code(lambda: r.denoised_pixels) == ESTATE                      # nothing was allocated on the way
+    assert ck.code(lambda: r.denoise_blend()) == ESTATE and ck.code(lambda: r.blend_weight) == ESTATE      # before half A exists
+    assert ck.code(lambda: r.denoise_blend(iterations=9)) == EINVAL and ck.code(lambda: r.denoise_blend(radius=4)) == EINVAL      # parameters come first
+    assert ck.code(lambda: r.denoised_pixels) == ESTATE                      # nothing was allocated on the way
     r.set_half_mode(per_sample=True)                                       # a dealing call makes A: everything so far is one batch
     r.sample(2)
     assert r.denoise_blend(1, 0.0, 1).pixels_estimated == 16 * 12
@@ -253,7 +221,7 @@ def test_a_new_resolution_frees_the_weight_buffer():
     assert r.blend_weight.shape == (33, 17)
     cfg2 = cfg.copy(width=17, height=9)
     r.set_config(cfg2)
-    assert _code(lambda: r.blend_weight) == ESTATE and _code(lambda: r.denoise_blend()) == ESTATE
+    assert ck.code(lambda: r.blend_weight) == ESTATE and ck.code(lambda: r.denoise_blend()) == ESTATE
     for n in (2, 2):
         r.sample(n)
         r.half_update()
@@ -275,7 +243,7 @@ def test_hostile_image_buffer(frame, family):
     r.half_update()
     r.sample(2)
     r.half_update()
-    ib2, a, feats = r.image_buffer, r.half_buffer, _feats(r)
+    ib2, a, feats = r.image_buffer, r.half_buffer, ck.feats(r)
     for radius, z, denoise in ((1, 0.0, {}), (3, 0.0, dict(iterations=2, demodulate=1, **hz.SIGMAS)), (3, 2.0, {}), (2, 0.0, dict(iterations=0))):
         stats = r.denoise_blend(radius, z, 1, **denoise)
         out, t, st = bl.denoise_blend(cfg, ib2, a, feats, radius, z, 1, **denoise)
@@ -293,7 +261,7 @@ def test_scripted_sequence_against_the_restatement():
     counts are fractional: min_half_samples decides which pixels are usable); refresh; a second size, where the call is refused
     until halves exist again."""
     w, h = 33, 17
-    scene, cfg = _scene("cornell_v3", w, h)
+    scene, cfg = ck.scene("cornell_v3", w, h)
     r = Renderer(scene, cfg)
     r.refresh()                                            # (reproject wants one since set_config)
     r.set_half_mode(warp=True)
@@ -323,23 +291,23 @@ def test_scripted_sequence_against_the_restatement():
     stats = r.denoise_blend(2, 0.0, 1, **p)
     assert stats.pixels_estimated == 0 and np.all(r.blend_weight == 1)
     r.post_process()
-    _same(r.denoised_pixels, r.image_pixels, "an empty frame shows what post_process shows")
+    ck.same(r.denoised_pixels, r.image_pixels, "an empty frame shows what post_process shows")
     r.set_config(cfg.copy(width=20, height=13))
-    assert _code(lambda: r.denoise_blend(2, 0.0, 1, **p)) == ESTATE and _code(lambda: r.blend_weight) == ESTATE
+    assert ck.code(lambda: r.denoise_blend(2, 0.0, 1, **p)) == ESTATE and ck.code(lambda: r.blend_weight) == ESTATE
 
 
 # ------------------------------------------------------------------ 6. the loop
 def test_render_adaptive_denoised_ends_with_the_blend():
     w = h = 32
-    scene, cfg = _scene("cornell_v3", w, h)
+    scene, cfg = ck.scene("cornell_v3", w, h)
     r, s = Renderer(scene, cfg), Renderer(scene, cfg)
     args = (0.02, 40, 8, 1)
     traced, stats = r.render_adaptive_denoised(*args, blend=True, iterations=3)
     traced_s, stats_s = s.render_adaptive_denoised(*args, iterations=3)
     assert traced == traced_s and stats.pixels_above == stats_s.pixels_above      # the stop rule is unchanged
-    _same(r.image_buffer, s.image_buffer, "image_buffer")
-    _same(r.half_buffer, s.half_buffer, "half_buffer")
+    ck.same(r.image_buffer, s.image_buffer, "image_buffer")
+    ck.same(r.half_buffer, s.half_buffer, "half_buffer")
     out, t, _ = _want(r, cfg, None, None, None, iterations=3)
-    _same(r.denoised_pixels, out, "denoised_pixels")
-    _same(r.blend_weight, t, "blend_weight")
-    assert _code(lambda: s.blend_weight) == ESTATE
+    ck.same(r.denoised_pixels, out, "denoised_pixels")
+    ck.same(r.blend_weight, t, "blend_weight")
+    assert ck.code(lambda: s.blend_weight) == ESTATE

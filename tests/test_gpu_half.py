@@ -7,55 +7,23 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import checks as ck
 import half_ref_lib as hl
-from raytracingpbr_amd import Camera, Config, Renderer, cornell_box, src_scene
-from raytracingpbr_amd._capi import RtpbrError
+from checks import EINVAL, ESTATE
+from raytracingpbr_amd import Camera, Renderer
 from raytracingpbr_amd.dataclass import NoiseStats
 from raytracingpbr_amd.renderer import (BUF_DENOISED_ERROR, BUF_DENOISED_PIXELS, BUF_HALF_BUFFER, BUF_IMAGE_BUFFER, BUF_MOMENTS, BUF_MOTION,
                                         BUF_NOISE, BUF_SELECTION)
 
 pytestmark = pytest.mark.gpu
 
-ESTATE, EINVAL = -4, -1
-COUNTERS = ("samples", "raycasts", "march_steps", "hits", "sky_lookups", "deposits")
 FRAMES = [(7, 5), (33, 17), (64, 48)]      # smaller than any tile and than the radius-3 window; partial tiles both ways; whole tiles
-
-
-def _scene(name, w, h):
-    if name == "cornell_v3":                  # a closed room: no misses
-        return cornell_box("v3", aspect=w / h), Config.cornell_v3(w, h, 0, 3)
-    return src_scene(aspect=w / h, tokyo=True), Config.scene_demo(w, h, 5, 8)      # 7 objects under the gradient sky: misses, object -1
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a
-
-
-def _same(got, want, what):
-    bad = _bits(got) != _bits(want)
-    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _feats(r):
-    return {"albedo": r.feature_albedo, "normal": r.feature_normal, "depth": r.feature_depth, "object": r.feature_object}
-
-
-def _counters(r):
-    c = r.counters()
-    return [getattr(c, k) for k in COUNTERS]
-
-
-def _code(fn):
-    with pytest.raises(RtpbrError) as e:
-        fn()
-    return e.value.code
 
 
 def _update(r, model):
     r.half_update()
     model.update(r.image_buffer)
-    _same(r.half_buffer, model.a, "half_buffer")
+    ck.same(r.half_buffer, model.a, "half_buffer")
 
 
 def _stripe(w, h):
@@ -67,7 +35,7 @@ def _stripe(w, h):
 
 def _dealt(name, w, h):
     """the issue's sequence: two full batches, a selected one, and a sample nobody dealt (it lies in B)"""
-    scene, cfg = _scene(name, w, h)
+    scene, cfg = ck.scene(name, w, h)
     r, model = Renderer(scene, cfg), hl.Halves(w, h)
     r.sample(2)
     _update(r, model)
@@ -85,11 +53,11 @@ def _dealt(name, w, h):
 def _check_error(r, cfg, model, threshold, radius, **denoise):
     stats = r.denoise_error(threshold, radius, **denoise)
     ib = r.image_buffer
-    want, st, _ = hl.denoise_error(cfg, ib, model.a, _feats(r), radius=radius, threshold=threshold, **denoise)
+    want, st, _ = hl.denoise_error(cfg, ib, model.a, ck.feats(r), radius=radius, threshold=threshold, **denoise)
     got = r.denoised_error
-    _same(got, want, f"denoised_error (radius {radius}, {denoise})")
-    assert (stats.pixels_estimated, stats.pixels_above) == st[:2], (stats, st)
-    assert np.float32(stats.max_noise).view(np.uint32) == np.float32(st[2]).view(np.uint32) and stats.max_noise == got.max()
+    ck.same(got, want, f"denoised_error (radius {radius}, {denoise})")
+    ck.stats_same(stats, st, f"radius {radius}, {denoise}")
+    assert stats.max_noise == got.max()
     return got, stats
 
 
@@ -148,7 +116,7 @@ def test_refresh_zeroes_a_and_the_halves_start_over():
     assert r.select_error(0.0) == 33 * 17
     r.sample(2)
     _update(r, model)
-    _same(r.half_buffer, r.image_buffer, "the first batch after a refresh goes to A")
+    ck.same(r.half_buffer, r.image_buffer, "the first batch after a refresh goes to A")
 
 
 def test_written_data_lies_in_b_and_every_pixel_is_selected():
@@ -168,7 +136,7 @@ def test_written_data_lies_in_b_and_every_pixel_is_selected():
 
 def test_reproject_keeps_its_bits_and_leaves_a_zero():
     w, h = 33, 17
-    scene, cfg = _scene("cornell_v3", w, h)
+    scene, cfg = ck.scene("cornell_v3", w, h)
     c = scene.camera
     cam = Camera((c.lookfrom[0] + 1.5, c.lookfrom[1] + 0.5, c.lookfrom[2]), tuple(c.lookat), tuple(c.vup), c.vfov, c.aspect, c.aperture, c.focus)
     plain, r = Renderer(scene, cfg), Renderer(scene, cfg)
@@ -180,14 +148,14 @@ def test_reproject_keeps_its_bits_and_leaves_a_zero():
     plain.reproject(cam)
     r.reproject(cam)
     ib = r.image_buffer
-    _same(ib, plain.image_buffer, "image_buffer after reproject")
-    _same(r._read(BUF_MOTION), plain._read(BUF_MOTION), "motion")
+    ck.same(ib, plain.image_buffer, "image_buffer after reproject")
+    ck.same(r._read(BUF_MOTION), plain._read(BUF_MOTION), "motion")
     assert not r.half_buffer.any() and (ib[..., 3] > 0).any()
     model.restart(ib)
     assert r.denoise_error(0.0).pixels_estimated == 0
     r.sample(2)
     plain.sample(2)
-    _same(r.image_buffer, plain.image_buffer, "image_buffer after the next samples")
+    ck.same(r.image_buffer, plain.image_buffer, "image_buffer after the next samples")
     _update(r, model)
     assert np.allclose(model.a[..., 3], 2.0, rtol=1e-6, atol=0)      # (b.w - sh.w on a warped, fractional count)
     _, stats = _check_error(r, cfg, model, 0.01, 2)
@@ -198,12 +166,12 @@ def test_a_new_resolution_frees_both_buffers():
     cfg, r, model = _dealt("cornell_v3", 33, 17)
     r.denoise_error(0.0)
     r.set_config(cfg.copy(width=17, height=9))
-    assert _code(lambda: r.half_buffer) == ESTATE and _code(lambda: r.denoised_error) == ESTATE
-    assert _code(lambda: r.denoise_error(0.0)) == ESTATE
+    assert ck.code(lambda: r.half_buffer) == ESTATE and ck.code(lambda: r.denoised_error) == ESTATE
+    assert ck.code(lambda: r.denoise_error(0.0)) == ESTATE
     r.sample(1)
     r.half_update()
-    _same(r.half_buffer, r.image_buffer, "half_buffer of the new frame")
-    assert _code(lambda: r.select_error(0.0)) == ESTATE and _code(lambda: r.denoised_error) == ESTATE
+    ck.same(r.half_buffer, r.image_buffer, "half_buffer of the new frame")
+    assert ck.code(lambda: r.select_error(0.0)) == ESTATE and ck.code(lambda: r.denoised_error) == ESTATE
 
 
 def test_denoise_error_writes_nothing_else():
@@ -212,20 +180,20 @@ def test_denoise_error_writes_nothing_else():
     r.noise_estimate(0.0)
     r.denoise()
     before = {b: r._read(b) for b in (BUF_DENOISED_PIXELS, BUF_IMAGE_BUFFER, BUF_MOMENTS, BUF_NOISE, BUF_HALF_BUFFER)}
-    counters = _counters(r)
+    counters = ck.counters(r)
     for iterations in (0, 1, 4):
         r.denoise_error(0.01, 3, iterations=iterations, demodulate=1)
         for b, a in before.items():
-            _same(r._read(b), a, f"buffer {b} after denoise_error")
-        assert _counters(r) == counters
+            ck.same(r._read(b), a, f"buffer {b} after denoise_error")
+        assert ck.counters(r) == counters
     r.select_error(0.01, 1)
     for b, a in before.items():
-        _same(r._read(b), a, f"buffer {b} after select_error")
+        ck.same(r._read(b), a, f"buffer {b} after select_error")
 
 
 def test_a_context_without_halves_keeps_todays_bits():
     """denoise, select_noisy and the sample path next to a context that tracks halves"""
-    scene, cfg = _scene("cornell_v3", 33, 17)
+    scene, cfg = ck.scene("cornell_v3", 33, 17)
     plain, r = Renderer(scene, cfg), Renderer(scene, cfg)
     r.track_halves = True
     for x in (plain, r):
@@ -237,8 +205,8 @@ def test_a_context_without_halves_keeps_todays_bits():
     r.denoise_error(0.01)
     assert plain.select_noisy(0.05, 1) == r.select_noisy(0.05, 1)
     for b in (BUF_IMAGE_BUFFER, BUF_DENOISED_PIXELS, BUF_MOMENTS, BUF_NOISE, BUF_SELECTION):
-        _same(r._read(b), plain._read(b), f"buffer {b}")
-    assert _code(lambda: plain.half_buffer) == ESTATE
+        ck.same(r._read(b), plain._read(b), f"buffer {b}")
+    assert ck.code(lambda: plain.half_buffer) == ESTATE
     assert np.all(r.half_buffer[..., 3] == 2)     # track_halves: a half_update after each sample()
 
 
@@ -248,7 +216,7 @@ def test_refusals_change_nothing():
     api, ctx = r.api, r._ctx
     nan = float("nan")
     # before the first denoise_error
-    assert _code(lambda: r.select_error(0.0)) == ESTATE and _code(lambda: r.denoised_error) == ESTATE
+    assert ck.code(lambda: r.select_error(0.0)) == ESTATE and ck.code(lambda: r.denoised_error) == ESTATE
     r.denoise_error(0.01)
     r.select_error(0.01, 1)
     before = {b: r._read(b) for b in (BUF_HALF_BUFFER, BUF_DENOISED_ERROR, BUF_SELECTION, BUF_IMAGE_BUFFER)}
@@ -258,28 +226,28 @@ def test_refusals_change_nothing():
     assert api.fn["select_error"](None, 0.0, 0, C.byref(n)) == EINVAL and api.fn["select_error"](ctx, 0.0, 0, None) == EINVAL
     for bad in ({"iterations": 9}, {"iterations": -1}, {"demodulate": 2}, {"sigma_color": 0.0}, {"sigma_normal": nan}, {"sigma_depth": -1.0},
                 {"sigma_albedo": float("inf")}, {"iterations": 8, "sigma_color": 1e-18}):
-        assert _code(lambda: r.denoise_error(0.0, **bad)) == EINVAL, bad
-        assert _code(lambda: r.denoise(**bad)) == EINVAL, bad      # exactly rtpbr_denoise's checks
+        assert ck.code(lambda: r.denoise_error(0.0, **bad)) == EINVAL, bad
+        assert ck.code(lambda: r.denoise(**bad)) == EINVAL, bad      # exactly rtpbr_denoise's checks
     for radius in (0, 4, -1):
-        assert _code(lambda: r.denoise_error(0.0, radius)) == EINVAL
+        assert ck.code(lambda: r.denoise_error(0.0, radius)) == EINVAL
     for thr in (-1.0, nan):
-        assert _code(lambda: r.denoise_error(thr)) == EINVAL and _code(lambda: r.select_error(thr)) == EINVAL
+        assert ck.code(lambda: r.denoise_error(thr)) == EINVAL and ck.code(lambda: r.select_error(thr)) == EINVAL
     for dilate in (-1, 4):
-        assert _code(lambda: r.select_error(0.0, dilate)) == EINVAL
+        assert ck.code(lambda: r.select_error(0.0, dilate)) == EINVAL
     for which in (BUF_HALF_BUFFER, BUF_DENOISED_ERROR):
-        assert _code(lambda: r._write(which, before.get(which))) == EINVAL
+        assert ck.code(lambda: r._write(which, before.get(which))) == EINVAL
     r.set_tiles(16, 16, 0, 2)
-    assert _code(r.half_update) == ESTATE and _code(lambda: r.denoise_error(0.0)) == ESTATE and _code(lambda: r.select_error(0.0)) == ESTATE
+    assert ck.code(r.half_update) == ESTATE and ck.code(lambda: r.denoise_error(0.0)) == ESTATE and ck.code(lambda: r.select_error(0.0)) == ESTATE
     r.set_tiles(0, 0, 0, 1)
     for b, a in before.items():
-        _same(r._read(b), a, f"buffer {b} after the refused calls")
+        ck.same(r._read(b), a, f"buffer {b} after the refused calls")
     # a NULL statistics pointer is allowed, as in rtpbr_noise_estimate
     assert api.fn["denoise_error"](ctx, None, None, 0.01, None) == 0
-    _same(r.denoised_error, before[BUF_DENOISED_ERROR], "denoised_error")
+    ck.same(r.denoised_error, before[BUF_DENOISED_ERROR], "denoised_error")
 
 
 def test_refusals_before_the_context_is_set_up():
-    scene, cfg = _scene("cornell_v3", 16, 12)
+    scene, cfg = ck.scene("cornell_v3", 16, 12)
     api = Renderer(scene, cfg).api
     ctx = C.c_void_p()
     api.call("create", 0, C.byref(ctx))
@@ -296,20 +264,20 @@ def test_refusals_before_the_context_is_set_up():
         api.call("destroy", ctx)
     r = Renderer(scene, cfg)
     r.sample(2)
-    assert _code(lambda: r.denoise_error(0.0)) == ESTATE and _code(lambda: r.half_buffer) == ESTATE      # before the first half_update
-    assert _code(lambda: r.denoise_error(0.0, iterations=9)) == EINVAL                                    # parameters come first
+    assert ck.code(lambda: r.denoise_error(0.0)) == ESTATE and ck.code(lambda: r.half_buffer) == ESTATE      # before the first half_update
+    assert ck.code(lambda: r.denoise_error(0.0, iterations=9)) == EINVAL                                    # parameters come first
 
 
 # ------------------------------------------------------------------ 4. the loop
 def test_render_adaptive_denoised_is_its_calls_one_by_one():
     w = h = 32
-    scene, cfg = _scene("cornell_v3", w, h)
+    scene, cfg = ck.scene("cornell_v3", w, h)
     error, max_spp, batch, dilate = 0.02, 24, 4, 1
     r = Renderer(scene, cfg)
     r.track_noise = r.track_halves = True
     traced, stats = r.render_adaptive_denoised(error, max_spp, batch, dilate, iterations=3)
     assert r.track_noise and r.track_halves                          # restored
-    assert _code(lambda: r.moments) == ESTATE                         # ... and off inside: no noise_update ran
+    assert ck.code(lambda: r.moments) == ESTATE                         # ... and off inside: no noise_update ran
     s = Renderer(scene, cfg)
     want_traced, used = 0, 0
     for _ in range(2):
@@ -327,10 +295,10 @@ def test_render_adaptive_denoised_is_its_calls_one_by_one():
     assert stats.pixels_above == 0 or used + batch > max_spp
     assert traced == want_traced and used > 2 * batch                # (the threshold is low enough for adaptive rounds)
     assert (stats.pixels_estimated, stats.pixels_above, stats.max_noise) == (st.pixels_estimated, st.pixels_above, st.max_noise)
-    _same(r.image_buffer, s.image_buffer, "image_buffer")
-    _same(r.half_buffer, s.half_buffer, "half_buffer")
+    ck.same(r.image_buffer, s.image_buffer, "image_buffer")
+    ck.same(r.half_buffer, s.half_buffer, "half_buffer")
     s.denoise(iterations=3)
-    _same(r.denoised_pixels, s.denoised_pixels, "denoised_pixels")
+    ck.same(r.denoised_pixels, s.denoised_pixels, "denoised_pixels")
 
 
 # ------------------------------------------------------------------ 5. random call sequences against a state model
@@ -342,7 +310,7 @@ def test_random_call_sequences(seed):
     """The model: the restatement's A and snapshot (None before the first half_update), the last error map (None before the first
     denoise_error).  After every call the half buffer is compared; the calls that report compare what they report."""
     w, h = 16, 12
-    scene, cfg = _scene("cornell_v3", w, h)
+    scene, cfg = ck.scene("cornell_v3", w, h)
     rng = np.random.default_rng(1000 + seed)
     r = Renderer(scene, cfg)
     r.refresh()                                    # (reproject needs a refresh since set_scene)
@@ -364,12 +332,12 @@ def test_random_call_sequences(seed):
         elif op == "denoise_error":
             radius, iterations = int(rng.integers(1, 4)), int(rng.integers(0, 3))
             if model is None:
-                assert _code(lambda: r.denoise_error(thr, radius, iterations=iterations)) == ESTATE
+                assert ck.code(lambda: r.denoise_error(thr, radius, iterations=iterations)) == ESTATE
             else:
                 err, _ = _check_error(r, cfg, model, thr, radius, iterations=iterations)
         elif op == "select_error":
             if err is None:
-                assert _code(lambda: r.select_error(thr, 1)) == ESTATE
+                assert ck.code(lambda: r.select_error(thr, 1)) == ESTATE
             else:
                 _check_select(r, model, err, thr, int(rng.integers(0, 3)))
         elif op == "refresh":
@@ -389,8 +357,8 @@ def test_random_call_sequences(seed):
             if model:
                 model.restart(ib)
         if model is None:
-            assert _code(lambda: r.half_buffer) == ESTATE, trace
+            assert ck.code(lambda: r.half_buffer) == ESTATE, trace
         else:
-            _same(r.half_buffer, model.a, f"half_buffer after {trace}")
+            ck.same(r.half_buffer, model.a, f"half_buffer after {trace}")
         if err is not None:
-            _same(r.denoised_error, err, f"denoised_error after {trace}")
+            ck.same(r.denoised_error, err, f"denoised_error after {trace}")

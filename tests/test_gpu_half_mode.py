@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import checks as ck
 import half_mode_ref_lib as hm
 import half_ref_lib as hl
 import noise_ref_lib as nr
@@ -27,7 +28,7 @@ ESTATE, EINVAL = -4, -1
 FRAMES = gh.FRAMES                       # (7, 5), (33, 17), (64, 48): less than a block; partial blocks both ways; whole blocks
 KS = (1, 3, 8, 12)                       # the scalar tail alone; scalar (K % 4 != 0); the 8-at-a-time path alone; both together
 N_REF = 2 * sum(KS)                      # a full-frame and a selected call of every K
-_scene, _same, _bits, _code, _counters, _stripe = gh._scene, gh._same, gh._bits, gh._code, gh._counters, gh._stripe
+_scene, _same, _bits, _code, _counters, _stripe = ck.scene, ck.same, ck.bits, ck.code, ck.counters, gh._stripe
 _fid = lambda f: f"{f[0]}x{f[1]}"      # noqa: E731
 
 _colours = {}

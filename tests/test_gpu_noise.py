@@ -4,11 +4,13 @@ error rules of include/rtpbr.h and Renderer.render_until."""
 import numpy as np
 import pytest
 
+import checks as ck
 import feature_ref_lib as fr
 import noise_ref_lib as nr
 import pool_ref_lib as pl
 import test_gpu_features_denoise as fd
 import test_gpu_reproject as rp
+from checks import EINVAL, ESTATE
 from raytracingpbr_amd import Config, cornell_box, src_scene
 from raytracingpbr_amd._capi import RtpbrError
 from raytracingpbr_amd.renderer import (BUF_DIFF_BUFFER, BUF_DIFF_PIXELS, BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_MOMENTS, BUF_NOISE,
@@ -16,17 +18,7 @@ from raytracingpbr_amd.renderer import (BUF_DIFF_BUFFER, BUF_DIFF_PIXELS, BUF_IM
 
 pytestmark = pytest.mark.gpu
 
-ESTATE, EINVAL = -4, -1
 W, H = 97, 61
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = _bits(got) != _bits(want)
-    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
 
 
 def _batches(r, t, n, per):
@@ -39,16 +31,16 @@ def _batches(r, t, n, per):
 
 def _check_estimate_and_guided(r, cfg, t, threshold=0.02, **params):
     ib = r.image_buffer
-    _same(r.moments, t.moments, "moments")
+    ck.same(r.moments, t.moments, "moments")
     st = r.noise_estimate(threshold)
     feats = fd._gpu_features(r)
     noise, var0, want = nr.estimate(ib, t.moments, feats["object"], threshold)
-    _same(r.noise, noise, "noise")
+    ck.same(r.noise, noise, "noise")
     assert (st.pixels_estimated, st.pixels_above) == want[:2]
     assert np.float32(st.max_noise).view(np.uint32) == np.float32(want[2]).view(np.uint32)
     r.denoise_guided(**params)
-    _same(r.denoised_pixels, nr.guided(cfg, ib, feats, var0, **params), "guided")
-    _same(r.noise, noise, "noise after denoise_guided")
+    ck.same(r.denoised_pixels, nr.guided(cfg, ib, feats, var0, **params), "guided")
+    ck.same(r.noise, noise, "noise after denoise_guided")
     return st, var0
 
 
@@ -99,7 +91,7 @@ def test_guided_levels_and_demodulation(iterations, demodulate):
     assert (r.noise[10:14, 20:27] == 0).all()
     # the zeroed pixels' next batch counts from the written state
     _batches(r, t, 1, 2)
-    _same(r.moments, t.moments, "moments after a write and another batch")
+    ck.same(r.moments, t.moments, "moments after a write and another batch")
 
 
 @pytest.mark.parametrize("demodulate", [0, 1])
@@ -113,9 +105,9 @@ def test_zero_levels_are_the_same_pass_in_both_filters(demodulate):
     r.denoise(iterations=0, demodulate=demodulate)
     plain = r.denoised_pixels
     r.denoise()                        # (something else in the buffer, so that the next call has to write it)
-    assert (_bits(r.denoised_pixels) != _bits(plain)).any()
+    assert (ck.bits(r.denoised_pixels) != ck.bits(plain)).any()
     r.denoise_guided(iterations=0, demodulate=demodulate)
-    _same(r.denoised_pixels, plain, "denoise_guided(iterations=0) against denoise(iterations=0)")
+    ck.same(r.denoised_pixels, plain, "denoise_guided(iterations=0) against denoise(iterations=0)")
 
 
 def test_a_frame_smaller_than_the_taps_and_the_pool_tile():
@@ -134,17 +126,17 @@ def test_a_frame_smaller_than_the_taps_and_the_pool_tile():
     feats = fd._gpu_features(r)
     fd._assert_features_equal(feats, fd._ref_features(scene, cfg))
     assert (feats["object"] >= 0).any()
-    _same(r.denoised_pixels, fr.denoise(cfg, ib, feats, 3), "denoise")
+    ck.same(r.denoised_pixels, fr.denoise(cfg, ib, feats, 3), "denoise")
     _, var0 = _check_estimate_and_guided(r, cfg, t, iterations=3)        # pooling off
     r.set_noise_estimator(4, 3, 0)                                       # three batches: every pixel is young and pools
     st = r.noise_estimate(0.02)
     noise, var_pooled, want = pl.estimate(ib, t.moments, feats["object"], 0.02, 4, 3)
-    _same(r.noise, noise, "pooled noise")
+    ck.same(r.noise, noise, "pooled noise")
     assert (st.pixels_estimated, st.pixels_above) == want[:2]
     assert np.float32(st.max_noise).view(np.uint32) == np.float32(want[2]).view(np.uint32)
     assert (var_pooled != var0).any(), "pooling changed nothing: the plain kernel would pass"
     r.denoise_guided(iterations=3)
-    _same(r.denoised_pixels, nr.guided(cfg, ib, feats, var_pooled, iterations=3), "guided on the pooled variance")
+    ck.same(r.denoised_pixels, nr.guided(cfg, ib, feats, var_pooled, iterations=3), "guided on the pooled variance")
 
 
 def test_young_pixels_use_the_neighbourhood():
@@ -189,7 +181,7 @@ def test_state_rules():
     ib[..., 3] += 5
     r.image_buffer = ib
     r.noise_update()
-    _same(r.moments, M, "moments after write_buffer + noise_update")
+    ck.same(r.moments, M, "moments after write_buffer + noise_update")
     for b in (BUF_MOMENTS, BUF_NOISE):
         with pytest.raises(RtpbrError) as e:
             r._write(b, np.zeros(r._shape(b)[0], np.float32))
@@ -234,8 +226,8 @@ def test_errors_and_a_refused_call_changes_nothing():
         assert e.value.code == ESTATE
     r.set_tiles(0, 0, 0, 1)
     for b, a in keep.items():
-        _same(r._read(b), a, f"buffer {b} after refused calls")
-    _same(r.denoised_pixels, den, "denoised_pixels after refused calls")
+        ck.same(r._read(b), a, f"buffer {b} after refused calls")
+    ck.same(r.denoised_pixels, den, "denoised_pixels after refused calls")
 
 
 @pytest.mark.parametrize("form", ["complete", "persistent"])
@@ -258,7 +250,7 @@ def test_the_calls_leave_everything_else_untouched(form):
     c1 = r.counters()
     assert [getattr(c0, f) for f, _ in c0._fields_] == [getattr(c1, f) for f, _ in c1._fields_]
     for b, a in before.items():
-        _same(r._read(b), a, f"buffer {b}")
+        ck.same(r._read(b), a, f"buffer {b}")
 
 
 @pytest.mark.parametrize("move", ["translate", "yaw", "vfov"])
@@ -276,17 +268,17 @@ def test_reproject_warps_the_moments(move):
     plain.reproject(new, **params)
     f0, f1 = fr.features(scene, cfg, old), fr.features(scene, cfg, new)
     want_ib, want_M = nr.reproject(cfg, old, new, ib, t.moments, f0, f1, **params)
-    _same(r.moments, want_M, "moments")
-    _same(r.image_buffer, want_ib, "image_buffer")
-    _same(r.image_buffer, plain.image_buffer, "image_buffer against a context that never tracked noise")
-    _same(r.motion, plain.motion, "motion")
+    ck.same(r.moments, want_M, "moments")
+    ck.same(r.image_buffer, want_ib, "image_buffer")
+    ck.same(r.image_buffer, plain.image_buffer, "image_buffer against a context that never tracked noise")
+    ck.same(r.motion, plain.motion, "motion")
     fd._assert_features_equal(fd._gpu_features(r), fd._gpu_features(plain))
     kept = want_ib[..., 3] > 0
     assert kept.any() and (~kept).any() and (want_M[~kept] == 0).all() and (want_M[kept][:, 3] > 1).all()
     # the snapshot is the warped image: the next batch holds the new samples only
     t.moments[:], t.snapshot[:] = want_M, want_ib
     _batches(r, t, 1, 2)
-    _same(r.moments, t.moments, "moments one batch after the reprojection")
+    ck.same(r.moments, t.moments, "moments one batch after the reprojection")
 
 
 def test_an_unchanged_camera_reproduces_the_moments():
@@ -295,7 +287,7 @@ def test_an_unchanged_camera_reproduces_the_moments():
     t = nr.Tracker(W, H)
     _batches(r, t, 3, 2)
     r.reproject(scene.camera, max_history=1e6)
-    _same(r.moments, t.moments, "moments after an identical reprojection")
+    ck.same(r.moments, t.moments, "moments after an identical reprojection")
 
 
 def test_render_until():
@@ -321,5 +313,5 @@ def test_track_noise_makes_every_sample_call_a_batch():
     for n in (1, 3, 2):
         r.sample(n)
         t.update(r.image_buffer)
-    _same(r.moments, t.moments, "moments")
+    ck.same(r.moments, t.moments, "moments")
     assert (r.moments[..., 3] == 3).all()

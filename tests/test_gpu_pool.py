@@ -5,31 +5,22 @@ one pixel behind a tile's edge in x and in y for either; 5 x 3 is smaller than t
 import numpy as np
 import pytest
 
+import checks as ck
 import feature_ref_lib as fr
 import noise_ref_lib as nr
 import pool_ref_lib as pl
 import select_ref_lib as sr
 import test_gpu_features_denoise as fd
 import test_gpu_reproject as rp
+from checks import EINVAL
 from oracle_backend import OracleRenderer
 from raytracingpbr_amd import Config, cornell_box, src_scene
 from raytracingpbr_amd._capi import RtpbrError
 
 pytestmark = pytest.mark.gpu
 
-EINVAL = -1
 THR = 0.02
 SIZES = [(64, 48), (67, 45), (5, 3), (17, 17), (5, 65)]
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a
-
-
-def _same(got, want, what):
-    bad = _bits(got) != _bits(want)
-    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
 
 
 def _scene(name, w, h):
@@ -44,7 +35,7 @@ def _check(r, pool_batches, radius, threshold=THR):
     r.set_noise_estimator(pool_batches, radius, 0)
     st = r.noise_estimate(threshold)
     noise, var0, want = pl.estimate(r.image_buffer, r.moments, r.feature_object, threshold, pool_batches, radius)
-    _same(r.noise, noise, f"noise (pool_batches {pool_batches}, radius {radius})")
+    ck.same(r.noise, noise, f"noise (pool_batches {pool_batches}, radius {radius})")
     assert (st.pixels_estimated, st.pixels_above) == want[:2]
     assert np.float32(st.max_noise).view(np.uint32) == np.float32(want[2]).view(np.uint32)
     return noise, var0
@@ -83,7 +74,7 @@ def test_bit_identical_to_the_restatement(name, size):
             noise, _ = _check(r, 4, radius)
             differs |= bool((noise != off).any())
             if K.min() >= 4:
-                _same(noise, off, "old pixels take today's estimate")
+                ck.same(noise, off, "old pixels take today's estimate")
     assert differs, "pooling never changed a value: the test would pass on the plain kernel"
     assert K.max() == (5 if cfg.kernel_form == 0 else 4)
 
@@ -146,12 +137,12 @@ def test_select_noisy_with_min_samples():
         thr = float(np.quantile(r.noise, 0.9))
         n = r.select_noisy(thr, dilate)
         noise = r.noise
-        _same(noise, pl.estimate(ib, r.moments, r.feature_object, thr, pool_batches, 2)[0], "noise written by select_noisy")
+        ck.same(noise, pl.estimate(ib, r.moments, r.feature_object, thr, pool_batches, 2)[0], "noise written by select_noisy")
         want = pl.select(noise, cnt, thr, dilate, ms)
-        _same(r.selection, want, f"selection (min_samples {ms}, dilate {dilate})")
+        ck.same(r.selection, want, f"selection (min_samples {ms}, dilate {dilate})")
         assert n == int(want.sum())
         if ms == 0:
-            _same(want, sr.select(noise, cnt, thr, dilate), "min_samples = 0 is the plain rule")
+            ck.same(want, sr.select(noise, cnt, thr, dilate), "min_samples = 0 is the plain rule")
         if ms == 5:
             assert (want[cnt == 4] == 1).all() and not (want[cnt == 7] == 1).all()
         if ms == 8:
@@ -167,8 +158,8 @@ def test_guided_filter_takes_the_pooled_variance():
         r.denoise_guided()
         noise, var0, _ = pl.estimate(ib, r.moments, feats["object"], 0.0, 8, radius)
         assert (var0 != var_off).any()
-        _same(r.noise, noise, "noise written by denoise_guided")
-        _same(r.denoised_pixels, nr.guided(cfg, ib, feats, var0), f"guided, radius {radius}")
+        ck.same(r.noise, noise, "noise written by denoise_guided")
+        ck.same(r.denoised_pixels, nr.guided(cfg, ib, feats, var0), f"guided, radius {radius}")
 
 
 def test_null_restores_todays_bits_and_refused_calls_change_nothing():
@@ -184,16 +175,16 @@ def test_null_restores_todays_bits_and_refused_calls_change_nothing():
         assert e.value.code == EINVAL, bad
     assert r.api.fn["set_noise_estimator"](None, None) == EINVAL
     st = r.noise_estimate(THR)
-    _same(r.noise, pooled, "noise after refused calls")
+    ck.same(r.noise, pooled, "noise after refused calls")
     n = r.select_noisy(THR, 0)
     assert n == int(pl.select(pooled, ib[..., 3], THR, 0, 6).sum())
     r.api.call("set_noise_estimator", r._ctx, None)
     st = r.noise_estimate(THR)
-    _same(r.noise, off, "noise after restoring the defaults")
+    ck.same(r.noise, off, "noise after restoring the defaults")
     assert (st.pixels_estimated, st.pixels_above) == want[:2]
     assert r.select_noisy(THR, 1) == int(sr.select(off, ib[..., 3], THR, 1).sum())
     r.denoise_guided()
-    _same(r.denoised_pixels, nr.guided(cfg, ib, fd._gpu_features(r), nr.estimate(ib, r.moments, obj)[1]), "guided after restoring")
+    ck.same(r.denoised_pixels, nr.guided(cfg, ib, fd._gpu_features(r), nr.estimate(ib, r.moments, obj)[1]), "guided after restoring")
 
 
 def test_the_setting_survives_refresh_and_set_config():
@@ -209,7 +200,7 @@ def test_the_setting_survives_refresh_and_set_config():
         st = r.noise_estimate(THR)
         ib = r.image_buffer
         noise, _, want = pl.estimate(ib, r.moments, r.feature_object, THR, 8, 2)
-        _same(r.noise, noise, "noise")
+        ck.same(r.noise, noise, "noise")
         assert (noise != nr.estimate(ib, r.moments, r.feature_object, THR)[0]).any()
         assert (st.pixels_estimated, st.pixels_above) == want[:2]
         assert r.select_noisy(THR, 0) == w * h   # min_samples = 6 > 4 samples
@@ -236,8 +227,8 @@ def test_an_adaptive_loop_of_four_rounds_against_the_cpu_composition():
         noise, _, _ = pl.estimate(ib, t.moments, obj, thr, 8, 2)
         mask = pl.select(noise, ib[..., 3], thr, 0, 3 * batch)
         n = r.select_noisy(thr, 0)
-        _same(r.noise, noise, f"round {rnd}: noise")
-        _same(r.selection, mask, f"round {rnd}: selection")
+        ck.same(r.noise, noise, f"round {rnd}: noise")
+        ck.same(r.selection, mask, f"round {rnd}: selection")
         assert n == int(mask.sum())
         r.sample_selected(batch)
         r.noise_update()
@@ -245,8 +236,8 @@ def test_an_adaptive_loop_of_four_rounds_against_the_cpu_composition():
         ib = np.where((mask != 0)[..., None], o.image_buffer, ib)
         o.image_buffer = ib
         t.update(ib)
-        _same(r.image_buffer, ib, f"round {rnd}: image_buffer")
-        _same(r.moments, t.moments, f"round {rnd}: moments")
+        ck.same(r.image_buffer, ib, f"round {rnd}: image_buffer")
+        ck.same(r.moments, t.moments, f"round {rnd}: moments")
         masks.append(mask)
     sizes = [int(m.sum()) for m in masks]
     print("selected per round:", sizes)

@@ -7,16 +7,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import checks as ck
 import present_ref_lib as pr
 import test_gpu_features_denoise as fd
 import test_present_ref as tp
+from checks import EINVAL, ESTATE
 from raytracingpbr_amd import Config, PresentParams, Renderer, cornell_box, imageio, src_scene
 from raytracingpbr_amd._capi import RtpbrError
 from raytracingpbr_amd.renderer import BUF_IMAGE_PIXELS, BUF_PRESENT
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, ESTATE = -1, -4
 SHAPES = [(1, 1), (1, 7), (7, 1), (2, 3), (5, 4), (63, 65), (64, 64), (65, 63), (127, 130), (130, 127), (257, 66)]
 FORMATS = {"rgb8": pr.FORMAT_RGB8, "rgba8": pr.FORMAT_RGBA8}
 F = np.float32
@@ -42,11 +43,6 @@ def _same(got, want, what):
     assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} against {want.shape} {want.dtype}"
     bad = got != want
     assert not bad.any(), f"{what}: {int(bad.sum())} bytes differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a
 
 
 def _counters(r):
@@ -98,11 +94,11 @@ def test_accum_is_post_process_without_its_writes(setup):
             shown[fmt, dither] = r.presented
     for a, b, name in zip(before, [r.image_buffer, r.image_pixels, r.diff_buffer, r.diff_pixels],
                           ["image_buffer", "image_pixels", "diff_buffer", "diff_pixels"]):
-        assert np.array_equal(_bits(a), _bits(b)), f"present(accum) changed {name}"
+        assert np.array_equal(ck.bits(a), ck.bits(b)), f"present(accum) changed {name}"
     assert _counters(r) == counters
     r.post_process()
     px = r.image_pixels
-    assert not np.array_equal(_bits(px), _bits(before[1])), "the second batch changed nothing: the test would pass on stale pixels"
+    assert not np.array_equal(ck.bits(px), ck.bits(before[1])), "the second batch changed nothing: the test would pass on stale pixels"
     for (fmt, dither), got in shown.items():
         r.present("pixels", fmt, dither)
         _same(got, r.presented, f"accum against post_process + pixels, {fmt} dither={dither}")
@@ -123,7 +119,7 @@ def test_denoised(shape):
     assert e.value.code == ESTATE
     r.denoise(iterations=2)
     d = r.denoised_pixels
-    assert not np.array_equal(_bits(d), _bits(r.image_pixels))
+    assert not np.array_equal(ck.bits(d), ck.bits(r.image_pixels))
     for fmt in FORMATS:
         for dither in (False, True):
             r.present("denoised", fmt, dither)
@@ -143,7 +139,7 @@ def test_nothing_else_moves():
         r.present(source)
     after = [r.image_buffer, r.image_pixels, r.denoised_pixels, r.diff_buffer, r.diff_pixels, r.ray_buffer]
     for a, b in zip(before, after):
-        assert np.array_equal(_bits(a), _bits(b))
+        assert np.array_equal(ck.bits(a), ck.bits(b))
     assert _counters(r) == counters
 
 

@@ -6,9 +6,11 @@ import math
 import numpy as np
 import pytest
 
+import checks as ck
 import feature_ref_lib as fr
 import reproject_ref_lib as rr
 import test_gpu_features_denoise as fd
+from checks import EINVAL, ESTATE
 from oracle_backend import OracleRenderer
 from raytracingpbr_amd import SHAPE, Camera, Config, Renderer, cornell_box, src_scene
 from raytracingpbr_amd._capi import RtpbrError
@@ -18,16 +20,11 @@ from raytracingpbr_amd.renderer import (BUF_FEAT_ALBEDO, BUF_FEAT_DEPTH, BUF_FEA
 
 pytestmark = pytest.mark.gpu
 
-ESTATE, EINVAL = -4, -1
 W, H = 97, 61
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _assert_same_bits(got, want, what):
-    bad = _bits(got) != _bits(want)
+    bad = ck.bits(got) != ck.bits(want)
     assert not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
 
 

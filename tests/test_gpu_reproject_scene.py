@@ -8,6 +8,7 @@ and no test may start a compiler."""
 import numpy as np
 import pytest
 
+import checks as ck
 import feature_ref_lib as fr
 import noise_ref_lib as nr
 import pool_ref_lib as pl
@@ -173,7 +174,7 @@ def test_a_still_camera_keeps_the_bits_of_everything_the_box_never_covers():
     f0, f1 = fr.features(scene, cfg), fr.features(new_scene, cfg)
     still = (f0["object"] == f1["object"]) & (f0["object"] >= 0) & (f0["object"] != 6)
     assert still.sum() > W * H // 2
-    assert np.array_equal(tg._bits(out[still]), tg._bits(ib[still]))
+    assert np.array_equal(ck.bits(out[still]), ck.bits(ib[still]))
     xs, ys = np.meshgrid(np.arange(W), np.arange(H), indexing="ij")
     own = (mv[..., 0] == xs) & (mv[..., 1] == ys)
     assert own[still].all()
@@ -376,7 +377,7 @@ def test_call_sequence_over_the_stateful_stages():
     f2 = fr.features(new_scene, cfg, cam2)
     want_ib, want_mv = rr.reproject(cfg, cam0, cam2, ib, f1, f2)
     ib_m, want_M = nr.reproject(cfg, cam0, cam2, ib, tracker.moments, f1, f2)
-    assert np.array_equal(tg._bits(ib_m), tg._bits(want_ib))
+    assert np.array_equal(ck.bits(ib_m), ck.bits(want_ib))
     r.reproject(cam2)
     _same(r.image_buffer, want_ib, "image_buffer after reproject")
     _same(r.motion, want_mv, "motion after reproject")

@@ -7,10 +7,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import checks as ck
 import noise_ref_lib as nr
 import sample_moments_ref_lib as sm
 import test_gpu_features_denoise as fd
 import test_gpu_reproject as rp
+from checks import EINVAL, ESTATE
 from oracle_backend import OracleRenderer
 from raytracingpbr_amd import Config, Renderer, cornell_box, src_scene
 from raytracingpbr_amd._capi import RtpbrError
@@ -18,8 +20,6 @@ from raytracingpbr_amd.renderer import BUF_IMAGE_BUFFER, BUF_MOMENTS, BUF_NOISE
 
 pytestmark = pytest.mark.gpu
 
-ESTATE, EINVAL = -4, -1
-COUNTERS = ("samples", "raycasts", "march_steps", "hits", "sky_lookups", "deposits")
 FRAMES = {"7x5": (7, 5), "20x13": (20, 13)}      # 35 pixels: less than a wave; 260: the second block holds 4 lanes
 KS = (1, 3, 8, 12, 20)                           # scalar loop; scalar; vector loop only; vector + remainder; vector + remainder
 N_REF = 20
@@ -29,20 +29,6 @@ def _scene(name, w, h):
     if name == "cornell_v3":
         return cornell_box("v3", aspect=w / h), Config.cornell_v3(w, h, 0, 3)
     return src_scene(aspect=w / h, tokyo=True), Config.scene_demo(w, h, 5, 16)      # spheres, boxes and a cylinder
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(got, want, what):
-    bad = _bits(got) != _bits(want)
-    assert got.shape == want.shape and not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _counters(r):
-    c = r.counters()
-    return [getattr(c, k) for k in COUNTERS]
 
 
 _colours = {}
@@ -61,11 +47,11 @@ def _ref_colours(scene_name, frame, n=N_REF):
 
 def _check(r, t, what=""):
     """moments and image_buffer against the CPU tracker; the snapshot through a noise_update, which must find nothing new"""
-    _same(r.image_buffer, t.image_buffer, what + "image_buffer")
-    _same(r.moments, t.moments, what + "moments")
-    _same(t.snapshot, t.image_buffer, what + "restated snapshot")
+    ck.same(r.image_buffer, t.image_buffer, what + "image_buffer")
+    ck.same(r.moments, t.moments, what + "moments")
+    ck.same(t.snapshot, t.image_buffer, what + "restated snapshot")
     r.noise_update()
-    _same(r.moments, t.moments, what + "moments after a noise_update (the snapshot is image_buffer)")
+    ck.same(r.moments, t.moments, what + "moments after a noise_update (the snapshot is image_buffer)")
 
 
 @pytest.mark.parametrize("K", KS)
@@ -79,15 +65,15 @@ def test_tracked_sample_matches_the_restatement_and_the_untracked_twin(scene_nam
     assert r.noise_per_sample is True
     r.sample(K)
     twin.sample(K)
-    _same(r.image_buffer, twin.image_buffer, "image_buffer against the untracked twin")
-    assert _counters(r) == _counters(twin) and r.counters().deposits == w * h * K
+    ck.same(r.image_buffer, twin.image_buffer, "image_buffer against the untracked twin")
+    assert ck.counters(r) == ck.counters(twin) and r.counters().deposits == w * h * K
     t = sm.Tracker(w, h).sample(_ref_colours(scene_name, frame, K))
     _check(r, t)
     assert (r.moments[..., 3] == K).all() and (r.moments[..., 2] == K).all()
     if K + 3 <= N_REF:      # a second tracked call continues both sums
         r.sample(3)
         twin.sample(3)
-        _same(r.image_buffer, twin.image_buffer, "image_buffer against the untracked twin, second call")
+        ck.same(r.image_buffer, twin.image_buffer, "image_buffer against the untracked twin, second call")
         _check(r, t.sample(_ref_colours(scene_name, frame)[K:K + 3]), "second call: ")
 
 
@@ -124,8 +110,8 @@ def test_sub_launches_of_3_3_and_2_samples():
         r.sample(8)
         assert r.last_sample_ms()[2] == (3 if budget == 1 << 20 else 1)
         got.append((r.moments, r.image_buffer))
-    _same(got[0][0], got[1][0], "moments, three sub-launches against one")
-    _same(got[0][1], got[1][1], "image_buffer, three sub-launches against one")
+    ck.same(got[0][0], got[1][0], "moments, three sub-launches against one")
+    ck.same(got[0][1], got[1][1], "image_buffer, three sub-launches against one")
     t = sm.Tracker(w, h).sample(sm.oracle_colours(OracleRenderer(scene, cfg), 0, 8))
     _check(r, t)
 
@@ -151,10 +137,10 @@ def test_selected_launch_leaves_unselected_pixels_alone(K):
     before = (r.moments, r.image_buffer)
     r.sample_selected(K)
     twin.sample_selected(K)
-    _same(r.image_buffer, twin.image_buffer, "image_buffer against the untracked twin")
-    assert _counters(r) == _counters(twin) and r.counters().deposits == int(mask.sum()) * K
+    ck.same(r.image_buffer, twin.image_buffer, "image_buffer against the untracked twin")
+    assert ck.counters(r) == ck.counters(twin) and r.counters().deposits == int(mask.sum()) * K
     keep = mask == 0
-    assert np.array_equal(_bits(r.moments)[keep], _bits(before[0])[keep]) and np.array_equal(_bits(r.image_buffer)[keep], _bits(before[1])[keep])
+    assert np.array_equal(ck.bits(r.moments)[keep], ck.bits(before[0])[keep]) and np.array_equal(ck.bits(r.image_buffer)[keep], ck.bits(before[1])[keep])
     _check(r, t.sample(c[4:4 + K], mask))
     assert np.array_equal(r.moments[..., 3], np.where(mask != 0, 4 + K, 4).astype(np.float32))
     # the sample index advanced for everybody: the next full-frame call deposits samples 4 + K ..
@@ -183,7 +169,7 @@ def test_the_snapshot_holds_all_four_words(selected, K):
     else:
         r.sample(K)
         t.sample(c[:K])
-    _same(r.moments, t.moments, "moments after the tracked call")
+    ck.same(r.moments, t.moments, "moments after the tracked call")
     r.set_noise_tracking(False)
     r.sample(2)                                   # one untracked batch of two samples on top of the tracked snapshot
     ib = r.image_buffer
@@ -191,13 +177,13 @@ def test_the_snapshot_holds_all_four_words(selected, K):
     ref = nr.Tracker(w, h)
     ref.moments, ref.snapshot = t.moments.copy(), t.snapshot.copy()
     ref.update(ib)
-    _same(r.moments, ref.moments, "moments after an untracked batch on the tracked snapshot")
+    ck.same(r.moments, ref.moments, "moments after an untracked batch on the tracked snapshot")
     # the check has teeth: the same batch on a snapshot with the right count and no colour gives other moments
     wrong = nr.Tracker(w, h)
     wrong.moments, wrong.snapshot = t.moments.copy(), t.snapshot.copy()
     wrong.snapshot[..., :3] = 0
     wrong.update(ib)
-    assert (_bits(wrong.moments) != _bits(ref.moments)).any()
+    assert (ck.bits(wrong.moments) != ck.bits(ref.moments)).any()
     assert (r.moments[..., 3] == t.moments[..., 3] + 1).all()
 
 
@@ -210,9 +196,9 @@ def test_a_full_mask_equals_the_unselected_call():
     a.select_mask(np.ones((w, h), np.uint8))
     a.sample_selected(8)
     b.sample(8)
-    _same(a.moments, b.moments, "moments")
-    _same(a.image_buffer, b.image_buffer, "image_buffer")
-    assert _counters(a) == _counters(b)
+    ck.same(a.moments, b.moments, "moments")
+    ck.same(a.image_buffer, b.image_buffer, "image_buffer")
+    assert ck.counters(a) == ck.counters(b)
     _check(a, sm.Tracker(w, h).sample(_ref_colours("cornell_v3", "20x13", 8)))
 
 
@@ -229,9 +215,9 @@ def test_mixed_with_noise_update_and_reproject():
     c_old = sm.oracle_colours(OracleRenderer(scene, cfg, old), 0, 4)
     t = sm.Tracker(w, h).sample(c_old)
     M = r.moments
-    _same(M, t.moments, "moments")
+    ck.same(M, t.moments, "moments")
     r.noise_update()
-    _same(r.moments, M, "moments after noise_update")
+    ck.same(r.moments, M, "moments after noise_update")
     r.render_features()
     old_feats = fd._gpu_features(r)
     ib = r.image_buffer
@@ -239,18 +225,18 @@ def test_mixed_with_noise_update_and_reproject():
     assert r.noise_per_sample and r.camera is new
     new_feats = fd._gpu_features(r)
     ib_w, M_w = nr.reproject(cfg, old, new, ib, M, old_feats, new_feats)
-    _same(r.image_buffer, ib_w, "warped image_buffer")
-    _same(r.moments, M_w, "warped moments")
+    ck.same(r.image_buffer, ib_w, "warped image_buffer")
+    ck.same(r.moments, M_w, "warped moments")
     t.moments, t.image_buffer, t.snapshot = M_w.copy(), ib_w.copy(), ib_w.copy()
     r.sample(4)
     # the sample index goes on across rtpbr_reproject: the new view's samples 4 .. 7
     c_new = sm.oracle_colours(OracleRenderer(scene, cfg, new), 4, 4)
     t.sample(c_new)
-    _same(r.image_buffer, t.image_buffer, "image_buffer after the second tracked call")
-    _same(r.moments, t.moments, "moments after the second tracked call")
+    ck.same(r.image_buffer, t.image_buffer, "image_buffer after the second tracked call")
+    ck.same(r.moments, t.moments, "moments after the second tracked call")
     st = r.noise_estimate(0.02)
     noise, _, want = nr.estimate(t.image_buffer, t.moments, fd._gpu_features(r)["object"], 0.02)
-    _same(r.noise, noise, "noise")
+    ck.same(r.noise, noise, "noise")
     assert (st.pixels_estimated, st.pixels_above) == want[:2]
 
 
@@ -266,7 +252,7 @@ def test_state_rules():
     r.set_noise_tracking(True)
     t2 = nr.Tracker(w, h)
     t2.update(r.image_buffer)
-    _same(r.moments, t2.moments, "moments after the set call")
+    ck.same(r.moments, t2.moments, "moments after the set call")
     t = sm.Tracker(w, h)
     t.moments, t.snapshot, t.image_buffer = t2.moments.copy(), t2.snapshot.copy(), r.image_buffer
     r.sample(3)
@@ -282,7 +268,7 @@ def test_state_rules():
     r.image_buffer = ib
     M = r.moments
     r.noise_update()
-    _same(r.moments, M, "moments after a write and a noise_update")
+    ck.same(r.moments, M, "moments after a write and a noise_update")
     t = sm.Tracker(w, h)
     t.moments, t.snapshot, t.image_buffer = M.copy(), ib.copy(), ib.copy()
     r.sample(2)
@@ -290,9 +276,9 @@ def test_state_rules():
     # OFF sets the mode and nothing else: the next call is a plain one, its samples are one batch of the next noise_update
     M = r.moments
     r.set_noise_tracking(False)
-    _same(r.moments, M, "moments after OFF")
+    ck.same(r.moments, M, "moments after OFF")
     r.sample(2)
-    _same(r.moments, M, "moments after an untracked call")
+    ck.same(r.moments, M, "moments after an untracked call")
     # a new resolution frees the buffers; the mode survives and the next tracked call makes them again, zeroed
     r.set_noise_tracking(True)
     w2, h2 = FRAMES["7x5"]
@@ -336,7 +322,7 @@ def test_refusals_change_nothing():
     r.sample(3)
     r.select_mask(_third(w, h))
     keep = {b: r._read(b) for b in (BUF_IMAGE_BUFFER, BUF_MOMENTS)}
-    counters = _counters(r)
+    counters = ck.counters(r)
     for mode in (2, -1, 7):
         assert r.api.fn["set_noise_tracking"](r._ctx, mode) == EINVAL
     r.set_tiles(16, 16, 0, 2)
@@ -348,9 +334,9 @@ def test_refusals_change_nothing():
     assert _code(r.sample, 1) == ESTATE
     r.set_option("precision", 0)
     assert r.noise_per_sample is True
-    assert _counters(r) == counters
+    assert ck.counters(r) == counters
     for b, a in keep.items():
-        _same(r._read(b), a, f"buffer {b} after refused calls")
+        ck.same(r._read(b), a, f"buffer {b} after refused calls")
     # ... and neither the mode nor the sample index moved: the next tracked call deposits samples 3 and 4
     r.sample(2)
     _check(r, sm.Tracker(w, h).sample(_ref_colours("cornell_v3", "20x13", 5)))
@@ -361,8 +347,8 @@ def test_refusals_change_nothing():
     p.set_noise_tracking(True)                   # the set call itself is noise_update: any form
     before, M = p.image_buffer, p.moments
     assert _code(p.sample, 1) == ESTATE
-    _same(p.image_buffer, before, "image_buffer")
-    _same(p.moments, M, "moments")
+    ck.same(p.image_buffer, before, "image_buffer")
+    ck.same(p.moments, M, "moments")
     p.set_noise_tracking(False)
     p.sample(1)
 
@@ -385,9 +371,9 @@ def test_render_until_and_render_adaptive_per_sample():
         if h_st.pixels_above == 0:
             break
     assert used == h_used and (st.pixels_estimated, st.pixels_above) == (h_st.pixels_estimated, h_st.pixels_above)
-    _same(r.image_buffer, host.image_buffer, "render_until: image_buffer")
-    _same(r.moments, host.moments, "render_until: moments")
-    _same(r.noise, host.noise, "render_until: noise")
+    ck.same(r.image_buffer, host.image_buffer, "render_until: image_buffer")
+    ck.same(r.moments, host.moments, "render_until: moments")
+    ck.same(r.noise, host.noise, "render_until: noise")
     assert (r.moments[..., 3] == used).all()
     # a one-batch budget is estimated from that batch alone
     one = Renderer(scene, cfg)
@@ -410,8 +396,8 @@ def test_render_until_and_render_adaptive_per_sample():
     h_st = host.noise_estimate(noise)
     assert traced == h_traced == int(a.image_buffer[..., 3].sum())
     assert (st.pixels_estimated, st.pixels_above) == (h_st.pixels_estimated, h_st.pixels_above)
-    _same(a.image_buffer, host.image_buffer, "render_adaptive: image_buffer")
-    _same(a.moments, host.moments, "render_adaptive: moments")
+    ck.same(a.image_buffer, host.image_buffer, "render_adaptive: image_buffer")
+    ck.same(a.moments, host.moments, "render_adaptive: moments")
     assert np.array_equal(a.moments[..., 3], a.image_buffer[..., 3]) and a.image_buffer[..., 3].min() >= batch
     with pytest.raises(ValueError):
         a.render_adaptive(noise, 0, per_sample=True)

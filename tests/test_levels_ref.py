@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import blend_ref_lib as bl
+import checks as ck
 import feature_ref_lib as fr
 import half_ref_lib as hl
 import hostile as hz
@@ -21,10 +22,6 @@ from raytracingpbr_amd.ibl import synthetic_env
 def _lum(c):
     c = np.asarray(c, np.float32)
     return (np.float32(0.299) * c[..., 0] + np.float32(0.587) * c[..., 1]) + np.float32(0.114) * c[..., 2]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _image(W, H, colour, count):
@@ -61,9 +58,9 @@ def test_every_level_of_the_ladder_is_the_filter_with_that_many_iterations():
         assert ladder.shape == (5, W, H, 3)
         for k in range(5):
             want = bl.filter(cfg, ib, feats, linear=True, iterations=k, demodulate=demodulate)
-            assert np.array_equal(_bits(ladder[k]), _bits(want)), (k, demodulate)
+            assert np.array_equal(ck.bits(ladder[k]), ck.bits(want)), (k, demodulate)
             # ... and a shorter ladder is the head of a longer one
-            assert np.array_equal(_bits(lv.filter_levels(cfg, ib, feats, iterations=k, demodulate=demodulate)), _bits(ladder[:k + 1]))
+            assert np.array_equal(ck.bits(lv.filter_levels(cfg, ib, feats, iterations=k, demodulate=demodulate)), ck.bits(ladder[:k + 1]))
         assert not ladder[:, 3:6, 4:9].any()
 
 
@@ -81,7 +78,7 @@ def test_identical_constant_halves_keep_every_level_and_give_the_denoised_frame(
             for z in (0.0, 2.0):
                 out, t, depth, st = f.blend(radius, z, 8)
                 assert np.all(t == 1) and np.all(depth == K) and st == (W * H, 0, 0.0)
-                assert np.array_equal(_bits(out), _bits(fr.denoise(cfg, ib, feats, iterations=K)))
+                assert np.array_equal(ck.bits(out), ck.bits(fr.denoise(cfg, ib, feats, iterations=K)))
 
 
 @pytest.mark.parametrize("radius", [1, 2, 3])
@@ -106,8 +103,8 @@ def test_noise_free_step_keeps_as_many_levels_as_see_no_blur(radius):
     assert np.all(depth[band0] == 0) and np.all(depth[band1] == 1) and np.all(depth[band2] == 2)
     assert np.all(t[band01] == 0) and np.all(t[band2] == 1)
     raw, den = fr.denoise(cfg, ib, feats, iterations=0, demodulate=0), fr.denoise(cfg, ib, feats, **p)
-    assert np.array_equal(_bits(out)[band01], _bits(raw)[band01]) and np.array_equal(_bits(out)[band2], _bits(den)[band2])
-    assert not np.array_equal(_bits(raw)[band0], _bits(den)[band0])
+    assert np.array_equal(ck.bits(out)[band01], ck.bits(raw)[band01]) and np.array_equal(ck.bits(out)[band2], ck.bits(den)[band2])
+    assert not np.array_equal(ck.bits(raw)[band0], ck.bits(den)[band0])
     assert st == (W * H, int(band01.sum()), 1.0)
 
 
@@ -120,7 +117,7 @@ def test_min_half_samples_gates_at_the_count_itself():
     den = lambda ib: fr.denoise(cfg, ib, feats, **p)      # noqa: E731
     ib, a = _step(W, H, 2 * (m - 1)), _step(W, H, m - 1)      # 7 + 7
     out, t, depth, st = lv.denoise_blend_levels(cfg, ib, a, feats, 3, 0.0, m, **p)
-    assert np.all(t == 1) and np.all(depth == 2) and st == (0, 0, 0.0) and np.array_equal(_bits(out), _bits(den(ib)))
+    assert np.all(t == 1) and np.all(depth == 2) and st == (0, 0, 0.0) and np.array_equal(ck.bits(out), ck.bits(den(ib)))
     ib, a = _step(W, H, 2 * m), _step(W, H, m)                # 8 + 8
     out, t, depth, st = lv.denoise_blend_levels(cfg, ib, a, feats, 3, 0.0, m, **p)
     assert st[0] == W * H and 0 < st[1] < W * H and (t == 0).any() and (depth == 0).any() and (depth == 1).any()
@@ -129,7 +126,7 @@ def test_min_half_samples_gates_at_the_count_itself():
     a[W // 2, 6] = 0.0
     out, t, depth, st = lv.denoise_blend_levels(cfg, ib, a, feats, 3, 0.0, m, **p)
     assert np.all(t[:, 2] == 1) and np.all(depth[:, 2] == 2) and t[W // 2, 6] == 1 and st[0] == W * H - W - 1
-    assert np.array_equal(_bits(out[:, 2]), _bits(den(ib)[:, 2]))
+    assert np.array_equal(ck.bits(out[:, 2]), ck.bits(den(ib)[:, 2]))
 
 
 def test_pixels_without_samples_and_no_levels():
@@ -143,10 +140,10 @@ def test_pixels_without_samples_and_no_levels():
         p = dict(iterations=K, demodulate=1)
         out, t, depth, st = lv.denoise_blend_levels(cfg, ib, a, feats, 2, 0.0, 8, **p)
         assert np.all(t[5:8, 2:5] == 1) and np.all(depth[5:8, 2:5] == K) and st[0] == W * H - 9
-        assert np.array_equal(_bits(out[5:8, 2:5]), _bits(fr.denoise(cfg, ib, feats, **p)[5:8, 2:5]))      # what post_process shows
+        assert np.array_equal(ck.bits(out[5:8, 2:5]), ck.bits(fr.denoise(cfg, ib, feats, **p)[5:8, 2:5]))      # what post_process shows
         if K == 0:
             assert np.all(t == 1) and np.all(depth == 0) and st[1:] == (0, 0.0)
-            assert np.array_equal(_bits(out), _bits(fr.denoise(cfg, ib, feats, **p)))
+            assert np.array_equal(ck.bits(out), ck.bits(fr.denoise(cfg, ib, feats, **p)))
 
 
 @pytest.mark.parametrize("family", hz.FAMILIES)

@@ -6,6 +6,7 @@ import re
 
 import numpy as np
 
+import checks as ck
 import feature_ref_lib as fr
 import reproject_ref_lib as rr
 from oracle_backend import OracleRenderer
@@ -23,10 +24,6 @@ def _history(w=W, h=H, spp=2, hit_eps=None):
     o = OracleRenderer(sc, cfg)
     o.sample(spp)
     return sc, cfg, o.image_buffer
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _moved(cam, dx):
@@ -58,7 +55,7 @@ def test_identical_camera_returns_the_buffer_bitwise():
     ib[3:6, 10:12] = 0.0                                # pixels without samples stay without
     f = fr.features(sc, cfg)
     out, motion = rr.reproject(cfg, sc.camera, sc.camera, ib, f, f, max_history=1e6)
-    assert np.array_equal(_bits(out), _bits(ib))
+    assert np.array_equal(ck.bits(out), ck.bits(ib))
     has = ib[..., 3] > 0
     xs, ys = np.meshgrid(np.arange(W), np.arange(H), indexing="ij")
     assert np.array_equal(motion[has], np.stack([xs, ys], -1)[has].astype(np.float32))
@@ -82,7 +79,7 @@ def test_one_pixel_pan_shifts_history_by_one_pixel():
             for y in range(H):
                 if f1["object"][x, y] == 0 and f0["object"][xs, y] == 0 and ib[xs, y, 3] > 0:
                     assert motion[x, y].tolist() == [xs, y], (x, y, motion[x, y])
-                    assert np.array_equal(_bits(out[x, y]), _bits(ib[xs, y])), (x, y)
+                    assert np.array_equal(ck.bits(out[x, y]), ck.bits(ib[xs, y])), (x, y)
                     checked += 1
         assert checked >= 150, checked
         # the column that comes into view at the frame's edge has no history
@@ -111,15 +108,15 @@ def test_cap_scales_sums_and_counts():
     f = fr.features(sc, cfg)
     out, _ = rr.reproject(cfg, sc.camera, sc.camera, ib, f, f, max_history=2.0)
     k = (np.float32(2.0) / ib[..., 3]).astype(np.float32)[..., None]
-    assert np.array_equal(_bits(out), _bits((ib * k).astype(np.float32)))
+    assert np.array_equal(ck.bits(out), ck.bits((ib * k).astype(np.float32)))
     np.testing.assert_allclose(out[..., 3], 2.0, rtol=1e-6)
     # a cap above the counts changes nothing
     out, _ = rr.reproject(cfg, sc.camera, sc.camera, ib, f, f, max_history=8.0)
-    assert np.array_equal(_bits(out), _bits(ib))
+    assert np.array_equal(ck.bits(out), ck.bits(ib))
 
 
 def test_python_reproject_defaults_match_the_header():
-    hdr = open(os.path.join(os.path.dirname(rr.DIR), "..", "include", "rtpbr.h")).read()
+    hdr = open(os.path.join(rr.ROOT, "include", "rtpbr.h")).read()
     found = {m.group(1).lower(): float(m.group(2)) for m in re.finditer(r"#define RTPBR_REPROJECT_DEFAULT_([A-Z_]+)\s+(-?[0-9.]+)f?", hdr)}
     assert found == {k: float(v) for k, v in ReprojectParams.DEFAULTS.items()}
     assert set(found) == {"max_history", "depth_tolerance", "normal_cos"}

@@ -20,7 +20,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import blend_display_ref_lib as bd    # noqa: E402
 import blend_error_ref_lib as be      # noqa: E402
 import feature_ref_lib as fr          # noqa: E402
 import half_ref_lib as hl             # noqa: E402
@@ -67,7 +66,7 @@ for h in a.halves:
         for _ in range(2):
             o.sample(h)
             hv.update(o.image_buffer)
-        got = (bd if a.bias == "display" else be).blend_error(cfg, o.image_buffer, hv.a, feats, window=a.window)
+        got = be.blend_error(cfg, o.image_buffer, hv.a, feats, window=a.window, display=a.bias == "display")
         outs.append(lum(got.denoised))
         ests.append(got)
     outs = np.array(outs)

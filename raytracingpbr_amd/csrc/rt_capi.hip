@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -24,9 +25,7 @@
 using namespace rt;
 
 static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_error);
-static int noise_alloc(rtpbr_ctx* c);
 static int half_restart(rtpbr_ctx* c, bool snapshot_image, bool keep_a = false);
-static int half_alloc(rtpbr_ctx* c);
 static int noise_stats_read(rtpbr_ctx* c, rtpbr_noise_stats* out);
 extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value);
 extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world);
@@ -109,77 +108,50 @@ extern "C" int rtpbr_create(int device, rtpbr_ctx** out) {
     return RTPBR_OK;
 }
 
-// buffers of rtpbr_render_features / rtpbr_denoise (allocated on first use)
-static void free_features(rtpbr_ctx* c) {
-    (void)hipFree(c->feat_albedo);
-    (void)hipFree(c->feat_normal);
-    (void)hipFree(c->feat_depth);
-    (void)hipFree(c->feat_object);
-    (void)hipFree(c->feat_guides);
-    (void)hipFree(c->denoised);
-    (void)hipFree(c->denoise_scratch);
-    (void)hipFree(c->hist_image);
-    (void)hipFree(c->hist_guides);
-    (void)hipFree(c->hist_object);
-    (void)hipFree(c->motion);
-    (void)hipFree(c->scene_motion);
-    c->scene_motion = nullptr;
-    c->feat_albedo = c->feat_normal = c->feat_depth = c->denoised = nullptr;
-    c->feat_object = c->hist_object = nullptr;
-    c->feat_guides = c->denoise_scratch = c->hist_image = c->hist_guides = nullptr;
-    c->motion = nullptr;
-    c->feat_valid = false;
+// ---- the frame buffers (RT_FRAME_BUFFERS, rt_ctx.hpp): every allocation, free and public lookup of a row is one of these three
+// the rows' names for frame_need
+enum FrameRow {
+#define X(m, T, bytes, group, zeroed, id, writable) ROW_##m,
+    RT_FRAME_BUFFERS(X)
+#undef X
+};
+
+// Allocate the rows that do not exist yet, zero-filled on the stream where the row says so.  The caller has made every refusal
+// of its own: a refused call allocates nothing.
+static int frame_need(rtpbr_ctx* c, std::initializer_list<FrameRow> rows) {
+    const size_t np = (size_t)c->cfg.width * c->cfg.height;
+    constexpr bool reported = false;
+    for (const FrameRow row : rows) {
+        switch (row) {
+#define X(m, T, bytes, group, zeroed, id, writable)                                                       \
+    case ROW_##m:                                                                                         \
+        if (!c->m) {                                                                                      \
+            if (const hipError_t e = hipMalloc(&c->m, bytes)) return rt_fail_hip("hipMalloc(" #m ")", e); \
+            if (zeroed) HIP_TRY(hipMemsetAsync(c->m, 0, bytes, c->stream));                               \
+        }                                                                                                 \
+        break;
+            RT_FRAME_BUFFERS(X)
+#undef X
+        }
+    }
+    return RTPBR_OK;
 }
 
-// buffers of rtpbr_noise_update / rtpbr_noise_estimate / rtpbr_denoise_guided (allocated on first use)
-static void free_noise(rtpbr_ctx* c) {
-    (void)hipFree(c->noise_moments);
-    (void)hipFree(c->noise_snapshot);
-    (void)hipFree(c->hist_moments);
-    (void)hipFree(c->noise_map);
-    (void)hipFree(c->noise_var);
-    c->noise_moments = c->noise_snapshot = c->hist_moments = nullptr;
-    c->noise_map = c->noise_var = nullptr;
-}
-
-// buffers of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error (allocated on first use)
-static void free_half(rtpbr_ctx* c) {
-    (void)hipFree(c->half_a);
-    (void)hipFree(c->half_snapshot);
-    (void)hipFree(c->hist_half);
-    (void)hipFree(c->half_b);
-    (void)hipFree(c->half_da);
-    (void)hipFree(c->half_db);
-    (void)hipFree(c->denoised_error);
-    (void)hipFree(c->half_fd);
-    (void)hipFree(c->blend_weight);
-    (void)hipFree(c->blend_depth);
-    (void)hipFree(c->levels_scratch);
-    (void)hipFree(c->blend_error);
-    (void)hipFree(c->blend_x);
-    (void)hipFree(c->blend_slope);
-    c->half_a = c->half_snapshot = c->hist_half = c->half_b = nullptr;
-    c->half_da = c->half_db = c->denoised_error = c->half_fd = c->blend_weight = c->blend_depth = nullptr;
-    c->levels_scratch = c->blend_x = nullptr;
-    c->blend_error = c->blend_slope = nullptr;
-}
-
-// the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (allocated on the first select call)
-static void free_selection(rtpbr_ctx* c) {
-    (void)hipFree(c->sel_mask);
-    (void)hipFree(c->sel_list);
-    (void)hipFree(c->sel_blocks);
-    c->sel_mask = nullptr;
-    c->sel_list = c->sel_blocks = nullptr;
-    c->sel_count = 0;
-    c->have_selection = false;
-}
-
-// the frame of rtpbr_present (allocated on the first present)
-static void free_present(rtpbr_ctx* c) {
-    (void)hipFree(c->present);
-    c->present = nullptr;
-    c->present_channels = 0;
+// Free and null every row of `groups` (FRAME_*), with the state that describes the group's contents
+static void frame_free(rtpbr_ctx* c, unsigned groups) {
+#define X(m, T, bytes, group, zeroed, id, writable) \
+    if (groups & (group)) {                         \
+        (void)hipFree(c->m);                        \
+        c->m = nullptr;                             \
+    }
+    RT_FRAME_BUFFERS(X)
+#undef X
+    if (groups & FRAME_FEATURES) c->feat_valid = false;
+    if (groups & FRAME_SELECTION) {
+        c->sel_count = 0;
+        c->have_selection = false;
+    }
+    if (groups & FRAME_PRESENT) c->present_channels = 0;
 }
 
 extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
@@ -187,11 +159,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);      // (an asynchronous read-back may still be copying out of the buffers)
-    (void)hipFree(c->image_buffer);
-    (void)hipFree(c->image_pixels);
-    (void)hipFree(c->ray_buffer);
-    (void)hipFree(c->diff_buffer);
-    (void)hipFree(c->diff_pixels);
+    frame_free(c, FRAME_ALL);
     (void)hipFree(c->objfull);
     (void)hipFree(c->env);
     (void)hipFree(c->env8);
@@ -201,11 +169,6 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->primary);
     (void)hipFree(c->cost_buffer);
     (void)hipFree(c->march_out);
-    free_features(c);
-    free_noise(c);
-    free_half(c);
-    free_selection(c);
-    free_present(c);
     (void)hipFree(c->noise_stats);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
@@ -290,35 +253,11 @@ extern "C" int rtpbr_set_config(rtpbr_ctx* c, const rtpbr_config* cfg) {
     c->feat_valid = false;
     c->history_ok = false;
     if (realloc_buf) {
-        size_t n = (size_t)cfg->width * cfg->height;
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->copy_stream) HIP_TRY(hipStreamSynchronize(c->copy_stream));
         for (int& t : c->read_pending) t = -1;
-        (void)hipFree(c->image_buffer);
-        (void)hipFree(c->image_pixels);
-        (void)hipFree(c->ray_buffer);
-        (void)hipFree(c->diff_buffer);
-        (void)hipFree(c->diff_pixels);
-        c->image_buffer = nullptr;
-        c->image_pixels = nullptr;
-        c->ray_buffer = nullptr;
-        c->diff_buffer = nullptr;
-        c->diff_pixels = nullptr;
-        free_features(c);
-        free_noise(c);
-        free_half(c);
-        free_selection(c);
-        free_present(c);
-        HIP_TRY(hipMalloc(&c->image_buffer, n * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c->image_pixels, n * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->ray_buffer, n * sizeof(rtpbr_ray)));
-        HIP_TRY(hipMemsetAsync(c->image_buffer, 0, n * sizeof(float4), c->stream));
-        HIP_TRY(hipMemsetAsync(c->image_pixels, 0, n * 3 * sizeof(float), c->stream));
-        HIP_TRY(hipMemsetAsync(c->ray_buffer, 0, n * sizeof(rtpbr_ray), c->stream));
-        HIP_TRY(hipMalloc(&c->diff_buffer, n * sizeof(float2)));
-        HIP_TRY(hipMalloc(&c->diff_pixels, n * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(c->diff_buffer, 0, n * sizeof(float2), c->stream));
-        HIP_TRY(hipMemsetAsync(c->diff_pixels, 0, n * sizeof(float), c->stream));
+        frame_free(c, FRAME_ALL);
+        if (int r = frame_need(c, {ROW_image_buffer, ROW_image_pixels, ROW_ray_buffer, ROW_diff_buffer, ROW_diff_pixels})) return r;
     }
     // bunny animation uniform: t = pi*frame/120 (bunny_sdf_glass.py:214)
     float t = PI * (float)cfg->frame / 120.0f;
@@ -745,7 +684,7 @@ extern "C" int rtpbr_set_tiles(rtpbr_ctx* c, int tw, int th, int rank, int world
 // A call that WRITES the buffers of `mask` (bit RTPBR_BUF_*) on the context's stream is ordered behind an asynchronous
 // read-back that still copies out of them (rtpbr_read_buffer_async) — on the device: the host does not block.
 int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
-    for (int b = 0; b <= RTPBR_BUF_BLEND_ERROR; b++)
+    for (int b = 0; b < RT_PUBLIC_BUFFERS; b++)
         if (((mask >> b) & 1u) && c->read_pending[b] >= 0) {
             // (a copy that has landed already needs no ordering: a cross-stream wait is a barrier packet the command processor
             // resolves in ~20 us — per frame that is what separates a pipelined viewer from the device-only rate — a query is ~1 us)
@@ -760,14 +699,32 @@ int rt_order_after_reads(rtpbr_ctx* c, unsigned mask) {
         }
     return RTPBR_OK;
 }
-enum : unsigned { W_IMAGE_BUFFER = 1u << RTPBR_BUF_IMAGE_BUFFER, W_IMAGE_PIXELS = 1u << RTPBR_BUF_IMAGE_PIXELS, W_RAY_BUFFER = 1u << RTPBR_BUF_RAY_BUFFER,
-                W_DIFF_BUFFER = 1u << RTPBR_BUF_DIFF_BUFFER, W_DIFF_PIXELS = 1u << RTPBR_BUF_DIFF_PIXELS };
+// ... the masks the writers pass
+enum : unsigned {
+    W_IMAGE_BUFFER = 1u << RTPBR_BUF_IMAGE_BUFFER,
+    W_IMAGE_PIXELS = 1u << RTPBR_BUF_IMAGE_PIXELS,
+    W_RAY_BUFFER = 1u << RTPBR_BUF_RAY_BUFFER,
+    W_DIFF_BUFFER = 1u << RTPBR_BUF_DIFF_BUFFER,
+    W_DIFF_PIXELS = 1u << RTPBR_BUF_DIFF_PIXELS,
+    W_FEATURES = (1u << RTPBR_BUF_FEAT_ALBEDO) | (1u << RTPBR_BUF_FEAT_NORMAL) | (1u << RTPBR_BUF_FEAT_DEPTH) | (1u << RTPBR_BUF_FEAT_OBJECT),
+    W_DENOISED = 1u << RTPBR_BUF_DENOISED_PIXELS,
+    W_MOTION = 1u << RTPBR_BUF_MOTION,
+    W_MOMENTS = 1u << RTPBR_BUF_MOMENTS,
+    W_NOISE = 1u << RTPBR_BUF_NOISE,
+    W_SELECTION = 1u << RTPBR_BUF_SELECTION,
+    W_PRESENT = 1u << RTPBR_BUF_PRESENT,
+    W_HALF = 1u << RTPBR_BUF_HALF_BUFFER,
+    W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR,
+    W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT,
+    W_DEPTH = 1u << RTPBR_BUF_BLEND_DEPTH,
+    W_BLEND_ERROR = 1u << RTPBR_BUF_BLEND_ERROR,
+};
 
 extern "C" int rtpbr_refresh(rtpbr_ctx* c) {
     if (!c || !c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
-    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | W_DIFF_PIXELS | (c->noise_moments ? 1u << RTPBR_BUF_MOMENTS : 0u))) return r;
+    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | W_DIFF_PIXELS | (c->noise_moments ? W_MOMENTS : 0u))) return r;
     size_t n = (size_t)c->cfg.width * c->cfg.height;
     if (c->noise_moments) {      // the noise estimate starts over with the image
         HIP_TRY(hipMemsetAsync(c->noise_moments, 0, n * sizeof(float4), c->stream));
@@ -1344,8 +1301,7 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     // (diff_buffer: instrumented builds write their per-wave records over it; a tracked call — rtpbr_set_noise_tracking — writes the moments)
     const bool tracked = c->noise_tracking == RTPBR_NOISE_TRACK_SAMPLES;
     const bool dealt = c->half_mode.per_sample != 0;      // ... and a dealing call — rtpbr_set_half_mode — half A
-    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | (tracked ? 1u << RTPBR_BUF_MOMENTS : 0u) |
-                                            (dealt ? 1u << RTPBR_BUF_HALF_BUFFER : 0u))) return r;
+    if (int r = rt_order_after_reads(c, W_IMAGE_BUFFER | W_RAY_BUFFER | W_DIFF_BUFFER | (tracked ? W_MOMENTS : 0u) | (dealt ? W_HALF : 0u))) return r;
     // A shading the previous call left pending (lazy shading of one-step launches) rides along only if this call is again a launch of the
     // wavefront split; otherwise it is launched now, while the previous call's work counters are still the current ones
     {
@@ -1390,10 +1346,10 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
     if (c->cfg.sky_kind == RTPBR_SKY_ENVMAP && !c->env) return fail(RTPBR_ESTATE, "sky_kind ENVMAP needs rtpbr_set_env first");
     // a tracked call folds into the moments and re-takes the snapshot: both exist (zeroed) from here on, as after rtpbr_noise_update
     if (tracked)
-        if (int r = noise_alloc(c)) return r;
+        if (int r = frame_need(c, {ROW_noise_moments, ROW_noise_snapshot})) return r;
     // a dealing call deals into half A and re-takes its snapshot: both exist (zeroed) from here on, as after rtpbr_half_update
     if (dealt)
-        if (int r = half_alloc(c)) return r;
+        if (int r = frame_need(c, {ROW_half_a, ROW_half_snapshot})) return r;
     static_assert((sizeof(Counters) + 64) % 16 == 0, "zero_next_counters / launch_zero fill 16-byte words");
     // This call's work counters (+ the claim counters behind them): the buffer whose turn it is, zeroed by the previous call's kernels
     // (or here, if that call launched none); this call's kernels zero the other one.
@@ -1492,18 +1448,6 @@ extern "C" int rtpbr_post_process(rtpbr_ctx* c) {
 
 // ---- first-hit features and the a-trous denoise (rt_features.hip): the filter the reference's post_process() leaves as a TODO
 // (src/postprocessor.py:30 "# ToDo: Post Denoise").  Whole-frame only: a rank of a tiled render holds part of the frame.
-static int features_alloc(rtpbr_ctx* c) {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->feat_albedo) HIP_TRY(hipMalloc(&c->feat_albedo, n * 3 * sizeof(float)));
-    if (!c->feat_normal) HIP_TRY(hipMalloc(&c->feat_normal, n * 3 * sizeof(float)));
-    if (!c->feat_depth) HIP_TRY(hipMalloc(&c->feat_depth, n * sizeof(float)));
-    if (!c->feat_object) HIP_TRY(hipMalloc(&c->feat_object, n * sizeof(int32_t)));
-    if (!c->feat_guides) HIP_TRY(hipMalloc(&c->feat_guides, n * sizeof(float4)));
-    return RTPBR_OK;
-}
-
-enum : unsigned { W_FEATURES = (1u << RTPBR_BUF_FEAT_ALBEDO) | (1u << RTPBR_BUF_FEAT_NORMAL) | (1u << RTPBR_BUF_FEAT_DEPTH) | (1u << RTPBR_BUF_FEAT_OBJECT),
-                  W_DENOISED = 1u << RTPBR_BUF_DENOISED_PIXELS };
 
 // The states every call on the whole frame refuses, in this order: no configuration, scene or camera yet; tiles of world > 1
 // (`tiles`: the call's message, `who` fills its %s if it has one); a bunny without its shape data.
@@ -1520,7 +1464,7 @@ extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
     if (int r = set_dev(c)) return r;
-    if (int r = features_alloc(c)) return r;
+    if (int r = frame_need(c, {ROW_feat_albedo, ROW_feat_normal, ROW_feat_depth, ROW_feat_object, ROW_feat_guides})) return r;
     if (int r = rt_order_after_reads(c, W_FEATURES)) return r;
     // the context's Params with the general march table (signature 0, no lazy box keys): what the run-time object-count instances read
     Params P = c->P;
@@ -1561,9 +1505,9 @@ static int denoise_params_check(int iterations, int demodulate, const float* sig
 // RTPBR_BUF_DENOISED_PIXELS and, from two levels on, the two halves of the levels' ping-pong; then ordered after the buffer's reads
 static int denoised_alloc(rtpbr_ctx* c, int iterations) {
     if (int r = set_dev(c)) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->denoised) HIP_TRY(hipMalloc(&c->denoised, n * 3 * sizeof(float)));
-    if (iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
+    if (int r = frame_need(c, {ROW_denoised})) return r;
+    if (iterations >= 2)
+        if (int r = frame_need(c, {ROW_denoise_scratch})) return r;
     return rt_order_after_reads(c, W_DENOISED);
 }
 
@@ -1651,7 +1595,6 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
 }
 
 // ---- temporal reuse (rt_reproject.hip): rtpbr_set_camera + rtpbr_refresh that keeps what the new view can reuse
-enum : unsigned { W_MOTION = 1u << RTPBR_BUF_MOTION, W_HALF = 1u << RTPBR_BUF_HALF_BUFFER };
 
 // p == NULL: the defaults; RTPBR_EINVAL for a parameter out of range
 static int reproject_params(const rtpbr_reproject_params* p, rtpbr_reproject_params& d) {
@@ -1688,19 +1631,17 @@ static int reproject_run(rtpbr_ctx* c, const rtpbr_camera* cam, const rtpbr_repr
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;      // the features of the old camera (and the old scene)
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->hist_image) HIP_TRY(hipMalloc(&c->hist_image, n * sizeof(float4)));
-    if (!c->hist_guides) HIP_TRY(hipMalloc(&c->hist_guides, n * sizeof(float4)));
-    if (!c->hist_object) HIP_TRY(hipMalloc(&c->hist_object, n * sizeof(int32_t)));
-    if (!c->motion) HIP_TRY(hipMalloc(&c->motion, n * sizeof(float2)));
-    if (objs && !c->scene_motion) HIP_TRY(hipMalloc(&c->scene_motion, sizeof(float) * MAX_OBJ * SCENE_MOTION_WORDS));
+    if (int r = frame_need(c, {ROW_hist_image, ROW_hist_guides, ROW_hist_object, ROW_motion})) return r;
+    if (objs)
+        if (int r = frame_need(c, {ROW_scene_motion})) return r;
     if (c->noise_moments) {      // the moments move with the image
-        if (!c->hist_moments) HIP_TRY(hipMalloc(&c->hist_moments, n * sizeof(float4)));
-        if (int r = rt_order_after_reads(c, 1u << RTPBR_BUF_MOMENTS)) return r;
+        if (int r = frame_need(c, {ROW_hist_moments})) return r;
+        if (int r = rt_order_after_reads(c, W_MOMENTS)) return r;
         HIP_TRY(hipMemcpyAsync(c->hist_moments, c->noise_moments, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     }
     const bool warp_half = c->half_mode.warp != 0 && c->half_a != nullptr;      // rtpbr_set_half_mode: half A moves with the image
     if (warp_half) {
-        if (!c->hist_half) HIP_TRY(hipMalloc(&c->hist_half, n * sizeof(float4)));
+        if (int r = frame_need(c, {ROW_hist_half})) return r;
         if (int r = rt_order_after_reads(c, W_HALF)) return r;
         HIP_TRY(hipMemcpyAsync(c->hist_half, c->half_a, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     }
@@ -1793,21 +1734,7 @@ extern "C" int rtpbr_reproject_scene(rtpbr_ctx* c, const rtpbr_camera* cam, cons
 }
 
 // ---- noise estimation and the variance-guided a-trous (rt_noise.hip)
-enum : unsigned { W_MOMENTS = 1u << RTPBR_BUF_MOMENTS, W_NOISE = 1u << RTPBR_BUF_NOISE };
 static const char* const NOISE_TILES = "rtpbr_noise_update / rtpbr_noise_estimate / rtpbr_denoise_guided work on the whole frame: not with tiles of world > 1";
-
-static int noise_alloc(rtpbr_ctx* c) {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->noise_moments) {
-        HIP_TRY(hipMalloc(&c->noise_moments, n * sizeof(float4)));
-        HIP_TRY(hipMemsetAsync(c->noise_moments, 0, n * sizeof(float4), c->stream));
-    }
-    if (!c->noise_snapshot) {
-        HIP_TRY(hipMalloc(&c->noise_snapshot, n * sizeof(float4)));
-        HIP_TRY(hipMemsetAsync(c->noise_snapshot, 0, n * sizeof(float4), c->stream));
-    }
-    return RTPBR_OK;
-}
 
 extern "C" int rtpbr_noise_update(rtpbr_ctx* c) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
@@ -1815,7 +1742,7 @@ extern "C" int rtpbr_noise_update(rtpbr_ctx* c) {
     if (c->world > 1) return fail(RTPBR_ESTATE, NOISE_TILES);
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
-    if (int r = noise_alloc(c)) return r;
+    if (int r = frame_need(c, {ROW_noise_moments, ROW_noise_snapshot})) return r;
     if (int r = rt_order_after_reads(c, W_MOMENTS)) return r;
     NoiseArgs A{};
     A.image_buffer = c->image_buffer;
@@ -1851,10 +1778,7 @@ static int noise_estimate_enqueue(rtpbr_ctx* c, float threshold) {
         if (int r = rtpbr_render_features(c)) return r;
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
-    if (int r = noise_alloc(c)) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->noise_map) HIP_TRY(hipMalloc(&c->noise_map, n * sizeof(float)));
-    if (!c->noise_var) HIP_TRY(hipMalloc(&c->noise_var, 3 * n * sizeof(float)));
+    if (int r = frame_need(c, {ROW_noise_moments, ROW_noise_snapshot, ROW_noise_map, ROW_noise_var})) return r;
     if (int r = rt_order_after_reads(c, W_NOISE)) return r;
     if (int r = noise_stats_zero(c)) return r;
     NoiseArgs A{};
@@ -1916,16 +1840,7 @@ static int noise_stats_read(rtpbr_ctx* c, rtpbr_noise_stats* out) {
 }
 
 // ---- adaptive sampling of the complete-path form (rt_select.hip): select pixels, trace only those
-enum : unsigned { W_SELECTION = 1u << RTPBR_BUF_SELECTION };
 static const char* const SELECT_TILES = "rtpbr_select_mask / rtpbr_select_noisy / rtpbr_sample_selected work on the whole frame: not with tiles of world > 1";
-
-static int selection_alloc(rtpbr_ctx* c) {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->sel_mask) HIP_TRY(hipMalloc(&c->sel_mask, n));
-    if (!c->sel_list) HIP_TRY(hipMalloc(&c->sel_list, n * sizeof(uint32_t)));
-    if (!c->sel_blocks) HIP_TRY(hipMalloc(&c->sel_blocks, ((size_t)select_blocks(c->cfg.width, c->cfg.height) + 1) * sizeof(uint32_t)));
-    return RTPBR_OK;
-}
 
 // mark, scan, scatter on the stream, then the list's length (4 bytes) comes back: blocks
 static int selection_build(rtpbr_ctx* c, SelectArgs& A, int rule, uint32_t* n_selected) {
@@ -1954,7 +1869,7 @@ extern "C" int rtpbr_select_mask(rtpbr_ctx* c, const uint8_t* mask, size_t nbyte
     if (c->world > 1) return fail(RTPBR_ESTATE, SELECT_TILES);
     if (nbytes != (size_t)c->cfg.width * c->cfg.height) return fail(RTPBR_EINVAL, "rtpbr_select_mask: the mask must hold width * height bytes");
     if (int r = set_dev(c)) return r;
-    if (int r = selection_alloc(c)) return r;
+    if (int r = frame_need(c, {ROW_sel_mask, ROW_sel_list, ROW_sel_blocks})) return r;
     if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
     // the caller's bytes go straight into RTPBR_BUF_SELECTION; the mark pass makes them 0 / 1 in place
     HIP_TRY(hipMemcpyAsync(c->sel_mask, mask, nbytes, hipMemcpyHostToDevice, c->stream));
@@ -1969,7 +1884,7 @@ extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uin
     if (dilate < 0 || dilate > 3) return fail(RTPBR_EINVAL, "rtpbr_select_noisy: dilate must be 0..3");
     if (int r = whole_frame_state(c, NOISE_TILES)) return r;
     if (int r = noise_estimate_enqueue(c, threshold)) return r;
-    if (int r = selection_alloc(c)) return r;
+    if (int r = frame_need(c, {ROW_sel_mask, ROW_sel_list, ROW_sel_blocks})) return r;
     if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
     SelectArgs A{};
     A.image_buffer = c->image_buffer;
@@ -2023,8 +1938,6 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
 }
 
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
-enum : unsigned { W_ERROR = 1u << RTPBR_BUF_DENOISED_ERROR, W_BLEND = 1u << RTPBR_BUF_BLEND_WEIGHT, W_DEPTH = 1u << RTPBR_BUF_BLEND_DEPTH,
-                  W_BLEND_ERROR = 1u << RTPBR_BUF_BLEND_ERROR };
 static const char* const HALF_TILES = "rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_blend_error_display / rtpbr_select_error / rtpbr_select_blend_error work on the whole frame: not with tiles of world > 1";
 
 // What refresh, rtpbr_write_buffer(RTPBR_BUF_IMAGE_BUFFER) and the reprojections do once A exists (enqueues only): A = 0 and the
@@ -2040,26 +1953,13 @@ static int half_restart(rtpbr_ctx* c, bool snapshot_image, bool keep_a) {
     return RTPBR_OK;
 }
 
-static int half_alloc(rtpbr_ctx* c) {
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->half_a) {
-        HIP_TRY(hipMalloc(&c->half_a, n * sizeof(float4)));
-        HIP_TRY(hipMemsetAsync(c->half_a, 0, n * sizeof(float4), c->stream));
-    }
-    if (!c->half_snapshot) {
-        HIP_TRY(hipMalloc(&c->half_snapshot, n * sizeof(float4)));
-        HIP_TRY(hipMemsetAsync(c->half_snapshot, 0, n * sizeof(float4), c->stream));
-    }
-    return RTPBR_OK;
-}
-
 extern "C" int rtpbr_half_update(rtpbr_ctx* c) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
     if (!c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
     if (c->world > 1) return fail(RTPBR_ESTATE, HALF_TILES);
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
-    if (int r = half_alloc(c)) return r;
+    if (int r = frame_need(c, {ROW_half_a, ROW_half_snapshot})) return r;
     if (int r = rt_order_after_reads(c, W_HALF)) return r;
     HalfArgs A{};
     A.image_buffer = c->image_buffer;
@@ -2095,7 +1995,7 @@ static int half_call_begin(rtpbr_ctx* c, const char* no_half, const char* who) {
 
 // B = image_buffer - A into its own buffer, enqueued here
 static int half_b_enqueue(rtpbr_ctx* c) {
-    if (!c->half_b) HIP_TRY(hipMalloc(&c->half_b, (size_t)c->cfg.width * c->cfg.height * sizeof(float4)));
+    if (int r = frame_need(c, {ROW_half_b})) return r;
     HalfArgs S{};
     S.image_buffer = c->image_buffer;
     S.half_a = c->half_a;
@@ -2126,11 +2026,9 @@ extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     if (radius < 1 || radius > 3) return fail(RTPBR_EINVAL, "rtpbr_denoise_error: radius must be 1..3");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
     if (int r = half_call_begin(c, "%s: no half buffer yet (rtpbr_half_update first)", "rtpbr_denoise_error")) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->half_da) HIP_TRY(hipMalloc(&c->half_da, n * 3 * sizeof(float)));
-    if (!c->half_db) HIP_TRY(hipMalloc(&c->half_db, n * 3 * sizeof(float)));
-    if (!c->denoised_error) HIP_TRY(hipMalloc(&c->denoised_error, n * sizeof(float)));
-    if (d.iterations >= 2 && !c->denoise_scratch) HIP_TRY(hipMalloc(&c->denoise_scratch, 2 * n * sizeof(float4)));
+    if (int r = frame_need(c, {ROW_half_da, ROW_half_db, ROW_denoised_error})) return r;
+    if (d.iterations >= 2)
+        if (int r = frame_need(c, {ROW_denoise_scratch})) return r;
     if (int r = rt_order_after_reads(c, W_ERROR)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
@@ -2167,11 +2065,7 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     rtpbr_blend_params b;
     if (int r = blend_params(e, "rtpbr_denoise_blend", b)) return r;
     if (int r = half_call_begin(c, BLEND_NO_HALF, "rtpbr_denoise_blend")) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->half_da) HIP_TRY(hipMalloc(&c->half_da, n * 3 * sizeof(float)));
-    if (!c->half_db) HIP_TRY(hipMalloc(&c->half_db, n * 3 * sizeof(float)));
-    if (!c->half_fd) HIP_TRY(hipMalloc(&c->half_fd, n * 3 * sizeof(float)));
-    if (!c->blend_weight) HIP_TRY(hipMalloc(&c->blend_weight, n * sizeof(float)));
+    if (int r = frame_need(c, {ROW_half_da, ROW_half_db, ROW_half_fd, ROW_blend_weight})) return r;
     if (int r = denoised_alloc(c, d.iterations)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
     if (int r = rt_order_after_reads(c, W_BLEND)) return r;
     if (!c->feat_valid)
@@ -2223,12 +2117,11 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     if (int r = half_call_begin(c, BLEND_NO_HALF, who)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     const int K = d.iterations;
-    if (!c->blend_weight) HIP_TRY(hipMalloc(&c->blend_weight, n * sizeof(float)));
-    if (!c->blend_depth) HIP_TRY(hipMalloc(&c->blend_depth, n * sizeof(float)));
-    if (!c->levels_scratch) HIP_TRY(hipMalloc(&c->levels_scratch, 6 * n * sizeof(float4)));
-    if (with_error && !c->blend_error) HIP_TRY(hipMalloc(&c->blend_error, n * sizeof(float)));
-    if (with_error && !c->blend_x) HIP_TRY(hipMalloc(&c->blend_x, 2 * n * sizeof(float4)));
-    if (display && !c->blend_slope) HIP_TRY(hipMalloc(&c->blend_slope, n * sizeof(float)));
+    if (int r = frame_need(c, {ROW_blend_weight, ROW_blend_depth, ROW_levels_scratch})) return r;
+    if (with_error)
+        if (int r = frame_need(c, {ROW_blend_error, ROW_blend_x})) return r;
+    if (display)
+        if (int r = frame_need(c, {ROW_blend_slope})) return r;
     if (int r = denoised_alloc(c, 0)) return r;      // (and behind reads of RTPBR_BUF_DENOISED_PIXELS)
     if (int r = rt_order_after_reads(c, W_BLEND | W_DEPTH | (with_error ? W_BLEND_ERROR : 0u))) return r;
     if (!c->feat_valid)
@@ -2334,7 +2227,7 @@ static int select_by_error(rtpbr_ctx* c, float* rtpbr_ctx::*plane, const char* w
     if (!(c->*plane) || !c->half_a) return fail(RTPBR_ESTATE, no_estimate, who);
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
-    if (int r = selection_alloc(c)) return r;
+    if (int r = frame_need(c, {ROW_sel_mask, ROW_sel_list, ROW_sel_blocks})) return r;
     if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
     SelectArgs A{};
     A.image_buffer = c->image_buffer;
@@ -2374,9 +2267,8 @@ extern "C" int rtpbr_present(rtpbr_ctx* c, const rtpbr_present_params* p) {
     if (!c->have_cfg || c->headless) return fail(RTPBR_ESTATE, "set_config first");
     if (d.source == RTPBR_PRESENT_DENOISED && !c->denoised) return fail(RTPBR_ESTATE, "rtpbr_present: no denoised image yet (rtpbr_denoise / rtpbr_denoise_guided first)");
     if (int r = set_dev(c)) return r;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
-    if (!c->present) HIP_TRY(hipMalloc(&c->present, n * 4));
-    if (int r = rt_order_after_reads(c, 1u << RTPBR_BUF_PRESENT)) return r;
+    if (int r = frame_need(c, {ROW_present})) return r;
+    if (int r = rt_order_after_reads(c, W_PRESENT)) return r;
     PresentArgs A{};
     A.cfg = c->cfg;
     A.src3 = d.source == RTPBR_PRESENT_DENOISED ? c->denoised : c->image_pixels;
@@ -2401,36 +2293,20 @@ extern "C" int rtpbr_sync(rtpbr_ctx* c) {
 
 static int buf_ptr(rtpbr_ctx* c, int which, void** p, size_t* n) {
     if (!c || !c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
-    size_t np = (size_t)c->cfg.width * c->cfg.height;
-    switch (which) {
-        case RTPBR_BUF_IMAGE_BUFFER: *p = c->image_buffer; *n = np * 16; return 0;
-        case RTPBR_BUF_IMAGE_PIXELS: *p = c->image_pixels; *n = np * 12; return 0;
-        case RTPBR_BUF_RAY_BUFFER: *p = c->ray_buffer; *n = np * sizeof(rtpbr_ray); return 0;
-        case RTPBR_BUF_DIFF_BUFFER: *p = c->diff_buffer; *n = np * 8; return 0;
-        case RTPBR_BUF_DIFF_PIXELS: *p = c->diff_pixels; *n = np * 4; return 0;
-        case RTPBR_BUF_FEAT_ALBEDO: *p = c->feat_albedo; *n = np * 12; break;
-        case RTPBR_BUF_FEAT_NORMAL: *p = c->feat_normal; *n = np * 12; break;
-        case RTPBR_BUF_FEAT_DEPTH: *p = c->feat_depth; *n = np * 4; break;
-        case RTPBR_BUF_FEAT_OBJECT: *p = c->feat_object; *n = np * 4; break;
-        case RTPBR_BUF_DENOISED_PIXELS: *p = c->denoised; *n = np * 12; break;
-        case RTPBR_BUF_MOTION: *p = c->motion; *n = np * 8; break;
-        case RTPBR_BUF_MOMENTS: *p = c->noise_moments; *n = np * 16; break;
-        case RTPBR_BUF_NOISE: *p = c->noise_map; *n = np * 4; break;
-        case RTPBR_BUF_SELECTION: *p = c->sel_mask; *n = np; break;
-        case RTPBR_BUF_PRESENT: *p = c->present; *n = np * (size_t)c->present_channels; break;
-        case RTPBR_BUF_HALF_BUFFER: *p = c->half_a; *n = np * 16; break;
-        case RTPBR_BUF_DENOISED_ERROR: *p = c->denoised_error; *n = np * 4; break;
-        case RTPBR_BUF_BLEND_WEIGHT: *p = c->blend_weight; *n = np * 4; break;
-        case RTPBR_BUF_BLEND_DEPTH: *p = c->blend_depth; *n = np * 4; break;
-        case RTPBR_BUF_BLEND_ERROR: *p = c->blend_error; *n = np * 4; break;
-        default: return fail(RTPBR_EINVAL, "unknown buffer id");
+    const size_t np = (size_t)c->cfg.width * c->cfg.height;
+    constexpr bool reported = true;
+    unsigned group = 0;
+#define X(m, T, bytes, g, zeroed, id, writable) \
+    if (id != FRAME_PRIVATE && which == id) {   \
+        *p = c->m;                              \
+        *n = bytes;                             \
+        group = g;                              \
     }
-    // (the feature and denoise buffers exist from the first rtpbr_render_features / rtpbr_denoise on, motion from the first
-    // rtpbr_reproject, the moments from the first rtpbr_noise_update / rtpbr_noise_estimate, the noise map from the first estimate,
-    // the packed frame from the first rtpbr_present, the half buffer from the first rtpbr_half_update, the error map from the first
-    // rtpbr_denoise_error, the blend weight from the first rtpbr_denoise_blend or rtpbr_denoise_blend_levels, the blend depth from
-    // the first rtpbr_denoise_blend_levels or rtpbr_blend_error, the blend error from the first rtpbr_blend_error)
-    if (!*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error first");
+    RT_FRAME_BUFFERS(X)
+#undef X
+    if (!group) return fail(RTPBR_EINVAL, "unknown buffer id");
+    // (the core buffers came with the configuration; the others exist from the call named in their row on)
+    if (group != FRAME_CORE && !*p) return fail(RTPBR_ESTATE, "buffer not allocated yet: call rtpbr_render_features / rtpbr_denoise / rtpbr_reproject / rtpbr_noise_* / rtpbr_select_* / rtpbr_present / rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error first");
     return 0;
 }
 
@@ -2531,7 +2407,7 @@ extern "C" int rtpbr_host_free(rtpbr_ctx* c, void* ptr) {
 extern "C" int rtpbr_write_buffer(rtpbr_ctx* c, int which, const void* src, size_t nbytes) {
     void* p;
     size_t n;
-    if (c && which >= RTPBR_BUF_FEAT_ALBEDO && which <= RTPBR_BUF_BLEND_ERROR)
+    if (c && which >= 0 && which < RT_PUBLIC_BUFFERS && !((RT_WRITABLE_BUFFERS >> which) & 1u))
         return fail(RTPBR_EINVAL, "the feature, denoise, motion, moments, noise, selection, present, half, error, blend-weight, blend-depth and blend-error buffers are outputs only");
     if (int r = buf_ptr(c, which, &p, &n)) return r;
     if (!src || nbytes != n) return fail(RTPBR_EINVAL, "source size does not match the buffer");
@@ -2694,42 +2570,83 @@ extern "C" int rtpbr_get_stream(rtpbr_ctx* c, void** stream) {
     return RTPBR_OK;
 }
 
+// The plain integer options: the key is the member's name, a value outside lo..hi is refused in the row's words.  replan: the
+// plan of the src/ pool kernel was made for the old value (order_valid, cost_steps).
+struct OptionRow {
+    const char* key;
+    int rtpbr_ctx::*member;
+    long long lo, hi;
+    bool replan;
+    const char* refusal;
+};
+#define OPTION(member, lo, hi, replan, refusal) {#member, &rtpbr_ctx::member, lo, hi, replan, refusal}
+static const OptionRow OPTION_ROWS[] = {
+    OPTION(wait_lanes, 1, 64, false, "wait_lanes must be 1..64"),
+    OPTION(shade_lanes, 1, 64, false, "shade_lanes must be 1..64"),
+    OPTION(jit_waves, 0, 8, false, "jit_waves must be 0 (default) .. 8"),
+    // every wave makes one claim past the end, so the 32-bit work counter overshoots by waves x chunk: the margin kept
+    // free below 2^32 (work_margin) covers 32 waves per CU x 8192
+    OPTION(chunk, 0, 8192, false, "chunk must be 0 (automatic) .. 8192"),
+    OPTION(sparse_lanes, 0, 64, false, "sparse_lanes must be 0 (never) .. 64"),
+    OPTION(src_plan, 0, 1, true, "src_plan must be 0 or 1"),
+    OPTION(plan_interval, 1, 1 << 20, false, "plan_interval must be 1 .. 2^20 bounce-steps"),
+    OPTION(heavy_own, 0, 128, true, "heavy_own must be 0 (no heavy waves) .. 128"),      // the plan's share of heavy pixels was sized for the old value
+    OPTION(chain_waves, 1, 2048, true, "chain_waves must be 1 .. 2048"),
+    OPTION(src_split, 0, 256, false, "src_split must be 0 (never) .. 256 (bounce-steps per launch up to which the wavefront split runs)"),
+    OPTION(env_packed, 0, 1, false, "env_packed must be 0 (float4 texels) or 1 (RGBA8 texels + 256-entry table: 8-bit sources, same values)"),
+    OPTION(src_lazy, 0, 1, false, "src_lazy must be 0 (every one-step launch shades) or 1 (the shading rides with the next launch's gen pass)"),
+    OPTION(split_head, -1, 1, false, "split_head must be -1 (automatic: small frames), 0 (the heavy head fills the first groups) or 1 (interleaved: one head entry per group)"),
+    OPTION(split_wait, 1, 64, false, "split_wait must be 1..64"),
+    OPTION(src_track, 0, 2, false, "src_track must be 0 (never), 1 (one-object bounds only) or 2 (one- and two-object bounds)"),
+    OPTION(src_op, 0, 7, false, "src_op must be 0 .. 7 (bit 0: object-parallel evaluation for sparse waves in the split march and chain kernels, bit 1: in the fused pool kernel, bit 2: the per-lane lean loop for lanes that track different objects)"),
+    OPTION(tiny_waves, 0, 65535, false, "tiny_waves must be 0 .. 65535"),
+    OPTION(tiny_own, 0, 128, false, "tiny_own must be 0 (no small heavy waves) .. 128"),
+    OPTION(leave_x8, 1, 4096, false, "leave_x8 must be 1 .. 4096 (eighths of a march iteration)"),
+    OPTION(heavy_prio, 0, 1, false, "heavy_prio must be 0 or 1"),
+    OPTION(heavy_mean_x16, 0, 1 << 20, false, "heavy_mean_x16 must be 0 .. 2^20"),
+    OPTION(heavy_bulk_x16, 0, 1 << 20, false, "heavy_bulk_x16 must be 0 .. 2^20"),
+    OPTION(grid_blocks, 0, 65535, false, "grid_blocks must be 0 (automatic) .. 65535"),
+    OPTION(ready_low, 0, 63, false, "ready_low must be 0..63"),
+    OPTION(refill_lanes, 1, 64, false, "refill_lanes must be 1..64"),
+    // 1 (default): rtpbr_sample() brackets its kernels with events (rtpbr_last_sample_ms / rtpbr_last_primary_ms); 0: none — an event
+    // is a barrier packet with a completion signal, and four of them cost a launch of a few hundred microseconds a fifth of its time
+    OPTION(timing, 0, 1, false, "timing must be 0 or 1"),
+    OPTION(stage_dense, 0, 1, false, "stage_dense must be 0 (item-linear staging) or 1 (records appended per claim in completion order)"),
+    OPTION(primary_split, 0, 2, false, "primary_split must be 0 (never), 1 (large launches) or 2 (always)"),
+    OPTION(drain_lanes, 0, 64, false, "drain_lanes must be 0..64"),
+    OPTION(primary_lean, 0, 1, false, "primary_lean must be 0 or 1"),
+    OPTION(lazy_sqrt, 0, 1, false, "lazy_sqrt must be 0 or 1"),
+    OPTION(jit, -1, 2, false, "jit must be -1 (when no ahead-of-time specialisation fits), 0 (never), 1 (always, falling back to the "
+                              "ahead-of-time instance if compilation is impossible) or 2 (always, an error otherwise)"),
+    OPTION(precision, 0, 1, false, "precision must be 0 (exactly rounded, the default) or 1 (tolerance flavour: hardware sqrt / rcp / sin / exp, contraction)"),
+    OPTION(jit_bake, 0, 2, false, "jit_bake must be 0, 1 (scene + configuration) or 2 (+ the camera frame: fixed-camera offline renders)"),
+    OPTION(specialize, 0, 1, false, "specialize must be 0 or 1"),
+    OPTION(mlp_mfma, 0, 1, false, "mlp_mfma must be 0 or 1"),
+    OPTION(mlp_lanes, 1, 64, false, "mlp_lanes must be 1..64"),
+    OPTION(mlp_full, 1, 65, false, "mlp_full must be 1..65 (65 = never compute both halves at once)"),
+    OPTION(swap_lanes, 0, 64, false, "swap_lanes must be 0 (automatic: 8 in the complete-path pool kernel, 12 in the src/ one) .. 64"),
+    OPTION(scheduler, -1, 1, false, "scheduler must be -1 (auto), 0 or 1"),
+    OPTION(waves_per_cu, 0, 32, false, "waves_per_cu must be 0..32"),
+};
+#undef OPTION
+
 extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value) {
     if (!c || !key) return fail(RTPBR_EINVAL, "null argument");
     if (int r = flush_shade(c)) return r;
+    for (const OptionRow& o : OPTION_ROWS)
+        if (!strcmp(key, o.key)) {
+            if (value < o.lo || value > o.hi) return fail(RTPBR_EINVAL, o.refusal);
+            c->*o.member = (int)value;
+            if (o.replan) {
+                c->order_valid = false;
+                c->cost_steps = 0;
+            }
+            return RTPBR_OK;
+        }
+    // the options that are more than a number within bounds
     if (!strcmp(key, "staging_bytes")) {
         if (value < (1 << 20)) return fail(RTPBR_EINVAL, "staging_bytes must be >= 1 MiB");
         c->staging_bytes = value;
-    } else if (!strcmp(key, "wait_lanes")) {
-        if (value < 1 || value > 64) return fail(RTPBR_EINVAL, "wait_lanes must be 1..64");
-        c->wait_lanes = (int)value;
-    } else if (!strcmp(key, "shade_lanes")) {
-        if (value < 1 || value > 64) return fail(RTPBR_EINVAL, "shade_lanes must be 1..64");
-        c->shade_lanes = (int)value;
-    } else if (!strcmp(key, "jit_waves")) {
-        if (value < 0 || value > 8) return fail(RTPBR_EINVAL, "jit_waves must be 0 (default) .. 8");
-        c->jit_waves = (int)value;
-    } else if (!strcmp(key, "chunk")) {
-        // every wave makes one claim past the end, so the 32-bit work counter overshoots by waves x chunk: the margin kept
-        // free below 2^32 (work_margin) covers 32 waves per CU x 8192
-        if (value < 0 || value > 8192) return fail(RTPBR_EINVAL, "chunk must be 0 (automatic) .. 8192");
-        c->chunk = (int)value;
-    } else if (!strcmp(key, "sparse_lanes")) {
-        if (value < 0 || value > 64) return fail(RTPBR_EINVAL, "sparse_lanes must be 0 (never) .. 64");
-        c->sparse_lanes = (int)value;
-    } else if (!strcmp(key, "src_plan")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "src_plan must be 0 or 1");
-        c->src_plan = (int)value;
-        c->order_valid = false;
-        c->cost_steps = 0;
-    } else if (!strcmp(key, "plan_interval")) {
-        if (value < 1 || value > (1 << 20)) return fail(RTPBR_EINVAL, "plan_interval must be 1 .. 2^20 bounce-steps");
-        c->plan_interval = (int)value;
-    } else if (!strcmp(key, "heavy_own")) {
-        if (value < 0 || value > 128) return fail(RTPBR_EINVAL, "heavy_own must be 0 (no heavy waves) .. 128");
-        c->heavy_own = (int)value;
-        c->order_valid = false;       // the plan's share of heavy pixels was sized for the old value
-        c->cost_steps = 0;
     } else if (!strcmp(key, "src_chain")) {
         if (value < 0 || value > 2) return fail(RTPBR_EINVAL, "src_chain must be 0 (never), 1 (when the device has room beside the pool kernel) or 2 (always: tests)");
         c->src_chain = (int)value;
@@ -2740,32 +2657,6 @@ extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value) 
     } else if (!strcmp(key, "chain_np_max")) {
         if (value < 0) return fail(RTPBR_EINVAL, "chain_np_max must be >= 0");
         c->chain_np_max = value;
-    } else if (!strcmp(key, "chain_waves")) {
-        if (value < 1 || value > 2048) return fail(RTPBR_EINVAL, "chain_waves must be 1 .. 2048");
-        c->chain_waves = (int)value;
-        c->order_valid = false;
-        c->cost_steps = 0;
-    } else if (!strcmp(key, "src_split")) {
-        if (value < 0 || value > 256) return fail(RTPBR_EINVAL, "src_split must be 0 (never) .. 256 (bounce-steps per launch up to which the wavefront split runs)");
-        c->src_split = (int)value;
-    } else if (!strcmp(key, "env_packed")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "env_packed must be 0 (float4 texels) or 1 (RGBA8 texels + 256-entry table: 8-bit sources, same values)");
-        c->env_packed = (int)value;
-    } else if (!strcmp(key, "src_lazy")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "src_lazy must be 0 (every one-step launch shades) or 1 (the shading rides with the next launch's gen pass)");
-        c->src_lazy = (int)value;
-    } else if (!strcmp(key, "split_head")) {
-        if (value < -1 || value > 1) return fail(RTPBR_EINVAL, "split_head must be -1 (automatic: small frames), 0 (the heavy head fills the first groups) or 1 (interleaved: one head entry per group)");
-        c->split_head = (int)value;
-    } else if (!strcmp(key, "split_wait")) {
-        if (value < 1 || value > 64) return fail(RTPBR_EINVAL, "split_wait must be 1..64");
-        c->split_wait = (int)value;
-    } else if (!strcmp(key, "src_track")) {
-        if (value < 0 || value > 2) return fail(RTPBR_EINVAL, "src_track must be 0 (never), 1 (one-object bounds only) or 2 (one- and two-object bounds)");
-        c->src_track = (int)value;
-    } else if (!strcmp(key, "src_op")) {
-        if (value < 0 || value > 7) return fail(RTPBR_EINVAL, "src_op must be 0 .. 7 (bit 0: object-parallel evaluation for sparse waves in the split march and chain kernels, bit 1: in the fused pool kernel, bit 2: the per-lane lean loop for lanes that track different objects)");
-        c->src_op = (int)value;
     } else if (!strcmp(key, "age_weights")) {
         // one hex digit per residency slot, oldest first (0x88888 = equal shares); 0 switches the weighting off
         if (value < 0 || value > 0xffffffffLL) return fail(RTPBR_EINVAL, "age_weights must be 0 (off) or up to 8 hex digits, one per residency slot");
@@ -2778,88 +2669,9 @@ extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value) 
     } else if (!strcmp(key, "age_tune")) {
         if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "age_tune must be 0 (equal shares) or 1 (self-tuned age-weighted shares)");
         c->age_on = (int)value;
-    } else if (!strcmp(key, "tiny_waves")) {
-        if (value < 0 || value > 65535) return fail(RTPBR_EINVAL, "tiny_waves must be 0 .. 65535");
-        c->tiny_waves = (int)value;
-    } else if (!strcmp(key, "tiny_own")) {
-        if (value < 0 || value > 128) return fail(RTPBR_EINVAL, "tiny_own must be 0 (no small heavy waves) .. 128");
-        c->tiny_own = (int)value;
-    } else if (!strcmp(key, "leave_x8")) {
-        if (value < 1 || value > 4096) return fail(RTPBR_EINVAL, "leave_x8 must be 1 .. 4096 (eighths of a march iteration)");
-        c->leave_x8 = (int)value;
-    } else if (!strcmp(key, "heavy_prio")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "heavy_prio must be 0 or 1");
-        c->heavy_prio = (int)value;
-    } else if (!strcmp(key, "heavy_mean_x16")) {
-        if (value < 0 || value > (1 << 20)) return fail(RTPBR_EINVAL, "heavy_mean_x16 must be 0 .. 2^20");
-        c->heavy_mean_x16 = (int)value;
-    } else if (!strcmp(key, "heavy_bulk_x16")) {
-        if (value < 0 || value > (1 << 20)) return fail(RTPBR_EINVAL, "heavy_bulk_x16 must be 0 .. 2^20");
-        c->heavy_bulk_x16 = (int)value;
-    } else if (!strcmp(key, "grid_blocks")) {
-        if (value < 0 || value > 65535) return fail(RTPBR_EINVAL, "grid_blocks must be 0 (automatic) .. 65535");
-        c->grid_blocks = (int)value;
     } else if (!strcmp(key, "residency")) {
         if (value < 1 || value > 256 || (value & (value - 1))) return fail(RTPBR_EINVAL, "residency must be a power of two, 1..256");
         c->residency = (int)value;
-    } else if (!strcmp(key, "ready_low")) {
-        if (value < 0 || value > 63) return fail(RTPBR_EINVAL, "ready_low must be 0..63");
-        c->ready_low = (int)value;
-    } else if (!strcmp(key, "refill_lanes")) {
-        if (value < 1 || value > 64) return fail(RTPBR_EINVAL, "refill_lanes must be 1..64");
-        c->refill_lanes = (int)value;
-    } else if (!strcmp(key, "timing")) {
-        // 1 (default): rtpbr_sample() brackets its kernels with events (rtpbr_last_sample_ms / rtpbr_last_primary_ms); 0: none — an event
-        // is a barrier packet with a completion signal, and four of them cost a launch of a few hundred microseconds a fifth of its time
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "timing must be 0 or 1");
-        c->timing = (int)value;
-    } else if (!strcmp(key, "stage_dense")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "stage_dense must be 0 (item-linear staging) or 1 (records appended per claim in completion order)");
-        c->stage_dense = (int)value;
-    } else if (!strcmp(key, "primary_split")) {
-        if (value < 0 || value > 2) return fail(RTPBR_EINVAL, "primary_split must be 0 (never), 1 (large launches) or 2 (always)");
-        c->primary_split = (int)value;
-    } else if (!strcmp(key, "drain_lanes")) {
-        if (value < 0 || value > 64) return fail(RTPBR_EINVAL, "drain_lanes must be 0..64");
-        c->drain_lanes = (int)value;
-    } else if (!strcmp(key, "primary_lean")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "primary_lean must be 0 or 1");
-        c->primary_lean = (int)value;
-    } else if (!strcmp(key, "lazy_sqrt")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "lazy_sqrt must be 0 or 1");
-        c->lazy_sqrt = (int)value;
-    } else if (!strcmp(key, "jit")) {
-        if (value < -1 || value > 2)
-            return fail(RTPBR_EINVAL, "jit must be -1 (when no ahead-of-time specialisation fits), 0 (never), 1 (always, falling back to the "
-                                      "ahead-of-time instance if compilation is impossible) or 2 (always, an error otherwise)");
-        c->jit = (int)value;
-    } else if (!strcmp(key, "precision")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "precision must be 0 (exactly rounded, the default) or 1 (tolerance flavour: hardware sqrt / rcp / sin / exp, contraction)");
-        c->precision = (int)value;
-    } else if (!strcmp(key, "jit_bake")) {
-        if (value < 0 || value > 2) return fail(RTPBR_EINVAL, "jit_bake must be 0, 1 (scene + configuration) or 2 (+ the camera frame: fixed-camera offline renders)");
-        c->jit_bake = (int)value;
-    } else if (!strcmp(key, "specialize")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "specialize must be 0 or 1");
-        c->specialize = (int)value;
-    } else if (!strcmp(key, "mlp_mfma")) {
-        if (value < 0 || value > 1) return fail(RTPBR_EINVAL, "mlp_mfma must be 0 or 1");
-        c->mlp_mfma = (int)value;
-    } else if (!strcmp(key, "mlp_lanes")) {
-        if (value < 1 || value > 64) return fail(RTPBR_EINVAL, "mlp_lanes must be 1..64");
-        c->mlp_lanes = (int)value;
-    } else if (!strcmp(key, "mlp_full")) {
-        if (value < 1 || value > 65) return fail(RTPBR_EINVAL, "mlp_full must be 1..65 (65 = never compute both halves at once)");
-        c->mlp_full = (int)value;
-    } else if (!strcmp(key, "swap_lanes")) {
-        if (value < 0 || value > 64) return fail(RTPBR_EINVAL, "swap_lanes must be 0 (automatic: 8 in the complete-path pool kernel, 12 in the src/ one) .. 64");
-        c->swap_lanes = (int)value;
-    } else if (!strcmp(key, "scheduler")) {
-        if (value < -1 || value > 1) return fail(RTPBR_EINVAL, "scheduler must be -1 (auto), 0 or 1");
-        c->scheduler = (int)value;
-    } else if (!strcmp(key, "waves_per_cu")) {
-        if (value < 0 || value > 32) return fail(RTPBR_EINVAL, "waves_per_cu must be 0..32");
-        c->waves_per_cu = (int)value;
     } else if (!strcmp(key, "reserve_spp")) {
         // allocate the staging of a `value`-spp rtpbr_sample() call now (complete-path form)
         if (!c->have_cfg || c->P.np <= 0) return fail(RTPBR_ESTATE, "set_config (and set_tiles) first");
@@ -2891,23 +2703,26 @@ extern "C" int rtpbr_test_math(rtpbr_ctx* c, int op, const float* a, const float
     if (int r = set_dev(c)) return r;
     float *da = nullptr, *db = nullptr, *dout = nullptr, *dout2 = nullptr;
     size_t nb = (size_t)n * sizeof(float);
-    HIP_TRY(hipMalloc(&da, nb));
-    HIP_TRY(hipMalloc(&dout, nb));
-    HIP_TRY(hipMalloc(&dout2, nb));
-    HIP_TRY(hipMemcpy(da, a, nb, hipMemcpyHostToDevice));
-    if (b) {
-        HIP_TRY(hipMalloc(&db, nb));
-        HIP_TRY(hipMemcpy(db, b, nb, hipMemcpyHostToDevice));
-    }
-    launch_math_probe(op, da, db, dout, dout2, n, c->stream);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, dout, nb, hipMemcpyDeviceToHost));
-    if (out2) HIP_TRY(hipMemcpy(out2, dout2, nb, hipMemcpyDeviceToHost));
+    const int rc = [&]() -> int {      // (every return leaves through the frees below)
+        HIP_TRY(hipMalloc(&da, nb));
+        HIP_TRY(hipMalloc(&dout, nb));
+        HIP_TRY(hipMalloc(&dout2, nb));
+        HIP_TRY(hipMemcpy(da, a, nb, hipMemcpyHostToDevice));
+        if (b) {
+            HIP_TRY(hipMalloc(&db, nb));
+            HIP_TRY(hipMemcpy(db, b, nb, hipMemcpyHostToDevice));
+        }
+        launch_math_probe(op, da, db, dout, dout2, n, c->stream);
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(out, dout, nb, hipMemcpyDeviceToHost));
+        if (out2) HIP_TRY(hipMemcpy(out2, dout2, nb, hipMemcpyDeviceToHost));
+        return RTPBR_OK;
+    }();
     (void)hipFree(da);
     (void)hipFree(db);
     (void)hipFree(dout);
     (void)hipFree(dout2);
-    return RTPBR_OK;
+    return rc;
 }
 
 // test hook: exhaustive check of the device sqrt_ against IEEE sqrt; *mismatches must come back 0
@@ -2916,10 +2731,13 @@ extern "C" int rtpbr_test_sqrt_exhaustive(rtpbr_ctx* c, unsigned long long* mism
     if (int r = set_dev(c)) return r;
     unsigned long long* d = nullptr;
     HIP_TRY(hipMalloc(&d, sizeof *d));
-    HIP_TRY(hipMemset(d, 0, sizeof *d));
-    launch_sqrt_exhaustive(d, c->stream);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(mismatches, d, sizeof *d, hipMemcpyDeviceToHost));
+    const int rc = [&]() -> int {      // (every return leaves through the free below)
+        HIP_TRY(hipMemset(d, 0, sizeof *d));
+        launch_sqrt_exhaustive(d, c->stream);
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(mismatches, d, sizeof *d, hipMemcpyDeviceToHost));
+        return RTPBR_OK;
+    }();
     (void)hipFree(d);
-    return RTPBR_OK;
+    return rc;
 }

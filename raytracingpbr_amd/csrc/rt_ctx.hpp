@@ -12,6 +12,7 @@
 #include "rt_half.hpp"
 #include "rt_noise.hpp"
 #include "rt_present.hpp"
+#include "rt_reproject.hpp"
 #include "rt_select.hpp"
 
 namespace rt {
@@ -94,6 +95,91 @@ int rt_fail_hip(const char* expr, hipError_t e);
         if (e_ != hipSuccess) return rt_fail_hip(#expr, e_);     \
     } while (0)
 
+// THE FRAME BUFFERS of a context, one row each: device memory sized by the resolution (bar scene_motion), made by the first call that
+// needs it (rt_capi.hip frame_need) and freed with its group (frame_free), by rtpbr_destroy or by rtpbr_set_config with a new resolution.
+//   X(member, element type, bytes, group, zeroed, id, writable)
+// bytes:    of the allocation and, for a public buffer, what rtpbr_buffer_device_ptr reports; an expression in `np` (W * H), `c` and
+//           `reported` (false where the row is allocated, true where its size is handed out: only the present frame tells them apart)
+// zeroed:   filled with zeros on the context's stream when it is allocated
+// id:       the buffer's RTPBR_BUF_* (include/rtpbr.h), FRAME_PRIVATE for a buffer the ABI does not hand out
+// writable: rtpbr_write_buffer accepts it
+// The core group is what rtpbr_set_config allocates; every other buffer is null (a public one answers RTPBR_ESTATE) until the call
+// named in its row, or a call that makes what that call makes, has run.
+enum : unsigned { FRAME_CORE = 1, FRAME_FEATURES = 2, FRAME_NOISE = 4, FRAME_HALF = 8, FRAME_SELECTION = 16, FRAME_PRESENT = 32,
+                  FRAME_ALL = FRAME_CORE | FRAME_FEATURES | FRAME_NOISE | FRAME_HALF | FRAME_SELECTION | FRAME_PRESENT };
+constexpr int FRAME_PRIVATE = -1;
+#define RT_FRAME_BUFFERS(X)                                                                                                                        \
+    X(image_buffer, float4, np * 16, FRAME_CORE, true, RTPBR_BUF_IMAGE_BUFFER, true)                                                               \
+    X(image_pixels, float, np * 12, FRAME_CORE, true, RTPBR_BUF_IMAGE_PIXELS, true)                                                                \
+    X(ray_buffer, rtpbr_ray, np * sizeof(rtpbr_ray), FRAME_CORE, true, RTPBR_BUF_RAY_BUFFER, true)                                                 \
+    X(diff_buffer, float2, np * 8, FRAME_CORE, true, RTPBR_BUF_DIFF_BUFFER, true)                                                                  \
+    X(diff_pixels, float, np * 4, FRAME_CORE, true, RTPBR_BUF_DIFF_PIXELS, true)                                                                   \
+    /* first-hit features and the denoised image (rt_features.hip): rtpbr_render_features, rtpbr_denoise; freeing the group clears feat_valid */   \
+    X(feat_albedo, float, np * 12, FRAME_FEATURES, false, RTPBR_BUF_FEAT_ALBEDO, false)         /* (W,H,3) */                                      \
+    X(feat_normal, float, np * 12, FRAME_FEATURES, false, RTPBR_BUF_FEAT_NORMAL, false)         /* (W,H,3) */                                      \
+    X(feat_depth, float, np * 4, FRAME_FEATURES, false, RTPBR_BUF_FEAT_DEPTH, false)                                                               \
+    X(feat_object, int32_t, np * 4, FRAME_FEATURES, false, RTPBR_BUF_FEAT_OBJECT, false)                                                           \
+    X(feat_guides, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                /* (normal, depth), the record an a-trous tap reads */ \
+    X(denoised, float, np * 12, FRAME_FEATURES, false, RTPBR_BUF_DENOISED_PIXELS, false)        /* (W,H,3) */                                      \
+    X(denoise_scratch, float4, np * 32, FRAME_FEATURES, false, FRAME_PRIVATE, false)            /* 2 x (W,H): the levels' ping-pong, from two levels on */ \
+    /* temporal reuse (rt_reproject.hip): rtpbr_reproject, rtpbr_reproject_scene */                                                                \
+    X(hist_image, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                 /* image_buffer before the move */                 \
+    X(hist_guides, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                /* the old camera's (normal, depth) records */     \
+    X(hist_object, int32_t, np * 4, FRAME_FEATURES, false, FRAME_PRIVATE, false)                /* the old camera's object indices */              \
+    X(motion, float2, np * 8, FRAME_FEATURES, false, RTPBR_BUF_MOTION, false)                                                                      \
+    X(scene_motion, float, sizeof(float) * rt::MAX_OBJ * rt::SCENE_MOTION_WORDS, FRAME_FEATURES, false, FRAME_PRIVATE, false) /* rtpbr_reproject_scene's per-object table on the device (rt_reproject.hpp) */ \
+    /* noise estimation and the guided filter (rt_noise.hip): rtpbr_noise_update, a tracked rtpbr_sample; the map and the variance from rtpbr_noise_estimate on */ \
+    X(noise_moments, float4, np * 16, FRAME_NOISE, true, RTPBR_BUF_MOMENTS, false)                                                                 \
+    X(noise_snapshot, float4, np * 16, FRAME_NOISE, true, FRAME_PRIVATE, false)                 /* image_buffer at the last rtpbr_noise_update */  \
+    X(hist_moments, float4, np * 16, FRAME_NOISE, false, FRAME_PRIVATE, false)                  /* the moments before a reprojection (once they exist) */ \
+    X(noise_map, float, np * 4, FRAME_NOISE, false, RTPBR_BUF_NOISE, false)                                                                        \
+    X(noise_var, float, np * 12, FRAME_NOISE, false, FRAME_PRIVATE, false)                      /* 3 x (W,H): the estimate's variance (-1: no samples), then the guided levels' ping-pong */ \
+    /* the two halves (rt_half.hip): rtpbr_half_update, a dealing rtpbr_sample */                                                                  \
+    X(half_a, float4, np * 16, FRAME_HALF, true, RTPBR_BUF_HALF_BUFFER, false)                                                                     \
+    X(half_snapshot, float4, np * 16, FRAME_HALF, true, FRAME_PRIVATE, false)                   /* image_buffer at the last rtpbr_half_update */   \
+    X(hist_half, float4, np * 16, FRAME_HALF, false, FRAME_PRIVATE, false)                      /* half A before a reprojection that carries it (rtpbr_set_half_mode, warp) */ \
+    /* ... rtpbr_denoise_error and the blend calls */                                                                                              \
+    X(half_b, float4, np * 16, FRAME_HALF, false, FRAME_PRIVATE, false)                         /* image_buffer - half_a, materialised per call */ \
+    X(half_da, float, np * 12, FRAME_HALF, false, FRAME_PRIVATE, false)                         /* (W,H,3): the filter's colour of half A (scratch of the call that fills it) */ \
+    X(half_db, float, np * 12, FRAME_HALF, false, FRAME_PRIVATE, false)                         /* ... of half B */                                \
+    X(denoised_error, float, np * 4, FRAME_HALF, false, RTPBR_BUF_DENOISED_ERROR, false)        /* rtpbr_denoise_error */                          \
+    X(half_fd, float, np * 12, FRAME_HALF, false, FRAME_PRIVATE, false)                         /* rtpbr_denoise_blend: the filter's linear colour of image_buffer */ \
+    X(blend_weight, float, np * 4, FRAME_HALF, false, RTPBR_BUF_BLEND_WEIGHT, false)            /* rtpbr_denoise_blend, rtpbr_denoise_blend_levels */ \
+    X(blend_depth, float, np * 4, FRAME_HALF, false, RTPBR_BUF_BLEND_DEPTH, false)              /* rtpbr_denoise_blend_levels */                   \
+    X(levels_scratch, float4, np * 96, FRAME_HALF, false, FRAME_PRIVATE, false)                 /* 6 x (W,H): a two-plane ping-pong of the levels' records for image_buffer, half A and half B each */ \
+    X(blend_error, float, np * 4, FRAME_HALF, false, RTPBR_BUF_BLEND_ERROR, false)              /* rtpbr_blend_error */                            \
+    X(blend_x, float4, np * 32, FRAME_HALF, false, FRAME_PRIVATE, false)                        /* 2 x (W,H): the running XA and XB of the levels (scratch of the call) */ \
+    X(blend_slope, float, np * 4, FRAME_HALF, false, FRAME_PRIVATE, false)                      /* rtpbr_blend_error_display: the slope s of every pixel (scratch of the call) */ \
+    /* the selection (rt_select.hip): the first select call; freeing the group clears sel_count and have_selection */                             \
+    X(sel_mask, uint8_t, np, FRAME_SELECTION, false, RTPBR_BUF_SELECTION, false)                                                                   \
+    X(sel_list, uint32_t, np * 4, FRAME_SELECTION, false, FRAME_PRIVATE, false)                 /* the selected pixels' buffer indices x * H + y, ascending */ \
+    X(sel_blocks, uint32_t, ((size_t)rt::select_blocks(c->cfg.width, c->cfg.height) + 1) * 4, FRAME_SELECTION, false, FRAME_PRIVATE, false) /* per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them */ \
+    /* the packed 8-bit frame of rtpbr_present (rt_present.hip), (H,W,C) top-down: room for C = 4, reported with the C of the last present;    \
+       freeing the group clears present_channels */                                                                                                \
+    X(present, uint8_t, np * (size_t)(reported ? c->present_channels : 4), FRAME_PRESENT, false, RTPBR_BUF_PRESENT, false)
+
+// the public ids are 0 .. RT_PUBLIC_BUFFERS - 1, each on exactly one row; RT_WRITABLE_BUFFERS: bit id of the rows rtpbr_write_buffer accepts
+#define RT_ROW_ID(m, T, bytes, group, zeroed, id, writable) id,
+constexpr int RT_FRAME_IDS[] = {RT_FRAME_BUFFERS(RT_ROW_ID)};
+#undef RT_ROW_ID
+constexpr int rt_rows_with_id(int id) {
+    int n = 0;
+    for (int v : RT_FRAME_IDS) n += v == id;
+    return n;
+}
+constexpr int RT_PUBLIC_BUFFERS = (int)(sizeof RT_FRAME_IDS / sizeof *RT_FRAME_IDS) - rt_rows_with_id(FRAME_PRIVATE);
+constexpr bool rt_ids_dense() {
+    for (int id = 0; id < RT_PUBLIC_BUFFERS; id++)
+        if (rt_rows_with_id(id) != 1) return false;
+    return true;
+}
+static_assert(rt_ids_dense(), "every RTPBR_BUF_* id from 0 to the last is on exactly one row of RT_FRAME_BUFFERS");
+static_assert(RT_PUBLIC_BUFFERS <= 32, "the masks of rt_order_after_reads are unsigned");
+constexpr unsigned rt_writable_bit(int id, bool writable) { return writable && id >= 0 ? 1u << id : 0u; }
+#define RT_ROW_WRITABLE(m, T, bytes, group, zeroed, id, writable) | rt_writable_bit(id, writable)
+constexpr unsigned RT_WRITABLE_BUFFERS = 0u RT_FRAME_BUFFERS(RT_ROW_WRITABLE);
+#undef RT_ROW_WRITABLE
+
 struct rtpbr_ctx {
     using Params = rt::Params;
     using ObjFull = rt::ObjFull;
@@ -110,12 +196,11 @@ struct rtpbr_ctx {
     int kind = rt::KIND_GENERIC;
     rtpbr_camera cam{};
     Params P{};
-    // device buffers
-    float4* image_buffer = nullptr;
-    float* image_pixels = nullptr;
-    rtpbr_ray* ray_buffer = nullptr;
-    float2* diff_buffer = nullptr;
-    float* diff_pixels = nullptr;
+    // device buffers: the frame buffers of the list above, a member per row ...
+#define RT_ROW_MEMBER(m, T, bytes, group, zeroed, id, writable) T* m = nullptr;
+    RT_FRAME_BUFFERS(RT_ROW_MEMBER)
+#undef RT_ROW_MEMBER
+    // ... and those with a lifetime of their own
     ObjFull* objfull = nullptr;
     float4* env = nullptr;
     uint32_t* env8 = nullptr;        // the same map as RGBA8 texels + a 256-entry table (8-bit sources only; option env_packed)
@@ -183,64 +268,22 @@ struct rtpbr_ctx {
     hipEvent_t ev_read_ready = nullptr;     // "everything enqueued so far" on the context's stream, as the copy stream sees it
     hipEvent_t ev_read_done[8] = {};        // ticket t -> slot t % 8
     int read_issued = 0;                    // tickets handed out so far (the next ticket)
-    int read_pending[20] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    int read_pending[RT_PUBLIC_BUFFERS];    // per RTPBR_BUF_*: the newest ticket whose copy reads it (-1: none that a writer would have to wait for)
+    rtpbr_ctx() {
+        for (int& t : read_pending) t = -1;
+    }
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
-    // first-hit features and the denoised image (rt_features.hip): allocated on first use, freed with the context or a new resolution
-    float* feat_albedo = nullptr;      // (W,H,3)
-    float* feat_normal = nullptr;      // (W,H,3)
-    float* feat_depth = nullptr;       // (W,H)
-    int32_t* feat_object = nullptr;    // (W,H)
-    float4* feat_guides = nullptr;     // (W,H): (normal, depth), the record an a-trous tap reads
+    // the state that goes with the frame buffers' groups
     bool feat_valid = false;           // the features describe the current scene, camera, configuration and shape data
-    float* denoised = nullptr;         // (W,H,3)
-    float4* denoise_scratch = nullptr; // 2 x (W,H): the levels' ping-pong
-    // temporal reuse (rtpbr_reproject, rt_reproject.hip): allocated on first use, freed with the features
-    float4* hist_image = nullptr;      // (W,H): image_buffer before the move
-    float4* hist_guides = nullptr;     // (W,H): the old camera's (normal, depth) records
-    int32_t* hist_object = nullptr;    // (W,H): the old camera's object indices
-    float2* motion = nullptr;          // (W,H): RTPBR_BUF_MOTION
-    float* scene_motion = nullptr;     // rtpbr_reproject_scene's per-object table on the device (MAX_OBJ x 25 words, rt_reproject.hpp)
     bool history_ok = false;           // no set_config / set_scene / set_shape_data / set_env since the last refresh or reproject
-    // noise estimation and the guided filter (rt_noise.hip): allocated on first use, freed with the context or a new resolution
-    float4* noise_moments = nullptr;   // (W,H): RTPBR_BUF_MOMENTS
-    float4* noise_snapshot = nullptr;  // (W,H): image_buffer at the last rtpbr_noise_update
-    float4* hist_moments = nullptr;    // (W,H): the moments before a reprojection
-    float* noise_map = nullptr;        // (W,H): RTPBR_BUF_NOISE
-    float* noise_var = nullptr;        // 3 x (W,H): the estimate's variance (-1: no samples), then the guided levels' ping-pong
     rt::NoiseStats* noise_stats = nullptr;
     int noise_tracking = RTPBR_NOISE_TRACK_OFF;      // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
     rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
                                           RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};      // rtpbr_set_noise_estimator: plain state, kept across refresh / set_config / set_scene / reproject
-    // the two halves and the error estimate of the denoised frame (rt_half.hip): half_a and half_snapshot from the first rtpbr_half_update
-    // on, the others from the first rtpbr_denoise_error on; freed with the context or a new resolution
-    float4* half_a = nullptr;          // (W,H): RTPBR_BUF_HALF_BUFFER
-    float4* half_snapshot = nullptr;   // (W,H): image_buffer at the last rtpbr_half_update
-    float4* hist_half = nullptr;       // (W,H): half A before a reprojection that carries it (rtpbr_set_half_mode, warp)
     rtpbr_half_mode half_mode{RTPBR_HALF_MODE_DEFAULT_PER_SAMPLE, RTPBR_HALF_MODE_DEFAULT_WARP};      // rtpbr_set_half_mode: plain state, kept across refresh / set_config / set_scene / reproject
-    float4* half_b = nullptr;          // (W,H): image_buffer - half_a, materialised per rtpbr_denoise_error
-    float* half_da = nullptr;          // (W,H,3): the filter's colour of half A (scratch of the call that fills it)
-    float* half_db = nullptr;          // (W,H,3): ... of half B
-    float* denoised_error = nullptr;   // (W,H): RTPBR_BUF_DENOISED_ERROR
-    // rtpbr_denoise_blend: from its first call on (it filters the halves into half_da / half_db too, in their linear form); freed with the halves
-    float* half_fd = nullptr;          // (W,H,3): the filter's linear colour of image_buffer
-    float* blend_weight = nullptr;     // (W,H): RTPBR_BUF_BLEND_WEIGHT
-    // rtpbr_denoise_blend_levels: from its first call on (it makes half_b and blend_weight too); freed with the halves
-    float* blend_depth = nullptr;      // (W,H): RTPBR_BUF_BLEND_DEPTH
-    float4* levels_scratch = nullptr;  // 6 x (W,H): a two-plane ping-pong of the levels' records for image_buffer, half A and half B each
-    // rtpbr_blend_error: from its first call on (it makes what rtpbr_denoise_blend_levels makes too); freed with the halves
-    float* blend_error = nullptr;      // (W,H): RTPBR_BUF_BLEND_ERROR
-    float4* blend_x = nullptr;         // 2 x (W,H): the running XA and XB of the levels (scratch of the call)
-    // rtpbr_blend_error_display: from its first call on (it makes what rtpbr_blend_error makes too); freed with the halves
-    float* blend_slope = nullptr;      // (W,H): the slope s of every pixel (scratch of the call)
-    // the selection of rtpbr_select_mask / rtpbr_select_noisy / rtpbr_select_error (rt_select.hip): allocated on the first select call, freed with the context or a new resolution
-    uint8_t* sel_mask = nullptr;       // (W,H): RTPBR_BUF_SELECTION
-    uint32_t* sel_list = nullptr;      // the selected pixels' buffer indices x * H + y, ascending (W * H entries of room)
-    uint32_t* sel_blocks = nullptr;    // per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them
     uint32_t sel_count = 0;            // entries of sel_list
     bool have_selection = false;
-    // the packed 8-bit frame of rtpbr_present (rt_present.hip): allocated on the first present, freed with the context or a new resolution
-    uint8_t* present = nullptr;        // (H,W,C) top-down, room for C = 4: RTPBR_BUF_PRESENT
-    int present_channels = 0;          // C of the last present (the buffer's reported size is W * H * C)
+    int present_channels = 0;          // C of the last present
     size_t march_np = 0;
     int src_chain = 1;            // src/ form, fused launches: the plan's chain set runs in the chain kernel beside the pool kernel (rt_chain.hpp)
     long long chain_np_max = 2500000;   // ... frames of more local pixels than this are throughput-bound: no chain set

@@ -396,3 +396,101 @@ def test_bench_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_pa
     vals = np.load(tmp_path / "a" / "image_buffer_sample.npy")
     pix = np.load(tmp_path / "a" / "image_buffer_sample_pixel.npy").astype(np.int64)
     assert len(np.unique(pix)) == len(pix) > 0 and np.array_equal(vals, img.reshape(-1, 4)[pix])
+
+
+# rtpbr_set_option, key by key: (key, lowest accepted value, highest accepted value or None, the refusal's message)
+OPTION_BOUNDS = [
+    ("staging_bytes", 1 << 20, None, "staging_bytes must be >= 1 MiB"),
+    ("wait_lanes", 1, 64, "wait_lanes must be 1..64"),
+    ("shade_lanes", 1, 64, "shade_lanes must be 1..64"),
+    ("jit_waves", 0, 8, "jit_waves must be 0 (default) .. 8"),
+    ("chunk", 0, 8192, "chunk must be 0 (automatic) .. 8192"),
+    ("sparse_lanes", 0, 64, "sparse_lanes must be 0 (never) .. 64"),
+    ("src_plan", 0, 1, "src_plan must be 0 or 1"),
+    ("plan_interval", 1, 1 << 20, "plan_interval must be 1 .. 2^20 bounce-steps"),
+    ("heavy_own", 0, 128, "heavy_own must be 0 (no heavy waves) .. 128"),
+    ("src_chain", 0, 2, "src_chain must be 0 (never), 1 (when the device has room beside the pool kernel) or 2 (always: tests)"),
+    ("chain_np_max", 0, None, "chain_np_max must be >= 0"),
+    ("chain_waves", 1, 2048, "chain_waves must be 1 .. 2048"),
+    ("src_split", 0, 256, "src_split must be 0 (never) .. 256 (bounce-steps per launch up to which the wavefront split runs)"),
+    ("env_packed", 0, 1, "env_packed must be 0 (float4 texels) or 1 (RGBA8 texels + 256-entry table: 8-bit sources, same values)"),
+    ("src_lazy", 0, 1, "src_lazy must be 0 (every one-step launch shades) or 1 (the shading rides with the next launch's gen pass)"),
+    ("split_head", -1, 1, "split_head must be -1 (automatic: small frames), 0 (the heavy head fills the first groups) or 1 (interleaved: one head entry per group)"),
+    ("split_wait", 1, 64, "split_wait must be 1..64"),
+    ("src_track", 0, 2, "src_track must be 0 (never), 1 (one-object bounds only) or 2 (one- and two-object bounds)"),
+    ("src_op", 0, 7, "src_op must be 0 .. 7 (bit 0: object-parallel evaluation for sparse waves in the split march and chain kernels, bit 1: in the fused pool kernel, bit 2: the per-lane lean loop for lanes that track different objects)"),
+    ("age_weights", 0, 0xffffffff, "age_weights must be 0 (off) or up to 8 hex digits, one per residency slot"),
+    ("age_tune", 0, 1, "age_tune must be 0 (equal shares) or 1 (self-tuned age-weighted shares)"),
+    ("tiny_waves", 0, 65535, "tiny_waves must be 0 .. 65535"),
+    ("tiny_own", 0, 128, "tiny_own must be 0 (no small heavy waves) .. 128"),
+    ("leave_x8", 1, 4096, "leave_x8 must be 1 .. 4096 (eighths of a march iteration)"),
+    ("heavy_prio", 0, 1, "heavy_prio must be 0 or 1"),
+    ("heavy_mean_x16", 0, 1 << 20, "heavy_mean_x16 must be 0 .. 2^20"),
+    ("heavy_bulk_x16", 0, 1 << 20, "heavy_bulk_x16 must be 0 .. 2^20"),
+    ("grid_blocks", 0, 65535, "grid_blocks must be 0 (automatic) .. 65535"),
+    ("residency", 1, 256, "residency must be a power of two, 1..256"),
+    ("ready_low", 0, 63, "ready_low must be 0..63"),
+    ("refill_lanes", 1, 64, "refill_lanes must be 1..64"),
+    ("timing", 0, 1, "timing must be 0 or 1"),
+    ("stage_dense", 0, 1, "stage_dense must be 0 (item-linear staging) or 1 (records appended per claim in completion order)"),
+    ("primary_split", 0, 2, "primary_split must be 0 (never), 1 (large launches) or 2 (always)"),
+    ("drain_lanes", 0, 64, "drain_lanes must be 0..64"),
+    ("primary_lean", 0, 1, "primary_lean must be 0 or 1"),
+    ("lazy_sqrt", 0, 1, "lazy_sqrt must be 0 or 1"),
+    ("jit", -1, 2, "jit must be -1 (when no ahead-of-time specialisation fits), 0 (never), 1 (always, falling back to the ahead-of-time instance if compilation is impossible) or 2 (always, an error otherwise)"),
+    ("precision", 0, 1, "precision must be 0 (exactly rounded, the default) or 1 (tolerance flavour: hardware sqrt / rcp / sin / exp, contraction)"),
+    ("jit_bake", 0, 2, "jit_bake must be 0, 1 (scene + configuration) or 2 (+ the camera frame: fixed-camera offline renders)"),
+    ("specialize", 0, 1, "specialize must be 0 or 1"),
+    ("mlp_mfma", 0, 1, "mlp_mfma must be 0 or 1"),
+    ("mlp_lanes", 1, 64, "mlp_lanes must be 1..64"),
+    ("mlp_full", 1, 65, "mlp_full must be 1..65 (65 = never compute both halves at once)"),
+    ("swap_lanes", 0, 64, "swap_lanes must be 0 (automatic: 8 in the complete-path pool kernel, 12 in the src/ one) .. 64"),
+    ("scheduler", -1, 1, "scheduler must be -1 (auto), 0 or 1"),
+    ("waves_per_cu", 0, 32, "waves_per_cu must be 0..32"),
+]
+
+
+def test_every_option_keeps_its_bounds_and_messages(tmp_path, monkeypatch):
+    """rtpbr_set_option on a context without a device: rtpbr_jit_prebuild applies its "key=value ..." string with it before
+    anything is compiled, so "key=value nosuchkey=0" answers "unknown option nosuchkey" exactly when the first pair was
+    accepted, and the pair's own message when it was refused.  Every key's lowest and highest value is accepted, the values
+    next to them are refused in the key's own words.  sample_base takes any value; reserve_spp's accepted values allocate
+    (they need a device): its refusal is checked."""
+    from raytracingpbr_amd import prebuild, workloads
+    from raytracingpbr_amd.dataclass import SDFObject
+    monkeypatch.setenv("HIPCC", "/nonexistent/hipcc")          # (a mistake in this test cannot start a compiler)
+    monkeypatch.setenv("RTPBR_JIT_CACHE", str(tmp_path))
+    lib = prebuild._lib()
+    wl = workloads.get("c2", 0, 0)
+    n = len(wl.scene.objects)
+    arr = (SDFObject * n)(*wl.scene.objects)
+    buf = C.create_string_buffer(1024)
+
+    def answer(options):
+        rc = lib.rtpbr_jit_prebuild(arr, n, 1 if wl.scene.scale10 else 0, C.byref(wl.cfg), C.byref(wl.scene.camera), 0, 0, 1,
+                                    options.encode(), buf, 1024)
+        return rc, lib.rtpbr_last_error().decode()
+
+    EINVAL = -1
+    unknown = (EINVAL, "unknown option nosuchkey")
+    assert answer("wait_lanes=65") == (EINVAL, "wait_lanes must be 1..64")
+    assert answer("wait_lanes=64 nosuchkey=0") == unknown
+    for key, lo, hi, msg in OPTION_BOUNDS:
+        assert answer("%s=%d nosuchkey=0" % (key, lo - 1)) == (EINVAL, msg), key
+        assert answer("%s=%d nosuchkey=0" % (key, lo)) == unknown, key
+        if hi is not None:
+            assert answer("%s=%d nosuchkey=0" % (key, hi)) == unknown, key
+            assert answer("%s=%d nosuchkey=0" % (key, hi + 1)) == (EINVAL, msg), key
+    for value in (1 << 40, 1 << 62):                           # the two 64-bit options have no upper bound
+        assert answer("staging_bytes=%d nosuchkey=0" % value) == unknown
+        assert answer("chain_np_max=%d nosuchkey=0" % value) == unknown
+    for value in (-1, 0, 12345, 0xffffffff):
+        assert answer("sample_base=%d nosuchkey=0" % value) == unknown
+    assert answer("residency=48") == (EINVAL, "residency must be a power of two, 1..256")
+    assert answer("age_weights=-1") == (EINVAL, "age_weights must be 0 (off) or up to 8 hex digits, one per residency slot")
+    assert answer("chain_np_max=-1") == (EINVAL, "chain_np_max must be >= 0")
+    assert answer("staging_bytes=5") == (EINVAL, "staging_bytes must be >= 1 MiB")
+    assert answer("jit=3")[1].startswith("jit must be -1 (when no ahead-of-time specialisation fits)")
+    assert answer("reserve_spp=0") == (EINVAL, "reserve_spp must be >= 1")
+    assert len(OPTION_BOUNDS) + 2 == 49 and len({k for k, _, _, _ in OPTION_BOUNDS}) == len(OPTION_BOUNDS)
+    assert not os.listdir(tmp_path)                            # nothing was compiled

@@ -45,8 +45,7 @@
 //                       entry's slope belongs to a pixel whose error word another block may already have written), and the
 //                       lane writes the root of variance + the window's mean of that.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that the CPU restatement matches bit for bit
-// (tests/half_ref/half_ref.c, tests/blend_ref/blend_ref.c, tests/levels_ref/levels_ref.c,
-// tests/blend_error_ref/blend_error_ref.c).
+// (tests/half_ref/half_ref.c, tests/post_ref/blend.h).
 #pragma once
 #include "rt_noise.hpp"
 

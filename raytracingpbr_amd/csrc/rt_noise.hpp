@@ -16,7 +16,7 @@
 //                       temporal pixel (2 <= K < pool_batches) takes max(own, pooled over its (2R+1)^2 window).  Every other
 //                       pixel takes noise_estimate's path.  launch_noise_estimate picks it only when pool_batches > 0.
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that a CPU restatement matches bit for bit
-// (tests/noise_ref/noise_ref.c).
+// (tests/post_ref/noise.h, tests/post_ref/filter.h).
 #pragma once
 #include "rt_types.hpp"
 

@@ -12,7 +12,7 @@
 //                      the object's frame into the old world (and its world-space normal turned back) before it is projected;
 //                      the per-object table (old and new position and matrix) is staged in LDS by every block.
 // The arithmetic is fixed operation by operation (include/rtpbr.h, rtpbr_reproject and rtpbr_reproject_scene) so that the CPU
-// restatements match bit for bit (tests/reproject_ref/reproject_ref.c, tests/reproject_scene_ref/reproject_scene_ref.c).
+// restatements match bit for bit (tests/post_ref/gather.h).
 #pragma once
 #include "rt_types.hpp"
 

@@ -1,17 +1,16 @@
-"""Test helper: the CPU restatement of rtpbr_blend_error and, with ``display``, of rtpbr_blend_error_display
-(tests/blend_error_ref/blend_error_ref.c), built on demand the way tests/levels_ref_lib.py builds the levels' (the oracle's source
-is included: hidden visibility, -Bsymbolic, only ber_* exported).
+"""Test helper: the CPU restatement of rtpbr_blend_error and, with ``display``, of rtpbr_blend_error_display (ber_blend_error of
+tests/post_ref/blend.h), built on demand by ref_build.
 
 The three ladders come from levels_ref_lib.Filtered (and with them the subtract pass of half_ref_lib); features come from
 feature_ref_lib.features() or from the renderer under test (dicts albedo / normal / depth / object)."""
-import ctypes as C
 from collections import namedtuple
 
 import numpy as np
 
 import levels_ref_lib as lv
-from raytracingpbr_amd.dataclass import BlendParams, ErrorParams
-from ref_build import F, I, Library, P, ROOT, ptr      # noqa: F401 (ROOT: for the tests)
+from blend_ref_lib import rule_args
+from raytracingpbr_amd.dataclass import ErrorParams
+from ref_build import POST_REF, ROOT, cfg_ptr, ptr, stats_of      # noqa: F401 (ROOT: for the tests)
 
 # error (W,H); stats = (pixels_estimated, pixels_above, max); denoised (W,H,3), weight, depth (W,H): what
 # rtpbr_denoise_blend_levels writes; variance = S / n, bias2 and slope = s per pixel (0 where the pixel is not valid).  With
@@ -19,31 +18,23 @@ from ref_build import F, I, Library, P, ROOT, ptr      # noqa: F401 (ROOT: for t
 # by: it is there to compare the two rules)
 BlendError = namedtuple("BlendError", "error stats denoised weight depth variance bias2 slope")
 
-_ref = Library("blend_error_ref", {
-    "ber_blend_error": [P, P, P, P, P, P, P, P, I, I, F, F, I, F, I, P, P, P, P, P, P],
-})
-build, lib = _ref.build, _ref.lib
+build, lib = POST_REF.build, POST_REF.lib
 
 
 def from_ladders(f, threshold=0.0, radius=None, z=None, min_half_samples=None, window=None, display=False):
     """rtpbr_blend_error (``display``: rtpbr_blend_error_display) on the ladders of a levels_ref_lib.Filtered: ``radius``, ``z``,
     ``min_half_samples`` are the blend's, ``window`` the error's radius."""
-    d = BlendParams.DEFAULTS
-    r = int(d["radius"] if radius is None else radius)
-    zz = np.float32(d["z"] if z is None else z)
-    m = int(d["min_half_samples"] if min_half_samples is None else min_half_samples)
     w = int(ErrorParams.DEFAULTS["radius"] if window is None else window)
     W, H = f.cfg.width, f.cfg.height
     out = np.empty((W, H, 3), np.float32)
     weight, depth, err = (np.empty((W, H), np.float32) for _ in range(3))
     parts = np.empty((3, W, H), np.float32)
     st = np.zeros(3, np.uint32)
-    rc = lib().ber_blend_error(C.cast(C.pointer(f.cfg), C.c_void_p), ptr(f.b), ptr(f.a), ptr(f.hb), ptr(f.fd), ptr(f.fa),
-                               ptr(f.fb), ptr(f.obj), f.K, r, float(zz * zz), float(np.float32(m)), w, float(threshold),
-                               1 if display else 0, ptr(out), ptr(weight), ptr(depth), ptr(err), ptr(parts), ptr(st))
+    rc = lib().ber_blend_error(cfg_ptr(f.cfg), ptr(f.b), ptr(f.a), ptr(f.hb), ptr(f.fd), ptr(f.fa), ptr(f.fb), ptr(f.obj), f.K,
+                               *rule_args(radius, z, min_half_samples), w, float(threshold), 1 if display else 0, ptr(out),
+                               ptr(weight), ptr(depth), ptr(err), ptr(parts), ptr(st))
     assert rc == 0, rc
-    stats = (int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0]))
-    return BlendError(err, stats, out, weight, depth, parts[0], parts[1], parts[2])
+    return BlendError(err, stats_of(st), out, weight, depth, parts[0], parts[1], parts[2])
 
 
 def blend_error(cfg, image_buffer, half_a, feats, threshold=0.0, radius=None, z=None, min_half_samples=None, window=None,

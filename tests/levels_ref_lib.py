@@ -1,38 +1,31 @@
-"""Test helper: the CPU restatement of rtpbr_denoise_blend_levels (tests/levels_ref/levels_ref.c), built on demand the way
-tests/blend_ref_lib.py builds the blend's (the oracle's source is included: hidden visibility, -Bsymbolic, only lr_* exported).
+"""Test helper: the CPU restatement of rtpbr_denoise_blend_levels (lr_* of tests/post_ref: filter.h, blend.h), built on demand by
+ref_build.
 
 The subtract pass goes through half_ref_lib; features come from feature_ref_lib.features() or from the renderer under test
 (dicts albedo / normal / depth / object)."""
-import ctypes as C
-
 import numpy as np
 
 import half_ref_lib as hl
-from raytracingpbr_amd.dataclass import BlendParams, DenoiseParams
-from ref_build import F, I, Library, P, ROOT, f32, ptr      # noqa: F401 (ROOT: for the tests)
+from blend_ref_lib import rule_args
+from raytracingpbr_amd.dataclass import DenoiseParams
+from ref_build import POST_REF, ROOT, cfg_ptr, f32, feats_of, pick, ptr, stats_of      # noqa: F401 (ROOT: for the tests)
 
-_ref = Library("levels_ref", {
-    "lr_filter_levels": [P, P, P, P, P, P, I, I, F, F, F, F, P],
-    "lr_blend_levels": [P, P, P, P, P, P, P, P, I, I, F, F, P, P, P, P],
-})
-build, lib = _ref.build, _ref.lib
+build, lib = POST_REF.build, POST_REF.lib
 
 
 def filter_levels(cfg, image_buffer, feats, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None,
                   sigma_albedo=None):
     """(K + 1, W, H, 3) — F_0 .. F_K of this buffer: rtpbr_denoise's filter with iterations = k, stopped before the tone map
     (+0 for a pixel without samples)."""
-    d = DenoiseParams.DEFAULTS
-    pick = lambda v, k: d[k] if v is None else v      # noqa: E731
+    d = pick(DenoiseParams.DEFAULTS)
     ib = f32(image_buffer)
-    f = {k: np.ascontiguousarray(feats[k]) for k in ("albedo", "normal", "depth", "object")}
-    assert f["object"].dtype == np.int32 and ib.shape == (cfg.width, cfg.height, 4)
-    K = int(pick(iterations, "iterations"))
+    f = feats_of(feats)
+    assert ib.shape == (cfg.width, cfg.height, 4)
+    K = int(d(iterations, "iterations"))
     out = np.empty((K + 1, cfg.width, cfg.height, 3), np.float32)
-    rc = lib().lr_filter_levels(C.cast(C.pointer(cfg), C.c_void_p), ptr(ib), ptr(f["albedo"]), ptr(f["normal"]), ptr(f["depth"]),
-                                ptr(f["object"]), K, int(pick(demodulate, "demodulate")), float(pick(sigma_color, "sigma_color")),
-                                float(pick(sigma_normal, "sigma_normal")), float(pick(sigma_depth, "sigma_depth")),
-                                float(pick(sigma_albedo, "sigma_albedo")), ptr(out))
+    rc = lib().lr_filter_levels(cfg_ptr(cfg), ptr(ib), *map(ptr, f), K, int(d(demodulate, "demodulate")),
+                                float(d(sigma_color, "sigma_color")), float(d(sigma_normal, "sigma_normal")),
+                                float(d(sigma_depth, "sigma_depth")), float(d(sigma_albedo, "sigma_albedo")), ptr(out))
     assert rc == 0, rc
     return out
 
@@ -52,18 +45,14 @@ class Filtered:
 
     def blend(self, radius=None, z=None, min_half_samples=None):
         """(denoised (W,H,3), weight T_K (W,H), depth (W,H), (pixels_estimated, pixels_above, max 1 - T_K))"""
-        d = BlendParams.DEFAULTS
-        r = int(d["radius"] if radius is None else radius)
-        zz = np.float32(d["z"] if z is None else z)
-        m = int(d["min_half_samples"] if min_half_samples is None else min_half_samples)
         W, H = self.cfg.width, self.cfg.height
         weight, depth, out = np.empty((W, H), np.float32), np.empty((W, H), np.float32), np.empty((W, H, 3), np.float32)
         st = np.zeros(3, np.uint32)
-        rc = lib().lr_blend_levels(C.cast(C.pointer(self.cfg), C.c_void_p), ptr(self.b), ptr(self.a), ptr(self.hb), ptr(self.fd),
-                                   ptr(self.fa), ptr(self.fb), ptr(self.obj), self.K, r, float(zz * zz), float(np.float32(m)),
-                                   ptr(weight), ptr(depth), ptr(out), ptr(st))
+        rc = lib().lr_blend_levels(cfg_ptr(self.cfg), ptr(self.b), ptr(self.a), ptr(self.hb), ptr(self.fd), ptr(self.fa), ptr(self.fb),
+                                   ptr(self.obj), self.K, *rule_args(radius, z, min_half_samples), ptr(weight), ptr(depth), ptr(out),
+                                   ptr(st))
         assert rc == 0, rc
-        return out, weight, depth, (int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0]))
+        return out, weight, depth, stats_of(st)
 
 
 def denoise_blend_levels(cfg, image_buffer, half_a, feats, radius=None, z=None, min_half_samples=None, **denoise):

@@ -1,22 +1,13 @@
 """Test helper: the CPU restatement of rtpbr_noise_update / rtpbr_noise_estimate / rtpbr_denoise_guided and of the moment warp
-of rtpbr_reproject (tests/noise_ref/noise_ref.c), built on demand the way tests/feature_ref_lib.py builds the feature reference
-(the oracle's flags, hidden visibility, -Bsymbolic: only nr_* exported).
+of rtpbr_reproject (nr_* of tests/post_ref: noise.h, filter.h, gather.h), built on demand by ref_build.
 
 Features come from feature_ref_lib.features() or from the renderer under test (dicts albedo / normal / depth / object)."""
-import ctypes as C
-
 import numpy as np
 
-from raytracingpbr_amd.dataclass import Camera, DenoiseGuidedParams, ReprojectParams
-from ref_build import F, I, Library, P, ROOT, f32, ptr      # noqa: F401 (ROOT: for the tests)
+from raytracingpbr_amd.dataclass import DenoiseGuidedParams, ReprojectParams
+from ref_build import GEOMETRY, POST_REF, ROOT, camera_of, cfg_ptr, f32, feats_of, pick, ptr, stats_of      # noqa: F401 (ROOT: for the tests)
 
-_ref = Library("noise_ref", {
-    "nr_update": [I, I, P, P, P],
-    "nr_estimate": [I, I, P, P, P, F, P, P, P],
-    "nr_guided": [P, P, P, P, P, P, P, I, I, F, F, F, F, P],
-    "nr_reproject": [P] * 11 + [F, F, F, P, P],
-})
-build, lib = _ref.build, _ref.lib
+build, lib = POST_REF.build, POST_REF.lib
 
 
 class Tracker:
@@ -53,45 +44,34 @@ def estimate(image_buffer, moments, obj, threshold=0.0):
     st = np.zeros(3, np.uint32)
     rc = lib().nr_estimate(W, H, ptr(ib), ptr(M), ptr(o), float(threshold), ptr(noise), ptr(var0), ptr(st))
     assert rc == 0, rc
-    return noise, var0, (int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0]))
+    return noise, var0, stats_of(st)
 
 
 def guided(cfg, image_buffer, feats, var0, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None,
            variance_floor=None):
     """(W,H,3) — what rtpbr_denoise_guided writes from this image_buffer, these features and this level-0 variance."""
-    d = DenoiseGuidedParams.DEFAULTS
-    pick = lambda v, k: d[k] if v is None else v      # noqa: E731
-    ib = f32(image_buffer)
-    f = {k: np.ascontiguousarray(feats[k]) for k in ("albedo", "normal", "depth", "object")}
-    assert f["object"].dtype == np.int32
-    v0 = f32(var0)
+    d = pick(DenoiseGuidedParams.DEFAULTS)
+    ib, v0 = f32(image_buffer), f32(var0)
+    f = feats_of(feats)
     out = np.empty((cfg.width, cfg.height, 3), np.float32)
-    rc = lib().nr_guided(C.cast(C.pointer(cfg), C.c_void_p), ptr(ib), ptr(f["albedo"]), ptr(f["normal"]), ptr(f["depth"]), ptr(f["object"]),
-                         ptr(v0), int(pick(iterations, "iterations")), int(pick(demodulate, "demodulate")), float(pick(sigma_color, "sigma_color")),
-                         float(pick(sigma_normal, "sigma_normal")), float(pick(sigma_depth, "sigma_depth")),
-                         float(pick(variance_floor, "variance_floor")), ptr(out))
+    rc = lib().nr_guided(cfg_ptr(cfg), ptr(ib), *map(ptr, f), ptr(v0), int(d(iterations, "iterations")), int(d(demodulate, "demodulate")),
+                         float(d(sigma_color, "sigma_color")), float(d(sigma_normal, "sigma_normal")),
+                         float(d(sigma_depth, "sigma_depth")), float(d(variance_floor, "variance_floor")), ptr(out))
     assert rc == 0, rc
     return out
-
-
-def _cam(c):
-    return c if isinstance(c, Camera) else Camera(*c)
 
 
 def reproject(cfg, old_camera, new_camera, image_buffer, moments, old_feats, new_feats, max_history=None, depth_tolerance=None,
               normal_cos=None):
     """(image_buffer (W,H,4), moments (W,H,4)) — what rtpbr_reproject leaves when the context tracks noise."""
-    d = ReprojectParams.DEFAULTS
-    pick = lambda v, k: d[k] if v is None else v      # noqa: E731
+    d = pick(ReprojectParams.DEFAULTS)
     W, H = cfg.width, cfg.height
     ib, M = f32(image_buffer), f32(moments)
-    o = {k: np.ascontiguousarray(old_feats[k]) for k in ("normal", "depth", "object")}
-    n = {k: np.ascontiguousarray(new_feats[k]) for k in ("normal", "depth", "object")}
+    o, n = feats_of(old_feats, GEOMETRY), feats_of(new_feats, GEOMETRY)
     out, mo = np.empty((W, H, 4), np.float32), np.empty((W, H, 4), np.float32)
-    c0, c1 = _cam(old_camera), _cam(new_camera)
-    rc = lib().nr_reproject(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(c0), C.c_void_p), C.cast(C.pointer(c1), C.c_void_p),
-                            ptr(ib), ptr(M), ptr(o["normal"]), ptr(o["depth"]), ptr(o["object"]), ptr(n["normal"]), ptr(n["depth"]),
-                            ptr(n["object"]), float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
-                            float(pick(normal_cos, "normal_cos")), ptr(out), ptr(mo))
+    c0, c1 = camera_of(old_camera), camera_of(new_camera)
+    rc = lib().nr_reproject(cfg_ptr(cfg), cfg_ptr(c0), cfg_ptr(c1), ptr(ib), ptr(M), *map(ptr, o), *map(ptr, n),
+                            float(d(max_history, "max_history")), float(d(depth_tolerance, "depth_tolerance")),
+                            float(d(normal_cos, "normal_cos")), ptr(out), ptr(mo))
     assert rc == 0, rc
     return out, mo

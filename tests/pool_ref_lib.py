@@ -8,7 +8,7 @@ exported), and the extended selection rule of rtpbr_select_noisy in numpy.
 import numpy as np
 
 import select_ref_lib as sr
-from ref_build import F, I, Library, P, ROOT, f32, ptr      # noqa: F401 (ROOT: for the tests)
+from ref_build import F, I, Library, P, ROOT, f32, ptr, stats_of      # noqa: F401 (ROOT: for the tests)
 
 _ref = Library("pool_ref", {
     "pr_estimate": [I, I, P, P, P, F, I, I, P, P, P],
@@ -28,7 +28,7 @@ def estimate(image_buffer, moments, obj, threshold=0.0, pool_batches=0, pool_rad
     rc = lib().pr_estimate(W, H, ptr(ib), ptr(M), ptr(o), float(threshold), int(pool_batches), int(pool_radius), ptr(noise),
                            ptr(var0), ptr(st))
     assert rc == 0, rc
-    return noise, var0, (int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0]))
+    return noise, var0, stats_of(st)
 
 
 def select(noise, count, threshold, dilate=0, min_samples=0):

@@ -1,41 +1,28 @@
-"""Test helper: the CPU restatement of rtpbr_reproject's gather (tests/reproject_ref/reproject_ref.c), built on demand the way
-tests/feature_ref_lib.py builds the feature reference (the oracle's flags, hidden visibility, -Bsymbolic: only rr_* exported).
+"""Test helper: the CPU restatement of rtpbr_reproject's gather (rr_reproject of tests/post_ref/gather.h), built on demand by
+ref_build.
 
 The old and new features come from feature_ref_lib.features()."""
-import ctypes as C
-
 import numpy as np
 
-from raytracingpbr_amd.dataclass import Camera, ReprojectParams
-from ref_build import F, Library, P, ROOT, ptr      # noqa: F401 (ROOT: for the tests)
+from raytracingpbr_amd.dataclass import ReprojectParams
+from ref_build import GEOMETRY, POST_REF, ROOT, camera_of, cfg_ptr, f32, feats_of, pick, ptr      # noqa: F401 (ROOT: for the tests)
 
-_ref = Library("reproject_ref", {
-    "rr_reproject": [P, P, P, P, P, P, P, P, P, P, F, F, F, P, P],
-})
-build, lib = _ref.build, _ref.lib
-
-
-def _cam(c):
-    return c if isinstance(c, Camera) else Camera(*c)
+build, lib = POST_REF.build, POST_REF.lib
 
 
 def reproject(cfg, old_camera, new_camera, image_buffer, old_feats, new_feats, max_history=None, depth_tolerance=None, normal_cos=None):
     """(image_buffer (W,H,4), motion (W,H,2)) — what rtpbr_reproject writes, from the old image_buffer and the old and new
     features (dicts as feature_ref_lib.features() returns them; None = the library default for a parameter)."""
-    d = ReprojectParams.DEFAULTS
-    pick = lambda v, k: d[k] if v is None else v      # noqa: E731
+    d = pick(ReprojectParams.DEFAULTS)
     W, H = cfg.width, cfg.height
-    ib = np.ascontiguousarray(image_buffer, dtype=np.float32)
+    ib = f32(image_buffer)
     assert ib.shape == (W, H, 4)
-    o = {k: np.ascontiguousarray(old_feats[k]) for k in ("normal", "depth", "object")}
-    n = {k: np.ascontiguousarray(new_feats[k]) for k in ("normal", "depth", "object")}
-    assert o["object"].dtype == np.int32 and n["object"].dtype == np.int32
+    o, n = feats_of(old_feats, GEOMETRY), feats_of(new_feats, GEOMETRY)
     out = np.empty((W, H, 4), np.float32)
     motion = np.empty((W, H, 2), np.float32)
-    c0, c1 = _cam(old_camera), _cam(new_camera)
-    rc = lib().rr_reproject(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(c0), C.c_void_p), C.cast(C.pointer(c1), C.c_void_p),
-                            ptr(ib), ptr(o["normal"]), ptr(o["depth"]), ptr(o["object"]), ptr(n["normal"]), ptr(n["depth"]),
-                            ptr(n["object"]), float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
-                            float(pick(normal_cos, "normal_cos")), ptr(out), ptr(motion))
+    c0, c1 = camera_of(old_camera), camera_of(new_camera)
+    rc = lib().rr_reproject(cfg_ptr(cfg), cfg_ptr(c0), cfg_ptr(c1), ptr(ib), *map(ptr, o), *map(ptr, n),
+                            float(d(max_history, "max_history")), float(d(depth_tolerance, "depth_tolerance")),
+                            float(d(normal_cos, "normal_cos")), ptr(out), ptr(motion))
     assert rc == 0, rc
     return out, motion

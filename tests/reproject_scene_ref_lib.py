@@ -1,29 +1,14 @@
-"""Test helper: the CPU restatement of rtpbr_reproject_scene's gather (tests/reproject_scene_ref/reproject_scene_ref.c), built on
-demand the way tests/reproject_ref_lib.py builds its library (the oracle's flags, hidden visibility, -Bsymbolic: only rs_*
-exported).
+"""Test helper: the CPU restatement of rtpbr_reproject_scene's gather (rs_* of tests/post_ref/gather.h), built on demand by
+ref_build.
 
 The old and new features come from feature_ref_lib.features() of the old and the new scene."""
-import ctypes as C
-
 import numpy as np
 
-from raytracingpbr_amd.dataclass import Camera, ReprojectParams, SDFObject
+from raytracingpbr_amd.dataclass import ReprojectParams, SDFObject
 from raytracingpbr_amd.scene import Scene
-from ref_build import F, I, Library, P, ptr
+from ref_build import GEOMETRY, POST_REF, camera_of, cfg_ptr, f32, feats_of, objects_of, pick, ptr
 
-_ref = Library("reproject_scene_ref", {
-    "rs_moved": [P, I, I, P, I, I, P],
-    "rs_reproject_scene": [P, P, P, P, I, P, I, I] + [P] * 8 + [F, F, F, P, P, P],
-})
-build, lib = _ref.build, _ref.lib
-
-
-def _cam(c):
-    return c if isinstance(c, Camera) else Camera(*c)
-
-
-def _objs(scene):
-    return (SDFObject * len(scene.objects))(*scene.objects)
+build, lib = POST_REF.build, POST_REF.lib
 
 
 def moved_scene(scene, moves):
@@ -43,12 +28,36 @@ def moved(old_scene, new_scene):
     the old one (what the call refuses with RTPBR_EINVAL)"""
     n0, n1 = len(old_scene.objects), len(new_scene.objects)
     out = np.zeros(max(n0, n1), np.int32)
-    rc = lib().rs_moved(C.cast(_objs(old_scene), C.c_void_p), n0, 1 if old_scene.scale10 else 0, C.cast(_objs(new_scene), C.c_void_p), n1,
-                        1 if new_scene.scale10 else 0, ptr(out))
+    t0, t1 = objects_of(old_scene), objects_of(new_scene)
+    rc = lib().rs_moved(cfg_ptr(t0), n0, 1 if old_scene.scale10 else 0, cfg_ptr(t1), n1, 1 if new_scene.scale10 else 0, ptr(out))
     if rc == -1:
         return None
     assert rc == 0, rc
     return out[:n0].astype(bool)
+
+
+def scene_gather(fn, cfg, old_scene, new_scene, old_camera, new_camera, image_buffer, rider, old_feats, new_feats, max_history,
+                 depth_tolerance, normal_cos):
+    """(image_buffer (W,H,4), motion (W,H,2), rider (W,H,4) or None) of ``fn``: rs_reproject_scene with the moments, or hm_gather
+    with half A, riding along (None = the library default for a parameter; new_camera None = the camera stays)"""
+    d = pick(ReprojectParams.DEFAULTS)
+    W, H = cfg.width, cfg.height
+    ib = f32(image_buffer)
+    M = None if rider is None else f32(rider)
+    assert ib.shape == (W, H, 4) and (M is None or M.shape == (W, H, 4))
+    o, n = feats_of(old_feats, GEOMETRY), feats_of(new_feats, GEOMETRY)
+    assert len(old_scene.objects) == len(new_scene.objects)
+    out = np.empty((W, H, 4), np.float32)
+    motion = np.empty((W, H, 2), np.float32)
+    mo = None if M is None else np.empty((W, H, 4), np.float32)
+    c0 = camera_of(old_camera)
+    c1 = c0 if new_camera is None else camera_of(new_camera)
+    t0, t1 = objects_of(old_scene), objects_of(new_scene)
+    rc = fn(cfg_ptr(cfg), cfg_ptr(c0), cfg_ptr(c1), cfg_ptr(t0), 1 if old_scene.scale10 else 0, cfg_ptr(t1), 1 if new_scene.scale10 else 0,
+            len(old_scene.objects), ptr(ib), ptr(M), *map(ptr, o), *map(ptr, n), float(d(max_history, "max_history")),
+            float(d(depth_tolerance, "depth_tolerance")), float(d(normal_cos, "normal_cos")), ptr(out), ptr(motion), ptr(mo))
+    assert rc == 0, rc
+    return out, motion, mo
 
 
 def reproject_scene(cfg, old_scene, new_scene, old_camera, new_camera, image_buffer, old_feats, new_feats, moments=None, max_history=None,
@@ -56,27 +65,5 @@ def reproject_scene(cfg, old_scene, new_scene, old_camera, new_camera, image_buf
     """(image_buffer (W,H,4), motion (W,H,2), moments (W,H,4) or None) — what rtpbr_reproject_scene writes, from the old
     image_buffer (and the old moments when the context tracks noise) and the features of the old and the new scene (dicts as
     feature_ref_lib.features() returns them; None = the library default for a parameter; new_camera None = the camera stays)."""
-    d = ReprojectParams.DEFAULTS
-    pick = lambda v, k: d[k] if v is None else v      # noqa: E731
-    W, H = cfg.width, cfg.height
-    ib = np.ascontiguousarray(image_buffer, dtype=np.float32)
-    assert ib.shape == (W, H, 4)
-    M = None if moments is None else np.ascontiguousarray(moments, dtype=np.float32)
-    assert M is None or M.shape == (W, H, 4)
-    o = {k: np.ascontiguousarray(old_feats[k]) for k in ("normal", "depth", "object")}
-    n = {k: np.ascontiguousarray(new_feats[k]) for k in ("normal", "depth", "object")}
-    assert o["object"].dtype == np.int32 and n["object"].dtype == np.int32
-    assert len(old_scene.objects) == len(new_scene.objects)
-    out = np.empty((W, H, 4), np.float32)
-    motion = np.empty((W, H, 2), np.float32)
-    mo = None if M is None else np.empty((W, H, 4), np.float32)
-    c0 = _cam(old_camera)
-    c1 = c0 if new_camera is None else _cam(new_camera)
-    rc = lib().rs_reproject_scene(C.cast(C.pointer(cfg), C.c_void_p), C.cast(C.pointer(c0), C.c_void_p), C.cast(C.pointer(c1), C.c_void_p),
-                                  C.cast(_objs(old_scene), C.c_void_p), 1 if old_scene.scale10 else 0, C.cast(_objs(new_scene), C.c_void_p),
-                                  1 if new_scene.scale10 else 0, len(old_scene.objects), ptr(ib), ptr(M), ptr(o["normal"]), ptr(o["depth"]),
-                                  ptr(o["object"]), ptr(n["normal"]), ptr(n["depth"]), ptr(n["object"]),
-                                  float(pick(max_history, "max_history")), float(pick(depth_tolerance, "depth_tolerance")),
-                                  float(pick(normal_cos, "normal_cos")), ptr(out), ptr(motion), ptr(mo))
-    assert rc == 0, rc
-    return out, motion, mo
+    return scene_gather(lib().rs_reproject_scene, cfg, old_scene, new_scene, old_camera, new_camera, image_buffer, moments, old_feats,
+                        new_feats, max_history, depth_tolerance, normal_cos)

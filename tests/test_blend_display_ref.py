@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_blend_error_display (tests/blend_error_ref/blend_error_ref.c with display set) that the GPU tests hold
+"""CPU tier: the restatement of rtpbr_blend_error_display (tests/post_ref/blend.h with display set) that the GPU tests hold
 the kernels to — the header's mirrors, the identities with rtpbr_denoise_error's and rtpbr_blend_error's restatements, known
 answers of the per-tap rule, the defect of the per-window rule it repairs, and the calibration of the estimate against the
 empirical error on the oracle."""

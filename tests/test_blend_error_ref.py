@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_blend_error (tests/blend_error_ref/blend_error_ref.c) that the GPU tests hold the kernels to
+"""CPU tier: the restatement of rtpbr_blend_error (tests/post_ref/blend.h) that the GPU tests hold the kernels to
 — the header's mirrors, the identity with rtpbr_denoise_error's restatement, known answers of the rule, and the calibration of
 the estimate against the empirical error on the oracle."""
 import os

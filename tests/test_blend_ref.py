@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_denoise_blend (tests/blend_ref/blend_ref.c) that the GPU tests hold the kernels to — its
+"""CPU tier: the restatement of rtpbr_denoise_blend (tests/post_ref/blend.h) that the GPU tests hold the kernels to — its
 filter against feature_ref's, known answers of the rule, and the measurement behind the rule's defaults on the oracle (DESIGN.md
 section 6l)."""
 import os

@@ -1,4 +1,4 @@
-"""CPU tier: the reference of the first-hit features and the a-trous denoise (tests/feature_ref/feature_ref.c) that the GPU
+"""CPU tier: the reference of the first-hit features and the a-trous denoise (tests/post_ref/features.h, filter.h) that the GPU
 tests hold rtpbr_render_features / rtpbr_denoise to."""
 import os
 import re

@@ -1,5 +1,5 @@
 """The bias-aware blend of the denoised and the raw frame on the GPU (rtpbr_denoise_blend, Renderer.denoise_blend).  Every comparison
-is ``==`` on bit patterns against the CPU restatement (tests/blend_ref/blend_ref.c) fed with the GPU's own image_buffer, half A and
+is ``==`` on bit patterns against the CPU restatement (tests/post_ref/blend.h) fed with the GPU's own image_buffer, half A and
 features; plus the buffer lifetime, state and error rules of include/rtpbr.h."""
 import ctypes as C
 

@@ -1,6 +1,6 @@
 """The error estimate of the level-blended frame with the bias in display space per tap, on the GPU (rtpbr_blend_error_display,
 Renderer.blend_error(bias="display"), Renderer.render_adaptive_denoised(stop="blend", bias="display")).  Every comparison is
-``==`` on bit patterns against the CPU restatement (tests/blend_error_ref/blend_error_ref.c with display set) fed with the GPU's
+``==`` on bit patterns against the CPU restatement (tests/post_ref/blend.h with display set) fed with the GPU's
 own image_buffer, half A and features; plus what the call shares with rtpbr_blend_error (the plane) and what it does not
 (anything else), and the state and error rules of include/rtpbr.h.  Shapes and states are those of
 tests/test_gpu_blend_error.py (tests/blend_error_states.py)."""

@@ -1,6 +1,6 @@
 """The error estimate of the level-blended frame on the GPU (rtpbr_blend_error, rtpbr_select_blend_error,
 Renderer.render_adaptive_denoised(stop="blend")).  Every comparison is ``==`` on bit patterns against the CPU restatement
-(tests/blend_error_ref/blend_error_ref.c) fed with the GPU's own image_buffer, half A and features; plus the buffer lifetime,
+(tests/post_ref/blend.h) fed with the GPU's own image_buffer, half A and features; plus the buffer lifetime,
 state and error rules of include/rtpbr.h."""
 import ctypes as C
 

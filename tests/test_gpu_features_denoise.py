@@ -1,5 +1,5 @@
 """First-hit feature buffers and the edge-aware a-trous denoise on the GPU (rtpbr_render_features, rtpbr_denoise), held bit for
-bit to the CPU reference tests/feature_ref/feature_ref.c, plus the buffer lifetime, ordering and error rules of include/rtpbr.h."""
+bit to the CPU reference tests/post_ref/features.h, filter.h, plus the buffer lifetime, ordering and error rules of include/rtpbr.h."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """The two-half error estimate of the denoised frame on the GPU (rtpbr_half_update, rtpbr_denoise_error, rtpbr_select_error,
 Renderer.render_adaptive_denoised).  Every comparison is ``==`` on bit patterns against the CPU restatement
-(tests/half_ref/half_ref.c, with the two filter runs through tests/feature_ref/feature_ref.c) fed with the GPU's own
+(tests/half_ref/half_ref.c, with the two filter runs through tests/post_ref/features.h, filter.h) fed with the GPU's own
 image_buffer and features; plus the buffer lifetime, state and error rules of include/rtpbr.h."""
 import ctypes as C
 

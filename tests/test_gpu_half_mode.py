@@ -1,6 +1,6 @@
 """rtpbr_set_half_mode on the GPU: halves dealt per sample inside the accumulate pass (per_sample) and half A carried through
 rtpbr_reproject / rtpbr_reproject_scene (warp).  Every comparison is ``==`` on bit patterns against the CPU restatement
-(tests/half_mode_ref/half_mode_ref.c) — the fold fed with the per-sample colours of the unchanged CPU oracle, the gather with the
+(tests/post_ref/half_mode.h, gather.h) — the fold fed with the per-sample colours of the unchanged CPU oracle, the gather with the
 GPU's own buffers and features — and against a twin renderer with the mode off; plus the state, lifetime and error rules of
 include/rtpbr.h."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """The bias-aware blend across the a-trous levels on the GPU (rtpbr_denoise_blend_levels, Renderer.denoise_blend_levels).  Every
-comparison is ``==`` on bit patterns against the CPU restatement (tests/levels_ref/levels_ref.c) fed with the GPU's own
+comparison is ``==`` on bit patterns against the CPU restatement (tests/post_ref/blend.h) fed with the GPU's own
 image_buffer, half A and features; plus the buffer lifetime, state and error rules of include/rtpbr.h."""
 import ctypes as C
 

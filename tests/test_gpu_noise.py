@@ -1,5 +1,5 @@
 """Noise estimation and the variance-guided a-trous on the GPU (rtpbr_noise_update, rtpbr_noise_estimate, rtpbr_denoise_guided,
-the moment warp of rtpbr_reproject), held bit for bit to the CPU restatement tests/noise_ref/noise_ref.c, plus the state and
+the moment warp of rtpbr_reproject), held bit for bit to the CPU restatement tests/post_ref/noise.h, filter.h, plus the state and
 error rules of include/rtpbr.h and Renderer.render_until."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""Temporal reuse on the GPU (rtpbr_reproject): the gather held bit for bit to the CPU restatement tests/reproject_ref/reproject_ref.c,
+"""Temporal reuse on the GPU (rtpbr_reproject): the gather held bit for bit to the CPU restatement tests/post_ref/gather.h,
 the oracle continuing from a reprojected image_buffer, the state and error rules of include/rtpbr.h, and the quality gain over
 refreshing on a moving camera."""
 import math

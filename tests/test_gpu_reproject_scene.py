@@ -1,5 +1,5 @@
 """Temporal reuse across rigid object motion on the GPU (rtpbr_reproject_scene): the gather held bit for bit to the CPU restatement
-tests/reproject_scene_ref/reproject_scene_ref.c, an unmoved table held to rtpbr_reproject itself, the oracle continuing from the
+tests/post_ref/gather.h, an unmoved table held to rtpbr_reproject itself, the oracle continuing from the
 warped image_buffer, the state and error rules of include/rtpbr.h, one call sequence over the stateful stages, and the quality
 gain over refreshing while a box slides and turns.
 

@@ -1,4 +1,4 @@
-"""rtpbr_set_half_mode on the CPU (tests/half_mode_ref/half_mode_ref.c): known answers of the per-sample dealing, its tie to
+"""rtpbr_set_half_mode on the CPU (tests/post_ref/half_mode.h, gather.h): known answers of the per-sample dealing, its tie to
 rtpbr_half_update's rule, the gather of half A (snap, A'.w <= b'.w under the cap, pixels without taps), the calibration of the
 two-half estimate right after a camera move with half A warped, and the header / library / binding.
 
@@ -57,9 +57,11 @@ def _moved(cam, frac, forward=0.0):
 
 # ------------------------------------------------------------------ the library and the interface
 def test_reference_builds_and_exports_only_hm():
+    """the library hm_* lives in exports its entry points and nothing of the oracle it includes, so that it never interposes with
+    oracle/librt_oracle.so"""
     out = subprocess.run(["nm", "-D", "--defined-only", hm.build()], check=True, capture_output=True, text=True).stdout
     names = sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
-    assert names == ["hm_fold", "hm_gather"], names
+    assert names == sorted(hm.POST_REF.functions) and len(names) == 16 and {"hm_fold", "hm_gather"} <= set(names), names
 
 
 def test_header_library_and_binding_agree():

@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_denoise_blend_levels (tests/levels_ref/levels_ref.c) that the GPU tests hold the kernels to —
+"""CPU tier: the restatement of rtpbr_denoise_blend_levels (tests/post_ref/blend.h) that the GPU tests hold the kernels to —
 its ladder of filters against blend_ref's filter, known answers of the rule, hostile buffers, and the measurement behind the rule
 on the oracle."""
 import os

@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of the noise estimate and the variance-guided a-trous (tests/noise_ref/noise_ref.c) that the GPU
+"""CPU tier: the restatement of the noise estimate and the variance-guided a-trous (tests/post_ref/noise.h, filter.h) that the GPU
 tests hold the kernels to, checked against what include/rtpbr.h promises and — the estimator's calibration — against the oracle."""
 import os
 import re

@@ -1,5 +1,5 @@
 """CPU tier of the pooled noise estimator (rtpbr_set_noise_estimator): the restatement tests/pool_ref/pool_ref.c that the GPU
-tests hold the kernel to, checked against today's estimate (noise_ref.c), against hand-computed answers, against what
+tests hold the kernel to, checked against today's estimate (tests/post_ref/noise.h), against hand-computed answers, against what
 include/rtpbr.h declares and — the point of the feature — in an adaptive loop driven on the oracle."""
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_reproject's gather (tests/reproject_ref/reproject_ref.c) that the GPU tests hold the
+"""CPU tier: the restatement of rtpbr_reproject's gather (tests/post_ref/gather.h) that the GPU tests hold the
 kernel to, checked against what the header promises: an unchanged camera reproduces the buffer, a one-pixel pan shifts it by one
 pixel, disoccluded pixels start from nothing and the cap scales sums and counts together."""
 import os

@@ -1,4 +1,4 @@
-"""CPU tier: the restatement of rtpbr_reproject_scene's gather (tests/reproject_scene_ref/reproject_scene_ref.c) that the GPU tests
+"""CPU tier: the restatement of rtpbr_reproject_scene's gather (tests/post_ref/gather.h) that the GPU tests
 hold the kernel to, checked against what the header promises: with no moved object it is rtpbr_reproject's restatement bit for
 bit, a box slid by k pixel widths carries its history k pixels along while everything else stays put, and the rigidity rule."""
 import ctypes as C

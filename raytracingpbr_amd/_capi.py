@@ -12,7 +12,7 @@ import ctypes as C
 import os
 
 from .config import Config
-from .dataclass import BlendParams, Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, ReprojectParams, SDFObject
+from .dataclass import BlendParams, Camera, Counters, CoverageParams, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, ReprojectParams, SDFObject
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RTPBR_HIP_LIB overrides the path (A/B of differently built HIP libraries); it must still be a HIP build
@@ -30,12 +30,14 @@ ENTRY_POINTS = [
     "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
     "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode", "denoise_blend",
     "denoise_blend_levels", "blend_error", "select_blend_error", "blend_error_display",
+    "render_coverage", "denoise_coverage", "read_coverage",
 ]
 # entry points newer than some libraries CApi drives (a CApi over a library without them simply lacks them: has() says so)
 ALWAYS_OPTIONAL = ("render_features", "denoise", "reproject", "noise_update", "noise_estimate", "denoise_guided",
                    "select_mask", "select_noisy", "sample_selected", "set_noise_estimator", "present", "reproject_scene",
                    "set_noise_tracking", "half_update", "denoise_error", "select_error", "set_half_mode", "denoise_blend",
-                   "denoise_blend_levels", "blend_error", "select_blend_error", "blend_error_display")
+                   "denoise_blend_levels", "blend_error", "select_blend_error", "blend_error_display",
+                   "render_coverage", "denoise_coverage", "read_coverage")
 
 
 class RtpbrError(RuntimeError):
@@ -117,6 +119,9 @@ class CApi:
             "select_blend_error": (C.c_int, [p, C.c_float, C.c_int, C.POINTER(C.c_uint32)]),
             "blend_error_display": (C.c_int, [p, C.POINTER(DenoiseParams), C.POINTER(BlendParams), C.POINTER(ErrorParams), C.c_float,
                                               C.POINTER(NoiseStats)]),
+            "render_coverage": (C.c_int, [p, C.POINTER(CoverageParams)]),
+            "denoise_coverage": (C.c_int, [p, C.POINTER(DenoiseParams), C.POINTER(CoverageParams), C.POINTER(NoiseStats)]),
+            "read_coverage": (C.c_int, [p, p, C.c_size_t]),
         }
         self.fn = {}
         for name, (res, args) in sig.items():

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rt_ctx.hpp"
+#include "rt_coverage.hpp"
 #include "rt_features.hpp"
 #include "rt_reproject.hpp"
 #include "rt_noise.hpp"
@@ -146,7 +147,7 @@ static void frame_free(rtpbr_ctx* c, unsigned groups) {
     }
     RT_FRAME_BUFFERS(X)
 #undef X
-    if (groups & FRAME_FEATURES) c->feat_valid = false;
+    if (groups & FRAME_FEATURES) c->feat_valid = c->cov_valid = false;
     if (groups & FRAME_SELECTION) {
         c->sel_count = 0;
         c->have_selection = false;
@@ -1487,6 +1488,7 @@ extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
     launch_features(P, A, c->kind, c->stream);
     HIP_TRY(hipGetLastError());
     c->feat_valid = true;
+    c->cov_valid = false;      // (built from the features that were)
     return RTPBR_OK;
 }
 
@@ -1531,15 +1533,17 @@ static DenoiseArgs denoise_args(rtpbr_ctx* c, int demodulate, const float* inv) 
 // the two planes of noise_var behind the estimate's (plane 0).  No level: the tone-map-only pass, the same for both.
 // in / out (rtpbr_denoise_error, rtpbr_denoise_blend): the filter of another (sum r, sum g, sum b, count) buffer into another
 // display buffer; the caller has allocated the ping-pong.  linear (plain filter, with out): the last level stops before the tone
-// map and out takes the linear colour after remodulation.
+// map and out takes the linear colour after remodulation.  cover_k (rtpbr_denoise_coverage; plain, linear, iterations > 0): the
+// coverage-weighted levels.
 static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
-                          const float4* in = nullptr, float* out = nullptr, bool linear = false) {
+                          const float4* in = nullptr, float* out = nullptr, bool linear = false, const float* cover_k = nullptr) {
     if (!out)
         if (int r = denoised_alloc(c, iterations)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     DenoiseArgs A = denoise_args(c, demodulate, inv);
     A.image_buffer = in ? in : c->image_buffer;
     A.out = out ? out : c->denoised;
+    if (cover_k) A.cover_k = cover_k;      // (shares var0's word: never with g)
     if (g) {
         A.var0 = c->noise_var;
         A.sc2 = g->sigma_color * g->sigma_color;
@@ -1557,7 +1561,7 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
             A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
         }
         A.step = 1 << k;
-        launch_atrous_level(A, first, last, g != nullptr, c->stream, linear && last);
+        launch_atrous_level(A, first, last, g != nullptr, c->stream, linear && last, cover_k != nullptr);
     }
     HIP_TRY(hipGetLastError());
     return RTPBR_OK;
@@ -1592,6 +1596,124 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
     return denoise_levels(c, d.iterations, d.demodulate, inv, nullptr);
+}
+
+// ---- sub-pixel coverage and the coverage-aware denoise (rt_coverage.hip)
+
+// v (NULL: the defaults) -> d, after the parameter checks of the two coverage calls
+static int coverage_params(const rtpbr_coverage_params* v, rtpbr_coverage_params& d) {
+    static_assert(sizeof(rtpbr_coverage_params) == 12, "three 4-byte members");
+    d = v ? *v : rtpbr_coverage_params{RTPBR_COVERAGE_DEFAULT_GRID, RTPBR_COVERAGE_DEFAULT_POWER, RTPBR_COVERAGE_DEFAULT_RESOLVE};
+    if (d.grid != 2 && d.grid != 4) return fail(RTPBR_EINVAL, "coverage grid must be 2 or 4");
+    if (d.power < 0 || d.power > 8) return fail(RTPBR_EINVAL, "coverage power must be 0..8");
+    if (d.resolve != 0 && d.resolve != 1) return fail(RTPBR_EINVAL, "coverage resolve must be 0 or 1");
+    return RTPBR_OK;
+}
+
+static CoverageArgs coverage_args(rtpbr_ctx* c, const rtpbr_coverage_params& d) {
+    CoverageArgs A{};
+    A.object = c->feat_object;
+    A.coverage = c->coverage;
+    A.list = c->cov_list;
+    A.k = c->cov_k;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    A.grid = d.grid;
+    A.power = d.power;
+    return A;
+}
+
+// The coverage plane at grid d.grid on the stream, unless it is there already; after whole_frame_state; sets the device.  The sub-rays are the feature
+// rays of the g-fold configuration: rtpbr_render_features' Params with that width, height and their reciprocals.
+static int coverage_enqueue(rtpbr_ctx* c, const rtpbr_coverage_params& d) {
+    if ((long long)d.grid * c->cfg.width > 65535 || (long long)d.grid * c->cfg.height > 65535)
+        return fail(RTPBR_EINVAL, "coverage: grid x resolution out of range (1..65535)");
+    if (int r = set_dev(c)) return r;
+    if (!c->feat_valid)
+        if (int r = rtpbr_render_features(c)) return r;
+    if (c->cov_valid && c->cov_rendered_grid == d.grid) return RTPBR_OK;
+    if (int r = frame_need(c, {ROW_coverage, ROW_cov_list})) return r;
+    Params P = c->P;
+    P.cfg = c->cfg;
+    P.cfg.width = d.grid * c->cfg.width;
+    P.cfg.height = d.grid * c->cfg.height;
+    P.cam.inv_w = 1.0f / (float)P.cfg.width;
+    P.cam.inv_h = 1.0f / (float)P.cfg.height;
+    P.n_obj = c->n_obj;
+    P.box_sig = 0;
+    P.box_lazy = 0;
+    pack_table(c->objm, c->n_obj, 0, P.objm);
+    P.objfull = c->objfull;
+    P.bunny = c->bunny;
+    const CoverageArgs A = coverage_args(c, d);
+    HIP_TRY(hipMemsetAsync(c->cov_list, 0, COVER_HEAD * sizeof(uint32_t), c->stream));
+    launch_cover_mark(A, c->stream);
+    launch_cover_rays(P, A, c->kind, c->n_cu, c->cover_blocks, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->cov_valid = true;
+    c->cov_rendered_grid = d.grid;
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_render_coverage(rtpbr_ctx* c, const rtpbr_coverage_params* v) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_coverage_params d;
+    if (int r = coverage_params(v, d)) return r;
+    if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
+    return coverage_enqueue(c, d);
+}
+
+extern "C" int rtpbr_denoise_coverage(rtpbr_ctx* c, const rtpbr_denoise_params* p, const rtpbr_coverage_params* v, rtpbr_noise_stats* out) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    rtpbr_denoise_params d;
+    rtpbr_coverage_params cv;
+    float inv[4];
+    if (int r = denoise_params(p, d, inv)) return r;
+    if (int r = coverage_params(v, cv)) return r;
+    if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
+    if (int r = coverage_enqueue(c, cv)) return r;
+    if (int r = frame_need(c, {ROW_cov_k, ROW_cov_linear})) return r;
+    // the weights and the frame's largest 1 - a; the resolved count starts at 0 (the list's length stays)
+    HIP_TRY(hipMemsetAsync(c->cov_list + 1, 0, 2 * sizeof(uint32_t), c->stream));
+    launch_cover_weights(coverage_args(c, cv), c->stream);
+    if (d.iterations == 0) {      // rtpbr_denoise's tone-map-only pass
+        if (int r = denoise_levels(c, 0, d.demodulate, inv, nullptr)) return r;
+    } else {
+        if (int r = denoised_alloc(c, d.iterations)) return r;
+        if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->cov_linear, true, c->cov_k)) return r;
+        ResolveArgs R{};
+        R.cfg = c->cfg;
+        R.image_buffer = c->image_buffer;
+        R.linear = c->cov_linear;
+        R.object = c->feat_object;
+        R.coverage = c->coverage;
+        R.k = c->cov_k;
+        R.head = c->cov_list;
+        R.out = c->denoised;
+        R.width = c->cfg.width;
+        R.height = c->cfg.height;
+        R.resolve = cv.resolve;
+        launch_cover_resolve(R, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!out) return RTPBR_OK;
+    uint32_t head[COVER_HEAD];
+    HIP_TRY(hipMemcpyAsync(head, c->cov_list, sizeof head, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->pixels_estimated = head[1];
+    out->pixels_above = head[0];
+    memcpy(&out->max_noise, &head[2], sizeof(float));
+    return RTPBR_OK;
+}
+
+extern "C" int rtpbr_read_coverage(rtpbr_ctx* c, void* dst, size_t nbytes) {
+    if (!c || !c->have_cfg) return fail(RTPBR_ESTATE, "set_config first");
+    if (!c->coverage) return fail(RTPBR_ESTATE, "no coverage yet: call rtpbr_render_coverage / rtpbr_denoise_coverage first");
+    if (!dst || nbytes != (size_t)c->cfg.width * c->cfg.height * sizeof(int4)) return fail(RTPBR_EINVAL, "destination size does not match the coverage plane");
+    if (int r = set_dev(c)) return r;
+    HIP_TRY(hipMemcpyAsync(dst, c->coverage, nbytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTPBR_OK;
 }
 
 // ---- temporal reuse (rt_reproject.hip): rtpbr_set_camera + rtpbr_refresh that keeps what the new view can reuse
@@ -2606,6 +2728,7 @@ static const OptionRow OPTION_ROWS[] = {
     OPTION(heavy_mean_x16, 0, 1 << 20, false, "heavy_mean_x16 must be 0 .. 2^20"),
     OPTION(heavy_bulk_x16, 0, 1 << 20, false, "heavy_bulk_x16 must be 0 .. 2^20"),
     OPTION(grid_blocks, 0, 65535, false, "grid_blocks must be 0 (automatic) .. 65535"),
+    OPTION(cover_blocks, 0, 65535, false, "cover_blocks must be 0 (automatic) .. 65535"),
     OPTION(ready_low, 0, 63, false, "ready_low must be 0..63"),
     OPTION(refill_lanes, 1, 64, false, "refill_lanes must be 1..64"),
     // 1 (default): rtpbr_sample() brackets its kernels with events (rtpbr_last_sample_ms / rtpbr_last_primary_ms); 0: none — an event

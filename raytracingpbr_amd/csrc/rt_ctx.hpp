@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_coverage.hpp"
 #include "rt_device.hpp"
 #include "rt_half.hpp"
 #include "rt_noise.hpp"
@@ -122,6 +123,11 @@ constexpr int FRAME_PRIVATE = -1;
     X(feat_guides, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                /* (normal, depth), the record an a-trous tap reads */ \
     X(denoised, float, np * 12, FRAME_FEATURES, false, RTPBR_BUF_DENOISED_PIXELS, false)        /* (W,H,3) */                                      \
     X(denoise_scratch, float4, np * 32, FRAME_FEATURES, false, FRAME_PRIVATE, false)            /* 2 x (W,H): the levels' ping-pong, from two levels on */ \
+    /* sub-pixel coverage (rt_coverage.hip): rtpbr_render_coverage, rtpbr_denoise_coverage; freeing the group clears cov_valid */                  \
+    X(coverage, int4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                     /* (n_own, second_object, n_second, n_sub): rtpbr_read_coverage */ \
+    X(cov_list, uint32_t, (np + rt::COVER_HEAD) * 4, FRAME_FEATURES, false, FRAME_PRIVATE, false) /* the head (length, resolved, bits of max 1 - a, 0), then the candidates' buffer indices */ \
+    X(cov_k, float, np * 4, FRAME_FEATURES, false, FRAME_PRIVATE, false)                        /* rtpbr_denoise_coverage: k, the weight of the pixel as a tap */ \
+    X(cov_linear, float, np * 12, FRAME_FEATURES, false, FRAME_PRIVATE, false)                  /* ... (W,H,3): the filter's linear colour, what the resolve reads */ \
     /* temporal reuse (rt_reproject.hip): rtpbr_reproject, rtpbr_reproject_scene */                                                                \
     X(hist_image, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                 /* image_buffer before the move */                 \
     X(hist_guides, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                /* the old camera's (normal, depth) records */     \
@@ -275,6 +281,8 @@ struct rtpbr_ctx {
     uint32_t* march_out = nullptr;     // np x u32 (wavefront split, rt_split.hpp); sized with cost_buffer
     // the state that goes with the frame buffers' groups
     bool feat_valid = false;           // the features describe the current scene, camera, configuration and shape data
+    bool cov_valid = false;            // the coverage describes the features as they are (meaningful while feat_valid), at grid cov_rendered_grid
+    int cov_rendered_grid = 0;                       // the grid the coverage plane was rendered at
     bool history_ok = false;           // no set_config / set_scene / set_shape_data / set_env since the last refresh or reproject
     rt::NoiseStats* noise_stats = nullptr;
     int noise_tracking = RTPBR_NOISE_TRACK_OFF;      // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
@@ -311,6 +319,7 @@ struct rtpbr_ctx {
     bool order_valid = false;
     long long cost_steps = 0;          // bounce-steps recorded in cost_buffer since the last plan
     int grid_blocks = 0;          // src/ form, pool scheduler: workgroups to launch (0 = automatic); tuning / test knob
+    int cover_blocks = 0;         // the sub-ray kernel of rtpbr_render_coverage: workgroups to launch (0 = automatic: eight per CU); tuning / test knob
     int swap_lanes = 0;           // 0 = automatic: 8 in the complete-path pool kernel, 12 in the src/ pool kernel (measured: rt_capi.hip)
     int mlp_lanes = 24;
     int mlp_full = 56;

@@ -105,9 +105,12 @@ constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pix
 // 4 more bytes per tap taken (40 / 36), one more 4-byte record written.
 // LINEAR (last level only; rtpbr_denoise_blend): out takes the linear colour after remodulation — exactly the value the other
 // form hands to tone_map — and +0 for a pixel without samples.
-template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false>
+// COVER (rtpbr_denoise_coverage; plain, its last level LINEAR): every tap but the centre's is weighted by k_q of the coverage plane
+// (rt_coverage.hpp), w = (h exp_(-min(e, 80))) k_q: 4 more bytes per tap taken.
+template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false, bool COVER = false>
 __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     static_assert(LAST || !LINEAR, "the linear form is a last level");
+    static_assert(!COVER || (!GUIDED && LAST == LINEAR), "the coverage-weighted form is the plain filter, linear at its last level");
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -209,7 +212,9 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
             // (+ |a_p - a_q|^2 ia = + 0: see above)
             // (e is clamped where exp no longer matters: a weight under 2e-35 against the centre's 9/64; far past it the Cephes
             // reduction of exp_ loses its argument and could overflow)
-            const float w = h * exp_(-fmin_(e, 80.0f));
+            float w = h * exp_(-fmin_(e, 80.0f));
+            if constexpr (COVER)
+                if (dx != 0 || dy != 0) w = w * A.cover_k[q];
             sw = sw + w;
             sx = sx + w * cq.x;
             sy = sy + w * cq.y;
@@ -269,9 +274,14 @@ static void launch_level(const DenoiseArgs& A, bool first, bool last, unsigned g
 }
 
 // step 0 (no level) is the iterations = 0 pass of both calls; linear: the plain filter's last level (or that pass) without the tone map
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear) {
+// cover: the coverage-weighted levels of rtpbr_denoise_coverage (step > 0, plain, linear exactly at the last level)
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear, bool cover) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (A.step == 0 && linear) hipLaunchKernelGGL(atrous_none<true>, dim3(grid), dim3(256), 0, st, A);
+    if (cover && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover && last) hipLaunchKernelGGL((atrous_level<false, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover) hipLaunchKernelGGL((atrous_level<false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (A.step == 0 && linear) hipLaunchKernelGGL(atrous_none<true>, dim3(grid), dim3(256), 0, st, A);
     else if (A.step == 0) hipLaunchKernelGGL(atrous_none<false>, dim3(grid), dim3(256), 0, st, A);
     else if (linear && first) hipLaunchKernelGGL((atrous_level<true, true, false, true>), dim3(grid), dim3(256), 0, st, A);
     else if (linear) hipLaunchKernelGGL((atrous_level<false, true, false, true>), dim3(grid), dim3(256), 0, st, A);

@@ -15,6 +15,7 @@
 //                        variance (rt_noise.hip's estimate at level 0) is filtered along with the squared weights; it travels
 //                        in a record of its own, 4 bytes, loaded only on taps that pass the object test.
 //   atrous_none          iterations = 0 of either call: the average, tone-mapped.
+//   COVER (rtpbr_denoise_coverage): the plain filter with every tap but the centre's weighted by the tap's coverage (rt_coverage.hpp).
 //   The last level and atrous_none have a LINEAR form (rtpbr_denoise_blend): the colour before the tone map goes to `out`.
 //   rtpbr_denoise_blend_levels reads the non-last levels' records themselves: level k's (colour, object index) is the filter with
 //   iterations = k before remodulation (level_blend, rt_half.hip).
@@ -49,8 +50,11 @@ struct DenoiseArgs {
     int32_t step;                 // 2^k
     int32_t demodulate;
     int32_t width, height;
-    // the guided instances only
-    const float* var0;            // level 0: v of noise_estimate (-1: no samples)
+    // the guided instances only (the coverage-weighted ones are plain: their plane shares var0's word, the layout stays as it was)
+    union {
+        const float* var0;        // level 0: v of noise_estimate (-1: no samples)
+        const float* cover_k;     // COVER (rtpbr_denoise_coverage, rt_coverage.hpp): (W,H) k = (n_own / S)^power, the weight of the pixel as somebody's tap
+    };
     const float* vsrc;            // levels > 0: the previous level's variance
     float* vdst;                  // every level but the last
     float sc2;                    // sigma_color * sigma_color
@@ -61,6 +65,7 @@ struct DenoiseArgs {
 RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), c.z / (1.0f + c.z)); }
 
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear = false);      // linear: last && !guided
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear = false,
+                         bool cover = false);      // linear: last && !guided; cover: !guided, linear == last, A.step > 0
 
 }  // namespace rt

@@ -106,6 +106,15 @@ class DenoiseParams(_Pod):
     DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 2.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "sigma_albedo": 0.1}
 
 
+class CoverageParams(_Pod):
+    """rtpbr_coverage_params (include/rtpbr.h): the sub-ray grid of rtpbr_render_coverage, and the tap-weight power and the edge
+    resolve of rtpbr_denoise_coverage."""
+    _fields_ = [("grid", C.c_int32), ("power", C.c_int32), ("resolve", C.c_int32)]
+
+    # include/rtpbr.h RTPBR_COVERAGE_DEFAULT_*, what the two calls use for NULL (tests/test_coverage_ref.py keeps the two equal)
+    DEFAULTS = {"grid": 4, "power": 4, "resolve": 1}
+
+
 class ReprojectParams(_Pod):
     """rtpbr_reproject_params (include/rtpbr.h): the history cap and the depth and normal tests of a reprojection tap."""
     _fields_ = [("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float)]

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .config import FORM, Config
-from .dataclass import BlendParams, Camera, Counters, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
+from .dataclass import BlendParams, Camera, Counters, CoverageParams, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
 BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
@@ -151,6 +151,33 @@ class Renderer:
         p = DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
                           float(v["sigma_depth"]), float(v["sigma_albedo"]))
         self.api.call("denoise", self._ctx, C.byref(p))
+
+    # ------------------------------------------------------------ coverage-aware denoise (include/rtpbr.h rtpbr_denoise_coverage)
+    def render_coverage(self, grid=None):
+        """Write ``coverage``: for every pixel next to a silhouette, how many of its ``grid`` x ``grid`` sub-rays (2 or 4) hit the
+        pixel's own object and which other object takes most of the rest.  ``None`` = the library's default, 4.  The features
+        are rendered first when stale; a sliver that passes between pixel centres is missed."""
+        d = CoverageParams.DEFAULTS
+        p = CoverageParams(int(d["grid"] if grid is None else grid), d["power"], d["resolve"])
+        self.api.call("render_coverage", self._ctx, C.byref(p))
+
+    def denoise_coverage(self, power=None, resolve=None, grid=None, **denoise) -> NoiseStats:
+        """``denoise`` (same keyword parameters) with every tap weighted by (its pixel's own-object coverage)^``power``, and with
+        the pixels that hold two objects resolved to the mix of the filter's result and the second object's 3x3 mean
+        (``resolve``), into ``denoised_pixels``.  ``None`` = the library's default.  Returns the NoiseStats words as (resolved
+        pixels, candidate pixels, largest 1 - coverage).  Blocks."""
+        unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise_coverage: unknown denoise parameters {sorted(unknown)}")
+        v = {k: denoise.get(k, d) if denoise.get(k) is not None else d for k, d in DenoiseParams.DEFAULTS.items()}
+        p = DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
+                          float(v["sigma_depth"]), float(v["sigma_albedo"]))
+        d = CoverageParams.DEFAULTS
+        cv = CoverageParams(int(d["grid"] if grid is None else grid), int(d["power"] if power is None else power),
+                            int(d["resolve"] if resolve is None else resolve))
+        s = NoiseStats()
+        self.api.call("denoise_coverage", self._ctx, C.byref(p), C.byref(cv), C.byref(s))
+        return s
 
     # ------------------------------------------------------------ temporal reuse (include/rtpbr.h rtpbr_reproject)
     def reproject(self, camera: Camera, max_history=None, depth_tolerance=None, normal_cos=None):
@@ -787,6 +814,13 @@ class Renderer:
     def blend_error_map(self):
         """(W,H): the last blend_error()'s root-mean-square error of each pixel's level-blended luminance, 0 where a half is empty"""
         return self._read(BUF_BLEND_ERROR)
+
+    @property
+    def coverage(self):
+        """(W,H,4) int32 (n_own, second_object, n_second, n_sub) as the last ``render_coverage`` / ``denoise_coverage`` wrote it"""
+        out = np.empty((self.config.width, self.config.height, 4), np.int32)
+        self.api.call("read_coverage", self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return out
 
     def ray_depth(self):
         return self.ray_buffer[..., 9].view(np.int32)

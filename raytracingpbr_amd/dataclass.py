@@ -96,7 +96,24 @@ assert C.sizeof(Ray) == 40 and C.sizeof(Material) == 40 and C.sizeof(Transform) 
 assert C.sizeof(SDFObject) == 116 and C.sizeof(Camera) == 52
 
 
-class DenoiseParams(_Pod):
+class _Params(_Pod):
+    """A parameter struct of a call: ``DEFAULTS`` holds, field by field, what the library uses when it is handed NULL."""
+
+    @classmethod
+    def pack(cls, null_if_default, *values, **given):
+        """The struct filled from ``values`` (in field order) and ``given`` (by name): a field not given, or given as ``None``,
+        takes its DEFAULTS entry, and each goes through int() or float() as its ctypes type says.  ``null_if_default``: ``None``
+        instead of the struct when nothing was given, for the caller that hands the library NULL then."""
+        given = {**dict(zip(cls.DEFAULTS, values)), **given}
+        unknown = set(given) - set(cls.DEFAULTS)
+        if unknown or len(values) > len(cls.DEFAULTS):
+            raise TypeError(f"{cls.__name__}: unknown parameters {sorted(unknown) or values[len(cls.DEFAULTS):]}")
+        if null_if_default and all(v is None for v in given.values()):
+            return None
+        return cls(*((float if t is C.c_float else int)(cls.DEFAULTS[k] if given.get(k) is None else given[k]) for k, t in cls._fields_))
+
+
+class DenoiseParams(_Params):
     """rtpbr_denoise_params (include/rtpbr.h): a-trous levels, albedo demodulation and the four edge-stopping sigmas."""
     _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float)]
@@ -106,7 +123,7 @@ class DenoiseParams(_Pod):
     DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 2.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "sigma_albedo": 0.1}
 
 
-class CoverageParams(_Pod):
+class CoverageParams(_Params):
     """rtpbr_coverage_params (include/rtpbr.h): the sub-ray grid of rtpbr_render_coverage, and the tap-weight power and the edge
     resolve of rtpbr_denoise_coverage."""
     _fields_ = [("grid", C.c_int32), ("power", C.c_int32), ("resolve", C.c_int32)]
@@ -115,7 +132,7 @@ class CoverageParams(_Pod):
     DEFAULTS = {"grid": 4, "power": 4, "resolve": 1}
 
 
-class ReprojectParams(_Pod):
+class ReprojectParams(_Params):
     """rtpbr_reproject_params (include/rtpbr.h): the history cap and the depth and normal tests of a reprojection tap."""
     _fields_ = [("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float)]
 
@@ -129,7 +146,7 @@ class NoiseStats(_Pod):
     _fields_ = [("pixels_estimated", C.c_uint32), ("pixels_above", C.c_uint32), ("max_noise", C.c_float)]
 
 
-class NoiseEstimator(_Pod):
+class NoiseEstimator(_Params):
     """rtpbr_noise_estimator (include/rtpbr.h): the optional estimator setting of a context — pooling of the young pixels'
     within-pixel sums of squares over the neighbours on the same object, and a minimum sample count for select_noisy."""
     _fields_ = [("pool_batches", C.c_int32), ("pool_radius", C.c_int32), ("min_samples", C.c_int32)]
@@ -139,7 +156,7 @@ class NoiseEstimator(_Pod):
     DEFAULTS = {"pool_batches": 0, "pool_radius": 3, "min_samples": 0}
 
 
-class ErrorParams(_Pod):
+class ErrorParams(_Params):
     """rtpbr_error_params (include/rtpbr.h): the window of rtpbr_denoise_error's two-half estimate."""
     _fields_ = [("radius", C.c_int32)]
 
@@ -147,7 +164,7 @@ class ErrorParams(_Pod):
     DEFAULTS = {"radius": 2}
 
 
-class BlendParams(_Pod):
+class BlendParams(_Params):
     """rtpbr_blend_params (include/rtpbr.h): the window, the significance gate and the minimum half size of rtpbr_denoise_blend."""
     _fields_ = [("radius", C.c_int32), ("z", C.c_float), ("min_half_samples", C.c_int32)]
 
@@ -155,7 +172,7 @@ class BlendParams(_Pod):
     DEFAULTS = {"radius": 3, "z": 2.0, "min_half_samples": 16}
 
 
-class HalfMode(_Pod):
+class HalfMode(_Params):
     """rtpbr_half_mode (include/rtpbr.h): halves dealt per sample by the sample calls, half A carried through the reprojections."""
     _fields_ = [("per_sample", C.c_int32), ("warp", C.c_int32)]
 
@@ -163,7 +180,7 @@ class HalfMode(_Pod):
     DEFAULTS = {"per_sample": 0, "warp": 0}
 
 
-class DenoiseGuidedParams(_Pod):
+class DenoiseGuidedParams(_Params):
     """rtpbr_denoise_guided_params (include/rtpbr.h): the a-trous whose colour term is measured in standard deviations of the
     pixel's estimated noise."""
     _fields_ = [("iterations", C.c_int32), ("demodulate", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
@@ -174,7 +191,7 @@ class DenoiseGuidedParams(_Pod):
     DEFAULTS = {"iterations": 4, "demodulate": 0, "sigma_color": 16.0, "sigma_normal": 0.3, "sigma_depth": 0.2, "variance_floor": 1e-3}
 
 
-class PresentParams(_Pod):
+class PresentParams(_Params):
     """rtpbr_present_params (include/rtpbr.h): which display buffer becomes the packed 8-bit frame, its pixel format, and
     whether the quantisation is ordered-dithered."""
     _fields_ = [("source", C.c_int32), ("format", C.c_int32), ("dither", C.c_int32)]

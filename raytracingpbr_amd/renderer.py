@@ -8,6 +8,7 @@ kernels ``render(camera_position, camera_lookat, camera_up, moving)``
 ``image_buffer`` (W,H,4) f32 = (sum r,g,b, count), ``image_pixels`` (W,H,3) f32,
 ``ray_buffer`` (W,H) of Ray; index [i, j] = column from the left, row from the bottom.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -17,26 +18,50 @@ from .config import FORM, Config
 from .dataclass import BlendParams, Camera, Counters, CoverageParams, DenoiseGuidedParams, DenoiseParams, ErrorParams, HalfMode, NoiseEstimator, NoiseStats, PresentParams, Ray, ReprojectParams, SDFObject
 from .scene import Scene
 
-BUF_IMAGE_BUFFER, BUF_IMAGE_PIXELS, BUF_RAY_BUFFER, BUF_DIFF_BUFFER, BUF_DIFF_PIXELS = 0, 1, 2, 3, 4
-# first-hit features (render_features) and the denoised display image (denoise); they exist from the first of those calls on
-BUF_FEAT_ALBEDO, BUF_FEAT_NORMAL, BUF_FEAT_DEPTH, BUF_FEAT_OBJECT, BUF_DENOISED_PIXELS = 5, 6, 7, 8, 9
-# old-frame pixel coordinates each pixel's history came from (reproject); exists from the first reproject() on
-BUF_MOTION = 10
-# luminance moments of the batch means (noise_update) and the per-pixel noise map (noise_estimate); they exist from the first of those calls on
-BUF_MOMENTS, BUF_NOISE = 11, 12
-# the pixel selection (select_mask / select_noisy): 1 = sample_selected traces the pixel; exists from the first select call on
-BUF_SELECTION = 13
-# the packed 8-bit frame (present): (H,W,C) uint8, top-down, C = 3 or 4 as the last present() said; exists from the first present() on
-BUF_PRESENT = 14
-# half A of the two-half split (half_update) and the estimated noise of the denoised frame (denoise_error); each exists from the first such call on
-BUF_HALF_BUFFER, BUF_DENOISED_ERROR = 15, 16
-# the weight of the last denoise_blend(): 1 = the denoised colour, 0 = the raw average; exists from the first denoise_blend() on
-BUF_BLEND_WEIGHT = 17
-# how many a-trous levels the last denoise_blend_levels() kept, 0..iterations; exists from the first denoise_blend_levels() on
-BUF_BLEND_DEPTH = 18
-# the estimated root-mean-square error of the level-blended frame's luminance (blend_error); exists from the first blend_error() on
-BUF_BLEND_ERROR = 19
+f32 = np.float32
+# The public buffers (include/rtpbr.h RTPBR_BUF_*), one row each: id, BUF_ name, shape after (W, H), dtype, the Renderer property
+# that reads it, whether Python can also assign to that property, the property's docstring.  Buffers 5 and up exist from the first
+# call that writes them on (the call their docstring names; the features: render_features, denoised_pixels: denoise).
+BUFFERS = [
+    (0, "IMAGE_BUFFER", (4,), f32, "image_buffer", True, None),
+    (1, "IMAGE_PIXELS", (3,), f32, "image_pixels", False, None),
+    (2, "RAY_BUFFER", (10,), f32, "ray_buffer", True, "(W,H,10) float32 view of Ray; the last column holds the int32 depth bit pattern."),
+    (3, "DIFF_BUFFER", (2,), f32, "diff_buffer", False, "adaptive-sampling statistics (src/fileds.py:21): (sum of display change, count)"),
+    (4, "DIFF_PIXELS", (), f32, "diff_pixels", False, None),
+    (5, "FEAT_ALBEDO", (3,), f32, "feature_albedo", False, None),
+    (6, "FEAT_NORMAL", (3,), f32, "feature_normal", False, None),
+    (7, "FEAT_DEPTH", (), f32, "feature_depth", False, None),
+    (8, "FEAT_OBJECT", (), np.int32, "feature_object", False, None),
+    (9, "DENOISED_PIXELS", (3,), f32, "denoised_pixels", False, None),
+    (10, "MOTION", (2,), f32, "motion", False,
+     "(W,H,2): the old-frame pixel coordinates the last reproject() took each pixel's history from, (-1,-1) = none"),
+    (11, "MOMENTS", (4,), f32, "moments", False,
+     "(W,H,4): (sum c L, sum c L^2, sum c, K) over the K batches noise_update() has folded in (with set_noise_tracking(True): "
+     "every sample is a batch, c = 1), c samples each, L the compressed luminance of the batch mean"),
+    (12, "NOISE", (), f32, "noise", False,
+     "(W,H): the last noise_estimate() / denoise_guided()'s standard deviation of each pixel's displayed luminance"),
+    (13, "SELECTION", (), np.uint8, "selection", False, "(W,H) uint8: 1 = selected by the last select_mask() / select_noisy()"),
+    # not a field: top-down, C = 3 or 4 as the last present() said, which the library knows (_shape asks it)
+    (14, "PRESENT", None, np.uint8, "presented", False, "(H, W, C) uint8: the frame of the last present(), top row first (blocking read)"),
+    (15, "HALF_BUFFER", (4,), f32, "half_buffer", False,
+     "(W,H,4): half A's (sum r, sum g, sum b, count) as half_update() dealt it; half B is image_buffer minus this"),
+    (16, "DENOISED_ERROR", (), f32, "denoised_error", False,
+     "(W,H): the last denoise_error()'s standard deviation of each pixel's denoised luminance, 0 where a half is empty"),
+    (17, "BLEND_WEIGHT", (), f32, "blend_weight", False,
+     "(W,H): the last denoise_blend()'s weight of the denoised colour, 1 where the halves are not usable or see no bias"),
+    (18, "BLEND_DEPTH", (), f32, "blend_depth", False,
+     "(W,H): how many a-trous levels the last denoise_blend_levels() kept, 0 (the raw average) .. iterations (the whole filter)"),
+    (19, "BLEND_ERROR", (), f32, "blend_error_map", False,
+     "(W,H): the last blend_error()'s root-mean-square error of each pixel's level-blended luminance, 0 where a half is empty"),
+]
+globals().update({"BUF_" + row[1]: row[0] for row in BUFFERS})      # BUF_IMAGE_BUFFER = 0, ...
+_TAIL_AND_DTYPE = {row[0]: row[2:4] for row in BUFFERS}
 ENV_RGB8, ENV_RGB32F = 0, 1
+
+
+def _ref(struct):
+    """a struct by address, NULL for None"""
+    return None if struct is None else C.byref(struct)
 
 
 class Renderer:
@@ -47,11 +72,11 @@ class Renderer:
         self.device = device
         self.samples_per_frame = 1           # SAMPLES_PER_FRAME, src/config.py:9
         self._host_arrays = {}               # address -> bytes of the page-locked blocks handed out by host_array()
-        self.noise_estimator = NoiseEstimator(**NoiseEstimator.DEFAULTS)      # what set_noise_estimator() last set
+        self.noise_estimator = NoiseEstimator.pack(False)      # what set_noise_estimator() last set
         self.track_noise = False             # True: every sample() call is one batch of the noise estimate (noise_update() after it)
         self.noise_per_sample = False        # what set_noise_tracking() last set: every SAMPLE is a batch, folded in by sample() itself
         self.track_halves = False            # True: every sample() / sample_selected() call is one batch of the two halves (half_update() after it)
-        self.half_mode = HalfMode(**HalfMode.DEFAULTS)      # what set_half_mode() last set
+        self.half_mode = HalfMode.pack(False)      # what set_half_mode() last set
         self.set_config(config)
         self.set_scene(scene)
         self.set_camera(camera if camera is not None else scene.camera)
@@ -134,6 +159,40 @@ class Renderer:
     def sync(self):
         self.api.call("sync", self._ctx)
 
+    def _count(self, name, *args) -> int:
+        """a call whose last argument is the uint32 it counts into"""
+        n = C.c_uint32()
+        self.api.call(name, self._ctx, *args, C.byref(n))
+        return int(n.value)
+
+    def _stats(self, name, *args) -> NoiseStats:
+        """a call whose last argument is the rtpbr_noise_stats it fills"""
+        s = NoiseStats()
+        self.api.call(name, self._ctx, *args, C.byref(s))
+        return s
+
+    @contextlib.contextmanager
+    def _loop_state(self, halves=False, noise_per_sample=False, half_per_sample=False):
+        """What a render loop that folds its batches itself sets for its duration and puts back after, however it ends:
+        ``track_noise`` off (``halves``: and ``track_halves``), per-sample noise tracking or per-sample halves on where asked."""
+        mode, half_mode = self.noise_per_sample, self.half_mode
+        if half_per_sample:
+            self.set_half_mode(True, bool(half_mode.warp))
+        keep = self.track_noise, self.track_halves
+        self.track_noise = False
+        if halves:
+            self.track_halves = False
+        try:
+            if noise_per_sample:
+                self.set_noise_tracking(True)
+            yield
+        finally:
+            self.track_noise, self.track_halves = keep
+            if noise_per_sample:
+                self.set_noise_tracking(mode)
+            if half_per_sample:
+                self.set_half_mode(bool(half_mode.per_sample), bool(half_mode.warp))
+
     # ------------------------------------------------------------ first-hit features and the denoise (include/rtpbr.h)
     def render_features(self):
         """One primary ray through every pixel centre: albedo, shading normal, depth and object index of the first hit."""
@@ -142,24 +201,15 @@ class Renderer:
     def denoise(self, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None):
         """Edge-aware a-trous filter of image_buffer into ``denoised_pixels`` (the features are rendered first when stale).
         ``None`` = the library's default for that parameter."""
-        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
-                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
-        if all(v is None for v in given.values()):
-            self.api.call("denoise", self._ctx, None)
-            return
-        v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-        p = DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                          float(v["sigma_depth"]), float(v["sigma_albedo"]))
-        self.api.call("denoise", self._ctx, C.byref(p))
+        p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        self.api.call("denoise", self._ctx, _ref(p))
 
     # ------------------------------------------------------------ coverage-aware denoise (include/rtpbr.h rtpbr_denoise_coverage)
     def render_coverage(self, grid=None):
         """Write ``coverage``: for every pixel next to a silhouette, how many of its ``grid`` x ``grid`` sub-rays (2 or 4) hit the
         pixel's own object and which other object takes most of the rest.  ``None`` = the library's default, 4.  The features
         are rendered first when stale; a sliver that passes between pixel centres is missed."""
-        d = CoverageParams.DEFAULTS
-        p = CoverageParams(int(d["grid"] if grid is None else grid), d["power"], d["resolve"])
-        self.api.call("render_coverage", self._ctx, C.byref(p))
+        self.api.call("render_coverage", self._ctx, C.byref(CoverageParams.pack(False, grid)))
 
     def denoise_coverage(self, power=None, resolve=None, grid=None, **denoise) -> NoiseStats:
         """``denoise`` (same keyword parameters) with every tap weighted by (its pixel's own-object coverage)^``power``, and with
@@ -169,15 +219,8 @@ class Renderer:
         unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
         if unknown:
             raise TypeError(f"denoise_coverage: unknown denoise parameters {sorted(unknown)}")
-        v = {k: denoise.get(k, d) if denoise.get(k) is not None else d for k, d in DenoiseParams.DEFAULTS.items()}
-        p = DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                          float(v["sigma_depth"]), float(v["sigma_albedo"]))
-        d = CoverageParams.DEFAULTS
-        cv = CoverageParams(int(d["grid"] if grid is None else grid), int(d["power"] if power is None else power),
-                            int(d["resolve"] if resolve is None else resolve))
-        s = NoiseStats()
-        self.api.call("denoise_coverage", self._ctx, C.byref(p), C.byref(cv), C.byref(s))
-        return s
+        p, cv = DenoiseParams.pack(False, **denoise), CoverageParams.pack(False, grid, power, resolve)
+        return self._stats("denoise_coverage", C.byref(p), C.byref(cv))
 
     # ------------------------------------------------------------ temporal reuse (include/rtpbr.h rtpbr_reproject)
     def reproject(self, camera: Camera, max_history=None, depth_tolerance=None, normal_cos=None):
@@ -185,13 +228,8 @@ class Renderer:
         the new view (first-hit depth, object and normal tests; count capped at ``max_history``), ``motion`` says where each
         pixel's history came from.  Needs a refresh() (or an earlier reproject()) since the last set_config / set_scene /
         set_shape_data / set_env.  ``None`` = the library's default for that parameter."""
-        given = {"max_history": max_history, "depth_tolerance": depth_tolerance, "normal_cos": normal_cos}
-        if all(v is None for v in given.values()):
-            self.api.call("reproject", self._ctx, C.byref(camera), None)
-        else:
-            v = {k: (ReprojectParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-            p = ReprojectParams(float(v["max_history"]), float(v["depth_tolerance"]), float(v["normal_cos"]))
-            self.api.call("reproject", self._ctx, C.byref(camera), C.byref(p))
+        p = ReprojectParams.pack(True, max_history, depth_tolerance, normal_cos)
+        self.api.call("reproject", self._ctx, C.byref(camera), _ref(p))
         self.camera = camera
 
     def reproject_scene(self, scene: Scene, camera: Camera = None, max_history=None, depth_tolerance=None, normal_cos=None):
@@ -203,14 +241,8 @@ class Renderer:
         rtpbr_reproject_scene).  ``None`` = the library's default for that parameter."""
         n = len(scene.objects)
         arr = (SDFObject * n)(*scene.objects)
-        cam = None if camera is None else C.byref(camera)
-        given = {"max_history": max_history, "depth_tolerance": depth_tolerance, "normal_cos": normal_cos}
-        if all(v is None for v in given.values()):
-            p = None
-        else:
-            v = {k: (ReprojectParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-            p = C.byref(ReprojectParams(float(v["max_history"]), float(v["depth_tolerance"]), float(v["normal_cos"])))
-        self.api.call("reproject_scene", self._ctx, cam, arr, n, 1 if scene.scale10 else 0, p)
+        p = ReprojectParams.pack(True, max_history, depth_tolerance, normal_cos)
+        self.api.call("reproject_scene", self._ctx, _ref(camera), arr, n, 1 if scene.scale10 else 0, _ref(p))
         self.scene = scene
         if camera is not None:
             self.camera = camera
@@ -238,7 +270,7 @@ class Renderer:
         its own variance and the one pooled from the within-pixel sums of squares of the pixels on its object within
         ``pool_radius`` (1..3), so a pixel whose few batches agree by chance is not taken for converged.  ``min_samples`` > 0:
         select_noisy also selects every pixel with fewer samples.  Kept across refresh / set_config / set_scene / reproject."""
-        e = NoiseEstimator(int(pool_batches), int(pool_radius), int(min_samples))
+        e = NoiseEstimator.pack(False, pool_batches, pool_radius, min_samples)
         self.api.call("set_noise_estimator", self._ctx, C.byref(e))
         self.noise_estimator = e
 
@@ -247,23 +279,14 @@ class Renderer:
         return how many pixels have samples, how many of them are noisier than ``threshold``, and the largest value.  Blocks.
         With ``set_noise_estimator(pool_batches=...)`` a pixel of two or more but fewer batches than that takes
         max(its own variance, the variance pooled over its neighbours on the same object): include/rtpbr.h has the rule."""
-        s = NoiseStats()
-        self.api.call("noise_estimate", self._ctx, float(threshold), C.byref(s))
-        return s
+        return self._stats("noise_estimate", float(threshold))
 
     def denoise_guided(self, iterations=None, demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, variance_floor=None):
         """The a-trous of ``denoise`` with the colour distance measured in standard deviations of each pixel's estimated noise
         (``sigma_color`` of them), the variance filtered along level by level.  Writes ``denoised_pixels`` and ``noise``.
         ``None`` = the library's default for that parameter."""
-        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
-                 "sigma_depth": sigma_depth, "variance_floor": variance_floor}
-        if all(v is None for v in given.values()):
-            self.api.call("denoise_guided", self._ctx, None)
-            return
-        v = {k: (DenoiseGuidedParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-        p = DenoiseGuidedParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                                float(v["sigma_depth"]), float(v["variance_floor"]))
-        self.api.call("denoise_guided", self._ctx, C.byref(p))
+        p = DenoiseGuidedParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, variance_floor)
+        self.api.call("denoise_guided", self._ctx, _ref(p))
 
     def render_until(self, noise: float, max_spp: int, batch_spp: int = 16, per_sample: bool = False):
         """Sample in batches of ``batch_spp`` (sample() calls of that size, each one batch of the noise estimate) until no pixel's
@@ -273,42 +296,20 @@ class Renderer:
         first estimate as soon as this call has traced two samples per pixel — after the first batch when ``batch_spp`` >= 2."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
-        if per_sample:
-            return self._render_until_per_sample(noise, int(max_spp), int(batch_spp))
-        keep, self.track_noise = self.track_noise, False
-        try:
+        batch, budget = int(batch_spp), int(max_spp)
+        with self._loop_state(noise_per_sample=per_sample):
             used, batches, stats = 0, 0, None
-            while used < max_spp:
-                n = min(int(batch_spp), int(max_spp) - used)
+            while used < budget:
+                n = min(batch, budget - used)
                 self.sample(n)
-                self.noise_update()
+                if not per_sample:
+                    self.noise_update()
                 used, batches = used + n, batches + 1
-                if batches >= 2 or used >= max_spp:
+                if (used if per_sample else batches) >= 2 or used >= budget:      # (the estimate needs two batches; per sample, two samples)
                     stats = self.noise_estimate(noise)
                     if stats.pixels_above == 0:
                         break
             return used, stats
-        finally:
-            self.track_noise = keep
-
-    def _render_until_per_sample(self, noise, max_spp, batch_spp):
-        keep, self.track_noise = self.track_noise, False
-        mode = self.noise_per_sample
-        try:
-            self.set_noise_tracking(True)
-            used, stats = 0, None
-            while used < max_spp:
-                n = min(batch_spp, max_spp - used)
-                self.sample(n)
-                used += n
-                if used >= 2 or used >= max_spp:
-                    stats = self.noise_estimate(noise)
-                    if stats.pixels_above == 0:
-                        break
-            return used, stats
-        finally:
-            self.track_noise = keep
-            self.set_noise_tracking(mode)
 
     # ------------------------------------------------------------ adaptive sampling (include/rtpbr.h rtpbr_select_* / rtpbr_sample_selected)
     def select_mask(self, mask) -> int:
@@ -317,16 +318,12 @@ class Renderer:
         m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
         if m.shape != (W, H):
             raise ValueError(f"expected a mask of shape {(W, H)}, got {m.shape}")
-        n = C.c_uint32()
-        self.api.call("select_mask", self._ctx, m.ctypes.data_as(C.c_void_p), m.nbytes, C.byref(n))
-        return int(n.value)
+        return self._count("select_mask", m.ctypes.data_as(C.c_void_p), m.nbytes)
 
     def select_noisy(self, threshold: float, dilate: int = 0) -> int:
         """Select the pixels without samples and those with a pixel noisier than ``threshold`` within ``dilate`` (0..3) pixels
         (Chebyshev distance), from a fresh noise estimate (``noise`` is written).  Returns how many.  Blocks."""
-        n = C.c_uint32()
-        self.api.call("select_noisy", self._ctx, float(threshold), int(dilate), C.byref(n))
-        return int(n.value)
+        return self._count("select_noisy", float(threshold), int(dilate))
 
     def sample_selected(self, n: int = 1):
         """``sample(n)`` through the selected pixels only: every other pixel keeps its bits, the sample index advances by ``n``
@@ -352,49 +349,27 @@ class Renderer:
         sample_selected as above without any noise_update()."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
-        batch = int(batch_spp)
+        batch, budget = int(batch_spp), int(max_spp)
         n_pix = self.config.width * self.config.height
-        if per_sample:
-            return self._render_adaptive_per_sample(noise, int(max_spp), batch, dilate, n_pix)
-        keep, self.track_noise = self.track_noise, False
-        try:
+        with self._loop_state(noise_per_sample=per_sample):
             traced, used = 0, 0
-            for _ in range(2):
-                n = min(batch, int(max_spp) - used)
+            for _ in range(1 if per_sample else 2):
+                n = min(batch, budget - used)
                 if n <= 0:
                     break
                 self.sample(n)
-                self.noise_update()
+                if not per_sample:
+                    self.noise_update()
                 traced, used = traced + n_pix * n, used + n
-            while used + batch <= int(max_spp):
+            while used + batch <= budget:
                 n_sel = self.select_noisy(noise, dilate)
                 if n_sel == 0:
                     break
                 self.sample_selected(batch)
-                self.noise_update()
+                if not per_sample:
+                    self.noise_update()
                 traced, used = traced + n_sel * batch, used + batch
             return traced, self.noise_estimate(noise)
-        finally:
-            self.track_noise = keep
-
-    def _render_adaptive_per_sample(self, noise, max_spp, batch, dilate, n_pix):
-        keep, self.track_noise = self.track_noise, False
-        mode = self.noise_per_sample
-        try:
-            self.set_noise_tracking(True)
-            used = min(batch, max_spp)
-            self.sample(used)
-            traced = n_pix * used
-            while used + batch <= max_spp:
-                n_sel = self.select_noisy(noise, dilate)
-                if n_sel == 0:
-                    break
-                self.sample_selected(batch)
-                traced, used = traced + n_sel * batch, used + batch
-            return traced, self.noise_estimate(noise)
-        finally:
-            self.track_noise = keep
-            self.set_noise_tracking(mode)
 
     # ------------------------------------------------------------ the error of the denoised frame (include/rtpbr.h rtpbr_half_update / rtpbr_denoise_error)
     def half_update(self):
@@ -410,7 +385,7 @@ class Renderer:
         sample() in the persistent-ray form, with option precision = 1 and with tiles of world > 1.  ``warp``: reproject() and
         reproject_scene() carry half A with the image instead of zeroing it, so pixels with history stay estimated across a
         move.  Both are off by default and kept across refresh / set_config / set_scene / reproject."""
-        m = HalfMode(1 if per_sample else 0, 1 if warp else 0)
+        m = HalfMode.pack(False, bool(per_sample), bool(warp))
         self.api.call("set_half_mode", self._ctx, C.byref(m))
         self.half_mode = m
 
@@ -421,25 +396,14 @@ class Renderer:
         window on each pixel's object.  Returns how many pixels have samples in both halves, how many of them are above
         ``threshold``, and the largest value.  Blocks.  Variance only: the filter's bias (blur) is the same in both halves and is
         not seen.  ``denoised_pixels`` is not written.  ``None`` = the library's default for that parameter."""
-        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
-                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
-        p = None
-        if any(v is not None for v in given.values()):
-            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
-        e = None if radius is None else C.byref(ErrorParams(int(radius)))
-        s = NoiseStats()
-        self.api.call("denoise_error", self._ctx, p, e, float(threshold), C.byref(s))
-        return s
+        p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        return self._stats("denoise_error", _ref(p), _ref(ErrorParams.pack(True, radius)), float(threshold))
 
     def select_error(self, threshold: float, dilate: int = 0) -> int:
         """select_noisy's counterpart on ``denoised_error`` as the last denoise_error() wrote it (not recomputed): the pixels
         without samples, those with an empty half, those below the estimator's ``min_samples`` and those with a pixel above
         ``threshold`` within ``dilate`` (0..3) pixels.  Returns how many.  Blocks."""
-        n = C.c_uint32()
-        self.api.call("select_error", self._ctx, float(threshold), int(dilate), C.byref(n))
-        return int(n.value)
+        return self._count("select_error", float(threshold), int(dilate))
 
     def denoise_blend(self, radius=None, z=None, min_half_samples=None, iterations=None, demodulate=None, sigma_color=None,
                       sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
@@ -449,21 +413,9 @@ class Renderer:
         whose halves both hold ``min_half_samples``; the weight leaves 1 only where the squared bias exceeds ``z`` standard
         errors.  Returns how many pixels had usable halves, how many of them got a weight below 1, and the largest 1 - weight.
         Blocks.  ``None`` = the library's default for that parameter."""
-        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
-                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
-        p = None
-        if any(v is not None for v in given.values()):
-            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
-        e = None
-        if radius is not None or z is not None or min_half_samples is not None:
-            d = BlendParams.DEFAULTS
-            e = C.byref(BlendParams(int(d["radius"] if radius is None else radius), float(d["z"] if z is None else z),
-                                    int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
-        s = NoiseStats()
-        self.api.call("denoise_blend", self._ctx, p, e, C.byref(s))
-        return s
+        p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        e = BlendParams.pack(True, radius, z, min_half_samples)
+        return self._stats("denoise_blend", _ref(p), _ref(e))
 
     def denoise_blend_levels(self, radius=None, z=None, min_half_samples=None, iterations=None, demodulate=None, sigma_color=None,
                              sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
@@ -473,21 +425,9 @@ class Renderer:
         ``denoised_pixels``, ``blend_weight`` (the product of the levels' weights: 1 = exactly ``denoise``'s colour) and
         ``blend_depth`` (the sum of the running products, 0..iterations: how many levels were kept).  Same parameters,
         defaults and statistics as denoise_blend.  Blocks."""
-        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
-                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
-        p = None
-        if any(v is not None for v in given.values()):
-            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
-        e = None
-        if radius is not None or z is not None or min_half_samples is not None:
-            d = BlendParams.DEFAULTS
-            e = C.byref(BlendParams(int(d["radius"] if radius is None else radius), float(d["z"] if z is None else z),
-                                    int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
-        s = NoiseStats()
-        self.api.call("denoise_blend_levels", self._ctx, p, e, C.byref(s))
-        return s
+        p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        e = BlendParams.pack(True, radius, z, min_half_samples)
+        return self._stats("denoise_blend_levels", _ref(p), _ref(e))
 
     def blend_error(self, threshold: float = 0.0, radius=None, z=None, min_half_samples=None, window=None, iterations=None,
                     demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None,
@@ -507,29 +447,14 @@ class Renderer:
         entry = "blend_error_display" if bias == "display" else "blend_error"
         if not self.api.has(entry):
             raise NotImplementedError(f"this library has no rtpbr_{entry}")
-        given = {"iterations": iterations, "demodulate": demodulate, "sigma_color": sigma_color, "sigma_normal": sigma_normal,
-                 "sigma_depth": sigma_depth, "sigma_albedo": sigma_albedo}
-        p = None
-        if any(v is not None for v in given.values()):
-            v = {k: (DenoiseParams.DEFAULTS[k] if x is None else x) for k, x in given.items()}
-            p = C.byref(DenoiseParams(int(v["iterations"]), int(v["demodulate"]), float(v["sigma_color"]), float(v["sigma_normal"]),
-                                      float(v["sigma_depth"]), float(v["sigma_albedo"])))
-        e = None
-        if radius is not None or z is not None or min_half_samples is not None:
-            d = BlendParams.DEFAULTS
-            e = C.byref(BlendParams(int(d["radius"] if radius is None else radius), float(d["z"] if z is None else z),
-                                    int(d["min_half_samples"] if min_half_samples is None else min_half_samples)))
-        w = None if window is None else C.byref(ErrorParams(int(window)))
-        s = NoiseStats()
-        self.api.call(entry, self._ctx, p, e, w, float(threshold), C.byref(s))
-        return s
+        p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+        e = BlendParams.pack(True, radius, z, min_half_samples)
+        return self._stats(entry, _ref(p), _ref(e), _ref(ErrorParams.pack(True, window)), float(threshold))
 
     def select_blend_error(self, threshold: float, dilate: int = 0) -> int:
         """select_error's rule on ``blend_error_map`` as the last blend_error() wrote it (not recomputed).  Returns how many
         pixels are selected.  Blocks."""
-        n = C.c_uint32()
-        self.api.call("select_blend_error", self._ctx, float(threshold), int(dilate), C.byref(n))
-        return int(n.value)
+        return self._count("select_blend_error", float(threshold), int(dilate))
 
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
                                  blend=False, *, stop="filter", bias="linear", **denoise_params):
@@ -562,12 +487,7 @@ class Renderer:
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
         n_pix = self.config.width * self.config.height
-        keep_noise, self.track_noise = self.track_noise, False
-        keep_halves, self.track_halves = self.track_halves, False
-        mode = self.half_mode
-        if per_sample:
-            self.set_half_mode(True, bool(mode.warp))
-        try:
+        with self._loop_state(halves=True, half_per_sample=per_sample):
             traced, used = 0, 0
             for _ in range(2):
                 n = min(batch, budget - used)
@@ -598,10 +518,6 @@ class Renderer:
             else:
                 self.denoise(**denoise_params)
             return traced, stats
-        finally:
-            self.track_noise, self.track_halves = keep_noise, keep_halves
-            if per_sample:
-                self.set_half_mode(bool(mode.per_sample), bool(mode.warp))
 
     # ------------------------------------------------------------ the present stage (include/rtpbr.h rtpbr_present)
     def present(self, source="pixels", format="rgba8", dither=False):
@@ -610,15 +526,10 @@ class Renderer:
         Bayer 8 x 8) and transposed into ``presented``: (H, W, 3 | 4) uint8, top row first — what a window, an encoder or an
         image file takes.  Asynchronous; returns nothing."""
         try:
-            p = PresentParams(PresentParams.SOURCES[source], PresentParams.FORMATS[format], 1 if dither else 0)
+            p = PresentParams.pack(False, PresentParams.SOURCES[source], PresentParams.FORMATS[format], bool(dither))
         except KeyError as e:
             raise ValueError(f"present: unknown source or format {e.args[0]!r}") from None
         self.api.call("present", self._ctx, C.byref(p))
-
-    @property
-    def presented(self):
-        """(H, W, C) uint8: the frame of the last present(), top row first (blocking read)"""
-        return self._read(BUF_PRESENT)
 
     def save_image(self, path, source="pixels", dither=False):
         """present(source, "rgb8", dither) and write the frame to ``path`` (any format Pillow knows by the extension): the bytes
@@ -633,15 +544,14 @@ class Renderer:
         if which == BUF_PRESENT:      # not a field: (H, W, C) with the last present's C, which the library knows (ESTATE before the first)
             _, n = self.device_ptr(which)
             return (H, W, n // (W * H)), np.uint8
-        return {BUF_IMAGE_BUFFER: ((W, H, 4), np.float32), BUF_IMAGE_PIXELS: ((W, H, 3), np.float32),
-                BUF_RAY_BUFFER: ((W, H, 10), np.float32), BUF_DIFF_BUFFER: ((W, H, 2), np.float32),
-                BUF_DIFF_PIXELS: ((W, H), np.float32), BUF_FEAT_ALBEDO: ((W, H, 3), np.float32),
-                BUF_FEAT_NORMAL: ((W, H, 3), np.float32), BUF_FEAT_DEPTH: ((W, H), np.float32), BUF_FEAT_OBJECT: ((W, H), np.int32),
-                BUF_DENOISED_PIXELS: ((W, H, 3), np.float32), BUF_MOTION: ((W, H, 2), np.float32),
-                BUF_MOMENTS: ((W, H, 4), np.float32), BUF_NOISE: ((W, H), np.float32), BUF_SELECTION: ((W, H), np.uint8),
-                BUF_HALF_BUFFER: ((W, H, 4), np.float32), BUF_DENOISED_ERROR: ((W, H), np.float32),
-                BUF_BLEND_WEIGHT: ((W, H), np.float32), BUF_BLEND_DEPTH: ((W, H), np.float32),
-                BUF_BLEND_ERROR: ((W, H), np.float32)}[which]
+        tail, dt = _TAIL_AND_DTYPE[which]
+        return (W, H) + tail, dt
+
+    def _destination(self, which, out):
+        """refuse an array that is not a buffer's shape and dtype, C-contiguous"""
+        shape, dt = self._shape(which)
+        if out.shape != tuple(shape) or out.dtype != np.dtype(dt) or not out.flags.c_contiguous:
+            raise ValueError(f"expected a C-contiguous {dt} array of shape {shape}")
 
     def _read(self, which):
         shape, dt = self._shape(which)
@@ -693,9 +603,7 @@ class Renderer:
         """Enqueue the copy of a buffer into a ``host_array()`` behind everything enqueued so far and return a ticket at once; the
         renderer's next kernels run while the copy is in flight (only a call that overwrites the buffer waits for it, on the
         device).  ``read_wait(ticket)`` blocks until ``out`` holds the frame."""
-        shape, dt = self._shape(which)
-        if out.shape != tuple(shape) or out.dtype != np.dtype(dt) or not out.flags.c_contiguous:
-            raise ValueError(f"expected a C-contiguous {dt} array of shape {shape}")
+        self._destination(which, out)
         t = C.c_int()
         self.api.call("read_buffer_async", self._ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(t))
         return t.value
@@ -705,9 +613,7 @@ class Renderer:
 
     def read_into(self, which, out):
         """field.to_numpy() into an array the caller keeps (any C-contiguous array of the buffer's shape and dtype)."""
-        shape, dt = self._shape(which)
-        if out.shape != tuple(shape) or out.dtype != np.dtype(dt) or not out.flags.c_contiguous:
-            raise ValueError(f"expected a C-contiguous {dt} array of shape {shape}")
+        self._destination(which, out)
         self.api.call("read_buffer", self._ctx, which, out.ctypes.data_as(C.c_void_p), out.nbytes)
         return out
 
@@ -717,103 +623,6 @@ class Renderer:
         if a.shape != shape:
             raise ValueError(f"expected shape {shape}, got {a.shape}")
         self.api.call("write_buffer", self._ctx, which, a.ctypes.data_as(C.c_void_p), a.nbytes)
-
-    @property
-    def image_buffer(self):
-        return self._read(BUF_IMAGE_BUFFER)
-
-    @image_buffer.setter
-    def image_buffer(self, arr):
-        self._write(BUF_IMAGE_BUFFER, arr)
-
-    @property
-    def image_pixels(self):
-        return self._read(BUF_IMAGE_PIXELS)
-
-    @property
-    def ray_buffer(self):
-        """(W,H,10) float32 view of Ray; the last column holds the int32 depth bit pattern."""
-        return self._read(BUF_RAY_BUFFER)
-
-    @ray_buffer.setter
-    def ray_buffer(self, arr):
-        self._write(BUF_RAY_BUFFER, arr)
-
-    @property
-    def diff_buffer(self):
-        """adaptive-sampling statistics (src/fileds.py:21): (sum of display change, count)"""
-        return self._read(BUF_DIFF_BUFFER)
-
-    @property
-    def diff_pixels(self):
-        return self._read(BUF_DIFF_PIXELS)
-
-    @property
-    def feature_albedo(self):
-        return self._read(BUF_FEAT_ALBEDO)
-
-    @property
-    def feature_normal(self):
-        return self._read(BUF_FEAT_NORMAL)
-
-    @property
-    def feature_depth(self):
-        return self._read(BUF_FEAT_DEPTH)
-
-    @property
-    def feature_object(self):
-        return self._read(BUF_FEAT_OBJECT)
-
-    @property
-    def denoised_pixels(self):
-        return self._read(BUF_DENOISED_PIXELS)
-
-    @property
-    def motion(self):
-        """(W,H,2): the old-frame pixel coordinates the last reproject() took each pixel's history from, (-1,-1) = none"""
-        return self._read(BUF_MOTION)
-
-    @property
-    def moments(self):
-        """(W,H,4): (sum c L, sum c L^2, sum c, K) over the K batches noise_update() has folded in (with set_noise_tracking(True):
-        every sample is a batch, c = 1), c samples each, L the
-        compressed luminance of the batch mean"""
-        return self._read(BUF_MOMENTS)
-
-    @property
-    def noise(self):
-        """(W,H): the last noise_estimate() / denoise_guided()'s standard deviation of each pixel's displayed luminance"""
-        return self._read(BUF_NOISE)
-
-    @property
-    def selection(self):
-        """(W,H) uint8: 1 = selected by the last select_mask() / select_noisy()"""
-        return self._read(BUF_SELECTION)
-
-    @property
-    def half_buffer(self):
-        """(W,H,4): half A's (sum r, sum g, sum b, count) as half_update() dealt it; half B is image_buffer minus this"""
-        return self._read(BUF_HALF_BUFFER)
-
-    @property
-    def denoised_error(self):
-        """(W,H): the last denoise_error()'s standard deviation of each pixel's denoised luminance, 0 where a half is empty"""
-        return self._read(BUF_DENOISED_ERROR)
-
-    @property
-    def blend_weight(self):
-        """(W,H): the last denoise_blend()'s weight of the denoised colour, 1 where the halves are not usable or see no bias"""
-        return self._read(BUF_BLEND_WEIGHT)
-
-    @property
-    def blend_depth(self):
-        """(W,H): how many a-trous levels the last denoise_blend_levels() kept, 0 (the raw average) .. iterations (the whole filter)"""
-        return self._read(BUF_BLEND_DEPTH)
-
-    @property
-    def blend_error_map(self):
-        """(W,H): the last blend_error()'s root-mean-square error of each pixel's level-blended luminance, 0 where a half is empty"""
-        return self._read(BUF_BLEND_ERROR)
 
     @property
     def coverage(self):
@@ -898,6 +707,15 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+
+def _buffer_property(which, writable, doc):
+    return property(lambda self: self._read(which), (lambda self, arr: self._write(which, arr)) if writable else None, doc=doc)
+
+
+for _which, _, _, _, _name, _writable, _doc in BUFFERS:      # r.image_buffer, r.image_pixels, ...: field.to_numpy() (blocking reads)
+    setattr(Renderer, _name, _buffer_property(_which, _writable, _doc))
+    getattr(Renderer, _name).__set_name__(Renderer, _name)      # (as in a class body: an assignment to a read-only one names it)
 
 
 def display_image(image_pixels: np.ndarray) -> np.ndarray:

@@ -114,6 +114,6 @@ def stats_of(st):
     return int(st[0]), int(st[1]), float(st[2:3].view(np.float32)[0])
 
 
-def pick(defaults):
-    """the chooser of a parameter: the caller's value, or the library default for ``None``"""
-    return lambda v, k: defaults[k] if v is None else v
+def fields(p):
+    """the fields of a parameter struct in order, as a restatement takes them: separate arguments"""
+    return [getattr(p, k) for k, _ in p._fields_]

@@ -5,7 +5,7 @@ The old and new features come from feature_ref_lib.features()."""
 import numpy as np
 
 from raytracingpbr_amd.dataclass import ReprojectParams
-from ref_build import GEOMETRY, POST_REF, ROOT, camera_of, cfg_ptr, f32, feats_of, pick, ptr      # noqa: F401 (ROOT: for the tests)
+from ref_build import GEOMETRY, POST_REF, ROOT, camera_of, cfg_ptr, f32, feats_of, fields, ptr      # noqa: F401 (ROOT: for the tests)
 
 build, lib = POST_REF.build, POST_REF.lib
 
@@ -13,7 +13,7 @@ build, lib = POST_REF.build, POST_REF.lib
 def reproject(cfg, old_camera, new_camera, image_buffer, old_feats, new_feats, max_history=None, depth_tolerance=None, normal_cos=None):
     """(image_buffer (W,H,4), motion (W,H,2)) — what rtpbr_reproject writes, from the old image_buffer and the old and new
     features (dicts as feature_ref_lib.features() returns them; None = the library default for a parameter)."""
-    d = pick(ReprojectParams.DEFAULTS)
+    p = ReprojectParams.pack(False, max_history, depth_tolerance, normal_cos)
     W, H = cfg.width, cfg.height
     ib = f32(image_buffer)
     assert ib.shape == (W, H, 4)
@@ -21,8 +21,6 @@ def reproject(cfg, old_camera, new_camera, image_buffer, old_feats, new_feats, m
     out = np.empty((W, H, 4), np.float32)
     motion = np.empty((W, H, 2), np.float32)
     c0, c1 = camera_of(old_camera), camera_of(new_camera)
-    rc = lib().rr_reproject(cfg_ptr(cfg), cfg_ptr(c0), cfg_ptr(c1), ptr(ib), *map(ptr, o), *map(ptr, n),
-                            float(d(max_history, "max_history")), float(d(depth_tolerance, "depth_tolerance")),
-                            float(d(normal_cos, "normal_cos")), ptr(out), ptr(motion))
+    rc = lib().rr_reproject(cfg_ptr(cfg), cfg_ptr(c0), cfg_ptr(c1), ptr(ib), *map(ptr, o), *map(ptr, n), *fields(p), ptr(out), ptr(motion))
     assert rc == 0, rc
     return out, motion

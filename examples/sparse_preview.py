@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Whole frames from a fraction of the pixels: sparse sampling on a lattice, completed by the filling denoise.
+
+    python examples/sparse_preview.py [--size 256 256] [--spp 4] [--period 2 2] [--out out/sparse] [--bench]
+
+Cornell v3.  First view: select_lattice -> sample_selected -> denoise_fill (rtpbr_denoise with option denoise_fill = 1: a pixel
+without samples takes the feature-weighted mean of the sampled pixels of its object) -> present("denoised").  Then the camera
+moves: reproject warps what the new view can reuse, and denoise_fill shows a whole frame before any new sample — the holes of the
+move filled.  Then px * py frames of the rotating lattice (Renderer.lattice_phase), each tracing one pixel of every cell, after
+which every pixel has samples.  Every step's frame is written as an image, next to the same step shown with its holes (denoise).
+--bench prints blocking wall times of each step, and of select_lattice by itself: its mask is built on the host and crosses to the
+device on every call.  Runs on the HIP library only.
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from raytracingpbr_amd import Camera, Config, Renderer, cornell_box      # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--size", type=int, nargs=2, default=(256, 256))
+ap.add_argument("--spp", type=int, default=4)
+ap.add_argument("--period", type=int, nargs=2, default=(2, 2))
+ap.add_argument("--out", default="out/sparse")
+ap.add_argument("--bench", action="store_true")
+a = ap.parse_args()
+
+W, H = a.size
+period = tuple(a.period)
+scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
+r = Renderer(scene, cfg)
+os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+
+
+def show(step):
+    filled, empty, deepest = r.denoise_fill()
+    r.save_image(f"{a.out}_{step}_filled.png", "denoised")
+    r.denoise()
+    r.save_image(f"{a.out}_{step}_holes.png", "denoised")
+    print(f"{step}: {filled} pixels filled, {empty} still empty, deepest level {deepest}")
+
+
+# the first view: one pixel of every cell
+n = r.select_lattice(period, (0, 0))
+r.refresh()
+r.sample_selected(a.spp)
+print(f"Cornell v3 {W}x{H}: {n} of {W * H} pixels traced at {a.spp} spp")
+show("first")
+
+# a camera move: the warped history has holes where the new view sees what the old one did not
+c = scene.camera
+moved = Camera(lookfrom=(c.lookfrom[0] + 4.0, c.lookfrom[1] + 1.0, c.lookfrom[2]), lookat=tuple(c.lookat), vup=tuple(c.vup), vfov=c.vfov,
+               aspect=W / H, aperture=c.aperture, focus=c.focus)
+r.reproject(moved)
+show("moved")
+
+# the rotating lattice: every pixel of a cell once per px * py frames
+for k in range(period[0] * period[1]):
+    r.select_lattice(period, Renderer.lattice_phase(k, period))
+    r.sample_selected(a.spp)
+    show(f"frame{k}")
+
+if a.bench:
+    def ms(fn, reps=20):
+        fn()
+        r.sync()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        r.sync()
+        return (time.perf_counter() - t0) / reps * 1e3
+
+    def lattice_frame():
+        r.select_lattice(period, (0, 0))
+        r.sample_selected(1)
+
+    r.select_lattice(period, (0, 0))
+    r.refresh()
+    r.sample_selected(a.spp)               # a sparse frame again: what denoise_fill is for
+    print(f"wall ms per call at {W}x{H}, lattice {period}: select_lattice {ms(lambda: r.select_lattice(period, (0, 0))):.3f}, "
+          f"select_lattice + sample_selected(1) {ms(lattice_frame):.3f}, sample(1) {ms(lambda: r.sample(1)):.3f}")
+    r.select_lattice(period, (0, 0))
+    r.refresh()
+    r.sample_selected(a.spp)
+    print(f"  denoise_fill {ms(r.denoise_fill):.3f}, denoise {ms(r.denoise):.3f}, present {ms(lambda: r.present('denoised')):.3f}, "
+          f"reproject {ms(lambda: r.reproject(moved)):.3f}")

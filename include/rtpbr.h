@@ -337,6 +337,34 @@ int rtpbr_post_process(rtpbr_ctx* ctx);
  *   The albedo is a per-object constant (0 on a miss) and taps never cross object indices, so a_q = a_p on every tap taken:
  *   the albedo term is always 0 and sigma_albedo has NO effect on the result (it is validated like the others and kept for
  *   the ABI; do not tune it).  The kernels skip the term; the definition above is what they compute.
+ * Option "denoise_fill" (rtpbr_set_option; 0 or 1, default 0): with 0 everything above holds, bit for bit.  With 1, rtpbr_denoise —
+ *   and only it: rtpbr_denoise_guided, rtpbr_denoise_coverage, rtpbr_denoise_error, the blend family, rtpbr_post_process and
+ *   rtpbr_present ignore the option and keep their bytes — reconstructs the pixels without samples from their neighbours.  Such
+ *   pixels are what rtpbr_reproject / rtpbr_reproject_scene leave where the new view sees what the old one did not, and what
+ *   rtpbr_select_mask + rtpbr_sample_selected leave unselected (a lattice of one pixel in four, say).
+ *     A pixel is LIVE at level k when it has a colour on entry to that level: at level 0 the pixels with image_buffer[p].w > 0;
+ *     the rest are EMPTY.  Tap set, tap order, h, the sums (from +0, no fma), ic_k / in / iz, the clamp min(e, 80) and the exp
+ *     are the filter's above.  A tap q is skipped, for live and empty centres alike, when it is outside the frame, when it is
+ *     not live on entry to this level, or when RTPBR_BUF_FEAT_OBJECT[q] != RTPBR_BUF_FEAT_OBJECT[p].
+ *     Live centre: the level above, operation for operation; the only difference is who is live — a pixel filled at an earlier
+ *       level is a tap like any other.
+ *     Empty centre p (its features are valid: they are rendered for every pixel): the same loop with the colour term of e taken
+ *       as +0, e = |n_p - n_q|^2 in + ((z_p - z_q) / max(z_p, 1e-6f))^2 iz (left to right), w = h exp(-min(e, 80)).  If
+ *       sum w > 0 after the loop, c_p = sum w c_q / sum w: p is live from the next level on and counts as FILLED AT LEVEL k.
+ *       Otherwise p stays empty.  Every level reads only its input: a fill never sees another fill of the same level.
+ *     Demodulation: at level 0 a tap's colour is its average divided by max(albedo_p, 1e-3f) — the centre's own albedo, which is
+ *       the tap's (one constant per object); a filled pixel is remodulated by its own albedo at the last level.
+ *     Last level: a pixel live on entry or filled there shows the configured tone map of its remodulated (c, 1); a pixel still
+ *       empty shows what rtpbr_post_process shows.
+ *     h >= 1/256 and exp(-80) ~ 1.8e-35, their product is a normal float: an empty pixel is filled at level k exactly when some
+ *       tap of that level is live on its object — a rule about reach (2 * 2^k pixels per axis), not about weights.
+ *   So: with iterations = 1 every pixel that has samples carries the bytes it has with the option off; on a frame where every
+ *   pixel has samples both settings give the same bytes at every iterations; iterations = 0 is the same call either way and
+ *   fills nothing.  image_buffer, the features, the selection, the noise moments, the halves, the work counters and sample_base
+ *   are untouched, and the refusals are those below.  rtpbr_get_counter names "fill_filled" (pixels that were empty at level 0
+ *   and got a colour), "fill_empty" (pixels still empty at the end) and "fill_deepest" (the highest level at which a pixel was
+ *   filled, 0 when none was) describe the last rtpbr_denoise that ran with the option at 1 and iterations > 0 (0 before any such
+ *   call; a refused call leaves them); they are counted by the filter's kernels, and reading them blocks.
  * Both return RTPBR_ESTATE with tiles of world > 1 (whole frames only) and RTPBR_EINVAL for bad parameters
  * (iterations outside 0..8, demodulate not 0/1, a sigma that is not finite and > 0 or whose 1/sigma^2 overflows, a
  * sigma_color whose 1/sigma^2 * 4^(iterations-1) overflows). */
@@ -1135,7 +1163,8 @@ int rtpbr_rccl_info(rtpbr_ctx* ctx, int* nranks, int* rank, int* version);
 int rtpbr_get_counters(rtpbr_ctx* ctx, rtpbr_counters* out);         /* blocking */
 /* One counter by name: the six above, plus "mlp_wave_evals" / "mlp_lane_evals" — 32-ray half passes of the
  * wave-cooperative neural-SDF network (bunny_sdf_glass.py:149-203 on the matrix cores) and the ray evaluations they
- * were needed for; their ratio / 32 is the slot utilisation of the MLP.  EINVAL for an unknown name. */
+ * were needed for; their ratio / 32 is the slot utilisation of the MLP; "fill_filled" / "fill_empty" / "fill_deepest": the last
+ * rtpbr_denoise with option denoise_fill = 1 (see rtpbr_denoise).  EINVAL for an unknown name. */
 int rtpbr_get_counter(rtpbr_ctx* ctx, const char* name, unsigned long long* out);
 /* Device time (HIP events on the context's stream) of the trace kernel launches and of
  * all kernels of the last rtpbr_sample() call, in milliseconds (blocking).  Option "timing" = 0 records no events
@@ -1154,6 +1183,8 @@ int rtpbr_get_stream(rtpbr_ctx* ctx, void** stream);
  * "residency" (persistent-ray form, pool scheduler: bounce-steps a pixel stays resident in a wave that owns more pixels
  * than the 128 it can hold; a power of two, default 32), "grid_blocks" (same kernel: workgroups to launch, 0 = automatic),
  * "cover_blocks" (the sub-ray kernel of rtpbr_render_coverage: workgroups to launch, 0 = automatic),
+ * "denoise_fill" (this one changes a result, rtpbr_denoise's alone: 1 = pixels without samples are reconstructed from their
+ * neighbours, 0 = default; see rtpbr_denoise),
  * "drain_lanes" (complete-path pool kernel: once the work has run out and nothing is parked, a wave with at most this many marching
  * lanes finishes their raycasts in the culled wave march of the primary kernel; default 16, 0 = never),
  * "primary_lean" (1, default: the coherent primary-ray kernel marches on in a one-object loop while its whole wave needs one object),

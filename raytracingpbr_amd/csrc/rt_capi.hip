@@ -171,6 +171,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->cost_buffer);
     (void)hipFree(c->march_out);
     (void)hipFree(c->noise_stats);
+    (void)hipFree(c->fill_counts);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
     rt_rccl_release(c);
@@ -1534,9 +1535,11 @@ static DenoiseArgs denoise_args(rtpbr_ctx* c, int demodulate, const float* inv) 
 // in / out (rtpbr_denoise_error, rtpbr_denoise_blend): the filter of another (sum r, sum g, sum b, count) buffer into another
 // display buffer; the caller has allocated the ping-pong.  linear (plain filter, with out): the last level stops before the tone
 // map and out takes the linear colour after remodulation.  cover_k (rtpbr_denoise_coverage; plain, linear, iterations > 0): the
-// coverage-weighted levels.
+// coverage-weighted levels.  fill (rtpbr_denoise with option denoise_fill = 1; plain, no in / out, iterations > 0): the filling levels,
+// which count into fill_counts (zeroed on the stream first).
 static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
-                          const float4* in = nullptr, float* out = nullptr, bool linear = false, const float* cover_k = nullptr) {
+                          const float4* in = nullptr, float* out = nullptr, bool linear = false, const float* cover_k = nullptr,
+                          bool fill = false) {
     if (!out)
         if (int r = denoised_alloc(c, iterations)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
@@ -1544,6 +1547,12 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
     A.image_buffer = in ? in : c->image_buffer;
     A.out = out ? out : c->denoised;
     if (cover_k) A.cover_k = cover_k;      // (shares var0's word: never with g)
+    if (fill) {
+        constexpr size_t bytes = (size_t)FILL_SHARDS * FILL_SHARD_WORDS * sizeof(uint32_t);
+        if (!c->fill_counts) HIP_TRY(hipMalloc(&c->fill_counts, bytes));
+        HIP_TRY(hipMemsetAsync(c->fill_counts, 0, bytes, c->stream));
+        A.fill = c->fill_counts;           // (shares vsrc's word: never with g)
+    }
     if (g) {
         A.var0 = c->noise_var;
         A.sc2 = g->sigma_color * g->sigma_color;
@@ -1561,7 +1570,7 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
             A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
         }
         A.step = 1 << k;
-        launch_atrous_level(A, first, last, g != nullptr, c->stream, linear && last, cover_k != nullptr);
+        launch_atrous_level(A, first, last, g != nullptr, c->stream, linear && last, cover_k != nullptr, fill);
     }
     HIP_TRY(hipGetLastError());
     return RTPBR_OK;
@@ -1595,7 +1604,8 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
     if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
-    return denoise_levels(c, d.iterations, d.demodulate, inv, nullptr);
+    // option denoise_fill: the filling levels (iterations = 0 has no level: nothing is filled, the counters keep the last filling call's)
+    return denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, nullptr, nullptr, false, nullptr, c->denoise_fill && d.iterations > 0);
 }
 
 // ---- sub-pixel coverage and the coverage-aware denoise (rt_coverage.hip)
@@ -2644,6 +2654,20 @@ extern "C" int rtpbr_get_counter(rtpbr_ctx* c, const char* name, unsigned long l
         }
     }
     else if (!strcmp(name, "jit_active")) *out = c->jit_mod ? 1 : 0;      // the last sample() ran a run-time compiled instance
+    else if (!strcmp(name, "fill_filled") || !strcmp(name, "fill_empty") || !strcmp(name, "fill_deepest")) {
+        // the last rtpbr_denoise with option denoise_fill = 1 and iterations > 0, as its kernels counted (0 before any)
+        *out = 0;
+        if (c->fill_counts) {
+            uint32_t sh[FILL_SHARDS * FILL_SHARD_WORDS];
+            HIP_TRY(hipMemcpyAsync(sh, c->fill_counts, sizeof sh, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            const int word = name[5] == 'f' ? 0 : name[5] == 'e' ? 1 : 2;
+            for (int s = 0; s < FILL_SHARDS; s++) {
+                const uint32_t v = sh[s * FILL_SHARD_WORDS + word];
+                *out = word == 2 ? (v > *out ? v : *out) : *out + v;
+            }
+        }
+    }
     else return fail(RTPBR_EINVAL, "unknown counter %s", name);
     return RTPBR_OK;
 }
@@ -2729,6 +2753,7 @@ static const OptionRow OPTION_ROWS[] = {
     OPTION(heavy_bulk_x16, 0, 1 << 20, false, "heavy_bulk_x16 must be 0 .. 2^20"),
     OPTION(grid_blocks, 0, 65535, false, "grid_blocks must be 0 (automatic) .. 65535"),
     OPTION(cover_blocks, 0, 65535, false, "cover_blocks must be 0 (automatic) .. 65535"),
+    OPTION(denoise_fill, 0, 1, false, "denoise_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise reconstructs them from their neighbours)"),
     OPTION(ready_low, 0, 63, false, "ready_low must be 0..63"),
     OPTION(refill_lanes, 1, 64, false, "refill_lanes must be 1..64"),
     // 1 (default): rtpbr_sample() brackets its kernels with events (rtpbr_last_sample_ms / rtpbr_last_primary_ms); 0: none — an event

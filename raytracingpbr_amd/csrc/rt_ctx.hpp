@@ -285,6 +285,8 @@ struct rtpbr_ctx {
     int cov_rendered_grid = 0;                       // the grid the coverage plane was rendered at
     bool history_ok = false;           // no set_config / set_scene / set_shape_data / set_env since the last refresh or reproject
     rt::NoiseStats* noise_stats = nullptr;
+    int denoise_fill = 0;              // option denoise_fill: 1 = rtpbr_denoise reconstructs the pixels without samples from their neighbours (atrous_level's FILL form)
+    uint32_t* fill_counts = nullptr;   // ... the counts of the last such call with iterations > 0, in shards (rt_features.hpp FILL_SHARDS) its kernels add to: counters "fill_*"
     int noise_tracking = RTPBR_NOISE_TRACK_OFF;      // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
     rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
                                           RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};      // rtpbr_set_noise_estimator: plain state, kept across refresh / set_config / set_scene / reproject

@@ -107,10 +107,17 @@ constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pix
 // form hands to tone_map — and +0 for a pixel without samples.
 // COVER (rtpbr_denoise_coverage; plain, its last level LINEAR): every tap but the centre's is weighted by k_q of the coverage plane
 // (rt_coverage.hpp), w = (h exp_(-min(e, 80))) k_q: 4 more bytes per tap taken.
-template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false, bool COVER = false>
+// FILL (rtpbr_denoise with option denoise_fill = 1; plain, never LINEAR): a centre without a colour (no samples, or not reached by
+// an earlier level) runs the same tap loop with the colour term of e taken as +0 — it has no colour to compare — and, when any
+// tap was taken (sw > 0), leaves as any other pixel does: its record carries its object index, so it is live from the next level
+// on; the last level remodulates it by its own albedo.  Its taps are the live pixels of its own object (A.object[p]; a level's
+// record of an empty pixel carries NO_SAMPLES and matches nobody).  One loop serves both kinds of centre: on a lattice they
+// alternate within a wave.  A.fill: FILL_SHARDS shards of (filled, empty, deepest level), summed / maximised by the reader.
+template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false, bool COVER = false, bool FILL = false>
 __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     static_assert(LAST || !LINEAR, "the linear form is a last level");
     static_assert(!COVER || (!GUIDED && LAST == LINEAR), "the coverage-weighted form is the plain filter, linear at its last level");
+    static_assert(!FILL || (!GUIDED && !LINEAR && !COVER), "the filling form is the plain filter with its tone map");
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -127,8 +134,10 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
         cp4 = A.src[i];
         op = __float_as_int(cp4.w);
         valid = op != NO_SAMPLES;
+        if constexpr (FILL)
+            if (!valid) op = A.object[i];
     }
-    if (!valid) {       // no samples: exactly what post_process shows, and nobody's neighbour
+    if (!FILL && !valid) {       // no samples: exactly what post_process shows, and nobody's neighbour
         if constexpr (LAST) {
             const vec3 t = LINEAR ? mk(0.0f, 0.0f, 0.0f) : tone_map(A.cfg, A.image_buffer[i]);
             A.out[(size_t)i * 3 + 0] = t.x;
@@ -206,7 +215,13 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
             const float4 gq_nz = A.guide_nz[q];
             const float h = HK[dx < 0 ? -dx : dx] * HK[dy < 0 ? -dy : dy];
             const float dz = (zp - gq_nz.w) / izp;
-            float e = sq3(rp - tonemap_r(cq)) * icp;
+            float e;
+            if constexpr (FILL) {      // (0 + x = x: the features' terms alone; a wave of empty centres skips the divides)
+                e = 0.0f;
+                if (valid) e = sq3(rp - tonemap_r(cq)) * icp;
+            } else {
+                e = sq3(rp - tonemap_r(cq)) * icp;
+            }
             e = e + sq3(np - xyz(gq_nz)) * A.in;
             e = e + (dz * dz) * A.iz;
             // (+ |a_p - a_q|^2 ia = + 0: see above)
@@ -220,6 +235,34 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
             sy = sy + w * cq.y;
             sz = sz + w * cq.z;
             if constexpr (GUIDED) sv = sv + (w * w) * vq;
+        }
+    }
+    if constexpr (FILL) {
+        const bool empty = !valid && !(sw > 0.0f);
+        // the counts: a wave that has something to report adds to its shard (lane 0 is in the frame whenever a lane of its wave is).
+        // On a lattice every wave fills pixels at level 0: the pixels filled are counted once, at the last level (empty at the
+        // start, a colour at the end); a level above 0 that fills raises the deepest level (level 0 leaves the zero it finds).
+        uint32_t* const shard = A.fill + (((blockIdx.x * 4u + (threadIdx.x >> 6)) % (uint32_t)FILL_SHARDS) * (uint32_t)FILL_SHARD_WORDS);
+        if constexpr (!FIRST) {
+            const unsigned long long mf = __ballot(!valid && !empty);
+            if ((threadIdx.x & 63) == 0 && mf != 0) atomicMax(shard + 2, (uint32_t)(31 - __clz(A.step)));
+        }
+        if constexpr (LAST) {
+            const bool was_empty = FIRST ? !valid : !(A.image_buffer[i].w > 0.0f);
+            const unsigned long long mf = __ballot(was_empty && !empty), me = __ballot(empty);
+            if ((threadIdx.x & 63) == 0 && mf != 0) atomicAdd(shard, (uint32_t)__popcll(mf));
+            if ((threadIdx.x & 63) == 0 && me != 0) atomicAdd(shard + 1, (uint32_t)__popcll(me));
+        }
+        if (empty) {      // no tap of this level was live on its object: as a pixel without samples leaves the other forms
+            if constexpr (LAST) {
+                const vec3 t = tone_map(A.cfg, A.image_buffer[i]);
+                A.out[(size_t)i * 3 + 0] = t.x;
+                A.out[(size_t)i * 3 + 1] = t.y;
+                A.out[(size_t)i * 3 + 2] = t.z;
+            } else {
+                A.dst[i] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(NO_SAMPLES));
+            }
+            return;
         }
     }
     vec3 c = mk(sx / sw, sy / sw, sz / sw);
@@ -275,9 +318,14 @@ static void launch_level(const DenoiseArgs& A, bool first, bool last, unsigned g
 
 // step 0 (no level) is the iterations = 0 pass of both calls; linear: the plain filter's last level (or that pass) without the tone map
 // cover: the coverage-weighted levels of rtpbr_denoise_coverage (step > 0, plain, linear exactly at the last level)
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear, bool cover) {
+// fill: the filling levels of rtpbr_denoise with option denoise_fill = 1 (step > 0, plain, never linear)
+void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear, bool cover, bool fill) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (cover && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
+    if (fill && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (fill && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (fill && last) hipLaunchKernelGGL((atrous_level<false, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (fill) hipLaunchKernelGGL((atrous_level<false, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
     else if (cover && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
     else if (cover && last) hipLaunchKernelGGL((atrous_level<false, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
     else if (cover) hipLaunchKernelGGL((atrous_level<false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);

@@ -16,6 +16,8 @@
 //                        in a record of its own, 4 bytes, loaded only on taps that pass the object test.
 //   atrous_none          iterations = 0 of either call: the average, tone-mapped.
 //   COVER (rtpbr_denoise_coverage): the plain filter with every tap but the centre's weighted by the tap's coverage (rt_coverage.hpp).
+//   FILL (rtpbr_denoise with option denoise_fill = 1): the plain filter in which a pixel without a colour takes the feature-weighted
+//   mean of the live taps on its object, at the first level that reaches one.
 //   The last level and atrous_none have a LINEAR form (rtpbr_denoise_blend): the colour before the tone map goes to `out`.
 //   rtpbr_denoise_blend_levels reads the non-last levels' records themselves: level k's (colour, object index) is the filter with
 //   iterations = k before remodulation (level_blend, rt_half.hip).
@@ -36,6 +38,10 @@ struct FeatArgs {
     float4* guide_nz;     // (W,H): (normal.xyz, depth)
 };
 
+// The counts of the FILL form: a wave adds to shard (its index in the grid) % FILL_SHARDS — (filled, empty, deepest level) in the first
+// three words of a 64-byte line of its own, so that the waves of a lattice frame, which all report, do not queue on one address.
+constexpr int FILL_SHARDS = 64, FILL_SHARD_WORDS = 16;
+
 // atrous_level arguments: one level
 struct DenoiseArgs {
     rtpbr_config cfg;             // tone map
@@ -55,7 +61,10 @@ struct DenoiseArgs {
         const float* var0;        // level 0: v of noise_estimate (-1: no samples)
         const float* cover_k;     // COVER (rtpbr_denoise_coverage, rt_coverage.hpp): (W,H) k = (n_own / S)^power, the weight of the pixel as somebody's tap
     };
-    const float* vsrc;            // levels > 0: the previous level's variance
+    union {
+        const float* vsrc;        // levels > 0: the previous level's variance
+        uint32_t* fill;           // FILL (rtpbr_denoise with option denoise_fill = 1; plain): the call's counts, FILL_SHARDS x FILL_SHARD_WORDS words
+    };
     float* vdst;                  // every level but the last
     float sc2;                    // sigma_color * sigma_color
     float floor;                  // variance_floor
@@ -66,6 +75,6 @@ RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), 
 
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
 void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear = false,
-                         bool cover = false);      // linear: last && !guided; cover: !guided, linear == last, A.step > 0
+                         bool cover = false, bool fill = false);      // linear: last && !guided; cover: !guided, linear == last, A.step > 0; fill: !guided, !linear, !cover, A.step > 0
 
 }  // namespace rt

@@ -204,6 +204,21 @@ class Renderer:
         p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
         self.api.call("denoise", self._ctx, _ref(p))
 
+    def denoise_fill(self, **denoise):
+        """``denoise`` (same keyword parameters) with option ``denoise_fill`` set for the call: a pixel without samples takes the
+        feature-weighted mean of the pixels of its object that have a colour, at the first a-trous level that reaches one
+        (include/rtpbr.h rtpbr_denoise).  Returns (pixels filled, pixels still empty, the deepest level that filled one).  The
+        option is 0 again afterwards, also when the call is refused.  Blocks."""
+        unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise_fill: unknown denoise parameters {sorted(unknown)}")
+        self.set_option("denoise_fill", 1)
+        try:
+            self.denoise(**denoise)
+        finally:
+            self.set_option("denoise_fill", 0)
+        return tuple(self.counter(k) for k in ("fill_filled", "fill_empty", "fill_deepest"))
+
     # ------------------------------------------------------------ coverage-aware denoise (include/rtpbr.h rtpbr_denoise_coverage)
     def render_coverage(self, grid=None):
         """Write ``coverage``: for every pixel next to a silhouette, how many of its ``grid`` x ``grid`` sub-rays (2 or 4) hit the
@@ -319,6 +334,44 @@ class Renderer:
         if m.shape != (W, H):
             raise ValueError(f"expected a mask of shape {(W, H)}, got {m.shape}")
         return self._count("select_mask", m.ctypes.data_as(C.c_void_p), m.nbytes)
+
+    def select_lattice(self, period=(2, 2), phase=(0, 0)) -> int:
+        """Select the pixels with ``x % px == phx and y % py == phy``: one pixel of every ``px`` x ``py`` cell, for sparse frames
+        that ``denoise_fill`` completes.  Periods 1..8 per axis, 0 <= phase < period.  The mask is built on the host and crosses
+        to the device with the call (W * H bytes).  Returns how many pixels are selected."""
+        (px, py), (phx, phy) = self._lattice_args(period, phase)
+        W, H = self.config.width, self.config.height
+        return self.select_mask(np.logical_and.outer(np.arange(W) % px == phx, np.arange(H) % py == phy))
+
+    @staticmethod
+    def _lattice_args(period, phase):
+        try:
+            (px, py), (phx, phy) = period, phase
+        except (TypeError, ValueError):
+            raise ValueError("lattice period and phase are pairs (x, y)") from None
+        for v in (px, py, phx, phy):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("lattice period and phase must be integers")
+        if not (1 <= px <= 8 and 1 <= py <= 8):
+            raise ValueError(f"lattice period must be 1..8 per axis, got {(px, py)}")
+        if not (0 <= phx < px and 0 <= phy < py):
+            raise ValueError(f"lattice phase must be 0 <= phase < period, got {(phx, phy)} for period {(px, py)}")
+        return (int(px), int(py)), (int(phx), int(phy))
+
+    @staticmethod
+    def lattice_phase(frame: int, period=(2, 2)):
+        """The phase of frame ``frame`` of a rotating lattice: every pixel of a period cell is visited once per ``px * py`` frames.
+        (2, 2): (0,0), (1,1), (1,0), (0,1) — the diagonal first, so that two frames already spread over both axes.  Any other
+        period: frame k of a cycle takes cell index j = (k * step) % (px * py), step the smallest integer above px * py / 2
+        coprime to px * py (1 when px * py <= 2), as (j % px, j // px): consecutive frames land far apart."""
+        (px, py), _ = Renderer._lattice_args(period, (0, 0))
+        n = px * py
+        k = int(frame) % n
+        if (px, py) == (2, 2):
+            return ((0, 0), (1, 1), (1, 0), (0, 1))[k]
+        step = 1 if n <= 2 else next(s for s in range(n // 2 + 1, 2 * n) if np.gcd(s, n) == 1)
+        j = (k * step) % n
+        return (j % px, j // px)
 
     def select_noisy(self, threshold: float, dilate: int = 0) -> int:
         """Select the pixels without samples and those with a pixel noisier than ``threshold`` within ``dilate`` (0..3) pixels

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Whole frames from a fraction of the pixels: sparse sampling on a lattice, completed by the filling denoise.
 
-    python examples/sparse_preview.py [--size 256 256] [--spp 4] [--period 2 2] [--out out/sparse] [--bench]
+    python examples/sparse_preview.py [--size 256 256] [--spp 4] [--period 2 2] [--out out/sparse] [--coverage-fill] [--bench]
 
 Cornell v3.  First view: select_lattice -> sample_selected -> denoise_fill (rtpbr_denoise with option denoise_fill = 1: a pixel
 without samples takes the feature-weighted mean of the sampled pixels of its object) -> present("denoised").  Then the camera
@@ -9,7 +9,9 @@ moves: reproject warps what the new view can reuse, and denoise_fill shows a who
 move filled.  Then px * py frames of the rotating lattice (Renderer.lattice_phase), each tracing one pixel of every cell, after
 which every pixel has samples.  Every step's frame is written as an image, next to the same step shown with its holes (denoise).
 --bench prints blocking wall times of each step, and of select_lattice by itself: its mask is built on the host and crosses to the
-device on every call.  Runs on the HIP library only.
+device on every call.  --coverage-fill fills with denoise_coverage_fill instead (rtpbr_denoise_coverage with option coverage_fill =
+1: the holes filled inside the coverage-weighted levels, the two-object pixels resolved, filled ones included) and shows the holes
+with denoise_coverage.  Runs on the HIP library only.
 """
 import argparse
 import os
@@ -24,6 +26,7 @@ ap.add_argument("--size", type=int, nargs=2, default=(256, 256))
 ap.add_argument("--spp", type=int, default=4)
 ap.add_argument("--period", type=int, nargs=2, default=(2, 2))
 ap.add_argument("--out", default="out/sparse")
+ap.add_argument("--coverage-fill", action="store_true")
 ap.add_argument("--bench", action="store_true")
 a = ap.parse_args()
 
@@ -34,10 +37,14 @@ r = Renderer(scene, cfg)
 os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
 
 
+def fill():
+    return r.denoise_coverage_fill()[1] if a.coverage_fill else r.denoise_fill()
+
+
 def show(step):
-    filled, empty, deepest = r.denoise_fill()
+    filled, empty, deepest = fill()
     r.save_image(f"{a.out}_{step}_filled.png", "denoised")
-    r.denoise()
+    r.denoise_coverage() if a.coverage_fill else r.denoise()
     r.save_image(f"{a.out}_{step}_holes.png", "denoised")
     print(f"{step}: {filled} pixels filled, {empty} still empty, deepest level {deepest}")
 
@@ -84,5 +91,7 @@ if a.bench:
     r.select_lattice(period, (0, 0))
     r.refresh()
     r.sample_selected(a.spp)
+    if a.coverage_fill:
+        print(f"  denoise_coverage_fill {ms(r.denoise_coverage_fill):.3f}, denoise_coverage {ms(r.denoise_coverage):.3f}")
     print(f"  denoise_fill {ms(r.denoise_fill):.3f}, denoise {ms(r.denoise):.3f}, present {ms(lambda: r.present('denoised')):.3f}, "
           f"reproject {ms(lambda: r.reproject(moved)):.3f}")

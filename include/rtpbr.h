@@ -1080,7 +1080,45 @@ int rtpbr_present(rtpbr_ctx* ctx, const rtpbr_present_params* p);   /* NULL = th
  *     pixel wide next to a dark one keeps its colour), never a mean of neighbours.
  *   denoised = the configured tone map of (F_p, 1); a pixel without samples shows what rtpbr_post_process shows, is nobody's tap
  *   and nobody's E2 neighbour, and is not resolved.  power = 0 with resolve = 0 gives rtpbr_denoise's bytes.
- *   out (may be NULL): pixels_estimated = the resolved pixels, pixels_above = the candidates, max_noise = the largest 1 - a. */
+ *   out (may be NULL): pixels_estimated = the resolved pixels, pixels_above = the candidates, max_noise = the largest 1 - a.
+ * Option "coverage_fill" (rtpbr_set_option; 0 or 1, default 0): with 0 everything above holds, bit for bit.  With 1,
+ *   rtpbr_denoise_coverage — and only it: rtpbr_denoise, rtpbr_denoise_guided, rtpbr_denoise_error, the blend family,
+ *   rtpbr_post_process, rtpbr_present and rtpbr_render_coverage never read the option and keep their bytes, and option "denoise_fill"
+ *   still does not touch rtpbr_denoise_coverage — reconstructs the pixels without samples (the holes rtpbr_reproject* leaves, the
+ *   pixels rtpbr_select_mask + rtpbr_sample_selected did not trace: both concentrate at silhouettes) inside the coverage-weighted
+ *   levels, and resolves them as it resolves the others.  It applies with iterations > 0; iterations = 0 is the same call as with
+ *   0, fills nothing, and the counters below keep the last filling call's values.
+ *     A pixel is LIVE at level k when it has a colour on entry to that level: at level 0 the pixels with image_buffer[p].w > 0;
+ *     the rest are EMPTY.  A tap q is skipped, for live and empty centres alike, when it is outside the frame, when it is not live
+ *     on entry to this level, or when RTPBR_BUF_FEAT_OBJECT[q] != the centre's object index; an empty centre's object index is
+ *     RTPBR_BUF_FEAT_OBJECT[p] (the features are rendered for every pixel).
+ *     Live centre: the level above, operation for operation: w = (h exp(-min(e, 80))) k_q for every tap but its own.  The only
+ *       difference is who is live — a pixel filled at an earlier level is a tap like any other.
+ *     Empty centre p: the same loop, same tap order, with the colour term of e taken as +0,
+ *       e = |n_p - n_q|^2 in + ((z_p - z_q) / max(z_p, 1e-6f))^2 iz (left to right), w = (h exp(-min(e, 80))) k_q for EVERY tap it
+ *       takes (its own position is not live and is never a tap); sw = sw + w, s = s + w c_q per channel, from +0, no fma.
+ *       If sw > 0 after the loop, c_p = s / sw: p is live from the next level on and counts as FILLED AT LEVEL k.  Otherwise p
+ *       stays empty.  Every level reads only its input: a fill never sees another fill of the same level.
+ *     Filling is decided by the COMPUTED sum, sw > 0 — it is not purely a rule about reach as rtpbr_denoise's fill is: k_q is 0
+ *       where n_own_q = 0 (power >= 1), and at power 8 the product of a small k_q with a weight near h exp(-80) ~ 7e-38 can
+ *       underflow to 0 in f32 (a denormal product is kept and counts as > 0).  A pixel all of whose reachable
+ *       live taps weigh 0 stays empty at that level.  Only at power = 0 (k_q = 1) does the rule reduce to "some tap of the level is
+ *       live on the pixel's object".
+ *     Demodulation: at level 0 a tap's colour is its average divided by max(albedo_p, 1e-3f), the centre's own albedo (one
+ *       constant per object); at the last level a filled pixel is remodulated by its own albedo, as every pixel is.  That linear
+ *       colour is its F_p.
+ *     Resolve: "with samples" above reads "has a colour after the last level", for the centre p and for its eight E2 neighbours
+ *       alike: a filled pixel with n_second > 0 is resolved by the same formula and counts in pixels_estimated.
+ *     A pixel still empty after the last level shows what rtpbr_post_process shows, is nobody's tap and nobody's E2 neighbour,
+ *       and is not resolved.
+ *   So: on a frame where every pixel has samples both settings give the same bytes and statistics at every iterations; with
+ *   resolve = 0 and iterations = 1 every pixel that has samples carries the bytes it has with the option off; power = 0 with
+ *   resolve = 0 gives the bytes and the counters of rtpbr_denoise with option denoise_fill = 1.  image_buffer, the features, the
+ *   coverage plane's contents, the selection, the work counters and sample_base are untouched; the refusals are those above.
+ *   rtpbr_get_counter names "fill_filled", "fill_empty" and "fill_deepest" (defined at rtpbr_denoise) describe the last filling call
+ *   of EITHER kind: rtpbr_denoise with denoise_fill = 1 or rtpbr_denoise_coverage with coverage_fill = 1, iterations > 0.
+ *   Keeps one more (W,H) 1-byte plane (who has a colour after the last level: written by that level, read by the resolve; no
+ *   buffer id), made by the first such call and freed by rtpbr_set_config with a new resolution. */
 typedef struct rtpbr_coverage_params {   /* 4-byte members, no padding */
     int32_t grid;       /* sub-rays per axis: 2 or 4                                                     */
     int32_t power;      /* 0..8: a tap's weight is (n_own / S)^power                                     */
@@ -1164,7 +1202,8 @@ int rtpbr_get_counters(rtpbr_ctx* ctx, rtpbr_counters* out);         /* blocking
 /* One counter by name: the six above, plus "mlp_wave_evals" / "mlp_lane_evals" — 32-ray half passes of the
  * wave-cooperative neural-SDF network (bunny_sdf_glass.py:149-203 on the matrix cores) and the ray evaluations they
  * were needed for; their ratio / 32 is the slot utilisation of the MLP; "fill_filled" / "fill_empty" / "fill_deepest": the last
- * rtpbr_denoise with option denoise_fill = 1 (see rtpbr_denoise).  EINVAL for an unknown name. */
+ * rtpbr_denoise with option denoise_fill = 1 or rtpbr_denoise_coverage with option coverage_fill = 1 (see rtpbr_denoise).  EINVAL
+ * for an unknown name. */
 int rtpbr_get_counter(rtpbr_ctx* ctx, const char* name, unsigned long long* out);
 /* Device time (HIP events on the context's stream) of the trace kernel launches and of
  * all kernels of the last rtpbr_sample() call, in milliseconds (blocking).  Option "timing" = 0 records no events
@@ -1184,7 +1223,8 @@ int rtpbr_get_stream(rtpbr_ctx* ctx, void** stream);
  * than the 128 it can hold; a power of two, default 32), "grid_blocks" (same kernel: workgroups to launch, 0 = automatic),
  * "cover_blocks" (the sub-ray kernel of rtpbr_render_coverage: workgroups to launch, 0 = automatic),
  * "denoise_fill" (this one changes a result, rtpbr_denoise's alone: 1 = pixels without samples are reconstructed from their
- * neighbours, 0 = default; see rtpbr_denoise),
+ * neighbours, 0 = default; see rtpbr_denoise), "coverage_fill" (the same for rtpbr_denoise_coverage, and its result alone: 1 = pixels
+ * without samples are reconstructed inside the coverage-weighted levels and resolved, 0 = default; see rtpbr_denoise_coverage),
  * "drain_lanes" (complete-path pool kernel: once the work has run out and nothing is parked, a wave with at most this many marching
  * lanes finishes their raycasts in the culled wave march of the primary kernel; default 16, 0 = never),
  * "primary_lean" (1, default: the coherent primary-ray kernel marches on in a one-object loop while its whole wave needs one object),

@@ -1536,7 +1536,8 @@ static DenoiseArgs denoise_args(rtpbr_ctx* c, int demodulate, const float* inv) 
 // display buffer; the caller has allocated the ping-pong.  linear (plain filter, with out): the last level stops before the tone
 // map and out takes the linear colour after remodulation.  cover_k (rtpbr_denoise_coverage; plain, linear, iterations > 0): the
 // coverage-weighted levels.  fill (rtpbr_denoise with option denoise_fill = 1; plain, no in / out, iterations > 0): the filling levels,
-// which count into fill_counts (zeroed on the stream first).
+// which count into fill_counts (zeroed on the stream first).  fill with cover_k (rtpbr_denoise_coverage with option coverage_fill = 1):
+// the coverage-weighted filling levels; the last writes cov_live (the caller has allocated it) beside out.
 static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
                           const float4* in = nullptr, float* out = nullptr, bool linear = false, const float* cover_k = nullptr,
                           bool fill = false) {
@@ -1552,6 +1553,7 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
         if (!c->fill_counts) HIP_TRY(hipMalloc(&c->fill_counts, bytes));
         HIP_TRY(hipMemsetAsync(c->fill_counts, 0, bytes, c->stream));
         A.fill = c->fill_counts;           // (shares vsrc's word: never with g)
+        if (cover_k) A.live = c->cov_live; // (shares vdst's word: never with g)
     }
     if (g) {
         A.var0 = c->noise_var;
@@ -1690,7 +1692,12 @@ extern "C" int rtpbr_denoise_coverage(rtpbr_ctx* c, const rtpbr_denoise_params* 
         if (int r = denoise_levels(c, 0, d.demodulate, inv, nullptr)) return r;
     } else {
         if (int r = denoised_alloc(c, d.iterations)) return r;
-        if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->cov_linear, true, c->cov_k)) return r;
+        // option coverage_fill: the filling levels and the resolve that asks them who has a colour (not read with iterations = 0: no
+        // level, nothing is filled, the counters keep the last filling call's)
+        const bool fill = c->coverage_fill != 0;
+        if (fill)
+            if (int r = frame_need(c, {ROW_cov_live})) return r;
+        if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->cov_linear, true, c->cov_k, fill)) return r;
         ResolveArgs R{};
         R.cfg = c->cfg;
         R.image_buffer = c->image_buffer;
@@ -1703,6 +1710,7 @@ extern "C" int rtpbr_denoise_coverage(rtpbr_ctx* c, const rtpbr_denoise_params* 
         R.width = c->cfg.width;
         R.height = c->cfg.height;
         R.resolve = cv.resolve;
+        R.live = fill ? c->cov_live : nullptr;
         launch_cover_resolve(R, c->stream);
     }
     HIP_TRY(hipGetLastError());
@@ -2655,7 +2663,8 @@ extern "C" int rtpbr_get_counter(rtpbr_ctx* c, const char* name, unsigned long l
     }
     else if (!strcmp(name, "jit_active")) *out = c->jit_mod ? 1 : 0;      // the last sample() ran a run-time compiled instance
     else if (!strcmp(name, "fill_filled") || !strcmp(name, "fill_empty") || !strcmp(name, "fill_deepest")) {
-        // the last rtpbr_denoise with option denoise_fill = 1 and iterations > 0, as its kernels counted (0 before any)
+        // the last rtpbr_denoise with option denoise_fill = 1 or rtpbr_denoise_coverage with option coverage_fill = 1, iterations > 0, as
+        // its kernels counted (0 before any)
         *out = 0;
         if (c->fill_counts) {
             uint32_t sh[FILL_SHARDS * FILL_SHARD_WORDS];
@@ -2754,6 +2763,7 @@ static const OptionRow OPTION_ROWS[] = {
     OPTION(grid_blocks, 0, 65535, false, "grid_blocks must be 0 (automatic) .. 65535"),
     OPTION(cover_blocks, 0, 65535, false, "cover_blocks must be 0 (automatic) .. 65535"),
     OPTION(denoise_fill, 0, 1, false, "denoise_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise reconstructs them from their neighbours)"),
+    OPTION(coverage_fill, 0, 1, false, "coverage_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise_coverage reconstructs them from their neighbours)"),
     OPTION(ready_low, 0, 63, false, "ready_low must be 0..63"),
     OPTION(refill_lanes, 1, 64, false, "refill_lanes must be 1..64"),
     // 1 (default): rtpbr_sample() brackets its kernels with events (rtpbr_last_sample_ms / rtpbr_last_primary_ms); 0: none — an event

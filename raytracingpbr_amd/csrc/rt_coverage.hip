@@ -138,8 +138,11 @@ __global__ void __launch_bounds__(256) cover_weights(const CoverageArgs A) {
 // The resolve and the tone map of rtpbr_denoise_coverage.  Block (16, 16): thread (tx, ty) has pixel (16 bx + tx, 16 by + ty), ty along
 // y, the buffers' contiguous index.  The tile and its halo, 18 x 18 cells of (F, object word, k): object word -3 = outside the frame
 // or without samples (matches no second object: those are >= -1).
+// FILL (option coverage_fill = 1): "with samples" is "has a colour after the last level", the byte the filling last level wrote
+// into A.live (atrous_level's COVER and FILL form, rt_features.hip) — for the centre and for its eight neighbours alike.
 constexpr int RES_T = 16, RES_P = RES_T + 2;
 constexpr int RES_NONE = -3;
+template <bool FILL>
 __global__ void __launch_bounds__(256) cover_resolve(const ResolveArgs A) {
     __shared__ float tf[RES_P * RES_P][3];
     __shared__ int to[RES_P * RES_P];
@@ -153,7 +156,7 @@ __global__ void __launch_bounds__(256) cover_resolve(const ResolveArgs A) {
         float fx = 0.0f, fy = 0.0f, fz = 0.0f, k = 0.0f;
         if (xq >= 0 && xq < W && yq >= 0 && yq < H) {
             const size_t q = (size_t)xq * (size_t)H + (size_t)yq;
-            if (A.image_buffer[q].w > 0.0f) {
+            if (FILL ? A.live[q] != 0 : A.image_buffer[q].w > 0.0f) {
                 o = A.object[q];
                 fx = A.linear[q * 3 + 0];
                 fy = A.linear[q * 3 + 1];
@@ -176,7 +179,7 @@ __global__ void __launch_bounds__(256) cover_resolve(const ResolveArgs A) {
         const size_t i = (size_t)x * (size_t)H + (size_t)y;
         const int cc = (tx + 1) * RES_P + (ty + 1);
         vec3 t;
-        if (to[cc] == RES_NONE) {      // no samples: exactly what post_process shows
+        if (to[cc] == RES_NONE) {      // no samples (FILL: and no level reached it): exactly what post_process shows
             t = tone_map(A.cfg, A.image_buffer[i]);
         } else {
             vec3 F = mk(tf[cc][0], tf[cc][1], tf[cc][2]);
@@ -244,7 +247,8 @@ void launch_cover_weights(const CoverageArgs& A, hipStream_t st) {
 
 void launch_cover_resolve(const ResolveArgs& A, hipStream_t st) {
     const dim3 grid((unsigned)((A.width + RES_T - 1) / RES_T), (unsigned)((A.height + RES_T - 1) / RES_T));
-    hipLaunchKernelGGL(cover_resolve, grid, dim3(256), 0, st, A);
+    if (A.live) hipLaunchKernelGGL(cover_resolve<true>, grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(cover_resolve<false>, grid, dim3(256), 0, st, A);
 }
 
 }  // namespace rt

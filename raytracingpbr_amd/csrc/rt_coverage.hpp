@@ -15,6 +15,7 @@
 //                     rt_features.hip), and the largest 1 - n_own / S of the frame.
 //   cover_resolve     one lane per pixel, 16 x 16 tiles with a one-pixel halo of (F, object word, k) in LDS: the edge resolve on
 //                     the filter's LINEAR result F and the tone map of every pixel (include/rtpbr.h, rtpbr_denoise_coverage).
+//                     Its FILL form (option coverage_fill = 1) takes who has a colour from the plane the filling last level wrote.
 // The arithmetic is fixed operation by operation in include/rtpbr.h; tests/coverage_ref restates it on the CPU.
 #pragma once
 #include "rt_types.hpp"
@@ -44,6 +45,7 @@ struct ResolveArgs {
     float* out;                   // (W,H,3) denoised display colour
     int32_t width, height;
     int32_t resolve;
+    const uint8_t* live;          // option coverage_fill = 1: (W,H) 1 = the pixel has a colour after the last level (then that, not the count, says who is shown, tapped and resolved); else null
 };
 
 void launch_cover_mark(const CoverageArgs& A, hipStream_t st);                              // the caller has zeroed the head

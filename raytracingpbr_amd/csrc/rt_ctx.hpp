@@ -128,6 +128,7 @@ constexpr int FRAME_PRIVATE = -1;
     X(cov_list, uint32_t, (np + rt::COVER_HEAD) * 4, FRAME_FEATURES, false, FRAME_PRIVATE, false) /* the head (length, resolved, bits of max 1 - a, 0), then the candidates' buffer indices */ \
     X(cov_k, float, np * 4, FRAME_FEATURES, false, FRAME_PRIVATE, false)                        /* rtpbr_denoise_coverage: k, the weight of the pixel as a tap */ \
     X(cov_linear, float, np * 12, FRAME_FEATURES, false, FRAME_PRIVATE, false)                  /* ... (W,H,3): the filter's linear colour, what the resolve reads */ \
+    X(cov_live, uint8_t, np, FRAME_FEATURES, false, FRAME_PRIVATE, false)                       /* ... with option coverage_fill = 1: 1 = the pixel has a colour after the last level (written by that level, read by the resolve) */ \
     /* temporal reuse (rt_reproject.hip): rtpbr_reproject, rtpbr_reproject_scene */                                                                \
     X(hist_image, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                 /* image_buffer before the move */                 \
     X(hist_guides, float4, np * 16, FRAME_FEATURES, false, FRAME_PRIVATE, false)                /* the old camera's (normal, depth) records */     \
@@ -286,7 +287,8 @@ struct rtpbr_ctx {
     bool history_ok = false;           // no set_config / set_scene / set_shape_data / set_env since the last refresh or reproject
     rt::NoiseStats* noise_stats = nullptr;
     int denoise_fill = 0;              // option denoise_fill: 1 = rtpbr_denoise reconstructs the pixels without samples from their neighbours (atrous_level's FILL form)
-    uint32_t* fill_counts = nullptr;   // ... the counts of the last such call with iterations > 0, in shards (rt_features.hpp FILL_SHARDS) its kernels add to: counters "fill_*"
+    int coverage_fill = 0;             // option coverage_fill: 1 = rtpbr_denoise_coverage does the same (atrous_level's COVER and FILL form, cover_resolve's FILL form)
+    uint32_t* fill_counts = nullptr;   // ... the counts of the last such call of either kind with iterations > 0, in shards (rt_features.hpp FILL_SHARDS) its kernels add to: counters "fill_*"
     int noise_tracking = RTPBR_NOISE_TRACK_OFF;      // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
     rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,
                                           RTPBR_NOISE_ESTIMATOR_DEFAULT_MIN_SAMPLES};      // rtpbr_set_noise_estimator: plain state, kept across refresh / set_config / set_scene / reproject

@@ -113,11 +113,16 @@ constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pix
 // on; the last level remodulates it by its own albedo.  Its taps are the live pixels of its own object (A.object[p]; a level's
 // record of an empty pixel carries NO_SAMPLES and matches nobody).  One loop serves both kinds of centre: on a lattice they
 // alternate within a wave.  A.fill: FILL_SHARDS shards of (filled, empty, deepest level), summed / maximised by the reader.
+// COVER and FILL (rtpbr_denoise_coverage with option coverage_fill = 1; LINEAR at the last level as COVER is): every tap an empty
+// centre takes is weighted by k_q as well (its own position is not live and never a tap), so whether it is filled is the computed
+// sw > 0, not reach alone: k_q may be 0, and k_q times a weight near h exp_(-80) may underflow.  The linear plane has no object word:
+// the last level writes A.live, 1 for a pixel that leaves with a colour and 0 beside the +0 of a pixel still empty.
 template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false, bool COVER = false, bool FILL = false>
 __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
     static_assert(LAST || !LINEAR, "the linear form is a last level");
     static_assert(!COVER || (!GUIDED && LAST == LINEAR), "the coverage-weighted form is the plain filter, linear at its last level");
-    static_assert(!FILL || (!GUIDED && !LINEAR && !COVER), "the filling form is the plain filter with its tone map");
+    static_assert(!FILL || !GUIDED, "the filling form is the plain filter");
+    static_assert(!FILL || !LINEAR || COVER, "the filling form is linear only as the coverage-weighted filter's last level");
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -255,15 +260,17 @@ __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
         }
         if (empty) {      // no tap of this level was live on its object: as a pixel without samples leaves the other forms
             if constexpr (LAST) {
-                const vec3 t = tone_map(A.cfg, A.image_buffer[i]);
+                const vec3 t = LINEAR ? mk(0.0f, 0.0f, 0.0f) : tone_map(A.cfg, A.image_buffer[i]);
                 A.out[(size_t)i * 3 + 0] = t.x;
                 A.out[(size_t)i * 3 + 1] = t.y;
                 A.out[(size_t)i * 3 + 2] = t.z;
+                if constexpr (LINEAR) A.live[i] = 0;
             } else {
                 A.dst[i] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(NO_SAMPLES));
             }
             return;
         }
+        if constexpr (LINEAR) A.live[i] = 1;
     }
     vec3 c = mk(sx / sw, sy / sw, sz / sw);
     if constexpr (LAST) {
@@ -318,10 +325,15 @@ static void launch_level(const DenoiseArgs& A, bool first, bool last, unsigned g
 
 // step 0 (no level) is the iterations = 0 pass of both calls; linear: the plain filter's last level (or that pass) without the tone map
 // cover: the coverage-weighted levels of rtpbr_denoise_coverage (step > 0, plain, linear exactly at the last level)
-// fill: the filling levels of rtpbr_denoise with option denoise_fill = 1 (step > 0, plain, never linear)
+// fill: the filling levels of rtpbr_denoise with option denoise_fill = 1 (step > 0, plain, never linear), or with cover those of
+// rtpbr_denoise_coverage with option coverage_fill = 1 (linear exactly at the last level)
 void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear, bool cover, bool fill) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (fill && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
+    if (cover && fill && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, true, true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover && fill && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover && fill && last) hipLaunchKernelGGL((atrous_level<false, true, false, true, true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (cover && fill) hipLaunchKernelGGL((atrous_level<false, false, false, false, true, true>), dim3(grid), dim3(256), 0, st, A);
+    else if (fill && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
     else if (fill && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
     else if (fill && last) hipLaunchKernelGGL((atrous_level<false, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
     else if (fill) hipLaunchKernelGGL((atrous_level<false, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);

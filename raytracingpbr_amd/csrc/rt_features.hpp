@@ -18,6 +18,8 @@
 //   COVER (rtpbr_denoise_coverage): the plain filter with every tap but the centre's weighted by the tap's coverage (rt_coverage.hpp).
 //   FILL (rtpbr_denoise with option denoise_fill = 1): the plain filter in which a pixel without a colour takes the feature-weighted
 //   mean of the live taps on its object, at the first level that reaches one.
+//   COVER and FILL together (rtpbr_denoise_coverage with option coverage_fill = 1): the empty centre's taps carry the coverage weight
+//   too, and the last level, LINEAR, writes who has a colour into a (W,H) byte plane for the resolve (rt_coverage.hip).
 //   The last level and atrous_none have a LINEAR form (rtpbr_denoise_blend): the colour before the tone map goes to `out`.
 //   rtpbr_denoise_blend_levels reads the non-last levels' records themselves: level k's (colour, object index) is the filter with
 //   iterations = k before remodulation (level_blend, rt_half.hip).
@@ -65,7 +67,10 @@ struct DenoiseArgs {
         const float* vsrc;        // levels > 0: the previous level's variance
         uint32_t* fill;           // FILL (rtpbr_denoise with option denoise_fill = 1; plain): the call's counts, FILL_SHARDS x FILL_SHARD_WORDS words
     };
-    float* vdst;                  // every level but the last
+    union {
+        float* vdst;              // every level but the last
+        uint8_t* live;            // COVER and FILL, the last level (LINEAR): (W,H) 1 = the pixel has a colour, 0 = still empty (out takes +0)
+    };
     float sc2;                    // sigma_color * sigma_color
     float floor;                  // variance_floor
 };
@@ -75,6 +80,6 @@ RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), 
 
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
 void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear = false,
-                         bool cover = false, bool fill = false);      // linear: last && !guided; cover: !guided, linear == last, A.step > 0; fill: !guided, !linear, !cover, A.step > 0
+                         bool cover = false, bool fill = false);      // linear: last && !guided; cover: !guided, linear == last, A.step > 0; fill: !guided, A.step > 0, linear only with cover
 
 }  // namespace rt

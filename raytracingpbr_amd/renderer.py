@@ -237,6 +237,23 @@ class Renderer:
         p, cv = DenoiseParams.pack(False, **denoise), CoverageParams.pack(False, grid, power, resolve)
         return self._stats("denoise_coverage", C.byref(p), C.byref(cv))
 
+    def denoise_coverage_fill(self, power=None, resolve=None, grid=None, **denoise):
+        """``denoise_coverage`` (same parameters) with option ``coverage_fill`` set for the call: a pixel without samples takes
+        the coverage- and feature-weighted mean of the pixels of its object that have a colour, at the first a-trous level whose
+        weighted sum over them is above 0, and the resolve treats a pixel that has a colour after the last level as one with
+        samples (include/rtpbr.h rtpbr_denoise_coverage).  Returns (``denoise_coverage``'s NoiseStats, (pixels filled, pixels
+        still empty, the deepest level that filled one)).  The option is 0 again afterwards, also when the call is refused.
+        Blocks."""
+        unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise_coverage_fill: unknown denoise parameters {sorted(unknown)}")
+        self.set_option("coverage_fill", 1)
+        try:
+            stats = self.denoise_coverage(power, resolve, grid, **denoise)
+        finally:
+            self.set_option("coverage_fill", 0)
+        return stats, tuple(self.counter(k) for k in ("fill_filled", "fill_empty", "fill_deepest"))
+
     # ------------------------------------------------------------ temporal reuse (include/rtpbr.h rtpbr_reproject)
     def reproject(self, camera: Camera, max_history=None, depth_tolerance=None, normal_cos=None):
         """set_camera(camera) + refresh() that keeps what the new view can reuse: the accumulated image_buffer is warped into

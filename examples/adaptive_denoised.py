@@ -6,10 +6,13 @@ Renderer.render_adaptive, whose stop rule describes the raw average, at the same
     python examples/adaptive_denoised.py --size 256 256 --error 0.03 --max-spp 256
     python examples/adaptive_denoised.py --size 64 64 --max-spp 32 --ref-spp 256       # a run of seconds
     python examples/adaptive_denoised.py --bench             # the calls DESIGN.md section 6j times, at 1920x1080
+    python examples/adaptive_denoised.py --size 64 64 --max-spp 32 --ref-spp 256 --coverage   # ... ending with the coverage-aware level blend
 
 Prints the pixel-samples both loops spent and both results' display RMSE against a converged frame.  The estimate is variance
 only: the denoised frame stops moving early, and what remains of its error is the filter's bias, which more samples of the same
-loop do not remove.  Headless; runs on the HIP library only.
+loop do not remove.  --coverage: the denoised loop ends with the level blend on the coverage-weighted
+filter (render_adaptive_denoised(blend="levels", coverage=True)) instead of denoise().  Headless; runs on the
+HIP library only.
 """
 import argparse
 import os
@@ -28,6 +31,7 @@ ap.add_argument("--batch", type=int, default=4, help="batch of the denoised loop
 ap.add_argument("--dilate", type=int, default=1)
 ap.add_argument("--bounces", type=int, default=4)
 ap.add_argument("--ref-spp", type=int, default=2048, help="samples per pixel of the converged frame (other sample indices)")
+ap.add_argument("--coverage", action="store_true", help='end the denoised loop with blend="levels", coverage=True')
 ap.add_argument("--bench", action="store_true")
 a = ap.parse_args()
 
@@ -75,7 +79,12 @@ ref = np.clip(ref_r.image_pixels, 0, 1).astype(np.float64)
 n_pix = W * H
 
 r = Renderer(scene, cfg)
-traced, stats = r.render_adaptive_denoised(a.error, a.max_spp, a.batch, a.dilate)
+if a.coverage:
+    traced, stats = r.render_adaptive_denoised(a.error, a.max_spp, a.batch, a.dilate, blend="levels", coverage=True)
+    print(f"the loop ended with denoise_blend_levels_coverage: {r.counter('blend_resolved')} pixels resolved, "
+          f"mean depth {float(r.blend_depth.mean()):.2f}")
+else:
+    traced, stats = r.render_adaptive_denoised(a.error, a.max_spp, a.batch, a.dilate)
 r.post_process()
 print(f"render_adaptive_denoised({a.error}): {traced} pixel-samples ({traced / n_pix:.1f} spp mean), "
       f"{stats.pixels_above} of {stats.pixels_estimated} pixels above, largest estimate {stats.max_noise:.4f}")

@@ -930,6 +930,53 @@ int rtpbr_select_blend_error(rtpbr_ctx* ctx, float threshold, int dilate, uint32
 int rtpbr_blend_error_display(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, const rtpbr_blend_params* e, const rtpbr_error_params* w,
                               float threshold, rtpbr_noise_stats* out);
 
+/* ---- The level blend on the coverage-weighted filter (options "blend_coverage", "blend_coverage_grid", "blend_coverage_power",
+ * "blend_coverage_resolve"; counter "blend_resolved").
+ *
+ * The three ladders of the three calls above are rtpbr_denoise's, which never takes a tap across object indices: a silhouette pixel
+ * is pulled to its centre ray's object, the halves read that as bias, and the blend hands the pixel back to its raw average.
+ * rtpbr_denoise_coverage (below) repairs exactly those pixels but is the plain filter only.  With option "blend_coverage" = 1
+ * (rtpbr_set_option; 0 or 1, default 0) rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display — and only they:
+ * rtpbr_denoise, rtpbr_denoise_guided, rtpbr_denoise_coverage, rtpbr_denoise_error, rtpbr_denoise_blend, rtpbr_post_process and
+ * rtpbr_present never read the four options and keep their bytes, and the three calls never read "denoise_fill" or "coverage_fill" —
+ * run the rule below with the rtpbr_coverage_params (grid, power, resolve) = ("blend_coverage_grid": 2 or 4, default 4;
+ * "blend_coverage_power": 0..8, default 4; "blend_coverage_resolve": 0 or 1, default 1).  It applies with K = iterations > 0; with
+ * iterations = 0 there is no level, the options are not read and the bytes are those of "blend_coverage" = 0.  With 0 everything
+ * above holds, bit for bit.
+ *   1. k_q = a_q * a_q * ... (power factors, left to right, 1.0f for power = 0), a_q = (float)n_own_q / (float)n_sub_q of the coverage
+ *      plane, which the call renders first at the option's grid when it is stale (as rtpbr_denoise_coverage does; the plane lives as
+ *      long as the features).
+ *   2. All three chains — image_buffer, half A, half B — run rtpbr_denoise_coverage's level: rtpbr_denoise's tap loop, same inputs,
+ *      same tap order, same clamp and exp, with w = (h exp(-min(e, 80))) k_q for every tap but the centre's own.  k is geometric,
+ *      so the one plane serves all three chains.  F_0 .. F_K of a chain are its levels after remodulation, as above.
+ *   3. The window statistics are unchanged: t_k, T_k = T_(k-1) t_k, RTPBR_BUF_BLEND_WEIGHT = T_K, RTPBR_BUF_BLEND_DEPTH = the sum of
+ *      the T_k, the running colour c = F_0 + the sum of T_k (F_k - F_(k-1)), and c = F_K itself where T_K == 1 — all on these ladders.
+ *   4. After the last level the blended LINEAR colour L_p = c (the value the plain rule hands to the tone map) goes to a private
+ *      (W,H,3) plane; a pixel without samples (image_buffer[p].w == 0) holds +0 there.
+ *   5. The resolve of rtpbr_denoise_coverage, operation for operation, with L in the place of its F and "with samples" =
+ *      image_buffer[q].w > 0: if resolve and n_second_p > 0, E2 = the k-weighted 3x3 mean (weights 1/2 edge, 1/3 corner) of L over
+ *      the neighbours with samples on second_object_p; if its sw > 0, L_p <- ((float)n_own L_p + (float)n_second E2) /
+ *      (float)(n_own + n_second) per channel and the pixel counts as resolved.  RTPBR_BUF_DENOISED_PIXELS = the configured tone map of
+ *      (L_p, 1); a pixel without samples shows what rtpbr_post_process shows, is nobody's tap and nobody's E2 neighbour, is not
+ *      resolved, and has weight 1 and depth K.
+ *   6. RTPBR_BUF_BLEND_ERROR (the two error calls) stays the estimate of the blended frame BEFORE the resolve: XA, XB, their four
+ *      luminances and the slope s are taken at the pre-resolve colour c, exactly as above, on these ladders.  The resolve moves only
+ *      two-object pixels, towards a neighbour mean the halves have no separate view of; an estimate of the resolved frame is not
+ *      made.  The statistics each call returns are its own as above (of T_K, of the error plane), before the resolve.
+ *   The three calls still write the same RTPBR_BUF_DENOISED_PIXELS, RTPBR_BUF_BLEND_WEIGHT and RTPBR_BUF_BLEND_DEPTH as one another.
+ *   So: with "blend_coverage_power" = 0 and "blend_coverage_resolve" = 0 every k is 1.0f and nothing is resolved — every output and
+ *   statistic equals the call with "blend_coverage" = 0, bit for bit; and where no pixel is usable (min_half_samples above every
+ *   half's count) every T is 1: RTPBR_BUF_DENOISED_PIXELS holds rtpbr_denoise_coverage's bytes for the same parameters, the weight is
+ *   1 and the depth K.
+ *   rtpbr_get_counter name "blend_resolved": the pixels the resolve changed in the last such call (option 1, iterations > 0); 0
+ *   before any; it blocks.  rtpbr_denoise_coverage's own count (its pixels_estimated) does not touch it.
+ *   Errors: with the option at 1 and iterations > 0 the calls refuse what rtpbr_denoise_coverage refuses — RTPBR_EINVAL "coverage:
+ *   grid x resolution out of range (1..65535)" when grid * width or grid * height exceeds 65535 — after their own parameter and
+ *   state checks and before anything changes; otherwise they keep their own refusals and state rules.  rtpbr_set_option refuses
+ *   a value out of range for each of the four keys in that key's own words.
+ *   Memory: the coverage plane, its list and the two planes of rtpbr_denoise_coverage (k, 4 bytes; the linear colour, 12 bytes a
+ *   pixel), shared with that call; no buffer id. */
+
 /* ---- Halves dealt per sample and carried through reprojection.
  *
  * Two switches of the section above, both off by default; with the defaults every buffer, counter and timing path is bit for bit
@@ -1202,8 +1249,9 @@ int rtpbr_get_counters(rtpbr_ctx* ctx, rtpbr_counters* out);         /* blocking
 /* One counter by name: the six above, plus "mlp_wave_evals" / "mlp_lane_evals" — 32-ray half passes of the
  * wave-cooperative neural-SDF network (bunny_sdf_glass.py:149-203 on the matrix cores) and the ray evaluations they
  * were needed for; their ratio / 32 is the slot utilisation of the MLP; "fill_filled" / "fill_empty" / "fill_deepest": the last
- * rtpbr_denoise with option denoise_fill = 1 or rtpbr_denoise_coverage with option coverage_fill = 1 (see rtpbr_denoise).  EINVAL
- * for an unknown name. */
+ * rtpbr_denoise with option denoise_fill = 1 or rtpbr_denoise_coverage with option coverage_fill = 1 (see rtpbr_denoise);
+ * "blend_resolved": the pixels the resolve changed in the last rtpbr_denoise_blend_levels / rtpbr_blend_error /
+ * rtpbr_blend_error_display with option blend_coverage = 1 (see rtpbr_blend_error_display).  EINVAL for an unknown name. */
 int rtpbr_get_counter(rtpbr_ctx* ctx, const char* name, unsigned long long* out);
 /* Device time (HIP events on the context's stream) of the trace kernel launches and of
  * all kernels of the last rtpbr_sample() call, in milliseconds (blocking).  Option "timing" = 0 records no events
@@ -1225,6 +1273,10 @@ int rtpbr_get_stream(rtpbr_ctx* ctx, void** stream);
  * "denoise_fill" (this one changes a result, rtpbr_denoise's alone: 1 = pixels without samples are reconstructed from their
  * neighbours, 0 = default; see rtpbr_denoise), "coverage_fill" (the same for rtpbr_denoise_coverage, and its result alone: 1 = pixels
  * without samples are reconstructed inside the coverage-weighted levels and resolved, 0 = default; see rtpbr_denoise_coverage),
+ * "blend_coverage" (changes the results of rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display alone: 1 = their
+ * ladders are the coverage-weighted filter's and two-object pixels are resolved, 0 = default) with "blend_coverage_grid" (2 or 4,
+ * default 4), "blend_coverage_power" (0..8, default 4) and "blend_coverage_resolve" (0 or 1, default 1), the rtpbr_coverage_params of
+ * those calls; see rtpbr_blend_error_display,
  * "drain_lanes" (complete-path pool kernel: once the work has run out and nothing is parked, a wave with at most this many marching
  * lanes finishes their raycasts in the culled wave march of the primary kernel; default 16, 0 = never),
  * "primary_lean" (1, default: the coherent primary-ray kernel marches on in a one-object loop while its whole wave needs one object),

@@ -172,6 +172,7 @@ extern "C" int rtpbr_destroy(rtpbr_ctx* c) {
     (void)hipFree(c->march_out);
     (void)hipFree(c->noise_stats);
     (void)hipFree(c->fill_counts);
+    (void)hipFree(c->blend_resolved);
     (void)hipFree(c->order);
     (void)hipFree(c->plan);
     rt_rccl_release(c);
@@ -2240,7 +2241,12 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
 
 // ---- the same blend across the a-trous levels (level_blend<R, FIRST, LAST>, rt_half.hip), and with `window` the error estimate of
 // its frame (rtpbr_blend_error: the ERR instances and blend_error<R>; `display`, rtpbr_blend_error_display: the slope goes to a
-// plane of its own and the DISPLAY instances read it per tap)
+// plane of its own and the DISPLAY instances read it per tap).
+// Option blend_coverage = 1 with K > 0 (all three calls; with no level the option is not read): the three chains run atrous_level's
+// COVER form on the one plane k of cover_weights, the running colour lives in cov_linear where the LIN last level leaves it
+// linear, and cover_resolve makes RTPBR_BUF_DENOISED_PIXELS from it ("has a colour" = image_buffer's count > 0).  Weight, depth,
+// both sets of statistics and the error plane are those of the colour before the resolve.  cov_k and cov_linear are rtpbr_denoise_coverage's planes: both calls run on the
+// context's one stream and neither keeps them across calls.
 static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_params* p, const rtpbr_blend_params* e,
                         const rtpbr_error_params* w, bool with_error, bool display, float threshold, rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
@@ -2257,6 +2263,10 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     if (int r = half_call_begin(c, BLEND_NO_HALF, who)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     const int K = d.iterations;
+    const bool cover = c->blend_coverage != 0 && K > 0;
+    const rtpbr_coverage_params cv{c->blend_coverage_grid, c->blend_coverage_power, c->blend_coverage_resolve};
+    if (cover && ((long long)cv.grid * c->cfg.width > 65535 || (long long)cv.grid * c->cfg.height > 65535))
+        return fail(RTPBR_EINVAL, "coverage: grid x resolution out of range (1..65535)");      // (coverage_enqueue's, before anything is allocated)
     if (int r = frame_need(c, {ROW_blend_weight, ROW_blend_depth, ROW_levels_scratch})) return r;
     if (with_error)
         if (int r = frame_need(c, {ROW_blend_error, ROW_blend_x})) return r;
@@ -2268,6 +2278,13 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         if (int r = rtpbr_render_features(c)) return r;
     if (int r = half_b_enqueue(c)) return r;
     if (int r = noise_stats_zero(c)) return r;
+    if (cover) {      // the plane (rendered when stale, at the option's grid), the weights and the resolved count at 0, as rtpbr_denoise_coverage
+        if (int r = coverage_enqueue(c, cv)) return r;
+        if (int r = frame_need(c, {ROW_cov_k, ROW_cov_linear})) return r;
+        if (!c->blend_resolved) HIP_TRY(hipMalloc(&c->blend_resolved, sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(c->cov_list + 1, 0, 2 * sizeof(uint32_t), c->stream));
+        launch_cover_weights(coverage_args(c, cv), c->stream);
+    }
     LevelsArgs A{};
     if (with_error) {      // the ERR instances: XA and XB beside the frame, the slope into the error plane (display: into its own)
         A.xa = c->blend_x;
@@ -2297,6 +2314,10 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     // the K levels of the three chains in lock step through the non-last instances: chain j keeps level k in plane 2 j + (k & 1),
     // so level k - 1 is still there when the window kernel compares the two
     DenoiseArgs F = denoise_args(c, d.demodulate, inv);
+    if (cover) {
+        F.cover_k = c->cov_k;      // k is geometric: one plane for the three chains
+        A.out = c->cov_linear;     // the running colour and, after the LIN last level, what the resolve reads
+    }
     const float4* const chain_in[3] = {c->image_buffer, c->half_a, c->half_b};
     for (int k = 0; k < K; k++) {      // k + 1 is the level's number in include/rtpbr.h
         const bool first = k == 0, last = k + 1 == K;
@@ -2310,7 +2331,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
             F.image_buffer = chain_in[j];
             F.src = before[j];
             F.dst = now[j];
-            launch_atrous_level(F, first, false, false, c->stream);
+            launch_atrous_level(F, first, false, false, c->stream, false, cover);
         }
         A.kd = now[0];
         A.ka = now[1];
@@ -2318,7 +2339,24 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         A.pd = before[0];
         A.pa = before[1];
         A.pb = before[2];
-        launch_level_blend(A, first, last, c->stream);
+        launch_level_blend(A, first, last, c->stream, cover);
+    }
+    if (cover) {      // the resolve and the tone map of every pixel, from the blended linear colour
+        ResolveArgs R{};
+        R.cfg = c->cfg;
+        R.image_buffer = c->image_buffer;
+        R.linear = c->cov_linear;
+        R.object = c->feat_object;
+        R.coverage = c->coverage;
+        R.k = c->cov_k;
+        R.head = c->cov_list;
+        R.out = c->denoised;
+        R.width = c->cfg.width;
+        R.height = c->cfg.height;
+        R.resolve = cv.resolve;
+        R.live = nullptr;
+        launch_cover_resolve(R, c->stream);
+        HIP_TRY(hipMemcpyAsync(c->blend_resolved, c->cov_list + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(hipGetLastError());
     if (!with_error) return noise_stats_read(c, out);
@@ -2677,6 +2715,17 @@ extern "C" int rtpbr_get_counter(rtpbr_ctx* c, const char* name, unsigned long l
             }
         }
     }
+    else if (!strcmp(name, "blend_resolved")) {
+        // the pixels the resolve changed in the last rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_blend_error_display with
+        // option blend_coverage = 1 and iterations > 0 (0 before any)
+        *out = 0;
+        if (c->blend_resolved) {
+            uint32_t v = 0;
+            HIP_TRY(hipMemcpyAsync(&v, c->blend_resolved, sizeof v, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            *out = v;
+        }
+    }
     else return fail(RTPBR_EINVAL, "unknown counter %s", name);
     return RTPBR_OK;
 }
@@ -2764,6 +2813,10 @@ static const OptionRow OPTION_ROWS[] = {
     OPTION(cover_blocks, 0, 65535, false, "cover_blocks must be 0 (automatic) .. 65535"),
     OPTION(denoise_fill, 0, 1, false, "denoise_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise reconstructs them from their neighbours)"),
     OPTION(coverage_fill, 0, 1, false, "coverage_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise_coverage reconstructs them from their neighbours)"),
+    OPTION(blend_coverage, 0, 1, false, "blend_coverage must be 0 (the plain filter's ladders) or 1 (rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display run the coverage-weighted ladders and the edge resolve)"),
+    OPTION(blend_coverage_grid, 2, 4, false, "blend_coverage_grid must be 2 or 4"),      // (3: refused in rtpbr_set_option)
+    OPTION(blend_coverage_power, 0, 8, false, "blend_coverage_power must be 0..8"),
+    OPTION(blend_coverage_resolve, 0, 1, false, "blend_coverage_resolve must be 0 or 1"),
     OPTION(ready_low, 0, 63, false, "ready_low must be 0..63"),
     OPTION(refill_lanes, 1, 64, false, "refill_lanes must be 1..64"),
     // 1 (default): rtpbr_sample() brackets its kernels with events (rtpbr_last_sample_ms / rtpbr_last_primary_ms); 0: none — an event
@@ -2794,6 +2847,7 @@ extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value) 
     for (const OptionRow& o : OPTION_ROWS)
         if (!strcmp(key, o.key)) {
             if (value < o.lo || value > o.hi) return fail(RTPBR_EINVAL, o.refusal);
+            if (o.member == &rtpbr_ctx::blend_coverage_grid && value == 3) return fail(RTPBR_EINVAL, o.refusal);      // (the one row with a gap)
             c->*o.member = (int)value;
             if (o.replan) {
                 c->order_valid = false;

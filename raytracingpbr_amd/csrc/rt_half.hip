@@ -269,6 +269,9 @@ __global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
 // two texels).  LAST hands blend_error<R> what it stages — (lum XA, display lum XA, lum XB, display lum XB) in the first plane —
 // and the slope s of the display luminance at the blended colour in the error plane, so the tone map runs per pixel and never per
 // staged entry.  The instances without ERR keep their code.
+// LIN (LAST only; option blend_coverage = 1): the last level stores the blended linear colour, +0 for a pixel without samples, in
+// the place of the display colour — A.out is a private plane in these calls, and cover_resolve tone-maps from it.  With ERR the
+// display colour is still computed, for the slope alone.  12 bytes written per pixel either way.
 RT_D vec3 lv_albedo(const LevelsArgs& A, size_t i) {
     if (!A.demodulate) return mk(1.0f, 1.0f, 1.0f);
     return mk(fmax_(A.albedo[i * 3 + 0], 1e-3f), fmax_(A.albedo[i * 3 + 1], 1e-3f), fmax_(A.albedo[i * 3 + 2], 1e-3f));
@@ -298,8 +301,9 @@ RT_D float4 lv_lums(const rtpbr_config& cfg, vec3 xa, vec3 xb) {
                        nz_lum(tone_map(cfg, make_float4(xb.x, xb.y, xb.z, 1.0f))));
 }
 
-template <int R, bool FIRST, bool LAST, bool ERR = false>
+template <int R, bool FIRST, bool LAST, bool ERR = false, bool LIN = false>
 __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
+    static_assert(LAST || !LIN, "the linear exit is a last level's");
     __shared__ float t_a[Win<R>::WORDS];
     __shared__ float t_q[Win<R>::WORDS];
     __shared__ float t_x[Win<R>::WORDS];
@@ -402,11 +406,12 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
             if (T == 1.0f) c = fk;      // every t_k was 1: rtpbr_denoise's bytes
             // (no samples: what post_process shows; T = 1 and depth = K by the sums above)
             const vec3 lin = c;
-            c = b.w > 0.0f ? tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)) : tone_map(A.cfg, b);
+            if constexpr (!LIN || ERR) c = b.w > 0.0f ? tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)) : tone_map(A.cfg, b);
             if constexpr (ERR) {
                 A.xa[p] = lv_lums(A.cfg, xa, xb);
                 A.slope[p] = b.w > 0.0f ? lv_slope(A.cfg, lin, c) : 0.0f;
             }
+            if constexpr (LIN) c = b.w > 0.0f ? lin : mk(0.0f, 0.0f, 0.0f);
         }
         A.weight[p] = T;
         A.depth[p] = depth;
@@ -555,24 +560,27 @@ void launch_half_blend(const BlendArgs& A, hipStream_t st) {
 }
 
 template <int R, bool ERR>
-static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hipStream_t st) {
+static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin) {
     const dim3 grid = tile_grid(A.width, A.height);
-    if (first && last) hipLaunchKernelGGL((level_blend<R, true, true, ERR>), grid, dim3(256), 0, st, A);
+    if (lin && first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, true>), grid, dim3(256), 0, st, A);
+    else if (lin) hipLaunchKernelGGL((level_blend<R, false, true, ERR, true>), grid, dim3(256), 0, st, A);
+    else if (first && last) hipLaunchKernelGGL((level_blend<R, true, true, ERR>), grid, dim3(256), 0, st, A);
     else if (first) hipLaunchKernelGGL((level_blend<R, true, false, ERR>), grid, dim3(256), 0, st, A);
     else if (last) hipLaunchKernelGGL((level_blend<R, false, true, ERR>), grid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL((level_blend<R, false, false, ERR>), grid, dim3(256), 0, st, A);
 }
 
-// no level (first && last && no records): the K = 0 pass.  A.xa (rtpbr_blend_error): the ERR instances
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st) {
+// no level (first && last && no records): the K = 0 pass.  A.xa (rtpbr_blend_error): the ERR instances.  lin (with last and
+// records only): the LIN instances
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin) {
     if (!A.kd) {
         if (A.xa) hipLaunchKernelGGL(level_blend_none<true>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         else hipLaunchKernelGGL(level_blend_none<false>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         return;
     }
     with_radius(A.radius, [&](auto r) {
-        if (A.xa) launch_level_blend_r<decltype(r)::value, true>(A, first, last, st);
-        else launch_level_blend_r<decltype(r)::value, false>(A, first, last, st);
+        if (A.xa) launch_level_blend_r<decltype(r)::value, true>(A, first, last, st, lin && last);
+        else launch_level_blend_r<decltype(r)::value, false>(A, first, last, st, lin && last);
     });
 }
 

@@ -36,6 +36,11 @@
 //                       window kernel stages — (lum XA, display lum XA, lum XB, display lum XB) — and in the error plane the
 //                       slope s of the display luminance at the blended colour: the tone map runs four times per pixel here and
 //                       never per staged entry.
+//   level_blend<.., LIN> the last level of the three calls with option blend_coverage = 1 (the chains then ran atrous_level's COVER
+//                       form): the blended linear colour — exactly the value the other form hands to tone_map, +0 for a pixel
+//                       without samples — stays in `out`, for these calls a private (W,H,3) plane that carried the running colour of
+//                       the levels before, from which cover_resolve (rt_coverage.hip) makes RTPBR_BUF_DENOISED_PIXELS.  Weight, depth, statistics and with ERR the slope and the four luminances are
+//                       those of the pre-resolve colour, computed as without LIN.
 //   blend_error<R>      rtpbr_blend_error's window kernel, in half_error<R>'s layout with four planes (e_q, x_q, usable_q, object):
 //                       e_q is half_error's with the blended halves' display luminances, x_q the product of the halves' (blended -
 //                       raw) in linear luminance; the lane sums both over the window on its object and writes the root of
@@ -105,7 +110,8 @@ struct LevelsArgs {
     const int32_t* object;        // RTPBR_BUF_FEAT_OBJECT
     float* weight;                // in / out: the running T_k; RTPBR_BUF_BLEND_WEIGHT after LAST
     float* depth;                 // in / out: the running sum of T_k; RTPBR_BUF_BLEND_DEPTH
-    float* out;                   // in / out: the running linear colour; LAST: RTPBR_BUF_DENOISED_PIXELS
+    float* out;                   // in / out: the running linear colour; LAST: RTPBR_BUF_DENOISED_PIXELS (LIN instances: a private plane that
+                                  // stays linear, +0 without samples — the struct does not grow, so every other instance keeps its kernarg offsets)
     NoiseStats* stats;            // out (zeroed before the launches; LAST adds to it)
     float4* xa;                   // ERR instances, in / out: the running XA; after LAST (lum XA, display lum XA, lum XB, display lum XB)
     float4* xb;                   // ... the running XB
@@ -134,7 +140,7 @@ struct BlendErrorArgs {
 };
 
 void launch_half_update(const HalfArgs& A, hipStream_t st);
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st);      // A.xa != nullptr: the ERR instances
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin = false);      // A.xa != nullptr: the ERR instances; lin: the last level's LIN instance (A.out stays linear)
 void launch_blend_error(const BlendErrorArgs& A, hipStream_t st);
 void launch_half_blend(const BlendArgs& A, hipStream_t st);
 void launch_half_subtract(const HalfArgs& A, hipStream_t st);

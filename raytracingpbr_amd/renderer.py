@@ -521,13 +521,51 @@ class Renderer:
         e = BlendParams.pack(True, radius, z, min_half_samples)
         return self._stats(entry, _ref(p), _ref(e), _ref(ErrorParams.pack(True, window)), float(threshold))
 
+    # ------------------------------------------------------------ the level blend on the coverage-weighted filter (include/rtpbr.h, option blend_coverage)
+    def _with_blend_coverage(self, power, resolve, grid, call):
+        """``call()`` with option ``blend_coverage`` set and its three parameters (``None`` = the library's default); the option is
+        0 again afterwards, also when the call is refused.  Returns (what ``call`` returns, counter ``blend_resolved``)."""
+        cv = CoverageParams.pack(False, grid, power, resolve)
+        self.set_option("blend_coverage", 1)
+        try:
+            for key in ("grid", "power", "resolve"):
+                self.set_option("blend_coverage_" + key, getattr(cv, key))
+            stats = call()
+        finally:
+            self.set_option("blend_coverage", 0)
+        return stats, self.counter("blend_resolved")
+
+    def denoise_blend_levels_coverage(self, power=None, resolve=None, grid=None, radius=None, z=None, min_half_samples=None, **denoise):
+        """``denoise_blend_levels`` (same parameters) on the coverage-weighted filter: the three ladders are ``denoise_coverage``'s
+        levels (every tap weighted by (its pixel's own-object coverage)^``power``, at ``grid`` x ``grid`` sub-rays), the windows'
+        rule is unchanged, and the pixels that hold two objects are resolved from the blended linear frame (``resolve``) before
+        the tone map.  ``blend_weight`` and ``blend_depth`` are the ladder's.  Returns (``denoise_blend_levels``' NoiseStats, the
+        pixels the resolve changed).  Blocks."""
+        unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
+        if unknown:
+            raise TypeError(f"denoise_blend_levels_coverage: unknown denoise parameters {sorted(unknown)}")
+        return self._with_blend_coverage(power, resolve, grid, lambda: self.denoise_blend_levels(radius, z, min_half_samples, **denoise))
+
+    def blend_error_coverage(self, threshold: float = 0.0, power=None, resolve=None, grid=None, radius=None, z=None,
+                             min_half_samples=None, window=None, bias="linear", **denoise):
+        """``blend_error`` (same parameters) on the coverage-weighted filter, as ``denoise_blend_levels_coverage``: the same
+        ``denoised_pixels``, ``blend_weight`` and ``blend_depth``, and ``blend_error_map`` as the estimate of the blended frame
+        BEFORE the resolve.  Returns (``blend_error``'s NoiseStats, the pixels the resolve changed).  Blocks."""
+        unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
+        if unknown:
+            raise TypeError(f"blend_error_coverage: unknown denoise parameters {sorted(unknown)}")
+        if bias not in ("linear", "display"):
+            raise ValueError('bias must be "linear" or "display"')
+        return self._with_blend_coverage(power, resolve, grid,
+                                         lambda: self.blend_error(threshold, radius, z, min_half_samples, window, bias=bias, **denoise))
+
     def select_blend_error(self, threshold: float, dilate: int = 0) -> int:
         """select_error's rule on ``blend_error_map`` as the last blend_error() wrote it (not recomputed).  Returns how many
         pixels are selected.  Blocks."""
         return self._count("select_blend_error", float(threshold), int(dilate))
 
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
-                                 blend=False, *, stop="filter", bias="linear", **denoise_params):
+                                 blend=False, *, stop="filter", bias="linear", coverage=None, **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -542,7 +580,10 @@ class Renderer:
         ``stop``: "filter" (the default) is the rule above.  "blend" (with ``blend="levels"`` only) loops on blend_error(error)
         -> select_blend_error(error, dilate) instead: the estimate is the error of the level-blended frame, variance and the
         bias the halves can see, and the call ends with the frame the last blend_error() wrote.
-        ``bias`` (with ``stop="blend"`` only): blend_error's ``bias``, "linear" (the default) or "display"."""
+        ``bias`` (with ``stop="blend"`` only): blend_error's ``bias``, "linear" (the default) or "display".
+        ``coverage`` (with ``blend="levels"`` only): ``None`` (the default) leaves the loop as it is; True or a dict of
+        ``power`` / ``resolve`` / ``grid`` makes the ending denoise_blend_levels() and the blend_error() estimates of
+        ``stop="blend"`` the coverage-weighted calls (denoise_blend_levels_coverage, blend_error_coverage)."""
         if isinstance(blend, str) and blend != "levels":
             raise ValueError('blend must be True, False or "levels"')
         if stop not in ("filter", "blend"):
@@ -553,6 +594,13 @@ class Renderer:
             raise ValueError('bias must be "linear" or "display"')
         if bias != "linear" and stop != "blend":
             raise ValueError('bias selects the rule of blend_error(): stop must be "blend"')
+        if coverage is not None:
+            if coverage is True:
+                coverage = {}
+            if not isinstance(coverage, dict) or set(coverage) - {"power", "resolve", "grid"}:
+                raise ValueError("coverage must be None, True or a dict of power / resolve / grid")
+            if blend != "levels":
+                raise ValueError('coverage selects the coverage-weighted level blend: blend must be "levels"')
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
@@ -568,7 +616,9 @@ class Renderer:
                     self.half_update()
                 traced, used = traced + n_pix * n, used + n
             while True:
-                if stop == "blend":
+                if stop == "blend" and coverage is not None:
+                    stats = self.blend_error_coverage(error, bias=bias, **coverage, **denoise_params)[0]
+                elif stop == "blend":
                     stats = self.blend_error(error, bias=bias, **denoise_params)
                 else:
                     stats = self.denoise_error(error, **denoise_params)
@@ -581,6 +631,8 @@ class Renderer:
                 traced, used = traced + n_sel * batch, used + batch
             if stop == "blend":
                 pass      # (the last blend_error() wrote the frame of the whole buffer)
+            elif blend == "levels" and coverage is not None:
+                self.denoise_blend_levels_coverage(**coverage, **denoise_params)
             elif blend == "levels":
                 self.denoise_blend_levels(**denoise_params)
             elif blend:

@@ -4,6 +4,7 @@
     python examples/adaptive_flythrough.py                       # Cornell v3 at 256x256, the 11 moves of reproject_flythrough.py
     python examples/adaptive_flythrough.py --size 64 64 --ref-spp 256 --frames 4      # a run of seconds
     python examples/adaptive_flythrough.py --bench               # the calls DESIGN.md section 6k times, at 1920x1080
+    python examples/adaptive_flythrough.py --show-moves          # what a viewer sees right after each move, before any new sample
 
 Every frame after the first is reproject(camera) + render_adaptive_denoised(error, max_spp, batch): two full-frame batches, then
 denoise_error -> select_error -> sample_selected until the estimated noise of the denoised picture is under ``error``.  Four
@@ -11,7 +12,10 @@ settings:
     warp off / on        reproject zeroes half A (the whole history lies in B) / carries it with the image;
     per_sample off / on  a batch goes whole to one half (half_update after each call) / every sample is dealt by the sample call.
 Per frame it prints the pixel-samples each setting spent and the display RMSE of its denoised frame against a converged frame at
-that camera (independent samples).  Headless; runs on the HIP library only.
+that camera (independent samples).  --show-moves runs one more pass with warp on and samples dealt per sample, and shows each
+moved frame BEFORE any new sample: denoise_blend_levels(fill=True) (option blend_fill: the disoccluded pixels filled by the level
+blend's own ladders) against denoise_blend_levels (the same frame with its holes) and denoise_fill; then the frame's loop runs as
+in the other settings, ending with the level blend.  Headless; runs on the HIP library only.
 """
 import argparse
 import os
@@ -32,6 +36,7 @@ ap.add_argument("--dilate", type=int, default=1)
 ap.add_argument("--bounces", type=int, default=3)
 ap.add_argument("--ref-spp", type=int, default=1024, help="samples per pixel of the converged frames (other sample indices)")
 ap.add_argument("--bench", action="store_true")
+ap.add_argument("--show-moves", action="store_true")
 a = ap.parse_args()
 
 
@@ -138,3 +143,21 @@ moved = slice(1, None) if len(cams) > 1 else slice(0, None)
 print(" mean  " + "  ".join(f"{np.mean([t for t, _, _ in rows[s][moved]]) / n_pix:14.2f} / {np.mean([e for _, e, _ in rows[s][moved]]):.4f}     "
                              for s in SETTINGS) + "  (moved frames)")
 print("final  " + "  ".join(f"{'RMSE':>14s} / {rows[s][-1][1]:.4f}     " for s in SETTINGS))
+
+if a.show_moves:      # each moved frame as a viewer meets it: warped history, no new sample yet
+    r = Renderer(scene, cfg, cams[0])
+    r.set_half_mode(per_sample=True, warp=True)
+    r.refresh()
+    print("right after each move, before any new sample (warp on, per_sample on): pixels without samples / filled / still empty; display RMSE "
+          "of denoise_blend_levels with its holes, denoise_fill, denoise_blend_levels(fill=True)")
+    for k, cam in enumerate(cams):
+        if k:
+            r.reproject(cam)
+            without = int((r.image_buffer[..., 3] == 0).sum())
+            r.denoise_blend_levels()
+            e_holes = rmse(r.denoised_pixels, refs[k])
+            r.denoise_fill()
+            e_fill = rmse(r.denoised_pixels, refs[k])
+            _, (filled, empty, _) = r.denoise_blend_levels(fill=True)
+            print(f"move {k:3d}: {without:6d} / {filled:6d} / {empty:6d}   {e_holes:.4f}  {e_fill:.4f}  {rmse(r.denoised_pixels, refs[k]):.4f}")
+        r.render_adaptive_denoised(a.error, a.max_spp, a.batch, a.dilate, per_sample=True, blend="levels")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Whole frames from a fraction of the pixels: sparse sampling on a lattice, completed by the filling denoise.
 
-    python examples/sparse_preview.py [--size 256 256] [--spp 4] [--period 2 2] [--out out/sparse] [--coverage-fill] [--bench]
+    python examples/sparse_preview.py [--size 256 256] [--spp 4] [--period 2 2] [--out out/sparse] [--coverage-fill] [--blend] [--bench]
 
 Cornell v3.  First view: select_lattice -> sample_selected -> denoise_fill (rtpbr_denoise with option denoise_fill = 1: a pixel
 without samples takes the feature-weighted mean of the sampled pixels of its object) -> present("denoised").  Then the camera
@@ -11,7 +11,10 @@ which every pixel has samples.  Every step's frame is written as an image, next 
 --bench prints blocking wall times of each step, and of select_lattice by itself: its mask is built on the host and crosses to the
 device on every call.  --coverage-fill fills with denoise_coverage_fill instead (rtpbr_denoise_coverage with option coverage_fill =
 1: the holes filled inside the coverage-weighted levels, the two-object pixels resolved, filled ones included) and shows the holes
-with denoise_coverage.  Runs on the HIP library only.
+with denoise_coverage.  --blend fills with the level blend instead (denoise_blend_levels(fill=True): rtpbr_denoise_blend_levels with
+option blend_fill = 1; with --coverage-fill its coverage-weighted form): the samples are dealt to the two halves as they are traced
+and the halves are carried through the move (set_half_mode(per_sample=True, warp=True)), so the best filter of the library shows
+every one of these frames without holes; the holes are shown with denoise_blend_levels.  Runs on the HIP library only.
 """
 import argparse
 import os
@@ -27,6 +30,7 @@ ap.add_argument("--spp", type=int, default=4)
 ap.add_argument("--period", type=int, nargs=2, default=(2, 2))
 ap.add_argument("--out", default="out/sparse")
 ap.add_argument("--coverage-fill", action="store_true")
+ap.add_argument("--blend", action="store_true")
 ap.add_argument("--bench", action="store_true")
 a = ap.parse_args()
 
@@ -34,19 +38,30 @@ W, H = a.size
 period = tuple(a.period)
 scene, cfg = cornell_box("v3", aspect=W / H), Config.cornell_v3(W, H, 0, 3)
 r = Renderer(scene, cfg)
+if a.blend:
+    r.set_half_mode(per_sample=True, warp=True)
 os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
 
 
 def fill():
+    if a.blend:
+        return (r.denoise_blend_levels_coverage(fill=True) if a.coverage_fill else r.denoise_blend_levels(fill=True))[1]
     return r.denoise_coverage_fill()[1] if a.coverage_fill else r.denoise_fill()
+
+
+def holes():
+    if a.blend:
+        return r.denoise_blend_levels_coverage() if a.coverage_fill else r.denoise_blend_levels()
+    return r.denoise_coverage() if a.coverage_fill else r.denoise()
 
 
 def show(step):
     filled, empty, deepest = fill()
     r.save_image(f"{a.out}_{step}_filled.png", "denoised")
-    r.denoise_coverage() if a.coverage_fill else r.denoise()
+    depth = f", mean blend depth {float(r.blend_depth.mean()):.2f}" if a.blend else ""
+    holes()
     r.save_image(f"{a.out}_{step}_holes.png", "denoised")
-    print(f"{step}: {filled} pixels filled, {empty} still empty, deepest level {deepest}")
+    print(f"{step}: {filled} pixels filled, {empty} still empty, deepest level {deepest}{depth}")
 
 
 # the first view: one pixel of every cell
@@ -91,6 +106,9 @@ if a.bench:
     r.select_lattice(period, (0, 0))
     r.refresh()
     r.sample_selected(a.spp)
+    if a.blend:
+        print(f"  denoise_blend_levels(fill=True) {ms(lambda: r.denoise_blend_levels(fill=True)):.3f}, "
+              f"denoise_blend_levels {ms(r.denoise_blend_levels):.3f}")
     if a.coverage_fill:
         print(f"  denoise_coverage_fill {ms(r.denoise_coverage_fill):.3f}, denoise_coverage {ms(r.denoise_coverage):.3f}")
     print(f"  denoise_fill {ms(r.denoise_fill):.3f}, denoise {ms(r.denoise):.3f}, present {ms(lambda: r.present('denoised')):.3f}, "

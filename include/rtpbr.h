@@ -977,6 +977,49 @@ int rtpbr_blend_error_display(rtpbr_ctx* ctx, const rtpbr_denoise_params* p, con
  *   Memory: the coverage plane, its list and the two planes of rtpbr_denoise_coverage (k, 4 bytes; the linear colour, 12 bytes a
  *   pixel), shared with that call; no buffer id. */
 
+/* ---- The level blend that fills pixels without samples (option "blend_fill"; counters "fill_filled", "fill_empty", "fill_deepest").
+ *
+ * In the three calls above a pixel whose count is 0 is no tap of any of the three ladders and is shown as rtpbr_post_process shows
+ * it: a frame after rtpbr_reproject, or one traced on a lattice (rtpbr_select_mask + rtpbr_sample_selected), keeps its holes.  With
+ * option "blend_fill" = 1 (rtpbr_set_option; 0 or 1, default 0) rtpbr_denoise_blend_levels, rtpbr_blend_error and
+ * rtpbr_blend_error_display — and only they: every other call never reads the option and keeps its bytes, and the three calls never
+ * read "denoise_fill" or "coverage_fill" — run the rule below.  It applies with K = iterations > 0; with iterations = 0 there is no
+ * level to fill from, the option is not read, the holes stay and the three counters keep what they held.  With 0 everything above
+ * holds, bit for bit.
+ *   1. All three chains — image_buffer, half A, half B — run the filling level of rtpbr_denoise with option "denoise_fill" = 1 (see
+ *      rtpbr_denoise): a pixel that holds no colour at a level (count 0 at level 1; not filled by an earlier level later) runs the
+ *      same tap loop over the pixels of ITS object index that hold one, with the colour term of e taken as +0 (e = 0.0f; e = e +
+ *      the normal term; e = e + the depth term), and holds the quotient s / sw from the next level on when sw > 0; otherwise it
+ *      stays without a colour.  With option "blend_coverage" = 1 the chains run the filling level of rtpbr_denoise_coverage with
+ *      option "coverage_fill" = 1 instead: every tap such a centre takes is weighted by k_q as well, on the one plane k.  A pixel that
+ *      holds a colour runs its level exactly as without the option, and the pixels filled before are among its taps.  Each chain
+ *      fills its own empty pixels: a pixel with samples in one half only (one sample: A = 1, B = 0) is filled in the other half's
+ *      ladder.  F_0 .. F_K of a chain are its levels after remodulation, +0 where a level holds no colour.
+ *   2. Pixels with samples (image_buffer[p].w > 0): everything above, on these ladders — the same usable test (cA >= m and cB >= m:
+ *      a pixel whose count is 0 has cA + cB = 0 and m >= 1, so it is never usable and enters nobody's window sums), the same
+ *      windows, t_k, T_k, depth, running colour, statistics, XA, XB, slope and error plane.
+ *   3. A pixel whose count is 0, after the last level: if level K of image_buffer's chain holds a colour for it, it is shown with
+ *      every t_k = 1 — RTPBR_BUF_DENOISED_PIXELS = the configured tone map of (F_K, 1), the remodulated last level by the pixel's own
+ *      albedo, RTPBR_BUF_BLEND_WEIGHT holds 1 and RTPBR_BUF_BLEND_DEPTH holds K.  If it holds none (no pixel of its object with a colour within
+ *      reach: 2 + 4 + .. + 2^K pixels along an axis) it is shown as rtpbr_post_process shows it, with weight 1 and depth 0.
+ *   4. With "blend_coverage" = 1 the private linear plane L holds F_K for a filled pixel and +0 for one still empty, the last level
+ *      writes beside it who has a colour (samples, or filled), and the resolve runs as rtpbr_denoise_coverage's with option
+ *      "coverage_fill" = 1: the centre is resolved, and a neighbour serves in E2, exactly when it has a colour.  A filled pixel
+ *      can be resolved and counts in "blend_resolved"; a pixel still empty shows what rtpbr_post_process shows.
+ *   5. Every estimate and selection still sees a filled pixel as a pixel without samples: RTPBR_BUF_BLEND_ERROR holds 0 for it, its
+ *      slope is 0, the statistics do not count it, and rtpbr_select_error / rtpbr_select_blend_error select it as they select a
+ *      pixel without samples.  No error estimate of the filled colour is made.
+ *   So: where image_buffer and both halves have no empty pixel, every output and statistic equals the call with "blend_fill" = 0,
+ *   bit for bit; where no pixel is usable (min_half_samples above every half's count) RTPBR_BUF_DENOISED_PIXELS holds the bytes of
+ *   rtpbr_denoise with "denoise_fill" = 1 (with "blend_coverage": of rtpbr_denoise_coverage with "coverage_fill" = 1) for the same
+ *   parameters, and the three counters are that call's.
+ *   rtpbr_get_counter names "fill_filled", "fill_empty", "fill_deepest" describe image_buffer's chain of the last filling call of ANY
+ *   kind (this one, rtpbr_denoise with "denoise_fill" = 1, rtpbr_denoise_coverage with "coverage_fill" = 1; iterations > 0): the pixels
+ *   without samples that hold a colour after level K, those that hold none, and the highest level, counted from 0, that filled one.
+ *   The halves' chains are not counted.
+ *   Errors: the calls keep their refusals and state rules.  rtpbr_set_option refuses a value other than 0 and 1 in the option's own
+ *   words.  Memory: no buffer id; with "blend_coverage" the byte plane of rtpbr_denoise_coverage's filling form (1 byte a pixel). */
+
 /* ---- Halves dealt per sample and carried through reprojection.
  *
  * Two switches of the section above, both off by default; with the defaults every buffer, counter and timing path is bit for bit
@@ -1163,7 +1206,8 @@ int rtpbr_present(rtpbr_ctx* ctx, const rtpbr_present_params* p);   /* NULL = th
  *   resolve = 0 gives the bytes and the counters of rtpbr_denoise with option denoise_fill = 1.  image_buffer, the features, the
  *   coverage plane's contents, the selection, the work counters and sample_base are untouched; the refusals are those above.
  *   rtpbr_get_counter names "fill_filled", "fill_empty" and "fill_deepest" (defined at rtpbr_denoise) describe the last filling call
- *   of EITHER kind: rtpbr_denoise with denoise_fill = 1 or rtpbr_denoise_coverage with coverage_fill = 1, iterations > 0.
+ *   of ANY kind: rtpbr_denoise with denoise_fill = 1, rtpbr_denoise_coverage with coverage_fill = 1 or a level blend call with
+ *   blend_fill = 1 (image_buffer's chain), iterations > 0.
  *   Keeps one more (W,H) 1-byte plane (who has a colour after the last level: written by that level, read by the resolve; no
  *   buffer id), made by the first such call and freed by rtpbr_set_config with a new resolution. */
 typedef struct rtpbr_coverage_params {   /* 4-byte members, no padding */
@@ -1249,7 +1293,8 @@ int rtpbr_get_counters(rtpbr_ctx* ctx, rtpbr_counters* out);         /* blocking
 /* One counter by name: the six above, plus "mlp_wave_evals" / "mlp_lane_evals" — 32-ray half passes of the
  * wave-cooperative neural-SDF network (bunny_sdf_glass.py:149-203 on the matrix cores) and the ray evaluations they
  * were needed for; their ratio / 32 is the slot utilisation of the MLP; "fill_filled" / "fill_empty" / "fill_deepest": the last
- * rtpbr_denoise with option denoise_fill = 1 or rtpbr_denoise_coverage with option coverage_fill = 1 (see rtpbr_denoise);
+ * rtpbr_denoise with option denoise_fill = 1, rtpbr_denoise_coverage with option coverage_fill = 1 (see rtpbr_denoise) or level
+ * blend call with option blend_fill = 1 (image_buffer's chain; see rtpbr_blend_error_display);
  * "blend_resolved": the pixels the resolve changed in the last rtpbr_denoise_blend_levels / rtpbr_blend_error /
  * rtpbr_blend_error_display with option blend_coverage = 1 (see rtpbr_blend_error_display).  EINVAL for an unknown name. */
 int rtpbr_get_counter(rtpbr_ctx* ctx, const char* name, unsigned long long* out);
@@ -1276,7 +1321,8 @@ int rtpbr_get_stream(rtpbr_ctx* ctx, void** stream);
  * "blend_coverage" (changes the results of rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display alone: 1 = their
  * ladders are the coverage-weighted filter's and two-object pixels are resolved, 0 = default) with "blend_coverage_grid" (2 or 4,
  * default 4), "blend_coverage_power" (0..8, default 4) and "blend_coverage_resolve" (0 or 1, default 1), the rtpbr_coverage_params of
- * those calls; see rtpbr_blend_error_display,
+ * those calls; see rtpbr_blend_error_display, "blend_fill" (changes the results of the same three calls alone: 1 = their ladders fill
+ * the pixels without samples and the frame shows them, 0 = default),
  * "drain_lanes" (complete-path pool kernel: once the work has run out and nothing is parked, a wave with at most this many marching
  * lanes finishes their raycasts in the culled wave march of the primary kernel; default 16, 0 = never),
  * "primary_lean" (1, default: the coherent primary-ray kernel marches on in a one-object loop while its whole wave needs one object),

@@ -1539,6 +1539,16 @@ static DenoiseArgs denoise_args(rtpbr_ctx* c, int demodulate, const float* inv) 
 // coverage-weighted levels.  fill (rtpbr_denoise with option denoise_fill = 1; plain, no in / out, iterations > 0): the filling levels,
 // which count into fill_counts (zeroed on the stream first).  fill with cover_k (rtpbr_denoise_coverage with option coverage_fill = 1):
 // the coverage-weighted filling levels; the last writes cov_live (the caller has allocated it) beside out.
+// The shards the filling kernels count into, zeroed on the stream: the call's own (what counters "fill_*" read), and behind them a
+// second set nobody reads (the half chains of the level blend with option blend_fill = 1 count there).
+constexpr size_t FILL_COUNT_WORDS = (size_t)FILL_SHARDS * FILL_SHARD_WORDS;
+static int fill_counts_zero(rtpbr_ctx* c) {
+    constexpr size_t bytes = 2 * FILL_COUNT_WORDS * sizeof(uint32_t);
+    if (!c->fill_counts) HIP_TRY(hipMalloc(&c->fill_counts, bytes));
+    HIP_TRY(hipMemsetAsync(c->fill_counts, 0, bytes, c->stream));
+    return RTPBR_OK;
+}
+
 static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
                           const float4* in = nullptr, float* out = nullptr, bool linear = false, const float* cover_k = nullptr,
                           bool fill = false) {
@@ -1550,9 +1560,7 @@ static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const fl
     A.out = out ? out : c->denoised;
     if (cover_k) A.cover_k = cover_k;      // (shares var0's word: never with g)
     if (fill) {
-        constexpr size_t bytes = (size_t)FILL_SHARDS * FILL_SHARD_WORDS * sizeof(uint32_t);
-        if (!c->fill_counts) HIP_TRY(hipMalloc(&c->fill_counts, bytes));
-        HIP_TRY(hipMemsetAsync(c->fill_counts, 0, bytes, c->stream));
+        if (int r = fill_counts_zero(c)) return r;
         A.fill = c->fill_counts;           // (shares vsrc's word: never with g)
         if (cover_k) A.live = c->cov_live; // (shares vdst's word: never with g)
     }
@@ -2247,6 +2255,10 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
 // linear, and cover_resolve makes RTPBR_BUF_DENOISED_PIXELS from it ("has a colour" = image_buffer's count > 0).  Weight, depth,
 // both sets of statistics and the error plane are those of the colour before the resolve.  cov_k and cov_linear are rtpbr_denoise_coverage's planes: both calls run on the
 // context's one stream and neither keeps them across calls.
+// Option blend_fill = 1 with K > 0 (all three calls; with no level the option is not read and nothing is filled): the three chains
+// run atrous_level's FILL form, with blend_coverage its COVER and FILL form, each filling its own empty pixels; image_buffer's chain
+// counts into the call's shards, the halves' into the set nobody reads.  The last level is level_blend's FILL instance, which shows
+// the pixels without samples from level K's record, counts them and (LIN) writes cov_live for cover_resolve's FILL form.
 static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_params* p, const rtpbr_blend_params* e,
                         const rtpbr_error_params* w, bool with_error, bool display, float threshold, rtpbr_noise_stats* out) {
     if (!c) return fail(RTPBR_EINVAL, "null ctx");
@@ -2264,6 +2276,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
     const int K = d.iterations;
     const bool cover = c->blend_coverage != 0 && K > 0;
+    const bool fill = c->blend_fill != 0 && K > 0;
     const rtpbr_coverage_params cv{c->blend_coverage_grid, c->blend_coverage_power, c->blend_coverage_resolve};
     if (cover && ((long long)cv.grid * c->cfg.width > 65535 || (long long)cv.grid * c->cfg.height > 65535))
         return fail(RTPBR_EINVAL, "coverage: grid x resolution out of range (1..65535)");      // (coverage_enqueue's, before anything is allocated)
@@ -2284,7 +2297,11 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         if (!c->blend_resolved) HIP_TRY(hipMalloc(&c->blend_resolved, sizeof(uint32_t)));
         HIP_TRY(hipMemsetAsync(c->cov_list + 1, 0, 2 * sizeof(uint32_t), c->stream));
         launch_cover_weights(coverage_args(c, cv), c->stream);
+        if (fill)
+            if (int r = frame_need(c, {ROW_cov_live})) return r;
     }
+    if (fill)
+        if (int r = fill_counts_zero(c)) return r;
     LevelsArgs A{};
     if (with_error) {      // the ERR instances: XA and XB beside the frame, the slope into the error plane (display: into its own)
         A.xa = c->blend_x;
@@ -2331,7 +2348,8 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
             F.image_buffer = chain_in[j];
             F.src = before[j];
             F.dst = now[j];
-            launch_atrous_level(F, first, false, false, c->stream, false, cover);
+            if (fill) F.fill = c->fill_counts + (j == 0 ? 0 : FILL_COUNT_WORDS);      // (shares vsrc's word: the plain filter)
+            launch_atrous_level(F, first, false, false, c->stream, false, cover, fill);
         }
         A.kd = now[0];
         A.ka = now[1];
@@ -2339,7 +2357,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         A.pd = before[0];
         A.pa = before[1];
         A.pb = before[2];
-        launch_level_blend(A, first, last, c->stream, cover);
+        launch_level_blend(A, first, last, c->stream, cover, fill ? c->fill_counts : nullptr, fill && cover ? c->cov_live : nullptr);
     }
     if (cover) {      // the resolve and the tone map of every pixel, from the blended linear colour
         ResolveArgs R{};
@@ -2354,7 +2372,7 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         R.width = c->cfg.width;
         R.height = c->cfg.height;
         R.resolve = cv.resolve;
-        R.live = nullptr;
+        R.live = fill ? c->cov_live : nullptr;      // option blend_fill: "has a colour" is what the LIN last level wrote
         launch_cover_resolve(R, c->stream);
         HIP_TRY(hipMemcpyAsync(c->blend_resolved, c->cov_list + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     }
@@ -2701,8 +2719,8 @@ extern "C" int rtpbr_get_counter(rtpbr_ctx* c, const char* name, unsigned long l
     }
     else if (!strcmp(name, "jit_active")) *out = c->jit_mod ? 1 : 0;      // the last sample() ran a run-time compiled instance
     else if (!strcmp(name, "fill_filled") || !strcmp(name, "fill_empty") || !strcmp(name, "fill_deepest")) {
-        // the last rtpbr_denoise with option denoise_fill = 1 or rtpbr_denoise_coverage with option coverage_fill = 1, iterations > 0, as
-        // its kernels counted (0 before any)
+        // the last rtpbr_denoise with option denoise_fill = 1, rtpbr_denoise_coverage with option coverage_fill = 1 or level blend call
+        // with option blend_fill = 1 (image_buffer's chain), iterations > 0, as its kernels counted (0 before any)
         *out = 0;
         if (c->fill_counts) {
             uint32_t sh[FILL_SHARDS * FILL_SHARD_WORDS];
@@ -2814,6 +2832,7 @@ static const OptionRow OPTION_ROWS[] = {
     OPTION(denoise_fill, 0, 1, false, "denoise_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise reconstructs them from their neighbours)"),
     OPTION(coverage_fill, 0, 1, false, "coverage_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise_coverage reconstructs them from their neighbours)"),
     OPTION(blend_coverage, 0, 1, false, "blend_coverage must be 0 (the plain filter's ladders) or 1 (rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display run the coverage-weighted ladders and the edge resolve)"),
+    OPTION(blend_fill, 0, 1, false, "blend_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display reconstruct them from their neighbours)"),
     OPTION(blend_coverage_grid, 2, 4, false, "blend_coverage_grid must be 2 or 4"),      // (3: refused in rtpbr_set_option)
     OPTION(blend_coverage_power, 0, 8, false, "blend_coverage_power must be 0..8"),
     OPTION(blend_coverage_resolve, 0, 1, false, "blend_coverage_resolve must be 0 or 1"),

@@ -288,11 +288,12 @@ struct rtpbr_ctx {
     rt::NoiseStats* noise_stats = nullptr;
     int denoise_fill = 0;              // option denoise_fill: 1 = rtpbr_denoise reconstructs the pixels without samples from their neighbours (atrous_level's FILL form)
     int coverage_fill = 0;             // option coverage_fill: 1 = rtpbr_denoise_coverage does the same (atrous_level's COVER and FILL form, cover_resolve's FILL form)
-    uint32_t* fill_counts = nullptr;   // ... the counts of the last such call of either kind with iterations > 0, in shards (rt_features.hpp FILL_SHARDS) its kernels add to: counters "fill_*"
+    uint32_t* fill_counts = nullptr;   // ... the counts of the last such call of any kind (option blend_fill's calls included) with iterations > 0, in shards (rt_features.hpp FILL_SHARDS) its kernels add to: counters "fill_*"; a second set behind them takes what nobody reads
     int blend_coverage = 0;            // option blend_coverage: 1 = rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_blend_error_display run the coverage-aware rule (atrous_level's COVER form, level_blend's LIN form, cover_resolve)
     int blend_coverage_grid = RTPBR_COVERAGE_DEFAULT_GRID;         // ... rtpbr_coverage_params.grid of those calls
     int blend_coverage_power = RTPBR_COVERAGE_DEFAULT_POWER;       // ... .power
     int blend_coverage_resolve = RTPBR_COVERAGE_DEFAULT_RESOLVE;   // ... .resolve
+    int blend_fill = 0;                // option blend_fill: 1 = the same three calls fill the pixels without samples (atrous_level's FILL form in all three chains, level_blend's FILL form at the last level, with blend_coverage cover_resolve's FILL form)
     uint32_t* blend_resolved = nullptr; // ... the pixels the resolve of the last such call changed, copied on the stream from cov_list's head (rtpbr_denoise_coverage counts in the same word): counter "blend_resolved"
     int noise_tracking = RTPBR_NOISE_TRACK_OFF;     // rtpbr_set_noise_tracking: plain state, kept across refresh / set_config / set_scene / reproject
     rtpbr_noise_estimator noise_estimator{RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_BATCHES, RTPBR_NOISE_ESTIMATOR_DEFAULT_POOL_RADIUS,

@@ -90,7 +90,6 @@ RT_D vec3 start_colour(float4 b, vec3 ac, int demod) {
     vec3 c = mk(b.x / b.w, b.y / b.w, b.z / b.w);
     return demod ? mk(c.x / ac.x, c.y / ac.y, c.z / ac.z) : c;
 }
-constexpr int NO_SAMPLES = -2;      // object word of a level's output for a pixel without samples: matches no object index (>= -1)
 
 // One a-trous level.  Taps: dy outer, dx inner, -2..2, at p + step (dx, dy); h = H[|dx|] H[|dy|], H = {3/8, 1/4, 1/16};
 // e = |r(c_p) - r(c_q)|^2 ic + |n_p - n_q|^2 in + ((z_p - z_q) / max(z_p, 1e-6))^2 iz + |a_p - a_q|^2 ia (left to right),

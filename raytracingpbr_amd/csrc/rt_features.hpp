@@ -44,6 +44,10 @@ struct FeatArgs {
 // three words of a 64-byte line of its own, so that the waves of a lattice frame, which all report, do not queue on one address.
 constexpr int FILL_SHARDS = 64, FILL_SHARD_WORDS = 16;
 
+// object word of a level's output record for a pixel without a colour: matches no object index (>= -1).  level_blend's FILL instances
+// (rt_half.hip) ask the last level's record of image_buffer's chain whether the ladder gave the pixel one.
+constexpr int NO_SAMPLES = -2;
+
 // atrous_level arguments: one level
 struct DenoiseArgs {
     rtpbr_config cfg;             // tone map

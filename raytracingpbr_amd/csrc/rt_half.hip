@@ -1,6 +1,8 @@
 // rt_half.hip — kernels of rtpbr_half_update / rtpbr_denoise_error / rtpbr_denoise_blend / rtpbr_denoise_blend_levels / rtpbr_blend_error / rtpbr_blend_error_display (see rt_half.hpp).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "rt_half.hpp"
 #include "rt_device.hpp"
 
@@ -272,6 +274,12 @@ __global__ void __launch_bounds__(256) half_blend(const BlendArgs A) {
 // LIN (LAST only; option blend_coverage = 1): the last level stores the blended linear colour, +0 for a pixel without samples, in
 // the place of the display colour — A.out is a private plane in these calls, and cover_resolve tone-maps from it.  With ERR the
 // display colour is still computed, for the slope alone.  12 bytes written per pixel either way.
+// FILL (LAST only; option blend_fill = 1, the chains ran atrous_level's filling form): a pixel without samples in image_buffer is
+// never usable and its running state is nobody's; the last level shows it from level K's record of image_buffer's chain alone.  A
+// colour there: the remodulated F_K, as every t_k = 1 would give (T = 1, depth K: the sums above).  NO_SAMPLES: what post_process
+// shows, T = 1, depth 0.  A wave with such pixels adds their counts to its shard of A.fill, as atrous_level's last level does;
+// LIN writes A.live beside the colour (1: samples or filled).  ERR: the slope of such a pixel stays 0 and its luminances are never
+// read (blend_error<R> stages a pixel with samples in both halves).  No new load: the record and the texel are the centre's.
 RT_D vec3 lv_albedo(const LevelsArgs& A, size_t i) {
     if (!A.demodulate) return mk(1.0f, 1.0f, 1.0f);
     return mk(fmax_(A.albedo[i * 3 + 0], 1e-3f), fmax_(A.albedo[i * 3 + 1], 1e-3f), fmax_(A.albedo[i * 3 + 2], 1e-3f));
@@ -301,9 +309,10 @@ RT_D float4 lv_lums(const rtpbr_config& cfg, vec3 xa, vec3 xb) {
                        nz_lum(tone_map(cfg, make_float4(xb.x, xb.y, xb.z, 1.0f))));
 }
 
-template <int R, bool FIRST, bool LAST, bool ERR = false, bool LIN = false>
-__global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
+template <int R, bool FIRST, bool LAST, bool ERR = false, bool LIN = false, bool FILL = false>
+__global__ void __launch_bounds__(256) level_blend(const std::conditional_t<FILL, LevelsFillArgs, LevelsArgs> A) {
     static_assert(LAST || !LIN, "the linear exit is a last level's");
+    static_assert(LAST || !FILL, "the filled pixels are shown by the last level");
     __shared__ float t_a[Win<R>::WORDS];
     __shared__ float t_q[Win<R>::WORDS];
     __shared__ float t_x[Win<R>::WORDS];
@@ -346,6 +355,7 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
     const int lx = (int)threadIdx.x / ERR_TY, ly = (int)threadIdx.x % ERR_TY;
     const int x = x0 + lx, y = y0 + ly;
     bool usable = false;
+    bool filled = false, empty = false;      // FILL: a pixel without samples that level K's record gives a colour / does not
     float T = 1.0f;
     if (x < W && y < H) {
         float t = 1.0f;
@@ -356,7 +366,8 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
         }
         const size_t p = (size_t)x * (size_t)H + (size_t)y;
         const vec3 ac = lv_albedo(A, p);
-        const vec3 fk = lv_record(A.kd[p], ac, A.demodulate);
+        const float4 rk = A.kd[p];
+        const vec3 fk = lv_record(rk, ac, A.demodulate);
         float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if constexpr (FIRST || LAST) b = A.image_buffer[p];
         vec3 f0, c;
@@ -405,13 +416,25 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
         if constexpr (LAST) {
             if (T == 1.0f) c = fk;      // every t_k was 1: rtpbr_denoise's bytes
             // (no samples: what post_process shows; T = 1 and depth = K by the sums above)
+            bool coloured = b.w > 0.0f;
+            if constexpr (FILL) {
+                if (!coloured) {
+                    filled = __float_as_int(rk.w) != NO_SAMPLES;
+                    empty = !filled;
+                    coloured = filled;
+                    T = 1.0f;
+                    c = fk;
+                    if (empty) depth = 0.0f;
+                }
+            }
             const vec3 lin = c;
-            if constexpr (!LIN || ERR) c = b.w > 0.0f ? tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)) : tone_map(A.cfg, b);
+            if constexpr (!LIN || ERR) c = coloured ? tone_map(A.cfg, make_float4(c.x, c.y, c.z, 1.0f)) : tone_map(A.cfg, b);
             if constexpr (ERR) {
                 A.xa[p] = lv_lums(A.cfg, xa, xb);
                 A.slope[p] = b.w > 0.0f ? lv_slope(A.cfg, lin, c) : 0.0f;
             }
-            if constexpr (LIN) c = b.w > 0.0f ? lin : mk(0.0f, 0.0f, 0.0f);
+            if constexpr (LIN) c = coloured ? lin : mk(0.0f, 0.0f, 0.0f);
+            if constexpr (LIN && FILL) A.live[p] = coloured ? 1 : 0;
         }
         A.weight[p] = T;
         A.depth[p] = depth;
@@ -421,6 +444,13 @@ __global__ void __launch_bounds__(256) level_blend(const LevelsArgs A) {
     }
     // pixels_above = usable pixels with T_K < 1 (1 - T_K > 0 exactly then), max_noise = the largest 1 - T_K
     if constexpr (LAST) nz_stats(A.stats, 0.0f, blk, usable, 1.0f - T, blockIdx.y * gridDim.x + blockIdx.x);
+    if constexpr (FILL) {      // (every lane of the block arrives here; a lane outside the frame reports nothing)
+        const uint32_t wave = (blockIdx.y * gridDim.x + blockIdx.x) * 4u + (threadIdx.x >> 6);
+        uint32_t* const shard = A.fill + (wave % (uint32_t)FILL_SHARDS) * (uint32_t)FILL_SHARD_WORDS;
+        const unsigned long long mf = __ballot(filled), me = __ballot(empty);
+        if ((threadIdx.x & 63) == 0 && mf != 0) atomicAdd(shard, (uint32_t)__popcll(mf));
+        if ((threadIdx.x & 63) == 0 && me != 0) atomicAdd(shard + 1, (uint32_t)__popcll(me));
+    }
 }
 
 // K = 0 of rtpbr_denoise_blend_levels (the frame is atrous_none's): weight 1, depth 0, and the count of usable pixels.  ERR: XA,
@@ -560,8 +590,19 @@ void launch_half_blend(const BlendArgs& A, hipStream_t st) {
 }
 
 template <int R, bool ERR>
-static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin) {
+static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin, uint32_t* fill, uint8_t* live) {
     const dim3 grid = tile_grid(A.width, A.height);
+    if (fill && last) {
+        LevelsFillArgs B{};
+        static_cast<LevelsArgs&>(B) = A;
+        B.fill = fill;
+        B.live = live;
+        if (lin && first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, true, true>), grid, dim3(256), 0, st, B);
+        else if (lin) hipLaunchKernelGGL((level_blend<R, false, true, ERR, true, true>), grid, dim3(256), 0, st, B);
+        else if (first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, false, true>), grid, dim3(256), 0, st, B);
+        else hipLaunchKernelGGL((level_blend<R, false, true, ERR, false, true>), grid, dim3(256), 0, st, B);
+        return;
+    }
     if (lin && first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, true>), grid, dim3(256), 0, st, A);
     else if (lin) hipLaunchKernelGGL((level_blend<R, false, true, ERR, true>), grid, dim3(256), 0, st, A);
     else if (first && last) hipLaunchKernelGGL((level_blend<R, true, true, ERR>), grid, dim3(256), 0, st, A);
@@ -571,16 +612,16 @@ static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hip
 }
 
 // no level (first && last && no records): the K = 0 pass.  A.xa (rtpbr_blend_error): the ERR instances.  lin (with last and
-// records only): the LIN instances
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin) {
+// records only): the LIN instances.  fill (with last and records only): the FILL instances
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin, uint32_t* fill, uint8_t* live) {
     if (!A.kd) {
         if (A.xa) hipLaunchKernelGGL(level_blend_none<true>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         else hipLaunchKernelGGL(level_blend_none<false>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
         return;
     }
     with_radius(A.radius, [&](auto r) {
-        if (A.xa) launch_level_blend_r<decltype(r)::value, true>(A, first, last, st, lin && last);
-        else launch_level_blend_r<decltype(r)::value, false>(A, first, last, st, lin && last);
+        if (A.xa) launch_level_blend_r<decltype(r)::value, true>(A, first, last, st, lin && last, fill, live);
+        else launch_level_blend_r<decltype(r)::value, false>(A, first, last, st, lin && last, fill, live);
     });
 }
 

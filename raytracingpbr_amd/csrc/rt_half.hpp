@@ -41,6 +41,15 @@
 //                       without samples — stays in `out`, for these calls a private (W,H,3) plane that carried the running colour of
 //                       the levels before, from which cover_resolve (rt_coverage.hip) makes RTPBR_BUF_DENOISED_PIXELS.  Weight, depth, statistics and with ERR the slope and the four luminances are
 //                       those of the pre-resolve colour, computed as without LIN.
+//   level_blend<.., FILL> the last level of the three calls with option blend_fill = 1 (the chains then ran atrous_level's FILL form, or
+//                       COVER and FILL: a pixel without samples takes a colour at the first level that reaches its object).  A pixel
+//                       whose image_buffer count is 0 is shown from the last record of image_buffer's chain: a colour there is the
+//                       remodulated F_K (weight 1, depth K — the running sums' values, the pixel was never usable), NO_SAMPLES
+//                       leaves what post_process shows (weight 1, depth 0).  The lane counts both kinds into the call's shards
+//                       (rt_features.hpp FILL_SHARDS; the levels raised the deepest level already) and, with LIN, writes the
+//                       byte plane cover_resolve's FILL form reads.  The two pointers live in LevelsFillArgs, which only these
+//                       instances take: LevelsArgs and every other instance's argument block stay as they were.  The levels before
+//                       the last need no form of their own: what they leave of such a pixel the last level overwrites.
 //   blend_error<R>      rtpbr_blend_error's window kernel, in half_error<R>'s layout with four planes (e_q, x_q, usable_q, object):
 //                       e_q is half_error's with the blended halves' display luminances, x_q the product of the halves' (blended -
 //                       raw) in linear luminance; the lane sums both over the window on its object and writes the root of
@@ -52,6 +61,7 @@
 // The arithmetic is fixed operation by operation (include/rtpbr.h) so that the CPU restatement matches bit for bit
 // (tests/half_ref/half_ref.c, tests/post_ref/blend.h).
 #pragma once
+#include "rt_features.hpp"
 #include "rt_noise.hpp"
 
 namespace rt {
@@ -124,6 +134,12 @@ struct LevelsArgs {
     int32_t radius;               // 1..3
 };
 
+// level_blend's FILL instances (last level, option blend_fill = 1): LevelsArgs and, behind it, what only they need
+struct LevelsFillArgs : LevelsArgs {
+    uint32_t* fill;               // the call's counts: FILL_SHARDS x FILL_SHARD_WORDS words (filled, empty, deepest level), as atrous_level's
+    uint8_t* live;                // LIN: out, (W,H) 1 = the pixel has a colour (samples, or filled by level K), 0 = still empty (out takes +0)
+};
+
 struct BlendErrorArgs {
     const float4* lx;             // (W,H): (lum XA, display lum XA, lum XB, display lum XB) as level_blend's LAST ERR instance left it
     const float4* half_a;         // A: the count word cA, PA
@@ -140,7 +156,10 @@ struct BlendErrorArgs {
 };
 
 void launch_half_update(const HalfArgs& A, hipStream_t st);
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin = false);      // A.xa != nullptr: the ERR instances; lin: the last level's LIN instance (A.out stays linear)
+// A.xa != nullptr: the ERR instances; lin: the last level's LIN instance (A.out stays linear); fill != nullptr: the last level's FILL
+// instance (live: with lin, the plane it writes)
+void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin = false, uint32_t* fill = nullptr,
+                        uint8_t* live = nullptr);
 void launch_blend_error(const BlendErrorArgs& A, hipStream_t st);
 void launch_half_blend(const BlendArgs& A, hipStream_t st);
 void launch_half_subtract(const HalfArgs& A, hipStream_t st);

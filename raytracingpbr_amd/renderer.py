@@ -487,21 +487,39 @@ class Renderer:
         e = BlendParams.pack(True, radius, z, min_half_samples)
         return self._stats("denoise_blend", _ref(p), _ref(e))
 
+    def _with_blend_fill(self, call):
+        """``call()`` with option ``blend_fill`` set; the option is 0 again afterwards, also when the call is refused.  Returns
+        (what ``call`` returns, (pixels filled, pixels still empty, the deepest level that filled one))."""
+        self.set_option("blend_fill", 1)
+        try:
+            result = call()
+        finally:
+            self.set_option("blend_fill", 0)
+        return result, tuple(self.counter(k) for k in ("fill_filled", "fill_empty", "fill_deepest"))
+
     def denoise_blend_levels(self, radius=None, z=None, min_half_samples=None, iterations=None, demodulate=None, sigma_color=None,
-                             sigma_normal=None, sigma_depth=None, sigma_albedo=None) -> NoiseStats:
+                             sigma_normal=None, sigma_depth=None, sigma_albedo=None, fill=False) -> NoiseStats:
         """denoise_blend's rule applied to every a-trous level against the next finer one instead of to the whole filter
         against the raw average: where the halves see a level blurring, that level's increment and every coarser one are scaled
         down, so the filter narrows per pixel and keeps the noise reduction of the levels that hold.  Writes
         ``denoised_pixels``, ``blend_weight`` (the product of the levels' weights: 1 = exactly ``denoise``'s colour) and
         ``blend_depth`` (the sum of the running products, 0..iterations: how many levels were kept).  Same parameters,
-        defaults and statistics as denoise_blend.  Blocks."""
+        defaults and statistics as denoise_blend.  Blocks.
+        ``fill``: with option ``blend_fill`` set for the call (include/rtpbr.h): the three ladders fill their pixels without
+        samples as ``denoise_fill`` does, and a pixel without samples that the whole buffer's ladder reached is shown with its
+        last level's colour (``blend_weight`` 1, ``blend_depth`` = iterations; one it did not reach stays as post_process shows
+        it, depth 0).  The return value is then (the NoiseStats, (pixels filled, pixels still empty, the deepest level that
+        filled one))."""
+        if fill:
+            return self._with_blend_fill(lambda: self.denoise_blend_levels(radius, z, min_half_samples, iterations, demodulate, sigma_color,
+                                                                           sigma_normal, sigma_depth, sigma_albedo))
         p = DenoiseParams.pack(True, iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
         e = BlendParams.pack(True, radius, z, min_half_samples)
         return self._stats("denoise_blend_levels", _ref(p), _ref(e))
 
     def blend_error(self, threshold: float = 0.0, radius=None, z=None, min_half_samples=None, window=None, iterations=None,
                     demodulate=None, sigma_color=None, sigma_normal=None, sigma_depth=None, sigma_albedo=None,
-                    bias="linear") -> NoiseStats:
+                    bias="linear", fill=False) -> NoiseStats:
         """denoise_blend_levels (same parameters, same ``denoised_pixels``, ``blend_weight`` and ``blend_depth``) and besides
         ``blend_error_map``: the estimated root-mean-square error of the luminance of the frame it shows.  The levels' weights
         are applied to each half's own ladder; the difference of the two blended halves gives the variance, the product of their
@@ -511,9 +529,15 @@ class Renderer:
         ``bias``: "linear" (the default) averages the squared bias in linear radiance and converts the mean with the slope of the
         tone map at the centre pixel; "display" (rtpbr_blend_error_display) converts each tap's product with the tap's own slope
         before summing, so a saturated pixel in the window no longer lends its linear bias to its neighbours.  Both write
-        ``blend_error_map``: the last call wins."""
+        ``blend_error_map``: the last call wins.
+        ``fill``: as denoise_blend_levels' — the frame shows the filled pixels, the estimate still sees them as pixels without
+        samples (0 in ``blend_error_map``, selected by select_blend_error); the return value becomes (the NoiseStats, (filled,
+        empty, deepest))."""
         if bias not in ("linear", "display"):
             raise ValueError('bias must be "linear" or "display"')
+        if fill:
+            return self._with_blend_fill(lambda: self.blend_error(threshold, radius, z, min_half_samples, window, iterations, demodulate,
+                                                                  sigma_color, sigma_normal, sigma_depth, sigma_albedo, bias))
         entry = "blend_error_display" if bias == "display" else "blend_error"
         if not self.api.has(entry):
             raise NotImplementedError(f"this library has no rtpbr_{entry}")
@@ -535,27 +559,37 @@ class Renderer:
             self.set_option("blend_coverage", 0)
         return stats, self.counter("blend_resolved")
 
-    def denoise_blend_levels_coverage(self, power=None, resolve=None, grid=None, radius=None, z=None, min_half_samples=None, **denoise):
+    def denoise_blend_levels_coverage(self, power=None, resolve=None, grid=None, radius=None, z=None, min_half_samples=None, fill=False,
+                                      **denoise):
         """``denoise_blend_levels`` (same parameters) on the coverage-weighted filter: the three ladders are ``denoise_coverage``'s
         levels (every tap weighted by (its pixel's own-object coverage)^``power``, at ``grid`` x ``grid`` sub-rays), the windows'
         rule is unchanged, and the pixels that hold two objects are resolved from the blended linear frame (``resolve``) before
         the tone map.  ``blend_weight`` and ``blend_depth`` are the ladder's.  Returns (``denoise_blend_levels``' NoiseStats, the
-        pixels the resolve changed).  Blocks."""
+        pixels the resolve changed).  Blocks.
+        ``fill``: with option ``blend_fill`` set for the call: the ladders fill as ``denoise_coverage_fill`` does and the resolve
+        treats a filled pixel as one with a colour; the return value becomes (that pair, (filled, empty, deepest))."""
         unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
         if unknown:
             raise TypeError(f"denoise_blend_levels_coverage: unknown denoise parameters {sorted(unknown)}")
+        if fill:
+            return self._with_blend_fill(lambda: self.denoise_blend_levels_coverage(power, resolve, grid, radius, z, min_half_samples,
+                                                                                    **denoise))
         return self._with_blend_coverage(power, resolve, grid, lambda: self.denoise_blend_levels(radius, z, min_half_samples, **denoise))
 
     def blend_error_coverage(self, threshold: float = 0.0, power=None, resolve=None, grid=None, radius=None, z=None,
-                             min_half_samples=None, window=None, bias="linear", **denoise):
+                             min_half_samples=None, window=None, bias="linear", fill=False, **denoise):
         """``blend_error`` (same parameters) on the coverage-weighted filter, as ``denoise_blend_levels_coverage``: the same
         ``denoised_pixels``, ``blend_weight`` and ``blend_depth``, and ``blend_error_map`` as the estimate of the blended frame
-        BEFORE the resolve.  Returns (``blend_error``'s NoiseStats, the pixels the resolve changed).  Blocks."""
+        BEFORE the resolve.  Returns (``blend_error``'s NoiseStats, the pixels the resolve changed).  Blocks.
+        ``fill``: as denoise_blend_levels_coverage's; the return value becomes (that pair, (filled, empty, deepest))."""
         unknown = set(denoise) - set(DenoiseParams.DEFAULTS)
         if unknown:
             raise TypeError(f"blend_error_coverage: unknown denoise parameters {sorted(unknown)}")
         if bias not in ("linear", "display"):
             raise ValueError('bias must be "linear" or "display"')
+        if fill:
+            return self._with_blend_fill(lambda: self.blend_error_coverage(threshold, power, resolve, grid, radius, z, min_half_samples,
+                                                                           window, bias, **denoise))
         return self._with_blend_coverage(power, resolve, grid,
                                          lambda: self.blend_error(threshold, radius, z, min_half_samples, window, bias=bias, **denoise))
 
@@ -565,7 +599,7 @@ class Renderer:
         return self._count("select_blend_error", float(threshold), int(dilate))
 
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
-                                 blend=False, *, stop="filter", bias="linear", coverage=None, **denoise_params):
+                                 blend=False, *, stop="filter", bias="linear", coverage=None, fill=False, **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -583,9 +617,17 @@ class Renderer:
         ``bias`` (with ``stop="blend"`` only): blend_error's ``bias``, "linear" (the default) or "display".
         ``coverage`` (with ``blend="levels"`` only): ``None`` (the default) leaves the loop as it is; True or a dict of
         ``power`` / ``resolve`` / ``grid`` makes the ending denoise_blend_levels() and the blend_error() estimates of
-        ``stop="blend"`` the coverage-weighted calls (denoise_blend_levels_coverage, blend_error_coverage)."""
+        ``stop="blend"`` the coverage-weighted calls (denoise_blend_levels_coverage, blend_error_coverage).
+        ``fill`` (with ``blend="levels"`` only): option ``blend_fill`` is set for the duration of the call, so every level-blend
+        call of the loop fills the pixels without samples; the return value becomes ((pixel-samples traced, NoiseStats), (filled,
+        empty, deepest) of the last filling call)."""
         if isinstance(blend, str) and blend != "levels":
             raise ValueError('blend must be True, False or "levels"')
+        if fill:
+            if blend != "levels":
+                raise ValueError('fill selects the filling level blend: blend must be "levels"')
+            return self._with_blend_fill(lambda: self.render_adaptive_denoised(error, max_spp, batch_spp, dilate, per_sample, blend, stop=stop,
+                                                                               bias=bias, coverage=coverage, **denoise_params))
         if stop not in ("filter", "blend"):
             raise ValueError('stop must be "filter" or "blend"')
         if stop == "blend" and blend != "levels":

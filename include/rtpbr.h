@@ -230,7 +230,7 @@ enum { RTPBR_BUF_IMAGE_BUFFER = 0,   /* T7 image_buffer  (W,H,4) f32: (sum r, su
        RTPBR_BUF_NOISE        = 12,  /* (W,H)   f32 estimated standard deviation of lum(r(displayed average))          */
        /* the pixel selection (rtpbr_select_mask / rtpbr_select_noisy): allocated on the first select call, RTPBR_ESTATE before;
         * output only */
-       RTPBR_BUF_SELECTION    = 13,  /* (W,H)   u8  1 = selected: what rtpbr_sample_selected traces                           */
+       RTPBR_BUF_SELECTION    = 13,  /* (W,H)   u8  1 = selected: what rtpbr_sample_selected traces (select_tiers > 1: 1 + tier) */
        /* the packed 8-bit frame (rtpbr_present): allocated on the first present, RTPBR_ESTATE before; output only.  NOT in the
         * field layout: (H,W,C) u8, row 0 = the TOP row of the picture, x fastest, C = 3 or 4 as the last present said */
        RTPBR_BUF_PRESENT      = 14,
@@ -674,7 +674,38 @@ int rtpbr_set_noise_tracking(rtpbr_ctx* ctx, int mode);
  *
  * Errors: RTPBR_ESTATE before set_config / set_scene / set_camera and with tiles of world > 1; rtpbr_sample_selected also before
  * any select call, in the persistent-ray form (it has cfg.adaptive_sampling) and with option precision = 1.  RTPBR_EINVAL for
- * NULL pointers, nbytes != W * H, n < 0, a threshold that is not >= 0, dilate outside 0..3.  A refused call changes nothing. */
+ * NULL pointers, nbytes != W * H, n < 0, a threshold that is not >= 0, dilate outside 0..3.  A refused call changes nothing.
+ *
+ * Tiers: a share of the batch per pixel.  rtpbr_set_option "select_tiers" = T (1..8, default 1: everything above) and
+ *   "select_batch" = B (1..65536, default 16: the n the host will pass to rtpbr_sample_selected) are read by the select calls
+ *   (rtpbr_select_mask, rtpbr_select_noisy, rtpbr_select_error, rtpbr_select_blend_error) and by nothing else: a selection keeps
+ *   the tiers it was built with, changing either option afterwards does not alter it, and rtpbr_sample_selected reads neither.
+ *   With T > 1 every selected pixel p has a tier t in 0 .. T - 1; tier 0 is the full share.  Membership is the rule above, unchanged.
+ *     rtpbr_select_mask: byte b = 0: not selected; b >= 1: t = min(b, T) - 1 (1 = the full share, 2 = half of it, ...).
+ *     rtpbr_select_noisy / rtpbr_select_error / rtpbr_select_blend_error: a pixel selected because it has no samples, fewer than
+ *       min_samples or (the error rules) an empty half: t = 0.  Otherwise, with `plane` the call's plane (noise, denoised error,
+ *       blend error) and b = image_buffer[p], in f32, every operation exactly rounded, nothing contracted:
+ *         m    = fmaxf over the pixels q inside the frame with max(|dx|, |dy|) <= dilate and plane[q] > threshold, of plane[q]
+ *                (p is selected by the plane, so there is at least one)
+ *         r    = m / threshold
+ *         need = b.w * (r * r - 1.0f)
+ *         t    = the number of k in 1 .. T - 1 with need <= (float)max(1, B >> k)
+ *       The bounds fall with k, so the comparisons that hold are a prefix: t is the smallest share that covers `need`.  A NaN or
+ *       infinite `need` (threshold = 0, an infinite plane value) satisfies none: t = 0.  Reading: the plane is the standard
+ *       deviation of a mean of b.w samples, so `need` is how many more samples bring it to the threshold.  The window maximum
+ *       keeps dilate's mitigation: a quiet pixel beside a noisy one takes the noisy one's tier.
+ *   RTPBR_BUF_SELECTION holds 0 or 1 + t.  The list is ordered by tier, then by ascending buffer index within a tier; n_selected
+ *   is the total over all tiers.  rtpbr_get_counter "select_tier0" .. "select_tier7": the pixels in that tier of the current
+ *   selection (0 for tiers >= T and before any selection; with T = 1 select_tier0 = n_selected), answered from the host without a
+ *   synchronisation.
+ *   rtpbr_sample_selected(n) on a tiered selection: with the shares s_t = max(1, n >> t) for n >= 1 (s_T = 0), a pixel of tier t
+ *   receives the samples with absolute indices sample_base .. sample_base + s_t - 1, added in sample order, and skips the
+ *   indices up to sample_base + n - 1; sample_base advances by n, so a pixel's sample k is still the same ray whatever was
+ *   selected.  n = 0 traces nothing.  It runs as stages t = T - 1 .. 0, stage t tracing the indices sample_base + s_{t+1} ..
+ *   sample_base + s_t - 1 through the pixels of tiers 0 .. t (a prefix of the list), each an ordinary selected launch; stages with
+ *   s_t = s_{t+1} or no pixels are skipped.  Counters: samples = deposits = the sum over t of (pixels in tier t) * s_t;
+ *   rtpbr_last_sample_ms sums all stages and counts all their sub-launches.  Noise tracking, per-sample halves and every refusal
+ *   are those of the plain selected launch. */
 int rtpbr_select_mask(rtpbr_ctx* ctx, const uint8_t* mask, size_t nbytes, uint32_t* n_selected);
 int rtpbr_select_noisy(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 int rtpbr_sample_selected(rtpbr_ctx* ctx, int n);

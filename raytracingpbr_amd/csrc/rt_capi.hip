@@ -151,6 +151,9 @@ static void frame_free(rtpbr_ctx* c, unsigned groups) {
     if (groups & FRAME_SELECTION) {
         c->sel_count = 0;
         c->have_selection = false;
+        c->sel_tiers = 1;
+        for (uint32_t& l : c->sel_cum) l = 0;
+        c->sel_blocks_tiered = false;
     }
     if (groups & FRAME_PRESENT) c->present_channels = 0;
 }
@@ -1190,12 +1193,13 @@ static int launch_split_steps(rtpbr_ctx* c, int steps) {
 // complete-path form: `n` samples per owned pixel (the spp loop of cornell_box_v3/renderer.py:31-36), in sub-launches of as
 // many samples per pixel as the staging budget holds.  `selected` (rtpbr_sample_selected): the caller has set P.np to the selection
 // list's length (> 0) and P.order to the list — the general ahead-of-time instances with the list indirection, item-linear staging,
-// no primary split, no run-time instance (c->jit_mod is nullptr, P.box_sig 0).
-static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
+// no primary split, no run-time instance (c->jit_mod is nullptr, P.box_sig 0).  `fresh` is false for the later stages of a tiered
+// selected call (sample_selected_tiered): the call's first sub-launch was an earlier stage's.
+static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false, bool fresh = true) {
     Params& P = c->P;
     int left = n;
     if (int r = flush_shade(c)) return r;
-    c->dense_launches = 0;
+    if (fresh) c->dense_launches = 0;
     // per-sample noise tracking (rtpbr_set_noise_tracking): the accumulate pass folds every record into the moments (the callers
     // have refused what keeps no records and have allocated the moments and the snapshot)
     const bool tracked = c->noise_tracking == RTPBR_NOISE_TRACK_SAMPLES;
@@ -1263,7 +1267,7 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
             }
         }
         // [0] trace items, [1] primary groups: zeroed with the work counters by rtpbr_sample(); again before every further sub-launch
-        if (left != n) launch_zero(c->work_counter, 64, c->stream);
+        if (left != n || !fresh) launch_zero(c->work_counter, 64, c->stream);
         if (split) {
             NEXT_EVENT(c->evp, c->evp_used, pa);
             NEXT_EVENT(c->evp, c->evp_used, pb);
@@ -1295,6 +1299,30 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false) {
         c->sample_base += (uint32_t)K;
         left -= K;
     }
+    return RTPBR_OK;
+}
+
+// rtpbr_sample_selected(n) on a tiered selection (T = c->sel_tiers > 1; include/rtpbr.h): with the shares s_t = max(1, n >> t),
+// s_T = 0, stage t = T-1 .. 0 traces the sample indices base + s_{t+1} .. base + s_t - 1 through the first L_t entries of the list
+// (the pixels of tiers 0 .. t) — an ordinary selected launch each, P.np = L_t, the context's sample_base set for the stage.  The index
+// ranges ascend from stage to stage, so every pixel's records are added in sample order; a tier-t pixel skips s_t .. n - 1.
+// The caller has set P.order to the list and puts P.np back.
+static int sample_selected_tiered(rtpbr_ctx* c, int n) {
+    const uint32_t base = c->sample_base;
+    const int T = c->sel_tiers;
+    if (int r = flush_shade(c)) return r;
+    c->dense_launches = 0;
+    bool fresh = true;
+    for (int t = T - 1; t >= 0 && n > 0; t--) {
+        const int hi = (n >> t) > 1 ? n >> t : 1;
+        const int lo = t + 1 == T ? 0 : (n >> (t + 1)) > 1 ? n >> (t + 1) : 1;
+        if (hi == lo || c->sel_cum[t] == 0) continue;
+        c->P.np = (int32_t)c->sel_cum[t];
+        c->sample_base = base + (uint32_t)lo;
+        if (int r = sample_complete_path(c, hi - lo, true, fresh)) return r;
+        fresh = false;
+    }
+    c->sample_base = base + (uint32_t)n;
     return RTPBR_OK;
 }
 
@@ -1379,7 +1407,7 @@ static int sample_call(rtpbr_ctx* c, int n, bool selected) {
         if (c->sel_count > 0) {
             P.np = (int32_t)c->sel_count;
             P.order = c->sel_list;
-            r = sample_complete_path(c, n, true);
+            r = c->sel_tiers > 1 ? sample_selected_tiered(c, n) : sample_complete_path(c, n, true);
             P.np = np_keep;
             P.order = order_keep;
         } else {
@@ -1991,6 +2019,39 @@ static int noise_stats_read(rtpbr_ctx* c, rtpbr_noise_stats* out) {
 // ---- adaptive sampling of the complete-path form (rt_select.hip): select pixels, trace only those
 static const char* const SELECT_TILES = "rtpbr_select_mask / rtpbr_select_noisy / rtpbr_sample_selected work on the whole frame: not with tiles of world > 1";
 
+// ... with option select_tiers = T > 1 (A is filled, the selection's state cleared): the tiered passes, then the T cumulative counts
+// come back (4 T bytes) and stay on the context — rtpbr_sample_selected and the counters "select_tier*" read them there
+static int selection_build_tiered(rtpbr_ctx* c, const SelectArgs& A, int rule, int T, uint32_t* n_selected) {
+    if (!c->sel_blocks_tiered) {
+        // the first tiered selection of this frame size: sel_blocks gets the room of 8 tiers (nothing of the old one is kept)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->sel_blocks);
+        c->sel_blocks = nullptr;
+        c->sel_blocks_tiered = true;
+        if (int r = frame_need(c, {ROW_sel_blocks})) {
+            c->sel_blocks_tiered = false;
+            return r;
+        }
+    }
+    SelectTierArgs S{};
+    S.A = A;
+    S.A.blocks = c->sel_blocks;
+    S.tiers = T;
+    for (int k = 1; k < T; k++) S.bound[k - 1] = (float)((c->select_batch >> k) > 1 ? c->select_batch >> k : 1);
+    launch_select_tiered(S, rule, c->stream);
+    HIP_TRY(hipGetLastError());
+    uint32_t cum[SELECT_MAX_TIERS] = {};
+    const uint32_t nb = select_blocks(c->cfg.width, c->cfg.height);
+    HIP_TRY(hipMemcpyAsync(cum, c->sel_blocks + (size_t)T * nb + 1, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int t = 0; t < T; t++) c->sel_cum[t] = cum[t];
+    c->sel_tiers = T;
+    c->sel_count = cum[T - 1];
+    c->have_selection = true;
+    *n_selected = cum[T - 1];
+    return RTPBR_OK;
+}
+
 // mark, scan, scatter on the stream, then the list's length (4 bytes) comes back: blocks
 static int selection_build(rtpbr_ctx* c, SelectArgs& A, int rule, uint32_t* n_selected) {
     A.mask = c->sel_mask;
@@ -2000,12 +2061,17 @@ static int selection_build(rtpbr_ctx* c, SelectArgs& A, int rule, uint32_t* n_se
     A.height = c->cfg.height;
     c->have_selection = false;      // (until the new list's length is known)
     c->sel_count = 0;
+    c->sel_tiers = 1;
+    for (uint32_t& l : c->sel_cum) l = 0;
+    const int T = c->select_tiers;
+    if (T > 1) return selection_build_tiered(c, A, rule, T, n_selected);
     launch_select(A, rule, c->stream);
     HIP_TRY(hipGetLastError());
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, c->sel_blocks + select_blocks(c->cfg.width, c->cfg.height), sizeof total, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->sel_count = total;
+    c->sel_cum[0] = total;
     c->have_selection = true;
     *n_selected = total;
     return RTPBR_OK;
@@ -2679,6 +2745,13 @@ extern "C" int rtpbr_get_counter(rtpbr_ctx* c, const char* name, unsigned long l
     if (!c || !name || !out) return fail(RTPBR_EINVAL, "null argument");
     if (int r = set_dev(c)) return r;
     if (int r = flush_shade(c)) return r;
+    if (!strncmp(name, "select_tier", 11) && name[11] >= '0' && name[11] <= '7' && !name[12]) {
+        // the pixels in that tier of the current selection, as its select call read them back (no copy, no synchronisation): 0 for
+        // the tiers the selection does not have and before any selection; a binary selection is all tier 0
+        const int t = name[11] - '0';
+        *out = c->have_selection && t < c->sel_tiers ? c->sel_cum[t] - (t > 0 ? c->sel_cum[t - 1] : 0u) : 0u;
+        return RTPBR_OK;
+    }
     Counters h;
     HIP_TRY(hipMemcpyAsync(&h, c->counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2833,6 +2906,9 @@ static const OptionRow OPTION_ROWS[] = {
     OPTION(coverage_fill, 0, 1, false, "coverage_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise_coverage reconstructs them from their neighbours)"),
     OPTION(blend_coverage, 0, 1, false, "blend_coverage must be 0 (the plain filter's ladders) or 1 (rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display run the coverage-weighted ladders and the edge resolve)"),
     OPTION(blend_fill, 0, 1, false, "blend_fill must be 0 (pixels without samples stay as rtpbr_post_process shows them) or 1 (rtpbr_denoise_blend_levels, rtpbr_blend_error and rtpbr_blend_error_display reconstruct them from their neighbours)"),
+    // read by the select calls only: a selection keeps the tiers it was built with (rt_select.hpp, include/rtpbr.h)
+    OPTION(select_tiers, 1, 8, false, "select_tiers must be 1 (every selected pixel takes the whole batch of rtpbr_sample_selected) .. 8 (the select calls give every selected pixel one of that many shares of it)"),
+    OPTION(select_batch, 1, 65536, false, "select_batch must be 1 .. 65536 (the n the host will pass to rtpbr_sample_selected: with select_tiers > 1 the noise-driven select calls size the shares by it)"),
     OPTION(blend_coverage_grid, 2, 4, false, "blend_coverage_grid must be 2 or 4"),      // (3: refused in rtpbr_set_option)
     OPTION(blend_coverage_power, 0, 8, false, "blend_coverage_power must be 0..8"),
     OPTION(blend_coverage_resolve, 0, 1, false, "blend_coverage_resolve must be 0 or 1"),

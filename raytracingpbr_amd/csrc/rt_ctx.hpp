@@ -160,7 +160,7 @@ constexpr int FRAME_PRIVATE = -1;
     /* the selection (rt_select.hip): the first select call; freeing the group clears sel_count and have_selection */                             \
     X(sel_mask, uint8_t, np, FRAME_SELECTION, false, RTPBR_BUF_SELECTION, false)                                                                   \
     X(sel_list, uint32_t, np * 4, FRAME_SELECTION, false, FRAME_PRIVATE, false)                 /* the selected pixels' buffer indices x * H + y, ascending */ \
-    X(sel_blocks, uint32_t, ((size_t)rt::select_blocks(c->cfg.width, c->cfg.height) + 1) * 4, FRAME_SELECTION, false, FRAME_PRIVATE, false) /* per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them */ \
+    X(sel_blocks, uint32_t, (c->sel_blocks_tiered ? rt::select_tier_words(c->cfg.width, c->cfg.height) : (size_t)rt::select_blocks(c->cfg.width, c->cfg.height) + 1) * 4, FRAME_SELECTION, false, FRAME_PRIVATE, false) /* per block of 256 pixels: its count, then (scanned) where its entries start; the total behind them; from the first tiered selection on: that per tier, tier-major, and the tiers' cumulative counts */ \
     /* the packed 8-bit frame of rtpbr_present (rt_present.hip), (H,W,C) top-down: room for C = 4, reported with the C of the last present;    \
        freeing the group clears present_channels */                                                                                                \
     X(present, uint8_t, np * (size_t)(reported ? c->present_channels : 4), FRAME_PRESENT, false, RTPBR_BUF_PRESENT, false)
@@ -301,6 +301,11 @@ struct rtpbr_ctx {
     rtpbr_half_mode half_mode{RTPBR_HALF_MODE_DEFAULT_PER_SAMPLE, RTPBR_HALF_MODE_DEFAULT_WARP};      // rtpbr_set_half_mode: plain state, kept across refresh / set_config / set_scene / reproject
     uint32_t sel_count = 0;            // entries of sel_list
     bool have_selection = false;
+    int select_tiers = 1;              // option select_tiers: T of the NEXT select call (1 = the binary selection); a selection keeps the T it was built with
+    int select_batch = 16;             // option select_batch: B, the batch the host means to pass to rtpbr_sample_selected; the noise-driven rules size the tiers by it
+    int sel_tiers = 1;                 // T of the current selection
+    uint32_t sel_cum[rt::SELECT_MAX_TIERS] = {};      // ... L_t, its pixels of tiers 0 .. t (a prefix of sel_list); sel_cum[sel_tiers - 1] = sel_count: counters "select_tier*"
+    bool sel_blocks_tiered = false;    // sel_blocks has the room of a tiered selection (rt::select_tier_words): from the first select call with T > 1 on
     int present_channels = 0;          // C of the last present
     size_t march_np = 0;
     int src_chain = 1;            // src/ form, fused launches: the plan's chain set runs in the chain kernel beside the pool kernel (rt_chain.hpp)

@@ -33,4 +33,25 @@ struct SelectArgs {
 void launch_select(const SelectArgs& A, int rule, hipStream_t st);      // the three passes; A.blocks[n_blocks] = the list's length afterwards
 inline uint32_t select_blocks(int w, int h) { return (uint32_t)(((size_t)w * (size_t)h + 255) / 256); }
 
+// The tiered selection (option select_tiers = T > 1): every selected pixel carries a tier 0 .. T - 1 (include/rtpbr.h has the rule),
+// RTPBR_BUF_SELECTION holds 1 + tier, and the list is ordered by tier, then by buffer index, so that "the pixels of tiers 0 .. t" is
+// a prefix of it.
+//   select_mark_tiered_*   select_mark's membership; the tier from the window MAXIMUM of the plane (the walk cannot stop at the
+//                          first hit: from dilate 2 on the block stages its window in LDS, 2 d + 1 contiguous runs of the plane);
+//                          a ballot + popcount per tier and wave, the block's T counts into blocks[t * nb + block]
+//   select_scan            the same kernel over T * nb entries: tier-major starts, blocks[(t + 1) * nb] = L_t, the pixels of tiers
+//                          0 .. t, blocks[T * nb] = the total
+//   select_scatter_tiered  the rank among the wave's lanes of the SAME tier, earlier waves' counts of that tier from LDS
+//   select_tier_counts     L_0 .. L_{T-1} gathered into blocks[T * nb + 1 ..]: one copy of 4 T bytes to the host
+constexpr int SELECT_MAX_TIERS = 8;
+
+struct SelectTierArgs {
+    SelectArgs A;                          // blocks: room for select_tier_words() words
+    int32_t tiers;                         // T, 2 .. SELECT_MAX_TIERS
+    float bound[SELECT_MAX_TIERS - 1];     // noisy, error: bound[k - 1] = (float)max(1, select_batch >> k), k = 1 .. T - 1
+};
+
+void launch_select_tiered(const SelectTierArgs& S, int rule, hipStream_t st);      // the four passes; blocks[T * n_blocks + 1 + t] = L_t afterwards
+inline size_t select_tier_words(int w, int h) { return (size_t)select_blocks(w, h) * SELECT_MAX_TIERS + 1 + SELECT_MAX_TIERS; }
+
 }  // namespace rt

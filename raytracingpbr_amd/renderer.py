@@ -40,7 +40,7 @@ BUFFERS = [
      "every sample is a batch, c = 1), c samples each, L the compressed luminance of the batch mean"),
     (12, "NOISE", (), f32, "noise", False,
      "(W,H): the last noise_estimate() / denoise_guided()'s standard deviation of each pixel's displayed luminance"),
-    (13, "SELECTION", (), np.uint8, "selection", False, "(W,H) uint8: 1 = selected by the last select_mask() / select_noisy()"),
+    (13, "SELECTION", (), np.uint8, "selection", False, "(W,H) uint8: 1 = selected by the last select_mask() / select_noisy(); after set_select_tiers(T > 1): 1 + the pixel's tier"),
     # not a field: top-down, C = 3 or 4 as the last present() said, which the library knows (_shape asks it)
     (14, "PRESENT", None, np.uint8, "presented", False, "(H, W, C) uint8: the frame of the last present(), top row first (blocking read)"),
     (15, "HALF_BUFFER", (4,), f32, "half_buffer", False,
@@ -77,6 +77,7 @@ class Renderer:
         self.noise_per_sample = False        # what set_noise_tracking() last set: every SAMPLE is a batch, folded in by sample() itself
         self.track_halves = False            # True: every sample() / sample_selected() call is one batch of the two halves (half_update() after it)
         self.half_mode = HalfMode.pack(False)      # what set_half_mode() last set
+        self.select_tiers = (1, 16)          # what set_select_tiers() last set: (tiers, batch)
         self.set_config(config)
         self.set_scene(scene)
         self.set_camera(camera if camera is not None else scene.camera)
@@ -172,10 +173,11 @@ class Renderer:
         return s
 
     @contextlib.contextmanager
-    def _loop_state(self, halves=False, noise_per_sample=False, half_per_sample=False):
+    def _loop_state(self, halves=False, noise_per_sample=False, half_per_sample=False, select_tiers=None):
         """What a render loop that folds its batches itself sets for its duration and puts back after, however it ends:
-        ``track_noise`` off (``halves``: and ``track_halves``), per-sample noise tracking or per-sample halves on where asked."""
-        mode, half_mode = self.noise_per_sample, self.half_mode
+        ``track_noise`` off (``halves``: and ``track_halves``), per-sample noise tracking or per-sample halves on where asked,
+        ``select_tiers`` = (tiers, batch) where given."""
+        mode, half_mode, tiers = self.noise_per_sample, self.half_mode, self.select_tiers
         if half_per_sample:
             self.set_half_mode(True, bool(half_mode.warp))
         keep = self.track_noise, self.track_halves
@@ -185,9 +187,13 @@ class Renderer:
         try:
             if noise_per_sample:
                 self.set_noise_tracking(True)
+            if select_tiers is not None:
+                self.set_select_tiers(*select_tiers)
             yield
         finally:
             self.track_noise, self.track_halves = keep
+            if select_tiers is not None:
+                self.set_select_tiers(*tiers)
             if noise_per_sample:
                 self.set_noise_tracking(mode)
             if half_per_sample:
@@ -344,13 +350,49 @@ class Renderer:
             return used, stats
 
     # ------------------------------------------------------------ adaptive sampling (include/rtpbr.h rtpbr_select_* / rtpbr_sample_selected)
-    def select_mask(self, mask) -> int:
-        """Select the pixels where ``mask`` (W,H) is nonzero — a region of interest.  Returns how many."""
+    def select_mask(self, mask, raw=False) -> int:
+        """Select the pixels where ``mask`` (W,H) is nonzero — a region of interest.  Returns how many.  ``raw``: the mask is
+        uint8 and its bytes cross as they are, which with ``set_select_tiers(T > 1)`` makes them tiers: 1 = the full share of
+        the batch, 2 = half of it, ... (bytes above T count as T)."""
         W, H = self.config.width, self.config.height
-        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if raw:
+            if np.asarray(mask).dtype != np.uint8:
+                raise TypeError("a raw mask must be uint8")
+            m = np.ascontiguousarray(mask)
+        else:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
         if m.shape != (W, H):
             raise ValueError(f"expected a mask of shape {(W, H)}, got {m.shape}")
         return self._count("select_mask", m.ctypes.data_as(C.c_void_p), m.nbytes)
+
+    def set_select_tiers(self, tiers: int = 1, batch: int = 16):
+        """Options ``select_tiers`` and ``select_batch`` for the select calls that follow: with ``tiers`` > 1 every selected pixel
+        gets one of that many shares of the batch — ``sample_selected(n)`` gives a pixel of tier t ``max(1, n >> t)`` samples —
+        and the noise-driven rules (select_noisy, select_error, select_blend_error) pick the smallest share of ``batch`` that
+        brings the pixel to the threshold (include/rtpbr.h).  1 (the default): every selected pixel takes the whole batch.
+        A selection keeps the tiers it was built with."""
+        tiers, batch = int(tiers), int(batch)
+        self.set_option("select_tiers", tiers)
+        self.set_option("select_batch", batch)
+        self.select_tiers = (tiers, batch)
+
+    @property
+    def selection_tiers(self):
+        """How many pixels of the current selection are in tier 0, 1, ...: a tuple of as many counts as ``set_select_tiers`` last
+        set tiers (no synchronisation: the select call brought them to the host)."""
+        return tuple(self.counter("select_tier%d" % t) for t in range(self.select_tiers[0]))
+
+    @staticmethod
+    def tier_shares(n: int, tiers: int):
+        """What ``sample_selected(n)`` gives a pixel of tier 0 .. ``tiers`` - 1: max(1, n >> t), nothing when n is 0."""
+        return tuple(max(1, n >> t) if n >= 1 else 0 for t in range(tiers))
+
+    def _selected_samples(self, n_sel, n):
+        """the pixel-samples sample_selected(n) traces through the current selection of n_sel pixels"""
+        tiers = self.select_tiers[0]
+        if tiers == 1:
+            return n_sel * n
+        return sum(c * s for c, s in zip(self.selection_tiers, self.tier_shares(n, tiers)))
 
     def select_lattice(self, period=(2, 2), phase=(0, 0)) -> int:
         """Select the pixels with ``x % px == phx and y % py == phy``: one pixel of every ``px`` x ``py`` cell, for sparse frames
@@ -404,7 +446,7 @@ class Renderer:
         if self.track_halves:
             self.half_update()
 
-    def render_adaptive(self, noise: float, max_spp: int, batch_spp: int = 16, dilate: int = 0, per_sample: bool = False):
+    def render_adaptive(self, noise: float, max_spp: int, batch_spp: int = 16, dilate: int = 0, per_sample: bool = False, tiers: int = 1):
         """``render_until`` that stops sampling a pixel once it is done: two full-frame batches of ``batch_spp`` (the temporal
         estimate needs two), then select_noisy(noise, dilate) -> sample_selected(batch_spp) -> noise_update() until nothing is
         selected or another batch would take a pixel past ``max_spp``.  Returns (pixel-samples traced, NoiseStats of the last
@@ -416,12 +458,16 @@ class Renderer:
         neighbours' spread counts while it is young), and ``min_samples`` keeps every pixel selected up to that count
         (DESIGN.md 6f).  ``per_sample``: with set_noise_tracking(True) for the duration of the call (restored after): ONE
         full-frame batch, whose ``batch_spp`` samples are that many batches of the estimate, then select_noisy ->
-        sample_selected as above without any noise_update()."""
+        sample_selected as above without any noise_update().  ``tiers`` > 1: with
+        set_select_tiers(tiers, batch_spp) for the duration of the call (restored after): every round gives a selected pixel the
+        smallest share ``max(1, batch_spp >> t)`` of the batch that its noise asks for, so one large batch does the work of many
+        small ones without overshooting the pixels that were nearly done; a pixel then holds samples
+        0 .. share - 1 of every round's ``batch_spp`` indices."""
         if not (batch_spp >= 1 and max_spp >= 1):
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
         n_pix = self.config.width * self.config.height
-        with self._loop_state(noise_per_sample=per_sample):
+        with self._loop_state(noise_per_sample=per_sample, select_tiers=(int(tiers), batch) if int(tiers) != 1 else None):
             traced, used = 0, 0
             for _ in range(1 if per_sample else 2):
                 n = min(batch, budget - used)
@@ -438,7 +484,7 @@ class Renderer:
                 self.sample_selected(batch)
                 if not per_sample:
                     self.noise_update()
-                traced, used = traced + n_sel * batch, used + batch
+                traced, used = traced + self._selected_samples(n_sel, batch), used + batch
             return traced, self.noise_estimate(noise)
 
     # ------------------------------------------------------------ the error of the denoised frame (include/rtpbr.h rtpbr_half_update / rtpbr_denoise_error)
@@ -599,7 +645,7 @@ class Renderer:
         return self._count("select_blend_error", float(threshold), int(dilate))
 
     def render_adaptive_denoised(self, error: float, max_spp: int, batch_spp: int = 4, dilate: int = 1, per_sample: bool = False,
-                                 blend=False, *, stop="filter", bias="linear", coverage=None, fill=False, **denoise_params):
+                                 blend=False, *, stop="filter", bias="linear", coverage=None, fill=False, tiers=1, **denoise_params):
         """``render_adaptive`` for a host that shows the DENOISED frame: two full-frame batches of ``batch_spp`` with a
         half_update() after each (both halves hold samples), then denoise_error(error) -> select_error(error, dilate) ->
         sample_selected(batch_spp) -> half_update() until no pixel's estimated denoised noise exceeds ``error`` or another batch
@@ -620,14 +666,16 @@ class Renderer:
         ``stop="blend"`` the coverage-weighted calls (denoise_blend_levels_coverage, blend_error_coverage).
         ``fill`` (with ``blend="levels"`` only): option ``blend_fill`` is set for the duration of the call, so every level-blend
         call of the loop fills the pixels without samples; the return value becomes ((pixel-samples traced, NoiseStats), (filled,
-        empty, deepest) of the last filling call)."""
+        empty, deepest) of the last filling call).
+        ``tiers`` > 1: with set_select_tiers(tiers, batch_spp) for the duration of the call (restored after), as in
+        render_adaptive: the select calls give every selected pixel the smallest share of the batch its estimated error asks for."""
         if isinstance(blend, str) and blend != "levels":
             raise ValueError('blend must be True, False or "levels"')
         if fill:
             if blend != "levels":
                 raise ValueError('fill selects the filling level blend: blend must be "levels"')
             return self._with_blend_fill(lambda: self.render_adaptive_denoised(error, max_spp, batch_spp, dilate, per_sample, blend, stop=stop,
-                                                                               bias=bias, coverage=coverage, **denoise_params))
+                                                                               bias=bias, coverage=coverage, tiers=tiers, **denoise_params))
         if stop not in ("filter", "blend"):
             raise ValueError('stop must be "filter" or "blend"')
         if stop == "blend" and blend != "levels":
@@ -647,7 +695,7 @@ class Renderer:
             raise ValueError("batch_spp and max_spp must be >= 1")
         batch, budget = int(batch_spp), int(max_spp)
         n_pix = self.config.width * self.config.height
-        with self._loop_state(halves=True, half_per_sample=per_sample):
+        with self._loop_state(halves=True, half_per_sample=per_sample, select_tiers=(int(tiers), batch) if int(tiers) != 1 else None):
             traced, used = 0, 0
             for _ in range(2):
                 n = min(batch, budget - used)
@@ -670,7 +718,7 @@ class Renderer:
                 self.sample_selected(batch)
                 if not per_sample:
                     self.half_update()
-                traced, used = traced + n_sel * batch, used + batch
+                traced, used = traced + self._selected_samples(n_sel, batch), used + batch
             if stop == "blend":
                 pass      # (the last blend_error() wrote the frame of the whole buffer)
             elif blend == "levels" and coverage is not None:

@@ -2,14 +2,17 @@
 """Whole frames from a fraction of the pixels: sparse sampling on a lattice, completed by the filling denoise.
 
     python examples/sparse_preview.py [--size 256 256] [--spp 4] [--period 2 2] [--out out/sparse] [--coverage-fill] [--blend] [--bench]
+                                      [--device-lattice]
 
 Cornell v3.  First view: select_lattice -> sample_selected -> denoise_fill (rtpbr_denoise with option denoise_fill = 1: a pixel
 without samples takes the feature-weighted mean of the sampled pixels of its object) -> present("denoised").  Then the camera
 moves: reproject warps what the new view can reuse, and denoise_fill shows a whole frame before any new sample — the holes of the
 move filled.  Then px * py frames of the rotating lattice (Renderer.lattice_phase), each tracing one pixel of every cell, after
 which every pixel has samples.  Every step's frame is written as an image, next to the same step shown with its holes (denoise).
---bench prints blocking wall times of each step, and of select_lattice by itself: its mask is built on the host and crosses to the
-device on every call.  --coverage-fill fills with denoise_coverage_fill instead (rtpbr_denoise_coverage with option coverage_fill =
+--bench prints blocking wall times of each step, and of select_lattice by itself on both of its paths: the default, whose mask is
+built on the host and crosses to the device on every call, and select_lattice(device=True), where the library builds the same
+selection on the device with one kernel and nothing crosses (option select_lattice).  --device-lattice selects that way in every
+step: the same frames, bit for bit.  --coverage-fill fills with denoise_coverage_fill instead (rtpbr_denoise_coverage with option coverage_fill =
 1: the holes filled inside the coverage-weighted levels, the two-object pixels resolved, filled ones included) and shows the holes
 with denoise_coverage.  --blend fills with the level blend instead (denoise_blend_levels(fill=True): rtpbr_denoise_blend_levels with
 option blend_fill = 1; with --coverage-fill its coverage-weighted form): the samples are dealt to the two halves as they are traced
@@ -32,6 +35,7 @@ ap.add_argument("--out", default="out/sparse")
 ap.add_argument("--coverage-fill", action="store_true")
 ap.add_argument("--blend", action="store_true")
 ap.add_argument("--bench", action="store_true")
+ap.add_argument("--device-lattice", action="store_true")
 a = ap.parse_args()
 
 W, H = a.size
@@ -65,7 +69,7 @@ def show(step):
 
 
 # the first view: one pixel of every cell
-n = r.select_lattice(period, (0, 0))
+n = r.select_lattice(period, (0, 0), device=a.device_lattice)
 r.refresh()
 r.sample_selected(a.spp)
 print(f"Cornell v3 {W}x{H}: {n} of {W * H} pixels traced at {a.spp} spp")
@@ -80,7 +84,7 @@ show("moved")
 
 # the rotating lattice: every pixel of a cell once per px * py frames
 for k in range(period[0] * period[1]):
-    r.select_lattice(period, Renderer.lattice_phase(k, period))
+    r.select_lattice(period, Renderer.lattice_phase(k, period), device=a.device_lattice)
     r.sample_selected(a.spp)
     show(f"frame{k}")
 
@@ -94,16 +98,18 @@ if a.bench:
         r.sync()
         return (time.perf_counter() - t0) / reps * 1e3
 
-    def lattice_frame():
-        r.select_lattice(period, (0, 0))
+    def lattice_frame(device):
+        r.select_lattice(period, (0, 0), device=device)
         r.sample_selected(1)
 
-    r.select_lattice(period, (0, 0))
+    r.select_lattice(period, (0, 0), device=a.device_lattice)
     r.refresh()
     r.sample_selected(a.spp)               # a sparse frame again: what denoise_fill is for
     print(f"wall ms per call at {W}x{H}, lattice {period}: select_lattice {ms(lambda: r.select_lattice(period, (0, 0))):.3f}, "
-          f"select_lattice + sample_selected(1) {ms(lattice_frame):.3f}, sample(1) {ms(lambda: r.sample(1)):.3f}")
-    r.select_lattice(period, (0, 0))
+          f"select_lattice + sample_selected(1) {ms(lambda: lattice_frame(False)):.3f}, sample(1) {ms(lambda: r.sample(1)):.3f}")
+    print(f"  built on the device: select_lattice {ms(lambda: r.select_lattice(period, (0, 0), device=True)):.3f}, "
+          f"select_lattice + sample_selected(1) {ms(lambda: lattice_frame(True)):.3f}")
+    r.select_lattice(period, (0, 0), device=a.device_lattice)
     r.refresh()
     r.sample_selected(a.spp)
     if a.blend:

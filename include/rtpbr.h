@@ -705,7 +705,24 @@ int rtpbr_set_noise_tracking(rtpbr_ctx* ctx, int mode);
  *   sample_base + s_t - 1 through the pixels of tiers 0 .. t (a prefix of the list), each an ordinary selected launch; stages with
  *   s_t = s_{t+1} or no pixels are skipped.  Counters: samples = deposits = the sum over t of (pixels in tier t) * s_t;
  *   rtpbr_last_sample_ms sums all stages and counts all their sub-launches.  Noise tracking, per-sample halves and every refusal
- *   are those of the plain selected launch. */
+ *   are those of the plain selected launch.
+ *
+ * Lattices built on the device: rtpbr_set_option "select_lattice" = px + 16 * py + 256 * phx + 4096 * phy is a command spelled as
+ *   an option (as "reserve_spp" is).  With 1 <= px, py <= 8, 0 <= phx < px, 0 <= phy < py and no other bits set it leaves the
+ *   context exactly as rtpbr_select_mask leaves it for the mask "x % px == phx && y % py == phy" (bytes 0 / 1): the same
+ *   RTPBR_BUF_SELECTION, the same n_selected = nx * ny with nx = phx < W ? (W - phx + px - 1) / px : 0 and ny likewise (the host
+ *   computes it the same way: nothing comes back), every lattice pixel in tier 0 of the current "select_tiers", the same
+ *   counters "select_tier*", and every later call answers as after that rtpbr_select_mask, bit for bit.  The call enqueues ONE
+ *   kernel and returns: no mask crosses to the device, nothing is counted or scanned, nothing blocks; it is ordered behind
+ *   asynchronous reads of RTPBR_BUF_SELECTION.  The list is in ascending buffer index, as rtpbr_select_mask's is (a build with
+ *   -DRT_LATTICE_ORDER=1 orders it in blocks of 8 x 8 lattice pixels instead; the order is not observable: a pixel's sample k is
+ *   the same ray wherever the pixel stands in the list).
+ *   Value 0 is accepted and does nothing (rtpbr_jit_prebuild option strings may carry it).  Every other value is refused with
+ *   RTPBR_EINVAL and RTPBR_SELECT_LATTICE_REFUSAL; a lattice is then refused as rtpbr_select_mask refuses, in its order and words:
+ *   RTPBR_ESTATE before set_config / set_scene / set_camera (and on a context without a device), RTPBR_ESTATE with tiles of
+ *   world > 1.  A refused call changes nothing. */
+#define RTPBR_SELECT_LATTICE_REFUSAL \
+    "select_lattice must be 0 (nothing) or px + 16 * py + 256 * phx + 4096 * phy with 1 <= px, py <= 8, 0 <= phx < px and 0 <= phy < py"
 int rtpbr_select_mask(rtpbr_ctx* ctx, const uint8_t* mask, size_t nbytes, uint32_t* n_selected);
 int rtpbr_select_noisy(rtpbr_ctx* ctx, float threshold, int dilate, uint32_t* n_selected);
 int rtpbr_sample_selected(rtpbr_ctx* ctx, int n);
@@ -1419,7 +1436,8 @@ int rtpbr_get_stream(rtpbr_ctx* ctx, void** stream);
  * samples per pixel, and a launch that has none (or a "chunk" that is none) keeps the item-linear records; 0, the default:
  * item-linear records always.  Same bits either way; 21 % fewer HBM writes and 7 % more time on the 1080p x 256 spp step),
  * "reserve_spp" (allocate the staging of a call of that many samples per pixel now instead of on
- * first use), "sample_base" (absolute index of the next sample: checkpoint/resume).
+ * first use), "select_lattice" (build the selection of a lattice on the device now: the adaptive-sampling section),
+ * "sample_base" (absolute index of the next sample: checkpoint/resume).
  * Returns RTPBR_EINVAL for unknown keys or out-of-range values. */
 int rtpbr_set_option(rtpbr_ctx* ctx, const char* key, long long value);
 

@@ -2093,6 +2093,39 @@ extern "C" int rtpbr_select_mask(rtpbr_ctx* c, const uint8_t* mask, size_t nbyte
     return selection_build(c, A, SELECT_MASK, n_selected);
 }
 
+// Option "select_lattice" (include/rtpbr.h): the state rtpbr_select_mask leaves for the lattice's mask, from ONE kernel that writes
+// the plane and the list (rt_select.hip select_lattice_build).  The count is known here, so nothing is copied either way and
+// nothing waits: the call enqueues and returns.  rtpbr_select_mask's refusals, in its order, once the value is a lattice.
+static int select_lattice_option(rtpbr_ctx* c, long long value) {
+    if (value == 0) return RTPBR_OK;
+    LatticeArgs A{};
+    if (!lattice_decode(value, &A.l)) return fail(RTPBR_EINVAL, RTPBR_SELECT_LATTICE_REFUSAL);
+    // (a context without a device has no frame to select in)
+    if (!c->have_cfg || !c->have_scene || !c->have_cam || c->headless) return fail(RTPBR_ESTATE, "set_config, set_scene and set_camera first");
+    if (c->world > 1) return fail(RTPBR_ESTATE, SELECT_TILES);
+    if (int r = set_dev(c)) return r;
+    if (int r = frame_need(c, {ROW_sel_mask, ROW_sel_list, ROW_sel_blocks})) return r;
+    if (int r = rt_order_after_reads(c, W_SELECTION)) return r;
+    lattice_count(&A.l, c->cfg.width, c->cfg.height);
+    A.mask = c->sel_mask;
+    A.list = c->sel_list;
+    A.width = c->cfg.width;
+    A.height = c->cfg.height;
+    c->have_selection = false;
+    c->sel_count = 0;
+    c->sel_tiers = 1;
+    for (uint32_t& l : c->sel_cum) l = 0;
+    launch_select_lattice(A, c->stream);
+    HIP_TRY(hipGetLastError());
+    // every lattice pixel is in tier 0 (the mask's byte 1): with select_tiers = T the pixels of tiers 0 .. t are all of them
+    const uint32_t n = A.l.nx * A.l.ny;
+    c->sel_tiers = c->select_tiers;
+    for (int t = 0; t < c->sel_tiers; t++) c->sel_cum[t] = n;
+    c->sel_count = n;
+    c->have_selection = true;
+    return RTPBR_OK;
+}
+
 extern "C" int rtpbr_select_noisy(rtpbr_ctx* c, float threshold, int dilate, uint32_t* n_selected) {
     if (!c || !n_selected) return fail(RTPBR_EINVAL, "null argument");
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "noise threshold must be >= 0");
@@ -2996,6 +3029,9 @@ extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value) 
         const long long K = value < kmax ? value : kmax;
         if (int r = ensure_staging(c, (size_t)c->P.np * (size_t)K, split_ok, !unstaged))
             return r == RTPBR_ENOMEM ? fail(RTPBR_ENOMEM, "reserve_spp: no device memory for the staging of that many samples per pixel") : r;
+    } else if (!strcmp(key, "select_lattice")) {
+        // build the selection of a lattice now, on the device (a command, as reserve_spp is)
+        return select_lattice_option(c, value);
     } else if (!strcmp(key, "sample_base")) {
         c->sample_base = (uint32_t)value;
     } else {

@@ -252,4 +252,48 @@ void launch_select(const SelectArgs& A, int rule, hipStream_t st) {
     hipLaunchKernelGGL(select_scatter, dim3(nb), dim3(256), 0, st, A);
 }
 
+// ---- the lattice selection (option "select_lattice"; the rule and the two orders: rt_lattice.hpp)
+
+// 0 (default): the ascending order, what select_mask makes of the same mask; 1: the tiled one — the build of the comparison.
+// Measured on the MI355X: the tiled list's selected launches are not faster than the ascending one's, on the glass
+// bunny's (2,2) lattice slower than the spread of the ascending list's own runs.
+#ifndef RT_LATTICE_ORDER
+#define RT_LATTICE_ORDER 0
+#endif
+constexpr int LATTICE_ORDER = RT_LATTICE_ORDER;
+
+// One lane per word of the plane: the four pixels i0 .. i0 + 3 along i = x * H + y (they may cross a column end), their bytes in one
+// store where all four are inside the frame (the plane is an allocation of its own, so i0 is word-aligned), and list[rank] = i for
+// those on the lattice: x < W and x % px == phx give a = x / px < nx, likewise b < ny, so rank < nx * ny <= W * H, the list's room.
+// Nothing is read, no lane waits for another.
+__global__ void __launch_bounds__(256) select_lattice_build(const LatticeArgs A) {
+    const uint32_t H = (uint32_t)A.height, n = (uint32_t)A.width * H;
+    const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4u;
+    if (i0 >= n) return;
+    const uint32_t px = (uint32_t)A.l.px, py = (uint32_t)A.l.py, phx = (uint32_t)A.l.phx, phy = (uint32_t)A.l.phy;
+    const uint32_t left = n - i0 < 4u ? n - i0 : 4u;
+    uint32_t x = i0 / H, y = i0 - x * H, word = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        if (k < left && x % px == phx && y % py == phy) {
+            word |= 1u << (8u * k);
+            A.list[lattice_rank(LATTICE_ORDER, x / px, y / py, A.l.nx, A.l.ny)] = i0 + k;
+        }
+        if (++y == H) {
+            y = 0;
+            x++;
+        }
+    }
+    if (left == 4u) {
+        *reinterpret_cast<uint32_t*>(A.mask + i0) = word;
+    } else {
+        for (uint32_t k = 0; k < left; k++) A.mask[i0 + k] = (uint8_t)(word >> (8u * k));
+    }
+}
+
+void launch_select_lattice(const LatticeArgs& A, hipStream_t st) {
+    const uint32_t words = (uint32_t)(((size_t)A.width * (size_t)A.height + 3) / 4);
+    hipLaunchKernelGGL(select_lattice_build, dim3((words + 255u) / 256u), dim3(256), 0, st, A);
+}
+
 }  // namespace rt

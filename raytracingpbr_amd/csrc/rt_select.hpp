@@ -10,6 +10,7 @@
 //                       the block's start from the scan: list[start + rank] = i.  Ascending i by construction, whatever the schedule.
 // Only the total comes back to the host (4 bytes).
 #pragma once
+#include "rt_lattice.hpp"
 #include "rt_types.hpp"
 
 namespace rt {
@@ -53,5 +54,18 @@ struct SelectTierArgs {
 
 void launch_select_tiered(const SelectTierArgs& S, int rule, hipStream_t st);      // the four passes; blocks[T * n_blocks + 1 + t] = L_t afterwards
 inline size_t select_tier_words(int w, int h) { return (size_t)select_blocks(w, h) * SELECT_MAX_TIERS + 1 + SELECT_MAX_TIERS; }
+
+// The lattice selection (option "select_lattice"): which pixels, how many and each one's list position are known in closed form
+// (rt_lattice.hpp), so ONE kernel writes the plane and the list, nothing is counted or scanned, and nothing comes back to the host.
+//   select_lattice_build   one lane per four pixels along i = x * H + y (one word of the plane); a lattice pixel also writes
+//                          list[rank] = i, rank in the order RT_LATTICE_ORDER (rt_select.hip) names: ascending unless built otherwise
+struct LatticeArgs {
+    uint8_t* mask;      // out: RTPBR_BUF_SELECTION, 0 / 1
+    uint32_t* list;     // out: the nx * ny lattice pixels' buffer indices
+    Lattice l;
+    int32_t width, height;
+};
+
+void launch_select_lattice(const LatticeArgs& A, hipStream_t st);
 
 }  // namespace rt

@@ -394,13 +394,27 @@ class Renderer:
             return n_sel * n
         return sum(c * s for c, s in zip(self.selection_tiers, self.tier_shares(n, tiers)))
 
-    def select_lattice(self, period=(2, 2), phase=(0, 0)) -> int:
+    def select_lattice(self, period=(2, 2), phase=(0, 0), device=False) -> int:
         """Select the pixels with ``x % px == phx and y % py == phy``: one pixel of every ``px`` x ``py`` cell, for sparse frames
-        that ``denoise_fill`` completes.  Periods 1..8 per axis, 0 <= phase < period.  The mask is built on the host and crosses
-        to the device with the call (W * H bytes).  Returns how many pixels are selected."""
+        that ``denoise_fill`` completes.  Periods 1..8 per axis, 0 <= phase < period.  Returns how many pixels are selected.
+        By default the mask is built on the host and crosses to the device with the call (W * H bytes), which blocks.
+        ``device=True``: the library builds the same selection on the device (option ``select_lattice``): one call that
+        enqueues one kernel and returns, no copy, no wait; the count is the closed form.  Same state and same samples
+        afterwards, bit for bit."""
         (px, py), (phx, phy) = self._lattice_args(period, phase)
         W, H = self.config.width, self.config.height
+        if device:
+            self.set_option("select_lattice", px + 16 * py + 256 * phx + 4096 * phy)
+            return self.lattice_count(W, H, (px, py), (phx, phy))
         return self.select_mask(np.logical_and.outer(np.arange(W) % px == phx, np.arange(H) % py == phy))
+
+    @staticmethod
+    def lattice_count(width, height, period, phase) -> int:
+        """How many pixels of a ``width`` x ``height`` frame are on the lattice: per axis (extent - phase + period - 1) // period,
+        0 where the phase is beyond the frame."""
+        def axis(extent, p, ph):
+            return (extent - ph + p - 1) // p if ph < extent else 0
+        return axis(width, period[0], phase[0]) * axis(height, period[1], phase[1])
 
     @staticmethod
     def _lattice_args(period, phase):

@@ -1491,24 +1491,32 @@ static int whole_frame_state(rtpbr_ctx* c, const char* tiles, const char* who = 
 }
 static const char* const FEATURE_TILES = "rtpbr_render_features / rtpbr_denoise work on the whole frame: not with tiles of world > 1";
 
-extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
-    if (!c) return fail(RTPBR_EINVAL, "null ctx");
-    if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
-    if (int r = set_dev(c)) return r;
-    if (int r = frame_need(c, {ROW_feat_albedo, ROW_feat_normal, ROW_feat_depth, ROW_feat_object, ROW_feat_guides})) return r;
-    if (int r = rt_order_after_reads(c, W_FEATURES)) return r;
-    // the context's Params with the general march table (signature 0, no lazy box keys): what the run-time object-count instances read
+// The Params of the feature rays at g x g rays per pixel (g = 1: rtpbr_render_features; the sub-rays of the coverage plane are the
+// feature rays of the g-fold configuration): the context's, with that width, height and their reciprocals and the general march
+// table (signature 0, no lazy box keys), which is what the run-time object-count instances read
+static Params feature_params(rtpbr_ctx* c, int g) {
     Params P = c->P;
     P.cfg = c->cfg;
-    P.cam.inv_w = 1.0f / (float)c->cfg.width;
-    P.cam.inv_h = 1.0f / (float)c->cfg.height;
+    P.cfg.width = g * c->cfg.width;
+    P.cfg.height = g * c->cfg.height;
+    P.cam.inv_w = 1.0f / (float)P.cfg.width;
+    P.cam.inv_h = 1.0f / (float)P.cfg.height;
     P.n_obj = c->n_obj;
     P.box_sig = 0;
     P.box_lazy = 0;
     pack_table(c->objm, c->n_obj, 0, P.objm);
     P.objfull = c->objfull;
     P.bunny = c->bunny;
-    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    return P;
+}
+
+extern "C" int rtpbr_render_features(rtpbr_ctx* c) {
+    if (!c) return fail(RTPBR_EINVAL, "null ctx");
+    if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
+    if (int r = set_dev(c)) return r;
+    if (int r = frame_need(c, {ROW_feat_albedo, ROW_feat_normal, ROW_feat_depth, ROW_feat_object, ROW_feat_guides})) return r;
+    if (int r = rt_order_after_reads(c, W_FEATURES)) return r;
+    const Params P = feature_params(c, 1);
     FeatArgs A;
     A.albedo = c->feat_albedo;
     A.normal = c->feat_normal;
@@ -1534,12 +1542,14 @@ static int denoise_params_check(int iterations, int demodulate, const float* sig
     return RTPBR_OK;
 }
 
-// RTPBR_BUF_DENOISED_PIXELS and, from two levels on, the two halves of the levels' ping-pong; then ordered after the buffer's reads
+// the two halves of a chain's ping-pong: from two levels on
+static int denoise_scratch_need(rtpbr_ctx* c, int iterations) { return iterations >= 2 ? frame_need(c, {ROW_denoise_scratch}) : RTPBR_OK; }
+
+// RTPBR_BUF_DENOISED_PIXELS and the ping-pong; then ordered after the buffer's reads
 static int denoised_alloc(rtpbr_ctx* c, int iterations) {
     if (int r = set_dev(c)) return r;
     if (int r = frame_need(c, {ROW_denoised})) return r;
-    if (iterations >= 2)
-        if (int r = frame_need(c, {ROW_denoise_scratch})) return r;
+    if (int r = denoise_scratch_need(c, iterations)) return r;
     return rt_order_after_reads(c, W_DENOISED);
 }
 
@@ -1558,15 +1568,6 @@ static DenoiseArgs denoise_args(rtpbr_ctx* c, int demodulate, const float* inv) 
     return A;
 }
 
-// The levels of either filter, after every refusal: level k reads half (k - 1) & 1 of denoise_scratch and writes half k & 1; the
-// first reads image_buffer, the last writes denoised.  g != nullptr: the guided kernel, whose variance goes the same way through
-// the two planes of noise_var behind the estimate's (plane 0).  No level: the tone-map-only pass, the same for both.
-// in / out (rtpbr_denoise_error, rtpbr_denoise_blend): the filter of another (sum r, sum g, sum b, count) buffer into another
-// display buffer; the caller has allocated the ping-pong.  linear (plain filter, with out): the last level stops before the tone
-// map and out takes the linear colour after remodulation.  cover_k (rtpbr_denoise_coverage; plain, linear, iterations > 0): the
-// coverage-weighted levels.  fill (rtpbr_denoise with option denoise_fill = 1; plain, no in / out, iterations > 0): the filling levels,
-// which count into fill_counts (zeroed on the stream first).  fill with cover_k (rtpbr_denoise_coverage with option coverage_fill = 1):
-// the coverage-weighted filling levels; the last writes cov_live (the caller has allocated it) beside out.
 // The shards the filling kernels count into, zeroed on the stream: the call's own (what counters "fill_*" read), and behind them a
 // second set nobody reads (the half chains of the level blend with option blend_fill = 1 count there).
 constexpr size_t FILL_COUNT_WORDS = (size_t)FILL_SHARDS * FILL_SHARD_WORDS;
@@ -1577,39 +1578,62 @@ static int fill_counts_zero(rtpbr_ctx* c) {
     return RTPBR_OK;
 }
 
-static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const rtpbr_denoise_guided_params* g,
-                          const float4* in = nullptr, float* out = nullptr, bool linear = false, const float* cover_k = nullptr,
-                          bool fill = false) {
-    if (!out)
+// a launcher found no instance for the form it was asked for and launched nothing (no call of include/rtpbr.h asks for one)
+static int no_instance(const char* family) { return fail(RTPBR_EHIP, "internal error: no instance of %s for the form asked for", family); }
+
+// where level k of `levels` stands, and the level in A: its step 2^k, the plain filter's colour weight and the ping-pong.  The level
+// reads plane (k - 1) & 1 of `planes` (n records each; not at LEVEL_FIRST, which reads A.image_buffer) and writes plane k & 1 (not at
+// LEVEL_LAST, which writes A.out).  variance: the guided filter's two planes (its colour weight is per pixel), which go the same way
+static unsigned level_position(int k, int levels) { return (k == 0 ? LEVEL_FIRST : 0u) | (k + 1 == levels ? LEVEL_LAST : 0u); }
+static void level_args(DenoiseArgs& A, int k, unsigned position, const float* inv, float4* planes, float* variance, size_t n) {
+    const bool first = (position & LEVEL_FIRST) != 0, last = (position & LEVEL_LAST) != 0;
+    const size_t before = (size_t)((k - 1) & 1) * n, now = (size_t)(k & 1) * n;
+    A.src = first ? nullptr : planes + before;
+    A.dst = last ? nullptr : planes + now;
+    if (variance) {
+        A.vsrc = first ? nullptr : variance + before;
+        A.vdst = last ? nullptr : variance + now;
+    } else {
+        A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
+    }
+    A.step = 1 << k;
+}
+
+// One run of the filter.  The calls that run the same filter on several buffers build it once and vary in and out.
+struct FilterChain {
+    const float4* in = nullptr;       // the (sum r, sum g, sum b, count) buffer; nullptr: image_buffer
+    float* out = nullptr;             // the last level's (W,H,3) plane; nullptr: RTPBR_BUF_DENOISED_PIXELS, allocated here with the ping-pong
+    unsigned form = 0;                // ATROUS_LINEAR (with out); ATROUS_FILL (iterations > 0): the levels count into fill_counts, zeroed first
+    const rtpbr_denoise_guided_params* guided = nullptr;      // ATROUS_GUIDED: the variance goes through noise_var's planes 1 and 2
+    const float* cover_k = nullptr;   // ATROUS_COVER (with ATROUS_LINEAR, iterations > 0); with ATROUS_FILL the last level writes cov_live
+    FilterChain on(const float4* in_, float* out_) const { return FilterChain{in_, out_, form, guided, cover_k}; }
+};
+
+// The levels of a chain, after every refusal, through the two halves of denoise_scratch.  No level: the tone-map-only pass
+static int denoise_levels(rtpbr_ctx* c, int iterations, int demodulate, const float* inv, const FilterChain& ch) {
+    if (!ch.out)
         if (int r = denoised_alloc(c, iterations)) return r;
     const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    const unsigned form = ch.form | (ch.guided ? ATROUS_GUIDED : 0u) | (ch.cover_k ? ATROUS_COVER : 0u);
     DenoiseArgs A = denoise_args(c, demodulate, inv);
-    A.image_buffer = in ? in : c->image_buffer;
-    A.out = out ? out : c->denoised;
-    if (cover_k) A.cover_k = cover_k;      // (shares var0's word: never with g)
-    if (fill) {
+    A.image_buffer = ch.in ? ch.in : c->image_buffer;
+    A.out = ch.out ? ch.out : c->denoised;
+    if (ch.cover_k) A.cover_k = ch.cover_k;      // (shares var0's word: never with guided)
+    if (form & ATROUS_FILL) {
         if (int r = fill_counts_zero(c)) return r;
-        A.fill = c->fill_counts;           // (shares vsrc's word: never with g)
-        if (cover_k) A.live = c->cov_live; // (shares vdst's word: never with g)
+        A.fill = c->fill_counts;                 // (shares vsrc's word: never with guided)
+        if (ch.cover_k) A.live = c->cov_live;    // (shares vdst's word: never with guided)
     }
-    if (g) {
+    if (ch.guided) {
         A.var0 = c->noise_var;
-        A.sc2 = g->sigma_color * g->sigma_color;
-        A.floor = g->variance_floor;
+        A.sc2 = ch.guided->sigma_color * ch.guided->sigma_color;
+        A.floor = ch.guided->variance_floor;
     }
-    if (iterations == 0) launch_atrous_level(A, true, true, false, c->stream, linear);      // (A.step = 0)
+    if (iterations == 0 && !launch_atrous_level(A, LEVEL_ONLY | form, c->stream)) return no_instance("atrous_level");      // (A.step = 0)
     for (int k = 0; k < iterations; k++) {
-        const bool first = k == 0, last = k + 1 == iterations;
-        A.src = first ? nullptr : c->denoise_scratch + (size_t)((k - 1) & 1) * n;
-        A.dst = last ? nullptr : c->denoise_scratch + (size_t)(k & 1) * n;
-        if (g) {
-            A.vsrc = first ? nullptr : c->noise_var + (size_t)(1 + ((k - 1) & 1)) * n;
-            A.vdst = last ? nullptr : c->noise_var + (size_t)(1 + (k & 1)) * n;
-        } else {
-            A.ic = inv[0] * (float)(1u << (2 * k));     // sigma_c halves at every level (exact: a power of two)
-        }
-        A.step = 1 << k;
-        launch_atrous_level(A, first, last, g != nullptr, c->stream, linear && last, cover_k != nullptr, fill);
+        const unsigned position = level_position(k, iterations);
+        level_args(A, k, position, inv, c->denoise_scratch, ch.guided ? c->noise_var + n : nullptr, n);
+        if (!launch_atrous_level(A, position | form, c->stream)) return no_instance("atrous_level");
     }
     HIP_TRY(hipGetLastError());
     return RTPBR_OK;
@@ -1644,7 +1668,9 @@ extern "C" int rtpbr_denoise(rtpbr_ctx* c, const rtpbr_denoise_params* p) {
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
     // option denoise_fill: the filling levels (iterations = 0 has no level: nothing is filled, the counters keep the last filling call's)
-    return denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, nullptr, nullptr, false, nullptr, c->denoise_fill && d.iterations > 0);
+    FilterChain ch;
+    if (c->denoise_fill && d.iterations > 0) ch.form = ATROUS_FILL;
+    return denoise_levels(c, d.iterations, d.demodulate, inv, ch);
 }
 
 // ---- sub-pixel coverage and the coverage-aware denoise (rt_coverage.hip)
@@ -1672,8 +1698,7 @@ static CoverageArgs coverage_args(rtpbr_ctx* c, const rtpbr_coverage_params& d) 
     return A;
 }
 
-// The coverage plane at grid d.grid on the stream, unless it is there already; after whole_frame_state; sets the device.  The sub-rays are the feature
-// rays of the g-fold configuration: rtpbr_render_features' Params with that width, height and their reciprocals.
+// The coverage plane at grid d.grid on the stream, unless it is there already; after whole_frame_state; sets the device.
 static int coverage_enqueue(rtpbr_ctx* c, const rtpbr_coverage_params& d) {
     if ((long long)d.grid * c->cfg.width > 65535 || (long long)d.grid * c->cfg.height > 65535)
         return fail(RTPBR_EINVAL, "coverage: grid x resolution out of range (1..65535)");
@@ -1682,26 +1707,41 @@ static int coverage_enqueue(rtpbr_ctx* c, const rtpbr_coverage_params& d) {
         if (int r = rtpbr_render_features(c)) return r;
     if (c->cov_valid && c->cov_rendered_grid == d.grid) return RTPBR_OK;
     if (int r = frame_need(c, {ROW_coverage, ROW_cov_list})) return r;
-    Params P = c->P;
-    P.cfg = c->cfg;
-    P.cfg.width = d.grid * c->cfg.width;
-    P.cfg.height = d.grid * c->cfg.height;
-    P.cam.inv_w = 1.0f / (float)P.cfg.width;
-    P.cam.inv_h = 1.0f / (float)P.cfg.height;
-    P.n_obj = c->n_obj;
-    P.box_sig = 0;
-    P.box_lazy = 0;
-    pack_table(c->objm, c->n_obj, 0, P.objm);
-    P.objfull = c->objfull;
-    P.bunny = c->bunny;
     const CoverageArgs A = coverage_args(c, d);
     HIP_TRY(hipMemsetAsync(c->cov_list, 0, COVER_HEAD * sizeof(uint32_t), c->stream));
     launch_cover_mark(A, c->stream);
-    launch_cover_rays(P, A, c->kind, c->n_cu, c->cover_blocks, c->stream);
+    launch_cover_rays(feature_params(c, d.grid), A, c->kind, c->n_cu, c->cover_blocks, c->stream);
     HIP_TRY(hipGetLastError());
     c->cov_valid = true;
     c->cov_rendered_grid = d.grid;
     return RTPBR_OK;
+}
+
+// The weights plane k and the frame's largest 1 - a from the coverage plane; the resolved count starts at 0 (the list's length stays)
+static int cover_weights_enqueue(rtpbr_ctx* c, const rtpbr_coverage_params& d) {
+    if (int r = frame_need(c, {ROW_cov_k, ROW_cov_linear})) return r;
+    HIP_TRY(hipMemsetAsync(c->cov_list + 1, 0, 2 * sizeof(uint32_t), c->stream));
+    launch_cover_weights(coverage_args(c, d), c->stream);
+    return RTPBR_OK;
+}
+
+// The resolve and the tone map of every pixel: RTPBR_BUF_DENOISED_PIXELS from the linear colour in cov_linear.  live: the byte plane a
+// filling last level wrote ("has a colour"), or nullptr ("has samples")
+static void cover_resolve_enqueue(rtpbr_ctx* c, const rtpbr_coverage_params& d, const uint8_t* live) {
+    ResolveArgs R{};
+    R.cfg = c->cfg;
+    R.image_buffer = c->image_buffer;
+    R.linear = c->cov_linear;
+    R.object = c->feat_object;
+    R.coverage = c->coverage;
+    R.k = c->cov_k;
+    R.head = c->cov_list;
+    R.out = c->denoised;
+    R.width = c->cfg.width;
+    R.height = c->cfg.height;
+    R.resolve = d.resolve;
+    R.live = live;
+    launch_cover_resolve(R, c->stream);
 }
 
 extern "C" int rtpbr_render_coverage(rtpbr_ctx* c, const rtpbr_coverage_params* v) {
@@ -1721,12 +1761,9 @@ extern "C" int rtpbr_denoise_coverage(rtpbr_ctx* c, const rtpbr_denoise_params* 
     if (int r = coverage_params(v, cv)) return r;
     if (int r = whole_frame_state(c, FEATURE_TILES)) return r;
     if (int r = coverage_enqueue(c, cv)) return r;
-    if (int r = frame_need(c, {ROW_cov_k, ROW_cov_linear})) return r;
-    // the weights and the frame's largest 1 - a; the resolved count starts at 0 (the list's length stays)
-    HIP_TRY(hipMemsetAsync(c->cov_list + 1, 0, 2 * sizeof(uint32_t), c->stream));
-    launch_cover_weights(coverage_args(c, cv), c->stream);
+    if (int r = cover_weights_enqueue(c, cv)) return r;
     if (d.iterations == 0) {      // rtpbr_denoise's tone-map-only pass
-        if (int r = denoise_levels(c, 0, d.demodulate, inv, nullptr)) return r;
+        if (int r = denoise_levels(c, 0, d.demodulate, inv, FilterChain{})) return r;
     } else {
         if (int r = denoised_alloc(c, d.iterations)) return r;
         // option coverage_fill: the filling levels and the resolve that asks them who has a colour (not read with iterations = 0: no
@@ -1734,21 +1771,11 @@ extern "C" int rtpbr_denoise_coverage(rtpbr_ctx* c, const rtpbr_denoise_params* 
         const bool fill = c->coverage_fill != 0;
         if (fill)
             if (int r = frame_need(c, {ROW_cov_live})) return r;
-        if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->cov_linear, true, c->cov_k, fill)) return r;
-        ResolveArgs R{};
-        R.cfg = c->cfg;
-        R.image_buffer = c->image_buffer;
-        R.linear = c->cov_linear;
-        R.object = c->feat_object;
-        R.coverage = c->coverage;
-        R.k = c->cov_k;
-        R.head = c->cov_list;
-        R.out = c->denoised;
-        R.width = c->cfg.width;
-        R.height = c->cfg.height;
-        R.resolve = cv.resolve;
-        R.live = fill ? c->cov_live : nullptr;
-        launch_cover_resolve(R, c->stream);
+        FilterChain ch;
+        ch.form = ATROUS_LINEAR | (fill ? ATROUS_FILL : 0u);
+        ch.cover_k = c->cov_k;
+        if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, ch.on(c->image_buffer, c->cov_linear))) return r;
+        cover_resolve_enqueue(c, cv, fill ? c->cov_live : nullptr);
     }
     HIP_TRY(hipGetLastError());
     if (!out) return RTPBR_OK;
@@ -2182,7 +2209,9 @@ extern "C" int rtpbr_denoise_guided(rtpbr_ctx* c, const rtpbr_denoise_guided_par
     } else if (!c->feat_valid) {
         if (int r = rtpbr_render_features(c)) return r;
     }
-    return denoise_levels(c, d.iterations, d.demodulate, inv, &d);
+    FilterChain ch;
+    ch.guided = &d;
+    return denoise_levels(c, d.iterations, d.demodulate, inv, ch);
 }
 
 // ---- the two-half error estimate of the denoised frame (rt_half.hip)
@@ -2275,15 +2304,15 @@ extern "C" int rtpbr_denoise_error(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
     if (!(threshold >= 0.0f)) return fail(RTPBR_EINVAL, "error threshold must be >= 0");
     if (int r = half_call_begin(c, "%s: no half buffer yet (rtpbr_half_update first)", "rtpbr_denoise_error")) return r;
     if (int r = frame_need(c, {ROW_half_da, ROW_half_db, ROW_denoised_error})) return r;
-    if (d.iterations >= 2)
-        if (int r = frame_need(c, {ROW_denoise_scratch})) return r;
+    if (int r = denoise_scratch_need(c, d.iterations)) return r;
     if (int r = rt_order_after_reads(c, W_ERROR)) return r;
     if (!c->feat_valid)
         if (int r = rtpbr_render_features(c)) return r;
     if (int r = half_b_enqueue(c)) return r;
     // the same filter on either half: "has samples" is the half's own count
-    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_a, c->half_da)) return r;
-    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_b, c->half_db)) return r;
+    const FilterChain ch{};
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, ch.on(c->half_a, c->half_da))) return r;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, ch.on(c->half_b, c->half_db))) return r;
     if (int r = noise_stats_zero(c)) return r;
     ErrorArgs A{};
     A.da = c->half_da;
@@ -2320,9 +2349,11 @@ extern "C" int rtpbr_denoise_blend(rtpbr_ctx* c, const rtpbr_denoise_params* p, 
         if (int r = rtpbr_render_features(c)) return r;
     if (int r = half_b_enqueue(c)) return r;
     // three runs of the same filter, each stopping before the tone map
-    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->image_buffer, c->half_fd, true)) return r;
-    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_a, c->half_da, true)) return r;
-    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, nullptr, c->half_b, c->half_db, true)) return r;
+    FilterChain ch;
+    ch.form = ATROUS_LINEAR;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, ch.on(c->image_buffer, c->half_fd))) return r;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, ch.on(c->half_a, c->half_da))) return r;
+    if (int r = denoise_levels(c, d.iterations, d.demodulate, inv, ch.on(c->half_b, c->half_db))) return r;
     if (int r = noise_stats_zero(c)) return r;
     BlendArgs A{};
     A.cfg = c->cfg;
@@ -2392,10 +2423,8 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     if (int r = noise_stats_zero(c)) return r;
     if (cover) {      // the plane (rendered when stale, at the option's grid), the weights and the resolved count at 0, as rtpbr_denoise_coverage
         if (int r = coverage_enqueue(c, cv)) return r;
-        if (int r = frame_need(c, {ROW_cov_k, ROW_cov_linear})) return r;
+        if (int r = cover_weights_enqueue(c, cv)) return r;
         if (!c->blend_resolved) HIP_TRY(hipMalloc(&c->blend_resolved, sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(c->cov_list + 1, 0, 2 * sizeof(uint32_t), c->stream));
-        launch_cover_weights(coverage_args(c, cv), c->stream);
         if (fill)
             if (int r = frame_need(c, {ROW_cov_live})) return r;
     }
@@ -2423,9 +2452,13 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
     A.width = c->cfg.width;
     A.height = c->cfg.height;
     A.radius = b.radius;
+    // the last level's FILL instance shows the pixels without samples, counts them and (LIN) writes cov_live for the resolve
+    uint32_t* const counts = fill ? c->fill_counts : nullptr;
+    uint8_t* const live = fill && cover ? c->cov_live : nullptr;
+    const unsigned blend_form = cover ? BLEND_LIN : 0u;
     if (K == 0) {      // rtpbr_denoise's pass, weight 1, depth 0
-        if (int r = denoise_levels(c, 0, d.demodulate, inv, nullptr)) return r;
-        launch_level_blend(A, true, true, c->stream);
+        if (int r = denoise_levels(c, 0, d.demodulate, inv, FilterChain{})) return r;
+        if (!launch_level_blend(A, LEVEL_ONLY | blend_form, c->stream, counts, live)) return no_instance("level_blend");
     }
     // the K levels of the three chains in lock step through the non-last instances: chain j keeps level k in plane 2 j + (k & 1),
     // so level k - 1 is still there when the window kernel compares the two
@@ -2434,21 +2467,19 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         F.cover_k = c->cov_k;      // k is geometric: one plane for the three chains
         A.out = c->cov_linear;     // the running colour and, after the LIN last level, what the resolve reads
     }
+    const unsigned chain_form = (cover ? ATROUS_COVER : 0u) | (fill ? ATROUS_FILL : 0u);
     const float4* const chain_in[3] = {c->image_buffer, c->half_a, c->half_b};
     for (int k = 0; k < K; k++) {      // k + 1 is the level's number in include/rtpbr.h
-        const bool first = k == 0, last = k + 1 == K;
+        const unsigned position = level_position(k, K), kept = position & LEVEL_FIRST;      // (a chain keeps every level's record: none is its last)
         float4* now[3];
         const float4* before[3];
-        F.ic = inv[0] * (float)(1u << (2 * k));
-        F.step = 1 << k;
         for (int j = 0; j < 3; j++) {
-            now[j] = c->levels_scratch + (size_t)(2 * j + (k & 1)) * n;
-            before[j] = first ? nullptr : c->levels_scratch + (size_t)(2 * j + ((k - 1) & 1)) * n;
             F.image_buffer = chain_in[j];
-            F.src = before[j];
-            F.dst = now[j];
+            level_args(F, k, kept, inv, c->levels_scratch + (size_t)(2 * j) * n, nullptr, n);
+            now[j] = F.dst;
+            before[j] = F.src;
             if (fill) F.fill = c->fill_counts + (j == 0 ? 0 : FILL_COUNT_WORDS);      // (shares vsrc's word: the plain filter)
-            launch_atrous_level(F, first, false, false, c->stream, false, cover, fill);
+            if (!launch_atrous_level(F, kept | chain_form, c->stream)) return no_instance("atrous_level");
         }
         A.kd = now[0];
         A.ka = now[1];
@@ -2456,23 +2487,10 @@ static int blend_levels(rtpbr_ctx* c, const char* who, const rtpbr_denoise_param
         A.pd = before[0];
         A.pa = before[1];
         A.pb = before[2];
-        launch_level_blend(A, first, last, c->stream, cover, fill ? c->fill_counts : nullptr, fill && cover ? c->cov_live : nullptr);
+        if (!launch_level_blend(A, position | blend_form, c->stream, counts, live)) return no_instance("level_blend");
     }
     if (cover) {      // the resolve and the tone map of every pixel, from the blended linear colour
-        ResolveArgs R{};
-        R.cfg = c->cfg;
-        R.image_buffer = c->image_buffer;
-        R.linear = c->cov_linear;
-        R.object = c->feat_object;
-        R.coverage = c->coverage;
-        R.k = c->cov_k;
-        R.head = c->cov_list;
-        R.out = c->denoised;
-        R.width = c->cfg.width;
-        R.height = c->cfg.height;
-        R.resolve = cv.resolve;
-        R.live = fill ? c->cov_live : nullptr;      // option blend_fill: "has a colour" is what the LIN last level wrote
-        launch_cover_resolve(R, c->stream);
+        cover_resolve_enqueue(c, cv, live);      // option blend_fill: "has a colour" is what the LIN last level wrote
         HIP_TRY(hipMemcpyAsync(c->blend_resolved, c->cov_list + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(hipGetLastError());

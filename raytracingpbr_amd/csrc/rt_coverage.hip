@@ -221,14 +221,6 @@ void launch_cover_mark(const CoverageArgs& A, hipStream_t st) {
     hipLaunchKernelGGL(cover_mark, dim3(grid), dim3(256), 0, st, A);
 }
 
-template <int G>
-static void launch_cover_rays_g(const Params& P, const CoverageArgs& A, int kind, unsigned grid, hipStream_t st) {
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((cover_rays<KIND_BOXES, G>), dim3(grid), dim3(256), 0, st, P, A);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((cover_rays<KIND_BUNNY, G>), dim3(grid), dim3(256), 0, st, P, A);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((cover_rays<KIND_MIXED, G>), dim3(grid), dim3(256), 0, st, P, A);
-    else hipLaunchKernelGGL((cover_rays<KIND_GENERIC, G>), dim3(grid), dim3(256), 0, st, P, A);
-}
-
 // The list's length stays on the device: the grid is what the whole frame would need, capped at eight blocks per CU (blocks > 0:
 // at that many, option cover_blocks), and the blocks stride over the list (a block past its end reads the length and leaves).
 void launch_cover_rays(const Params& P, const CoverageArgs& A, int kind, int n_cu, int blocks, hipStream_t st) {
@@ -236,8 +228,10 @@ void launch_cover_rays(const Params& P, const CoverageArgs& A, int kind, int n_c
     const size_t need = ((size_t)A.width * A.height + per_block - 1) / per_block;
     const size_t cap = blocks > 0 ? (size_t)blocks : (size_t)(n_cu > 0 ? n_cu : 256) * 8;
     const unsigned grid = (unsigned)(need < cap ? need : cap);
-    if (A.grid == 2) launch_cover_rays_g<2>(P, A, kind, grid, st);
-    else launch_cover_rays_g<4>(P, A, kind, grid, st);
+    with_kind(kind, [&](auto K) {      // (rt_capi.hip admits grid 2 and 4 only)
+        constexpr int KIND = K();
+        with_bools([&](auto two) { hipLaunchKernelGGL((cover_rays<KIND, two() ? 2 : 4>), dim3(grid), dim3(256), 0, st, P, A); }, A.grid == 2);
+    });
 }
 
 void launch_cover_weights(const CoverageArgs& A, hipStream_t st) {
@@ -247,8 +241,7 @@ void launch_cover_weights(const CoverageArgs& A, hipStream_t st) {
 
 void launch_cover_resolve(const ResolveArgs& A, hipStream_t st) {
     const dim3 grid((unsigned)((A.width + RES_T - 1) / RES_T), (unsigned)((A.height + RES_T - 1) / RES_T));
-    if (A.live) hipLaunchKernelGGL(cover_resolve<true>, grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL(cover_resolve<false>, grid, dim3(256), 0, st, A);
+    with_bools([&](auto FILL) { hipLaunchKernelGGL(cover_resolve<FILL()>, grid, dim3(256), 0, st, A); }, A.live != nullptr);
 }
 
 }  // namespace rt

@@ -8,13 +8,10 @@
 #include <cstddef>
 #include <type_traits>
 
+#include "rt_dispatch.hpp"      // the scene specialisations KIND_*
 #include "rt_types.hpp"
 
 namespace rt {
-
-// scene specialisations: GENERIC = analytic primitives (no neural SDF code), BOXES = all boxes
-// (Cornell), BUNNY = all objects are the neural bunny, MIXED = bunny next to analytic primitives
-enum { KIND_GENERIC = 0, KIND_BOXES = 1, KIND_BUNNY = 2, KIND_MIXED = 3 };
 
 // ---------------------------------------------------------------- F23 bunny MLP
 // examples/bunny/bunny_sdf_glass.py:149-203; weight layout: see tools/extract_bunny_weights.py.

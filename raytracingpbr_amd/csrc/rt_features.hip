@@ -118,10 +118,7 @@ RT_D vec3 start_colour(float4 b, vec3 ac, int demod) {
 // the last level writes A.live, 1 for a pixel that leaves with a colour and 0 beside the +0 of a pixel still empty.
 template <bool FIRST, bool LAST, bool GUIDED, bool LINEAR = false, bool COVER = false, bool FILL = false>
 __global__ void __launch_bounds__(256) atrous_level(const DenoiseArgs A) {
-    static_assert(LAST || !LINEAR, "the linear form is a last level");
-    static_assert(!COVER || (!GUIDED && LAST == LINEAR), "the coverage-weighted form is the plain filter, linear at its last level");
-    static_assert(!FILL || !GUIDED, "the filling form is the plain filter");
-    static_assert(!FILL || !LINEAR || COVER, "the filling form is linear only as the coverage-weighted filter's last level");
+    static_assert(atrous_form_ok(FIRST, LAST, GUIDED, LINEAR, COVER, FILL), "no such form (rt_dispatch.hpp)");
     const int H = A.height, W = A.width;
     const uint32_t n = (uint32_t)W * (uint32_t)H;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -308,44 +305,25 @@ __global__ void __launch_bounds__(256) atrous_none(const DenoiseArgs A) {
 
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)P.cfg.width * P.cfg.height + 255) / 256);
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((feature_rays<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, A);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((feature_rays<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P, A);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((feature_rays<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P, A);
-    else hipLaunchKernelGGL((feature_rays<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P, A);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((feature_rays<K()>), dim3(grid), dim3(256), 0, st, P, A); });
 }
 
-template <bool GUIDED>
-static void launch_level(const DenoiseArgs& A, bool first, bool last, unsigned grid, hipStream_t st) {
-    if (first && last) hipLaunchKernelGGL((atrous_level<true, true, GUIDED>), dim3(grid), dim3(256), 0, st, A);
-    else if (first) hipLaunchKernelGGL((atrous_level<true, false, GUIDED>), dim3(grid), dim3(256), 0, st, A);
-    else if (last) hipLaunchKernelGGL((atrous_level<false, true, GUIDED>), dim3(grid), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((atrous_level<false, false, GUIDED>), dim3(grid), dim3(256), 0, st, A);
-}
-
-// step 0 (no level) is the iterations = 0 pass of both calls; linear: the plain filter's last level (or that pass) without the tone map
-// cover: the coverage-weighted levels of rtpbr_denoise_coverage (step > 0, plain, linear exactly at the last level)
-// fill: the filling levels of rtpbr_denoise with option denoise_fill = 1 (step > 0, plain, never linear), or with cover those of
-// rtpbr_denoise_coverage with option coverage_fill = 1 (linear exactly at the last level)
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear, bool cover, bool fill) {
+bool launch_atrous_level(const DenoiseArgs& A, unsigned form, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (cover && fill && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, true, true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover && fill && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover && fill && last) hipLaunchKernelGGL((atrous_level<false, true, false, true, true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover && fill) hipLaunchKernelGGL((atrous_level<false, false, false, false, true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (fill && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (fill && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (fill && last) hipLaunchKernelGGL((atrous_level<false, true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (fill) hipLaunchKernelGGL((atrous_level<false, false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover && first && last) hipLaunchKernelGGL((atrous_level<true, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover && first) hipLaunchKernelGGL((atrous_level<true, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover && last) hipLaunchKernelGGL((atrous_level<false, true, false, true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (cover) hipLaunchKernelGGL((atrous_level<false, false, false, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (A.step == 0 && linear) hipLaunchKernelGGL(atrous_none<true>, dim3(grid), dim3(256), 0, st, A);
-    else if (A.step == 0) hipLaunchKernelGGL(atrous_none<false>, dim3(grid), dim3(256), 0, st, A);
-    else if (linear && first) hipLaunchKernelGGL((atrous_level<true, true, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (linear) hipLaunchKernelGGL((atrous_level<false, true, false, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (guided) launch_level<true>(A, first, last, grid, st);
-    else launch_level<false>(A, first, last, grid, st);
+    const bool first = (form & LEVEL_FIRST) != 0, last = (form & LEVEL_LAST) != 0;
+    const bool linear = (form & ATROUS_LINEAR) != 0 && last;
+    if (A.step == 0) {      // no level: the iterations = 0 pass
+        if ((form & (ATROUS_COVER | ATROUS_FILL)) != 0) return false;
+        with_bools([&](auto LN) { hipLaunchKernelGGL(atrous_none<LN()>, dim3(grid), dim3(256), 0, st, A); }, linear);
+        return true;
+    }
+    return with_bools(
+        [&](auto F, auto L, auto G, auto LN, auto C, auto FL) {
+            constexpr bool ok = atrous_form_ok(F(), L(), G(), LN(), C(), FL());
+            if constexpr (ok) hipLaunchKernelGGL((atrous_level<F(), L(), G(), LN(), C(), FL()>), dim3(grid), dim3(256), 0, st, A);
+            return ok;
+        },
+        first, last, (form & ATROUS_GUIDED) != 0, linear, (form & ATROUS_COVER) != 0, (form & ATROUS_FILL) != 0);
 }
 
 }  // namespace rt

@@ -82,8 +82,20 @@ struct DenoiseArgs {
 // r(c) = c / (1 + c): the compression the filter measures colour distances in and rt_noise.hip estimates the noise of
 RT_D vec3 tonemap_r(vec3 c) { return mk(c.x / (1.0f + c.x), c.y / (1.0f + c.y), c.z / (1.0f + c.z)); }
 
+// The form word of a filter launch: where the level stands in its chain, and the chain's kind.  LEVEL_* are level_blend's too.
+enum : unsigned {
+    LEVEL_FIRST = 1u,       // reads the (sum, count) buffer, not a record
+    LEVEL_LAST = 2u,        // writes `out`, not a record
+    LEVEL_ONLY = LEVEL_FIRST | LEVEL_LAST,
+    ATROUS_GUIDED = 4u,     // rtpbr_denoise_guided
+    ATROUS_LINEAR = 8u,     // the chain's last level (or its pass without a level) stops before the tone map; the levels before it are as without
+    ATROUS_COVER = 16u,     // A.cover_k weights the taps; a last level of it only with ATROUS_LINEAR
+    ATROUS_FILL = 32u,      // A.fill counts the pixels filled; with ATROUS_COVER the last level writes A.live
+};
+
 void launch_features(const Params& P, const FeatArgs& A, int kind, hipStream_t st);
-void launch_atrous_level(const DenoiseArgs& A, bool first, bool last, bool guided, hipStream_t st, bool linear = false,
-                         bool cover = false, bool fill = false);      // linear: last && !guided; cover: !guided, linear == last, A.step > 0; fill: !guided, A.step > 0, linear only with cover
+// A.step = 0 (no level, LEVEL_ONLY) is the tone-map-only pass of every chain without ATROUS_COVER and ATROUS_FILL.  false: the form
+// has no instance (atrous_form_ok, rt_dispatch.hpp), nothing was launched
+bool launch_atrous_level(const DenoiseArgs& A, unsigned form, hipStream_t st);
 
 }  // namespace rt

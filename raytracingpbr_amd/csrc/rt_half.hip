@@ -311,8 +311,7 @@ RT_D float4 lv_lums(const rtpbr_config& cfg, vec3 xa, vec3 xb) {
 
 template <int R, bool FIRST, bool LAST, bool ERR = false, bool LIN = false, bool FILL = false>
 __global__ void __launch_bounds__(256) level_blend(const std::conditional_t<FILL, LevelsFillArgs, LevelsArgs> A) {
-    static_assert(LAST || !LIN, "the linear exit is a last level's");
-    static_assert(LAST || !FILL, "the filled pixels are shown by the last level");
+    static_assert(level_blend_form_ok(FIRST, LAST, LIN, FILL), "no such form (rt_dispatch.hpp)");
     __shared__ float t_a[Win<R>::WORDS];
     __shared__ float t_q[Win<R>::WORDS];
     __shared__ float t_x[Win<R>::WORDS];
@@ -565,13 +564,6 @@ __global__ void __launch_bounds__(256) blend_error(const BlendErrorArgs A) {
 
 static unsigned grid_of(int w, int h) { return (unsigned)(((size_t)w * h + 255) / 256); }
 static dim3 tile_grid(int w, int h) { return dim3((unsigned)((w + ERR_TX - 1) / ERR_TX), (unsigned)((h + ERR_TY - 1) / ERR_TY)); }
-// f(integral_constant<int, R>) for the window kernels' R = radius (rt_capi.hip admits radius 1..3 only)
-template <class F>
-static void with_radius(int radius, F f) {
-    if (radius == 1) f(std::integral_constant<int, 1>{});
-    else if (radius == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 3>{});
-}
 
 void launch_half_update(const HalfArgs& A, hipStream_t st) {
     hipLaunchKernelGGL(half_update, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
@@ -582,55 +574,44 @@ void launch_half_subtract(const HalfArgs& A, hipStream_t st) {
 }
 
 void launch_half_error(const ErrorArgs& A, hipStream_t st) {
-    with_radius(A.radius, [&](auto r) { hipLaunchKernelGGL(half_error<decltype(r)::value>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
+    with_radius(A.radius, [&](auto R) { hipLaunchKernelGGL(half_error<R()>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
 }
 
 void launch_half_blend(const BlendArgs& A, hipStream_t st) {
-    with_radius(A.radius, [&](auto r) { hipLaunchKernelGGL(half_blend<decltype(r)::value>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
+    with_radius(A.radius, [&](auto R) { hipLaunchKernelGGL(half_blend<R()>, tile_grid(A.width, A.height), dim3(256), 0, st, A); });
 }
 
-template <int R, bool ERR>
-static void launch_level_blend_r(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin, uint32_t* fill, uint8_t* live) {
-    const dim3 grid = tile_grid(A.width, A.height);
-    if (fill && last) {
-        LevelsFillArgs B{};
-        static_cast<LevelsArgs&>(B) = A;
-        B.fill = fill;
-        B.live = live;
-        if (lin && first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, true, true>), grid, dim3(256), 0, st, B);
-        else if (lin) hipLaunchKernelGGL((level_blend<R, false, true, ERR, true, true>), grid, dim3(256), 0, st, B);
-        else if (first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, false, true>), grid, dim3(256), 0, st, B);
-        else hipLaunchKernelGGL((level_blend<R, false, true, ERR, false, true>), grid, dim3(256), 0, st, B);
-        return;
-    }
-    if (lin && first) hipLaunchKernelGGL((level_blend<R, true, true, ERR, true>), grid, dim3(256), 0, st, A);
-    else if (lin) hipLaunchKernelGGL((level_blend<R, false, true, ERR, true>), grid, dim3(256), 0, st, A);
-    else if (first && last) hipLaunchKernelGGL((level_blend<R, true, true, ERR>), grid, dim3(256), 0, st, A);
-    else if (first) hipLaunchKernelGGL((level_blend<R, true, false, ERR>), grid, dim3(256), 0, st, A);
-    else if (last) hipLaunchKernelGGL((level_blend<R, false, true, ERR>), grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((level_blend<R, false, false, ERR>), grid, dim3(256), 0, st, A);
-}
-
-// no level (first && last && no records): the K = 0 pass.  A.xa (rtpbr_blend_error): the ERR instances.  lin (with last and
-// records only): the LIN instances.  fill (with last and records only): the FILL instances
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin, uint32_t* fill, uint8_t* live) {
+// no level (no records): the K = 0 pass.  A.xa (rtpbr_blend_error): the ERR instances.  BLEND_LIN (with a last level only): the LIN
+// instances.  fill (with a last level only): the FILL instances, which take LevelsFillArgs
+bool launch_level_blend(const LevelsArgs& A, unsigned form, hipStream_t st, uint32_t* fill, uint8_t* live) {
+    const bool err = A.xa != nullptr;
     if (!A.kd) {
-        if (A.xa) hipLaunchKernelGGL(level_blend_none<true>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL(level_blend_none<false>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);
-        return;
+        with_bools([&](auto E) { hipLaunchKernelGGL(level_blend_none<E()>, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A); }, err);
+        return true;
     }
-    with_radius(A.radius, [&](auto r) {
-        if (A.xa) launch_level_blend_r<decltype(r)::value, true>(A, first, last, st, lin && last, fill, live);
-        else launch_level_blend_r<decltype(r)::value, false>(A, first, last, st, lin && last, fill, live);
+    const bool first = (form & LEVEL_FIRST) != 0, last = (form & LEVEL_LAST) != 0;
+    LevelsFillArgs B{};
+    static_cast<LevelsArgs&>(B) = A;
+    B.fill = fill;
+    B.live = live;
+    return with_radius(A.radius, [&](auto radius) {
+        constexpr int R = radius();
+        return with_bools(
+            [&](auto F, auto L, auto E, auto LN, auto FL) {
+                constexpr bool ok = level_blend_form_ok(F(), L(), LN(), FL());
+                if constexpr (ok && FL()) hipLaunchKernelGGL((level_blend<R, F(), L(), E(), LN(), true>), tile_grid(A.width, A.height), dim3(256), 0, st, B);
+                else if constexpr (ok) hipLaunchKernelGGL((level_blend<R, F(), L(), E(), LN(), false>), tile_grid(A.width, A.height), dim3(256), 0, st, A);
+                return ok;
+            },
+            first, last, err, (form & BLEND_LIN) != 0 && last, fill != nullptr && last);
     });
 }
 
 // A.slope != nullptr (rtpbr_blend_error_display): the DISPLAY instances
 void launch_blend_error(const BlendErrorArgs& A, hipStream_t st) {
-    with_radius(A.radius, [&](auto r) {
-        constexpr int R = decltype(r)::value;
-        if (A.slope) hipLaunchKernelGGL((blend_error<R, true>), tile_grid(A.width, A.height), dim3(256), 0, st, A);
-        else hipLaunchKernelGGL((blend_error<R, false>), tile_grid(A.width, A.height), dim3(256), 0, st, A);
+    with_radius(A.radius, [&](auto radius) {
+        constexpr int R = radius();
+        with_bools([&](auto D) { hipLaunchKernelGGL((blend_error<R, D()>), tile_grid(A.width, A.height), dim3(256), 0, st, A); }, A.slope != nullptr);
     });
 }
 

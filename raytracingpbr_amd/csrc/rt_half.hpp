@@ -156,10 +156,11 @@ struct BlendErrorArgs {
 };
 
 void launch_half_update(const HalfArgs& A, hipStream_t st);
-// A.xa != nullptr: the ERR instances; lin: the last level's LIN instance (A.out stays linear); fill != nullptr: the last level's FILL
-// instance (live: with lin, the plane it writes)
-void launch_level_blend(const LevelsArgs& A, bool first, bool last, hipStream_t st, bool lin = false, uint32_t* fill = nullptr,
-                        uint8_t* live = nullptr);
+// form: LEVEL_FIRST, LEVEL_LAST (rt_features.hpp) and BLEND_LIN: the last level is the LIN instance (A.out stays linear).  A.xa !=
+// nullptr: the ERR instances; fill != nullptr: the last level is the FILL instance (live: with BLEND_LIN, the plane it writes).
+// false: the form has no instance (level_blend_form_ok, rt_dispatch.hpp), nothing was launched
+enum : unsigned { BLEND_LIN = 4u };
+bool launch_level_blend(const LevelsArgs& A, unsigned form, hipStream_t st, uint32_t* fill, uint8_t* live);
 void launch_blend_error(const BlendErrorArgs& A, hipStream_t st);
 void launch_half_blend(const BlendArgs& A, hipStream_t st);
 void launch_half_subtract(const HalfArgs& A, hipStream_t st);

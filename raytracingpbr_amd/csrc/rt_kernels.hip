@@ -587,10 +587,7 @@ void launch_primary(const Params& P, int kind, int n_cu, hipStream_t st) {
     if (!P.cull_ok) {
         // the host could not bound the scene (non-finite / huge extent, steep cone, > 8 shapes): lock-step march
         // without culling; the NOBJ = 0 instances have no nearest_culled branch
-        if (kind == KIND_BOXES) hipLaunchKernelGGL((primary_rays<KIND_BOXES, 0>), dim3((unsigned)grid), dim3(256), 0, st, P);
-        else if (kind == KIND_BUNNY) hipLaunchKernelGGL((primary_rays<KIND_BUNNY, 0>), dim3((unsigned)grid), dim3(256), 0, st, P);
-        else if (kind == KIND_MIXED) hipLaunchKernelGGL((primary_rays<KIND_MIXED, 0>), dim3((unsigned)grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((primary_rays<KIND_GENERIC, 0>), dim3((unsigned)grid), dim3(256), 0, st, P);
+        with_kind(kind, [&](auto K) { hipLaunchKernelGGL((primary_rays<K(), 0>), dim3((unsigned)grid), dim3(256), 0, st, P); });
         return;
     }
     RT_DISPATCH_KIND(primary_rays, hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), 0, st, P));
@@ -638,74 +635,43 @@ void launch_accumulate_dealt(const Params& P, float4* moments, float4* snapshot,
     else hipLaunchKernelGGL(accumulate_samples_dealt, dim3(grid), dim3(256), 0, st, P, half_a, half_sh);
 }
 void launch_persistent_pool(const Params& P, int kind, int steps, int grid, hipStream_t st) {
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((persistent_pool<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, steps);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((persistent_pool<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P, steps);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((persistent_pool<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P, steps);
-    else hipLaunchKernelGGL((persistent_pool<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P, steps);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((persistent_pool<K()>), dim3(grid), dim3(256), 0, st, P, steps); });
 }
 void launch_chain_steps(const Params& P, int kind, int steps, int grid, hipStream_t st) {
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((chain_steps<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, steps);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((chain_steps<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P, steps);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((chain_steps<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P, steps);
-    else hipLaunchKernelGGL((chain_steps<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P, steps);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((chain_steps<K()>), dim3(grid), dim3(256), 0, st, P, steps); });
 }
 int persistent_pool_blocks_per_cu(int kind) {
     int per_cu = 0;
-    hipError_t e;
-    if (kind == KIND_BOXES) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_pool<KIND_BOXES>, 256, 0);
-    else if (kind == KIND_BUNNY) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_pool<KIND_BUNNY>, 256, 0);
-    else if (kind == KIND_MIXED) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_pool<KIND_MIXED>, 256, 0);
-    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_pool<KIND_GENERIC>, 256, 0);
+    const hipError_t e = with_kind(kind, [&](auto K) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persistent_pool<K()>, 256, 0); });
     return e == hipSuccess ? per_cu : 0;
 }
 void launch_persistent(const Params& P, int kind, int steps, hipStream_t st) {
     int grid = (P.np + 255) / 256;
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((persistent_steps<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P, steps);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((persistent_steps<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P, steps);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((persistent_steps<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P, steps);
-    else hipLaunchKernelGGL((persistent_steps<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P, steps);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((persistent_steps<K()>), dim3(grid), dim3(256), 0, st, P, steps); });
 }
 // the wavefront split of one src/ bounce-step (rt_split.hpp): gen and shade one lane per local pixel, march on persistent waves
 void launch_src_gen(const Params& P, int kind, hipStream_t st) {
     int grid = (P.np + 255) / 256;
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((src_gen<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((src_gen<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((src_gen<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((src_gen<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((src_gen<K()>), dim3(grid), dim3(256), 0, st, P); });
 }
 void launch_src_march(const Params& P, int kind, int grid, hipStream_t st) {
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((src_march<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((src_march<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((src_march<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((src_march<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((src_march<K()>), dim3(grid), dim3(256), 0, st, P); });
 }
 int src_march_blocks_per_cu(int kind) {
     int per_cu = 0;
-    hipError_t e;
-    if (kind == KIND_BOXES) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, src_march<KIND_BOXES>, 256, 0);
-    else if (kind == KIND_BUNNY) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, src_march<KIND_BUNNY>, 256, 0);
-    else if (kind == KIND_MIXED) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, src_march<KIND_MIXED>, 256, 0);
-    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, src_march<KIND_GENERIC>, 256, 0);
+    const hipError_t e = with_kind(kind, [&](auto K) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, src_march<K()>, 256, 0); });
     return e == hipSuccess ? per_cu : 0;
 }
-template <bool COUNT>
-static void launch_src_shade_gen_t(const Params& P, int kind, hipStream_t st) {
-    int grid = (P.np + 255) / 256;
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((src_shade_gen<KIND_BOXES, COUNT>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((src_shade_gen<KIND_BUNNY, COUNT>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((src_shade_gen<KIND_MIXED, COUNT>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((src_shade_gen<KIND_GENERIC, COUNT>), dim3(grid), dim3(256), 0, st, P);
-}
 void launch_src_shade_gen(const Params& P, int kind, bool count, hipStream_t st) {
-    if (count) launch_src_shade_gen_t<true>(P, kind, st);
-    else launch_src_shade_gen_t<false>(P, kind, st);
+    int grid = (P.np + 255) / 256;
+    with_kind(kind, [&](auto K) {
+        constexpr int KIND = K();
+        with_bools([&](auto COUNT) { hipLaunchKernelGGL((src_shade_gen<KIND, COUNT()>), dim3(grid), dim3(256), 0, st, P); }, count);
+    });
 }
 void launch_src_shade(const Params& P, int kind, hipStream_t st) {
     int grid = (P.np + 255) / 256;
-    if (kind == KIND_BOXES) hipLaunchKernelGGL((src_shade<KIND_BOXES>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_BUNNY) hipLaunchKernelGGL((src_shade<KIND_BUNNY>), dim3(grid), dim3(256), 0, st, P);
-    else if (kind == KIND_MIXED) hipLaunchKernelGGL((src_shade<KIND_MIXED>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((src_shade<KIND_GENERIC>), dim3(grid), dim3(256), 0, st, P);
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((src_shade<K()>), dim3(grid), dim3(256), 0, st, P); });
 }
 void launch_refresh(float4* ib, rtpbr_ray* rb, float2* db, float* dp, int adaptive, size_t n, hipStream_t st) {
     int grid = (int)((n + 255) / 256);

@@ -222,9 +222,7 @@ void launch_noise_update(const NoiseArgs& A, hipStream_t st) {
 void launch_noise_estimate(const NoiseArgs& A, hipStream_t st) {
     if (A.pool_batches > 0) {      // (rt_capi.hip admits radius 1..3 only)
         const dim3 grid((unsigned)((A.width + POOL_TX - 1) / POOL_TX), (unsigned)((A.height + POOL_TY - 1) / POOL_TY));
-        if (A.pool_radius == 1) hipLaunchKernelGGL(noise_estimate_pooled<1>, grid, dim3(256), 0, st, A);
-        else if (A.pool_radius == 2) hipLaunchKernelGGL(noise_estimate_pooled<2>, grid, dim3(256), 0, st, A);
-        else hipLaunchKernelGGL(noise_estimate_pooled<3>, grid, dim3(256), 0, st, A);
+        with_radius(A.pool_radius, [&](auto R) { hipLaunchKernelGGL(noise_estimate_pooled<R()>, grid, dim3(256), 0, st, A); });
         return;
     }
     hipLaunchKernelGGL(noise_estimate, dim3(grid_of(A.width, A.height)), dim3(256), 0, st, A);

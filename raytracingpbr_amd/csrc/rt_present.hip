@@ -88,21 +88,9 @@ __global__ void __launch_bounds__(256) present_kernel(const PresentArgs A) {
     }
 }
 
-template <bool ACCUM, bool RGBA>
-static void launch_present_2(const PresentArgs& A, bool dither, dim3 grid, hipStream_t st) {
-    if (dither) hipLaunchKernelGGL((present_kernel<ACCUM, RGBA, true>), grid, dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((present_kernel<ACCUM, RGBA, false>), grid, dim3(256), 0, st, A);
-}
-
 void launch_present(const PresentArgs& A, bool accum, bool rgba, bool dither, hipStream_t st) {
     const dim3 grid((unsigned)((A.width + PRESENT_TILE - 1) / PRESENT_TILE), (unsigned)((A.height + PRESENT_TILE - 1) / PRESENT_TILE));
-    if (accum) {
-        if (rgba) launch_present_2<true, true>(A, dither, grid, st);
-        else launch_present_2<true, false>(A, dither, grid, st);
-    } else {
-        if (rgba) launch_present_2<false, true>(A, dither, grid, st);
-        else launch_present_2<false, false>(A, dither, grid, st);
-    }
+    with_bools([&](auto AC, auto RG, auto DI) { hipLaunchKernelGGL((present_kernel<AC(), RG(), DI()>), grid, dim3(256), 0, st, A); }, accum, rgba, dither);
 }
 
 }  // namespace rt

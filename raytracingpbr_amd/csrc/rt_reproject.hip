@@ -1,6 +1,7 @@
 // rt_reproject.hip — the gather kernels of rtpbr_reproject and rtpbr_reproject_scene (see rt_reproject.hpp; the arithmetic is fixed in include/rtpbr.h).
 #include <hip/hip_runtime.h>
 
+#include "rt_dispatch.hpp"
 #include "rt_reproject.hpp"
 
 namespace rt {
@@ -211,18 +212,14 @@ __global__ void __launch_bounds__(256) reproject_gather_scene(const ReprojArgs A
 
 void launch_reproject(const ReprojArgs& A, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (A.hist_moments && A.hist_half) hipLaunchKernelGGL((reproject_gather<true, true>), dim3(grid), dim3(256), 0, st, A);
-    else if (A.hist_moments) hipLaunchKernelGGL((reproject_gather<true, false>), dim3(grid), dim3(256), 0, st, A);
-    else if (A.hist_half) hipLaunchKernelGGL((reproject_gather<false, true>), dim3(grid), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((reproject_gather<false, false>), dim3(grid), dim3(256), 0, st, A);
+    with_bools([&](auto M, auto HV) { hipLaunchKernelGGL((reproject_gather<M(), HV()>), dim3(grid), dim3(256), 0, st, A); },
+               A.hist_moments != nullptr, A.hist_half != nullptr);
 }
 
 void launch_reproject_scene(const ReprojArgs& A, const float* table, int n_obj, hipStream_t st) {
     const unsigned grid = (unsigned)(((size_t)A.width * A.height + 255) / 256);
-    if (A.hist_moments && A.hist_half) hipLaunchKernelGGL((reproject_gather_scene<true, true>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
-    else if (A.hist_moments) hipLaunchKernelGGL((reproject_gather_scene<true, false>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
-    else if (A.hist_half) hipLaunchKernelGGL((reproject_gather_scene<false, true>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
-    else hipLaunchKernelGGL((reproject_gather_scene<false, false>), dim3(grid), dim3(256), 0, st, A, table, n_obj);
+    with_bools([&](auto M, auto HV) { hipLaunchKernelGGL((reproject_gather_scene<M(), HV()>), dim3(grid), dim3(256), 0, st, A, table, n_obj); },
+               A.hist_moments != nullptr, A.hist_half != nullptr);
 }
 
 }  // namespace rt

@@ -3,10 +3,11 @@
  *         tests/blend_coverage_ref/san_main.c -o blend_coverage_san -lm && ./blend_coverage_san
  * The 24x16 two-object frame of tests/test_blend_coverage_ref.py (flat features, power-of-two radiances, coverage set by hand) with
  * holes in the interior and on either side of the silhouette and one pixel of share 0, through bc_filter_levels and the three
- * modes of bc_blend_coverage at 1 and 3 levels, radius 1..3, both resolve settings.  Exit 0 = the calls returned 0 and the resolved
- * counts are the expected ones. */
+ * modes of bc_blend_coverage at 1 and 3 levels, radius 1..3, both resolve settings; then a hostile 7x5 frame (special values in
+ * count and colour words) through the same calls.  Exit 0 = the calls returned 0 and the resolved counts are the expected ones. */
 #include "blend_coverage_ref.c"
 
+#include <float.h>
 #include <stdio.h>
 
 enum { W0 = 24, H0 = 16, N0 = W0 * H0 };
@@ -76,6 +77,56 @@ int main(void) {
                         }
                 for (int j = 0; j < 3; j++) free(f[j]);
             }
+    /* a hostile 7x5 frame (tests/hostile.py's words, by hand): NaN, +-inf, FLT_MAX, -0, -3, 2^-149, 2^24 and 1e30 in count words, NaN,
+     * +-inf, the pole -1 and -100 in colour words; two objects, the border columns with coverage 12 of 16.  The arrays above are
+     * larger than it needs.  Only the return codes are judged: the sanitizers judge the rest. */
+    {
+        enum { W1 = 7, H1 = 5, N1 = W1 * H1 };
+        static const float counts_w[] = {4.0f, NAN, 4.0f, INFINITY, -0.0f, 4.0f, -3.0f, 1.401298464e-45f, 4.0f, 16777216.0f, 1e30f, 0.0f,
+                                         -INFINITY, FLT_MAX};
+        static const float colour_w[] = {2.0f, 1.0f, NAN, 0.5f, INFINITY, 4.0f, -4.0f, 8.0f, -INFINITY, -400.0f, FLT_MAX, 0.25f};
+        cfg.width = W1;
+        cfg.height = H1;
+        for (int x = 0; x < W1; x++)
+            for (int y = 0; y < H1; y++) {
+                const int i = x * H1 + y, o = x >= 4, border = x == 3 || x == 4;
+                object[i] = o;
+                depth[i] = 3.0f;
+                for (int c = 0; c < 3; c++) {
+                    albedo[i * 3 + c] = 0.5f;
+                    normal[i * 3 + c] = c == 2 ? 1.0f : 0.0f;
+                    ib[i * 4 + c] = colour_w[(i * 3 + c) % (int)(sizeof colour_w / sizeof *colour_w)];
+                }
+                ib[i * 4 + 3] = counts_w[i % (int)(sizeof counts_w / sizeof *counts_w)];
+                cov[i * 4 + 0] = border ? 12 : 16;
+                cov[i * 4 + 1] = border ? 1 - o : -2;
+                cov[i * 4 + 2] = border ? 4 : 0;
+                cov[i * 4 + 3] = 16;
+            }
+        for (int i = 0; i < N1 * 4; i++) {
+            ha[i] = ib[i] * 0.5f;
+            hb[i] = ib[i] - ha[i];
+        }
+        for (int K = 1; K <= 4; K += 3)
+            for (int demodulate = 0; demodulate <= 1; demodulate++)
+                for (int power = 0; power <= 4; power += 4) {
+                    float* f[3];
+                    const float* in[3] = {ib, ha, hb};
+                    for (int j = 0; j < 3; j++) {
+                        f[j] = malloc((size_t)(K + 1) * N1 * 12);
+                        if (bc_filter_levels(&cfg, in[j], albedo, normal, depth, object, cov, K, demodulate, 0.5f, 0.3f, 0.05f, 0.1f, power, f[j]))
+                            failures++;
+                    }
+                    for (int mode = 0; mode <= 2; mode++)
+                        for (int radius = 1; radius <= 3; radius++) {
+                            uint32_t stats[3], resolved;
+                            if (bc_blend_coverage(&cfg, ib, ha, hb, f[0], f[1], f[2], object, cov, K, radius, radius == 2 ? 2.0f : 0.0f, 1.0f, power, 1,
+                                                  mode, 4 - radius, 0.05f, out, before, weight, dep, error, parts, stats, &resolved))
+                                failures++;
+                        }
+                    for (int j = 0; j < 3; j++) free(f[j]);
+                }
+    }
     free(albedo); free(normal); free(depth); free(ib); free(ha); free(hb); free(object); free(cov);
     free(out); free(before); free(weight); free(dep); free(error); free(parts);
     printf("blend_coverage_ref under the sanitizers: %d failures\n", failures);

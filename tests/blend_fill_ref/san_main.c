@@ -4,9 +4,11 @@
  * The 24x16 two-object frame of tests/test_blend_fill_ref.py (flat features, power-of-two radiances, coverage set by hand) with
  * holes in the interior, on either side of the silhouette and a 5x5 block, and then with object 1 left without any sample, through
  * bf_fill_levels (plain and coverage-weighted) and the three modes of bf_blend_fill at 1 and 3 levels, radius 1..3, both resolve
- * settings.  Exit 0 = the calls returned 0 and the counts are the expected ones. */
+ * settings; then a hostile 7x5 frame (special values in count and colour words) through the same calls.  Exit 0 = the calls returned 0
+ * and the counts are the expected ones. */
 #include "blend_fill_ref.c"
 
+#include <float.h>
 #include <stdio.h>
 
 enum { W0 = 24, H0 = 16, N0 = W0 * H0 };
@@ -89,6 +91,61 @@ int main(void) {
                                     failures++;
                                 }
                             }
+                    for (int j = 0; j < 3; j++) { free(f[j]); free(live[j]); }
+                }
+    }
+    /* a hostile 7x5 frame (tests/hostile.py's words, by hand): NaN, +-inf, FLT_MAX, -0, -3, 2^-149, 2^24 and 1e30 in count words, NaN,
+     * +-inf, the pole -1 and -100 in colour words; two objects, the border columns with coverage 12 of 16.  The arrays above are
+     * larger than it needs.  Only the return codes are judged: the sanitizers judge the rest. */
+    {
+        enum { W1 = 7, H1 = 5, N1 = W1 * H1 };
+        static const float counts_w[] = {4.0f, NAN, 4.0f, INFINITY, -0.0f, 4.0f, -3.0f, 1.401298464e-45f, 4.0f, 16777216.0f, 1e30f, 0.0f,
+                                         -INFINITY, FLT_MAX};
+        static const float colour_w[] = {2.0f, 1.0f, NAN, 0.5f, INFINITY, 4.0f, -4.0f, 8.0f, -INFINITY, -400.0f, FLT_MAX, 0.25f};
+        cfg.width = W1;
+        cfg.height = H1;
+        for (int x = 0; x < W1; x++)
+            for (int y = 0; y < H1; y++) {
+                const int i = x * H1 + y, o = x >= 4, border = x == 3 || x == 4;
+                object[i] = o;
+                depth[i] = 3.0f;
+                for (int c = 0; c < 3; c++) {
+                    albedo[i * 3 + c] = 0.5f;
+                    normal[i * 3 + c] = c == 2 ? 1.0f : 0.0f;
+                    ib[i * 4 + c] = colour_w[(i * 3 + c) % (int)(sizeof colour_w / sizeof *colour_w)];
+                }
+                ib[i * 4 + 3] = counts_w[i % (int)(sizeof counts_w / sizeof *counts_w)];
+                cov[i * 4 + 0] = border ? 12 : 16;
+                cov[i * 4 + 1] = border ? 1 - o : -2;
+                cov[i * 4 + 2] = border ? 4 : 0;
+                cov[i * 4 + 3] = 16;
+            }
+        for (int i = 0; i < N1 * 4; i++) {
+            ha[i] = ib[i] * 0.5f;
+            hb[i] = ib[i] - ha[i];
+        }
+        for (int K = 1; K <= 4; K += 3)
+            for (int demodulate = 0; demodulate <= 1; demodulate++)
+                for (int cover = 0; cover <= 1; cover++) {
+                    float* f[3];
+                    unsigned char* live[3];
+                    const float* in[3] = {ib, ha, hb};
+                    uint32_t counts[3];
+                    for (int j = 0; j < 3; j++) {
+                        f[j] = malloc((size_t)(K + 1) * N1 * 12);
+                        live[j] = malloc((size_t)(K + 1) * N1);
+                        if (bf_fill_levels(&cfg, in[j], albedo, normal, depth, object, cover ? cov : NULL, K, demodulate, 0.5f, 0.3f, 0.05f, 0.1f, 4,
+                                           f[j], live[j], j == 0 ? counts : NULL))
+                            failures++;
+                    }
+                    for (int mode = 0; mode <= 2; mode++)
+                        for (int radius = 1; radius <= 3; radius++) {
+                            uint32_t stats[3], resolved;
+                            if (bf_blend_fill(&cfg, ib, ha, hb, f[0], f[1], f[2], live[0] + (size_t)K * N1, object, cover ? cov : NULL, K, radius,
+                                              radius == 2 ? 2.0f : 0.0f, 1.0f, 4, 1, mode, 4 - radius, 0.05f, out, before, weight, dep, error,
+                                              parts, stats, &resolved))
+                                failures++;
+                        }
                     for (int j = 0; j < 3; j++) { free(f[j]); free(live[j]); }
                 }
     }

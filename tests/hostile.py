@@ -297,3 +297,93 @@ def oracle_post_process(scene, cfg, image_buffer):
     out = o.image_pixels
     o.close()
     return out
+
+
+# ---------------------------------------------------------------- the stages since: fill, coverage, blend error, blend options, tiers
+# Frames 97x61 with both families and 7x5 with family F (family N needs an object of 40 pixels); scene and config are
+# scene_cfg("v3", w, h); the sigmas are SIGMAS wherever a case does not say "defaults".
+FRAME_FAMILIES = (("97x61", "F"), ("97x61", "N"), ("7x5", "F"))
+LATTICES = (None, (2, 2), (4, 4))      # None: the only holes are the hostile counts +0, -0, -3 and NaN
+BLEND_THR = 0.05                       # threshold of the blend-error cases and of their select_blend_error
+TIER_MIN_SAMPLES = 3                   # the estimator's min_samples of the tier cases: "fewer than min_samples" is on
+
+
+def lattices_of(frame):
+    """on 7x5 a lattice wipes 23 - 51 % of the restatement's output (the guard is 10 %): that frame runs without one"""
+    return LATTICES if frame == "97x61" else (None,)
+
+
+def holes(image_buffer, lattice):
+    """the hostile buffer with holes cut: everything off the lattice (phase (0, 0)) is zero, as sample_selected leaves it on a
+    refreshed context.  Column x = 0 and row y = H - 1 = 60 keep every second (fourth) pixel of the planted edge."""
+    import fill_ref_lib as fi
+    if lattice is None:
+        return np.array(image_buffer, dtype=F32)
+    w, h = image_buffer.shape[:2]
+    return fi.masked(image_buffer, fi.lattice(w, h, lattice))
+
+
+def second_batch_on_lattice(scene, cfg, image_buffer, lattice, n=2):
+    """second_batch() where only the lattice was selected: what select_lattice + sample_selected(n) leave (the other pixels keep
+    their bits)"""
+    import fill_ref_lib as fi
+    out = second_batch(scene, cfg, image_buffer, n)
+    if lattice is None:
+        return out
+    w, h = image_buffer.shape[:2]
+    return np.where(fi.lattice(w, h, lattice)[..., None], out, np.asarray(image_buffer, F32))
+
+
+# (frame, family, lattice, iterations, demodulate): denoise_fill, and denoise_coverage_fill at the default grid and power with
+# resolve 0 and 1
+FILL_CASES = [(frame, family, lattice, it, demod) for frame, family in FRAME_FAMILIES for lattice in lattices_of(frame)
+              for it in (1, 2, 4) for demod in (0, 1)]
+FILL_RESOLVES = (0, 1)
+# (frame, family, iterations, demodulate, power, resolve)
+COVERAGE_CASES = [(frame, family, it, demod, power, resolve) for frame, family in FRAME_FAMILIES for it in (0, 1, 3) for demod in (0, 1)
+                  for power in (0, 4) for resolve in (0, 1)]
+# (radius, z, denoise parameters): the rule tuples of test_gpu_levels.py::test_hostile_image_buffer; min_half_samples = 1
+BLEND_RULES = ((1, 0.0, {}), (3, 0.0, dict(iterations=2, demodulate=1, **SIGMAS)), (3, 2.0, {}), (2, 0.0, dict(iterations=0)))
+BLEND_WINDOWS = (None, 1, 3)
+BLEND_DILATES = (0, 2)
+# (frame, family, display, radius, z, window, denoise); each is followed by select_blend_error(BLEND_THR, dilate in BLEND_DILATES)
+BLEND_ERROR_CASES = [(frame, family, display, radius, z, window, denoise) for frame, family in FRAME_FAMILIES for display in (False, True)
+                     for radius, z, denoise in BLEND_RULES for window in BLEND_WINDOWS]
+BLEND_MODES = ("levels", "linear", "display")
+BLEND_OPTION_DENOISE = ({}, dict(iterations=3, **SIGMAS))      # both run in every case
+BLEND_OPTION_RULE = dict(radius=2, z=0.0, min_half_samples=1)
+# (frame, family, mode, coverage, fill, lattice)
+BLEND_OPTION_CASES = [(frame, family, mode, cover, fill, lattice) for frame, family in FRAME_FAMILIES for mode in BLEND_MODES
+                      for cover, fill in ((1, 0), (0, 1), (1, 1)) for lattice in (lattices_of(frame)[:2] if fill else (None,))]
+# (family, call, threshold, tiers, batch, dilate) on 97x61.  Threshold 0.125 puts pixels into every tier for all three calls in
+# both families (asserted on the restatements, tests/test_hostile_buffers_ref.py); at threshold 0 every selected pixel is tier 0.
+TIER_CALLS = ("noisy", "error", "blend_error")
+TIER_THR = 0.125
+TIER_CASES = [(family, call, thr, tiers, batch, dilate) for family in FAMILIES for call in TIER_CALLS for thr in (0.0, TIER_THR)
+              for tiers, batch in ((4, 16), (8, 256), (2, 1)) for dilate in (0, 2)]
+# The planes the error calls select on: denoise_error(window 2) and blend_error(radius 2, z 0, min_half_samples 1, window 2) of
+# the 2-level demodulated filter.  Measured on the restatements at (8, 256), threshold 0.125, dilate 0: family F (182, 19, 15,
+# 474, 3353, 1635, 108, 38) and (182, 19, 16, 384, 3479, 1637, 102, 29), family N (12, 29, 27, 863, 3289, 1391, 33, 4) and (12,
+# 29, 27, 677, 3475, 1389, 35, 4).  (With the default filter, 4 levels at sigma_color 2, family N's denoise_error plane leaves tier
+# 2 empty at 0.125, and tiers 1 and 3 at its median 0.16203: the filter's parameters were changed, not the threshold.)
+TIER_DENOISE = dict(iterations=2, demodulate=1, **SIGMAS)
+TIER_BLEND = dict(radius=2, z=0.0, min_half_samples=1)
+
+
+# Preset v3's tone map (order 0) clamps last and shows a NaN as 0: in the tables above family N reaches the display as wiped pixels,
+# compared word for word as zeros.  One family-N case per display stage under preset v2 (order 1: a NaN gets through) puts the
+# NaN words themselves on both sides of the comparison; test_totals of the GPU file asks for them.
+NAN_PRESET = "v2"
+NAN_FILL_CASES = [("97x61", "N", (2, 2), 2, 0)]
+NAN_COVERAGE_CASES = [("97x61", "N", 3, 0, 4, 1)]
+NAN_BLEND_ERROR_CASES = [("97x61", "N", display, 3, 0.0, None, BLEND_RULES[1][2]) for display in (False, True)]
+NAN_BLEND_OPTION_CASES = [("97x61", "N", "levels", 1, 0, None), ("97x61", "N", "display", 1, 1, (2, 2)), ("97x61", "N", "linear", 0, 1, None)]
+
+
+def case_id(v):
+    """pytest ids of the case tuples: a dict of denoise parameters by its levels"""
+    if isinstance(v, dict):
+        return "defaults" if not v else f"K{v.get('iterations', 4)}" + ("d" if v.get("demodulate") else "")
+    if isinstance(v, tuple):
+        return "x".join(str(x) for x in v)
+    return str(v)

@@ -5,23 +5,38 @@
    (moments, half A, image_buffer after rtpbr_sample), this file makes them with the CPU models of the same calls
    (noise_ref_lib.Tracker, half_ref_lib.Halves) and the oracle's sample(), which the device is held to bit for bit elsewhere.
 2. Known answers of include/rtpbr.h's clauses for special values, pinned on the restatements: the pole of r(c) = c / (1 + c), the
-   no-samples test, the gather's cap on an infinite count, and the unsigned maximum of the noise statistics."""
+   no-samples test, the gather's cap on an infinite count, and the unsigned maximum of the noise statistics.
+3. The same for the stages since (the GPU tier is tests/test_gpu_hostile_display.py): the filling denoise, the coverage-aware
+   denoise without and with the fill, the blend error in both bias modes, the level blend with blend_coverage / blend_fill, and the
+   tiered selections — the guard of every case of hostile.py's tables, that the holes are real (fill_filled > 0, above half the
+   frame on a lattice from two levels on), that the restatement's counters equal fill_ref_lib.reach (numpy, no colour read, the
+   header's own `w > 0`), and that every tier occurs.
+4. Known answers of the header's clauses for the filling stages, on hand-made 5x5 and 7x5 single-object frames."""
 import functools
 
 import numpy as np
 import pytest
 
+import blend_coverage_ref_lib as bc
+import blend_error_ref_lib as be
+import blend_fill_ref_lib as bf
+import coverage_fill_ref_lib as cf
+import coverage_ref_lib as cl
 import feature_ref_lib as fr
+import fill_ref_lib as fi
 import half_ref_lib as hl
 import hostile as hz
+import levels_ref_lib as lv
 import noise_ref_lib as nr
 import pool_ref_lib as pl
 import reproject_ref_lib as rr
 import reproject_scene_ref_lib as rs
+import tier_ref_lib as tr
 from raytracingpbr_amd import Config, cornell_box
 
 F32 = np.float32
 NAN, INF = float("nan"), float("inf")
+NEVER = 16777216      # a min_half_samples above every count
 
 
 @functools.lru_cache(maxsize=None)
@@ -364,3 +379,341 @@ def test_the_gathers_cap_on_an_infinite_count():
     ib[x, y] = (1.5e38, -2e38, 0.25e38, hz.FLT_MAX)
     out, _ = rr.reproject(cfg, scene.camera, scene.camera, ib, feats, feats, max_history=64.0)
     assert np.isfinite(out[x, y]).all() and abs(out[x, y, 3] - 64.0) < 1e-3
+
+
+# ------------------------------------------------------------------ 3. the stages since: guard, holes, reach, tiers
+@functools.lru_cache(maxsize=None)
+def _cov(preset, frame):
+    scene, cfg, feats = _frame(preset, frame)
+    cov = cl.coverage(scene, cfg, feats=feats)
+    cov.setflags(write=False)
+    return cov
+
+
+@functools.lru_cache(maxsize=None)
+def _batches(preset, family, frame, lattice):
+    """(batch one, image_buffer after batch two, half A, moments): the hostile buffer, masked by the lattice where there is one, is
+    the first batch; the second is the oracle's sample(2) through the lattice (all of the frame without one)"""
+    scene, cfg, _ = _frame(preset, frame)
+    w, h = hz.FRAMES[frame]
+    ib = hz.holes(_buffer(preset, family, frame), lattice)
+    ib2 = hz.second_batch_on_lattice(scene, cfg, ib, lattice)
+    m, t = hl.Halves(w, h), nr.Tracker(w, h)
+    for b in (ib, ib2):
+        m.update(b)
+        t.update(b)
+    out = ib, ib2, m.a.copy(), t.moments.copy()
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _guard(what, **planes):
+    """hz.guard on every plane, and the [hostile] guard line DESIGN.md's table is made from"""
+    shares = {name: hz.guard(f"{what} {name}", p) for name, p in planes.items()}
+    print(f"[hostile] guard {what}: " + ", ".join(f"{name} {s:.3f}" for name, s in shares.items()))
+    return shares
+
+
+def _weight_and_depth_in_range(what, weight, depth, K):
+    """known answer 5: no NaN, [0, 1] and [0, K]"""
+    assert not np.isnan(weight).any() and np.all((weight >= 0) & (weight <= 1)), what
+    assert not np.isnan(depth).any() and np.all((depth >= 0) & (depth <= K)), what
+
+
+def _fill_case(preset, frame, family, lattice, iterations, demodulate):
+    scene, cfg, feats = _frame(preset, frame)
+    w, h = hz.FRAMES[frame]
+    ib = hz.holes(_buffer(preset, family, frame), lattice)
+    what = f"{preset} {frame} {family} lattice {lattice} {iterations} levels demodulate {demodulate}"
+    reach = fi.reach(ib[..., 3] > 0, feats["object"], iterations)[1]
+    out, counts = fi.denoise_fill(cfg, ib, feats, iterations, demodulate, **hz.SIGMAS)
+    _guard("denoise_fill " + what, frame=out)
+    outs = [out]
+    for resolve in hz.FILL_RESOLVES:
+        out2, st, counts2 = cf.denoise_coverage_fill(cfg, ib, feats, _cov(preset, frame), resolve=resolve, iterations=iterations,
+                                                     demodulate=demodulate, **hz.SIGMAS)
+        _guard(f"denoise_coverage_fill {what} resolve {resolve}", frame=out2)
+        assert counts2 == reach, (what, resolve, counts2, reach)
+        assert st[1] > 0 and (st[0] > 0) == bool(resolve), (what, st)
+        outs.append(out2)
+    assert counts == reach, (what, counts, reach)          # two independent references agree on who is filled
+    assert counts[0] > 0, what                             # a test that fills nothing compares nothing
+    if lattice is not None and iterations >= 2:
+        assert counts[0] > w * h / 2 and counts[2] >= 1, (what, counts)
+    return outs
+
+
+@pytest.mark.parametrize("frame,family,lattice,iterations,demodulate", hz.FILL_CASES, ids=hz.case_id)
+def test_guard_fill(frame, family, lattice, iterations, demodulate):
+    for out in _fill_case("v3", frame, family, lattice, iterations, demodulate):
+        assert not np.isnan(out).any()                     # tone-map order 0: the clamp shows a NaN as 0
+
+
+def _coverage_case(preset, frame, family, iterations, demodulate, power, resolve):
+    scene, cfg, feats = _frame(preset, frame)
+    out, st = cl.denoise_coverage(cfg, _buffer(preset, family, frame), feats, _cov(preset, frame), power, resolve, iterations, demodulate,
+                                  **hz.SIGMAS)
+    what = f"{preset} {frame} {family} {iterations} levels demodulate {demodulate} power {power} resolve {resolve}"
+    _guard("denoise_coverage " + what, frame=out)
+    assert st[1] > 0 and (st[0] > 0) == bool(resolve and iterations), (what, st)      # candidates; resolved exactly when asked for
+    if iterations == 0 or (power == 0 and resolve == 0):   # every purity weight is 1 and nothing is resolved: rtpbr_denoise's bytes,
+        plain = fr.denoise(cfg, _buffer(preset, family, frame), feats, iterations, demodulate, **hz.SIGMAS)      # from another file
+        assert _same(out, plain), what
+    return out
+
+
+@pytest.mark.parametrize("frame,family,iterations,demodulate,power,resolve", hz.COVERAGE_CASES, ids=hz.case_id)
+def test_guard_coverage(frame, family, iterations, demodulate, power, resolve):
+    assert not np.isnan(_coverage_case("v3", frame, family, iterations, demodulate, power, resolve)).any()
+
+
+def _blend_error_case(preset, frame, family, display, radius, z, window, denoise):
+    scene, cfg, feats = _frame(preset, frame)
+    w, h = hz.FRAMES[frame]
+    _, ib2, a, _ = _batches(preset, family, frame, None)
+    got = be.blend_error(cfg, ib2, a, feats, hz.BLEND_THR, radius, z, 1, window, display, **denoise)
+    what = f"{preset} {frame} {family} radius {radius} z {z} window {window} {hz.case_id(denoise)}"
+    _guard(("blend_error_display " if display else "blend_error ") + what, frame=got.denoised, error=got.error, weight=got.weight,
+           depth=got.depth)
+    _weight_and_depth_in_range(what, got.weight, got.depth, denoise.get("iterations", 4))
+    assert got.stats[0] > 0.5 * w * h, (what, got.stats)
+    with np.errstate(invalid="ignore"):                    # who is estimated, in numpy with the header's own `> 0` on both halves
+        both = (a[..., 3] > 0) & (ib2[..., 3] - a[..., 3] > 0)
+    assert got.stats[0] == int(both.sum()) and not got.error[~both].any(), (what, got.stats, int(both.sum()))
+    out, t, depth, _ = lv.denoise_blend_levels(cfg, ib2, a, feats, radius, z, 1, **denoise)      # the frame is the level blend's
+    assert _same(got.denoised, out) and _same(got.weight, t) and _same(got.depth, depth), what
+    for dilate in hz.BLEND_DILATES:
+        mask = hl.select(ib2, a, got.error, hz.BLEND_THR, dilate, hz.TIER_MIN_SAMPLES)
+        n = int(mask.sum())
+        assert 0 < n <= w * h, (what, dilate, n)          # (see everybody_is_above_the_threshold)
+        # two independent statements of the selection rule (C and numpy) agree on the hostile counts and the plane's NaN words
+        one_tier = tr.select(got.error, ib2[..., 3], hz.BLEND_THR, dilate, 1, 1, hz.TIER_MIN_SAMPLES, a[..., 3])
+        assert np.array_equal(mask, one_tier), (what, dilate)
+    n = int(hl.select(ib2, a, got.error, median_of(got.error), 0, hz.TIER_MIN_SAMPLES).sum())
+    assert 0 < n < w * h, (what, n)
+    return got
+
+
+def everybody_is_above_the_threshold():
+    """Why `0 < n < W * H` is asserted at the plane's median and not at 0.05.  With six samples a pixel most of the frame is above
+    0.05: on 97x61 select_blend_error(0.05, 0) selects 5408 pixels and more, and all 5917 in family N without a level; dilate 2
+    reaches everybody in more cases, and on 7x5 34 or 35 of 35 are selected at either.  Those selections are compared all the
+    same; every case also selects at the median of its own plane's finite positive values (from the restatement), dilate 0, where
+    neither nobody nor everybody is selected."""
+
+
+def median_of(plane):
+    """the median of a plane's finite positive values (the threshold of the 7x5 selections, from the restatement)"""
+    return float(np.median(plane[np.isfinite(plane) & (plane > 0)]))
+
+
+@pytest.mark.parametrize("frame,family,display,radius,z,window,denoise", hz.BLEND_ERROR_CASES, ids=hz.case_id)
+def test_guard_blend_error(frame, family, display, radius, z, window, denoise):
+    got = _blend_error_case("v3", frame, family, display, radius, z, window, denoise)
+    assert not np.isnan(got.denoised).any()      # (the error plane of the linear rule holds NaN words without a level: under the guard)
+
+
+def _blend_option_case(preset, frame, family, mode, cover, fill, lattice):
+    scene, cfg, feats = _frame(preset, frame)
+    w, h = hz.FRAMES[frame]
+    ib, ib2, a, _ = _batches(preset, family, frame, lattice)
+    if lattice is not None:      # the holes are holes in image_buffer, A and B alike
+        off = ~fi.lattice(w, h, lattice)
+        assert not ib2[off].any() and not a[off].any()
+    cov = _cov(preset, frame) if cover else None
+    seen = []
+    for denoise in hz.BLEND_OPTION_DENOISE:
+        K = denoise.get("iterations", 4)
+        what = f"{preset} {frame} {family} {mode} lattice {lattice} {hz.case_id(denoise)}"
+        if fill:
+            got = bf.blend_fill(cfg, ib2, a, feats, cov, mode, threshold=hz.BLEND_THR, **hz.BLEND_OPTION_RULE, **denoise)
+            stage = "blend_fill" + ("+coverage " if cover else " ")
+            reach_at, reach = fi.reach(ib2[..., 3] > 0, feats["object"], K)
+            assert got.counts == reach and got.counts[0] > 0, (what, got.counts, reach)
+            if lattice is not None:
+                assert got.counts[0] > w * h / 2 and got.counts[2] >= 1, (what, got.counts)
+            filled = reach_at >= 0             # known answer 4 on the hostile frames: weight exactly 1, depth exactly K
+            assert np.all(got.weight[filled] == 1) and np.all(got.depth[filled] == K) and np.all(got.depth[reach_at == -2] == 0), what
+        else:
+            got = bc.blend_coverage(cfg, ib2, a, feats, cov, mode, threshold=hz.BLEND_THR, **hz.BLEND_OPTION_RULE, **denoise)
+            stage = "blend_coverage "
+        planes = dict(frame=got.denoised, weight=got.weight, depth=got.depth)
+        if got.error is not None:
+            planes["error"] = got.error
+        _guard(stage + what, **planes)
+        _weight_and_depth_in_range(what, got.weight, got.depth, K)
+        assert got.stats[0] > 0 and (not cover or got.resolved > 0), (what, got.stats, got.resolved)
+        seen.append(got)
+        # with no usable pixel (min_half_samples above every count) the frame is the filter's own: the restatement of the blend
+        # against the restatement of rtpbr_denoise_coverage / rtpbr_denoise with denoise_fill / coverage_fill, on the hostile words
+        rule = dict(hz.BLEND_OPTION_RULE, min_half_samples=NEVER)
+        if fill:
+            never = bf.blend_fill(cfg, ib2, a, feats, cov, mode, threshold=hz.BLEND_THR, **rule, **denoise)
+            filter_s = cf.denoise_coverage_fill(cfg, ib2, feats, cov, **denoise)[::2] if cover else fi.denoise_fill(cfg, ib2, feats, **denoise)
+            assert never.counts == filter_s[1] == got.counts, what
+        else:
+            never = bc.blend_coverage(cfg, ib2, a, feats, cov, mode, threshold=hz.BLEND_THR, **rule, **denoise)
+            filter_s = cl.denoise_coverage(cfg, ib2, feats, cov, **denoise)
+            assert never.resolved == filter_s[1][0], what
+        assert _same(never.denoised, filter_s[0]) and np.all(never.weight == 1), what
+    return seen
+
+
+@pytest.mark.parametrize("frame,family,mode,cover,fill,lattice", hz.BLEND_OPTION_CASES, ids=hz.case_id)
+def test_guard_blend_options(frame, family, mode, cover, fill, lattice):
+    for got in _blend_option_case("v3", frame, family, mode, cover, fill, lattice):
+        assert not np.isnan(got.denoised).any()
+
+
+def test_family_n_reaches_the_display_as_nan_under_preset_v2():
+    """Preset v3 shows a NaN as 0, so the tables' family-N cases compare zeros; hostile.NAN_* are one case per display stage under
+    preset v2, where the NaN words themselves reach the frame.  The guard holds there too."""
+    for case in hz.NAN_FILL_CASES:
+        for out in _fill_case(hz.NAN_PRESET, *case):
+            assert np.isnan(out).any()
+    for case in hz.NAN_COVERAGE_CASES:
+        assert np.isnan(_coverage_case(hz.NAN_PRESET, *case)).any()
+    for case in hz.NAN_BLEND_ERROR_CASES:
+        assert np.isnan(_blend_error_case(hz.NAN_PRESET, *case).denoised).any()
+    for case in hz.NAN_BLEND_OPTION_CASES:
+        for got in _blend_option_case(hz.NAN_PRESET, *case):
+            assert np.isnan(got.denoised).any()
+
+
+def tier_plane(call, cfg, ib2, a, M, feats, thr):
+    """(the plane the call selects on, half A's counts or None) from the restatement of the call that writes it"""
+    if call == "noisy":
+        return nr.estimate(ib2, M, feats["object"], thr)[0], None
+    if call == "error":
+        return hl.denoise_error(cfg, ib2, a, feats, threshold=thr, **hz.TIER_DENOISE)[0], a[..., 3]
+    assert call == "blend_error"
+    return be.blend_error(cfg, ib2, a, feats, thr, **hz.TIER_BLEND, **hz.TIER_DENOISE).error, a[..., 3]
+
+
+@pytest.mark.parametrize("family,call,thr,tiers,batch,dilate", hz.TIER_CASES, ids=hz.case_id)
+def test_tiers_are_not_empty_sets(family, call, thr, tiers, batch, dilate):
+    scene, cfg, feats = _frame("v3")
+    _, ib2, a, M = _batches("v3", family, "97x61", None)
+    plane, half_count = tier_plane(call, cfg, ib2, a, M, feats, thr)
+    assert hz.guard(f"{call} plane {family}", plane) == 0.0
+    sel = tr.select(plane, ib2[..., 3], thr, dilate, tiers, batch, hz.TIER_MIN_SAMPLES, half_count)
+    counts = tr.counts(sel, tiers)
+    # who is selected at all is the parents' rule, stated in C: the tiers only split that set
+    member = pl.select(plane, ib2[..., 3], thr, dilate, hz.TIER_MIN_SAMPLES) if call == "noisy" else \
+        hl.select(ib2, a, plane, thr, dilate, hz.TIER_MIN_SAMPLES)
+    assert np.array_equal(sel != 0, member != 0)
+    print(f"[hostile] tiers {family} select_{call} threshold {thr} ({tiers},{batch}) dilate {dilate}: {counts}")
+    assert 0 < sum(counts) <= hz.W * hz.H
+    assert sel[~(ib2[..., 3] > 0)].all() and (sel[ib2[..., 3] < hz.TIER_MIN_SAMPLES] == 1).all()      # no samples, or too few: tier 0
+    if thr == 0.0:
+        assert sum(counts[1:]) == 0                        # r = m / 0 is infinite: need is infinite or NaN, no bound holds
+    elif dilate == 0 and (tiers, batch) != (2, 1):
+        assert min(counts) > 0, counts                     # every tier occurs
+    with np.errstate(all="ignore"):
+        need = ib2[..., 3] * ((plane / F32(thr)) ** 2 - F32(1))
+    hostile_need = (~np.isfinite(need)) & (plane > F32(thr)) & (ib2[..., 3] >= hz.TIER_MIN_SAMPLES)
+    assert (sel[hostile_need] == 1).all() and (hostile_need.any() or thr != 0.0)      # a NaN or infinite need is tier 0, not the last
+
+
+# ------------------------------------------------------------------ 4. known answers of the filling stages
+def _tiny(w, h, preset="v3"):
+    """(cfg, flat single-object features, an image buffer whose pixels all lack samples) — the tests switch pixels on"""
+    cfg = Config.cornell_v3(w, h, 0, 3) if preset == "v3" else Config.cornell_v2(w, h, 1, 3)
+    feats = _flat_features(w, h, np.zeros((w, h), np.int32))
+    return cfg, feats, np.zeros((w, h, 4), F32)
+
+
+def _shown(cfg, feats, mean):
+    """what the display shows for this linear colour: tone_map through a one-sample probe with no level"""
+    w, h = feats["object"].shape
+    probe = np.zeros((w, h, 4), F32)
+    probe[0, 0] = (*mean, 1.0)
+    return fr.denoise(cfg, probe, feats, 0, 0)[0, 0]
+
+
+@pytest.mark.parametrize("count", [NAN, -0.0, -3.0, 0.0], ids=["NaN", "-0", "-3", "+0"])
+def test_an_empty_centre_takes_exactly_its_one_live_neighbours_mean(count):
+    """Known answer 1.  `count > 0` is false: the centre is EMPTY whatever its colour words hold.  With flat features every tap
+    weight is h exp(-0) = h, and with one live pixel in reach the fill is (h c) / h = c, exact for these powers of two.  The same
+    through the coverage-weighted fill (a frame without candidates: every purity is 1) and through the level blend's fill."""
+    w = h = 5
+    cfg, feats, ib = _tiny(w, h)
+    mean = F32([0.5, 2.0, 0.25])
+    ib[3, 2] = (*(mean * 4), 4.0)
+    ib[2, 2] = (7.0, -1.0, NAN, count)
+    want = _shown(cfg, feats, mean)
+    reach_at, reach = fi.reach(ib[..., 3] > 0, feats["object"], 1)
+    assert reach == (19, 5, 0) and reach_at[2, 2] == 0 and reach_at[3, 2] == -1
+    cov = cl.bin_coverage(feats["object"], np.zeros((4 * w, 4 * h), np.int32), 4)
+    for out, counts in (fi.denoise_fill(cfg, ib, feats, 1, 0, **hz.SIGMAS),
+                        cf.denoise_coverage_fill(cfg, ib, feats, cov, iterations=1, demodulate=0, **hz.SIGMAS)[::2]):
+        assert counts == reach
+        assert _same(out[2, 2], want) and _same(out[3, 2], want), (out[2, 2], want)
+        assert _same(out[0, 2], fr.denoise(cfg, ib, feats, 0, 0)[0, 2])        # out of reach: what post_process shows
+    a = ib * F32(0.5)
+    got = bf.blend_fill(cfg, ib, a, feats, None, "levels", radius=1, z=0.0, min_half_samples=1, iterations=1, **hz.SIGMAS)
+    assert got.counts == reach and _same(got.denoised[2, 2], want)
+
+
+@pytest.mark.parametrize("count", [INF, 1e-45], ids=["+inf", "1e-45"])
+def test_an_infinite_or_denormal_count_is_live_and_a_tap(count):
+    """Known answer 2.  `count > 0` holds for +inf and for the smallest denormal: the pixel is LIVE, is not counted in fill_filled
+    and fills its empty neighbours with its mean colour / count — 0 for an infinite count, (1, 2, 4) for the colour words (1, 2, 4)
+    x 2^-149 over the count 2^-149 (the header does not say how the mean of a denormal count is formed; the restatement's
+    reading is the IEEE quotient colour / count, without flushing)."""
+    w = h = 5
+    cfg, feats, ib = _tiny(w, h)
+    tiny = F32(1e-45)
+    ib[2, 2] = (3.0, 5.0, 7.0, count) if count == INF else (tiny, F32(2) * tiny, F32(4) * tiny, tiny)
+    mean = F32([0, 0, 0]) if count == INF else F32([1, 2, 4])
+    want = _shown(cfg, feats, mean)
+    out, counts = fi.denoise_fill(cfg, ib, feats, 1, 0, **hz.SIGMAS)
+    assert counts == fi.reach(ib[..., 3] > 0, feats["object"], 1)[1] == (24, 0, 0)      # everybody but the live pixel itself
+    for x, y in ((2, 2), (1, 2), (4, 4), (0, 0)):
+        assert _same(out[x, y], want), (x, y, out[x, y], want)
+
+
+def test_a_nan_coloured_live_tap_fills_with_nan_counts_as_filled_and_stays_live():
+    """Known answer 3, under tone-map order 1 (preset v2), which shows a NaN as NaN (the ACES matrix mixes it into all three
+    channels).  The live pixel's colour is NaN in one channel; its empty neighbours take w * NaN / w = NaN, are counted in
+    fill_filled, and are live taps at the next level: a pixel only level 1 reaches is filled from them, NaN again.  Pixels out of
+    reach show what post_process shows (0 / 0 under this tone map: NaN as well, so the counters tell the two apart)."""
+    w, h = 7, 5
+    cfg, feats, ib = _tiny(w, h, "v2")
+    ib[0, 2] = (NAN, 8.0, 1.0, 4.0)
+    for K in (1, 2):
+        out, counts = fi.denoise_fill(cfg, ib, feats, K, 0, **hz.SIGMAS)
+        reach_at, reach = fi.reach(ib[..., 3] > 0, feats["object"], K)
+        assert counts == reach and counts[0] == int((reach_at >= 0).sum()) > 0 and counts[2] == K - 1
+        filled = reach_at >= 0
+        assert np.isnan(out[filled]).all() and np.isnan(out[0, 2]).all()
+        assert _same(out[reach_at == -2], fr.denoise(cfg, ib, feats, 0, 0)[reach_at == -2])
+    assert reach_at[4, 2] == 1 and reach_at[2, 2] == 0 and reach_at[6, 2] == 1                # level 1 went on from level 0's fills
+
+
+def test_blend_fill_gives_filled_pixels_weight_1_and_depth_k_and_leaves_the_unreached_to_post_process():
+    """Known answer 4.  Object 0 (x < 5) is sampled on the (2,2) lattice and has a hostile centre; object 1 (x >= 5) has no sample
+    at all and is never reached (taps do not cross objects): depth 0, weight 1 (the header's value for a pixel without usable
+    halves) and post_process's bytes."""
+    w, h = 7, 5
+    cfg = Config.cornell_v3(w, h, 0, 3)
+    obj = np.zeros((w, h), np.int32)
+    obj[5:] = 1
+    feats = _flat_features(w, h, obj)
+    keep = fi.lattice(w, h, (2, 2)) & (obj == 0)
+    ib = fi.masked(_plain(w, h), keep)
+    ib[5:, :, :3] = 9.0                                    # colour words without a count: shown as post_process shows them
+    ib[2, 2] = (1.0, 2.0, 3.0, NAN)
+    a = ib * F32(0.5)
+    shown = fr.denoise(cfg, ib, feats, 0, 0)
+    for K in (1, 3):
+        for mode in hz.BLEND_MODES:
+            got = bf.blend_fill(cfg, ib, a, feats, None, mode, radius=1, z=0.0, min_half_samples=1, iterations=K, **hz.SIGMAS)
+            reach_at, reach = fi.reach(ib[..., 3] > 0, obj, K)
+            assert got.counts == reach and reach[1] == int((obj == 1).sum())
+            filled, never = reach_at >= 0, reach_at == -2
+            assert filled[2, 2] and np.all(got.weight[filled] == 1) and np.all(got.depth[filled] == K)
+            assert np.all(got.depth[never] == 0) and np.all(got.weight[never] == 1)
+            assert _same(got.denoised[never], shown[never])
+            _weight_and_depth_in_range(f"{mode} K={K}", got.weight, got.depth, K)

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "librtpbr_hip.so")
 SOURCES = ["rt_kernels.hip", "rt_capi.hip", "rt_rccl.hip", "rt_jit.hip", "rt_features.hip", "rt_reproject.hip", "rt_noise.hip", "rt_select.hip", "rt_present.hip", "rt_half.hip", "rt_coverage.hip"]
-HEADERS = ["rt_math.hpp", "rt_types.hpp", "rt_item.hpp", "rt_device.hpp", "rt_dispatch.hpp", "rt_trace.hpp", "rt_persistent.hpp", "rt_split.hpp", "rt_chain.hpp", "rt_ctx.hpp", "rt_features.hpp", "rt_reproject.hpp", "rt_noise.hpp", "rt_select.hpp", "rt_lattice.hpp", "rt_present.hpp", "rt_half.hpp", "rt_coverage.hpp", "rt_jit_tu.hip", os.path.join("..", "..", "include", "rtpbr.h")]
+HEADERS = ["rt_math.hpp", "rt_types.hpp", "rt_item.hpp", "rt_device.hpp", "rt_dispatch.hpp", "rt_trace.hpp", "rt_persistent.hpp", "rt_split.hpp", "rt_chain.hpp", "rt_ctx.hpp", "rt_features.hpp", "rt_reproject.hpp", "rt_noise.hpp", "rt_select.hpp", "rt_lattice.hpp", "rt_launch_plan.hpp", "rt_present.hpp", "rt_half.hpp", "rt_coverage.hpp", "rt_jit_tu.hip", os.path.join("..", "..", "include", "rtpbr.h")]
 # -ffp-contract=off: only the fmaf written in rt_math.hpp are fused (bit-reproducible results);
 # no -ffast-math: f32 divide and sqrt stay correctly rounded.
 # -fno-slp-vectorize: the SLP vectoriser pairs independent f32 ops of neighbouring boxes into

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rt_ctx.hpp"
+#include "rt_launch_plan.hpp"
 #include "rt_coverage.hpp"
 #include "rt_features.hpp"
 #include "rt_reproject.hpp"
@@ -745,15 +746,12 @@ extern "C" int rtpbr_refresh(rtpbr_ctx* c) {
 
 static void pack_objects(rtpbr_ctx* c, Params& P) { pack_table(c->objm, c->n_obj, P.box_sig, P.objm); }
 
-// Staging (one 12-byte StageRec per item) and, for the primary split, the primary records (5 bytes per item: a float, then a byte).
+// Staging and, for the primary split, the primary records (what an item takes of each: rt_launch_plan.hpp).
 // Grown on demand; hipMalloc of several GB takes 50..700 ms, so callers that time whole frames can
 // reserve up front (option "reserve_spp").
 // Returns RTPBR_ENOMEM (nothing allocated, no sticky HIP error) when the device has no room: the caller then renders
 // with fewer samples per launch instead of failing.
-constexpr size_t PRIMARY_REC_BYTES = 5;     // float t_eval + one byte of idx | state
 // staging of `items` samples: the 12-byte records, then (dense staging) one fill count per chunk of >= 32 items and one byte per record
-constexpr size_t STAGE_ITEM_BYTES = 14;     // what a sample is budgeted at (12 + 1 + 4 / 32, rounded up)
-constexpr uint32_t DENSE_CHUNK_MIN = 32, DENSE_CHUNK_MAX = 256, DENSE_BATCH_MAX = 4096;
 static size_t stage_bytes(size_t items) { return items * sizeof(StageRec) + (items / DENSE_CHUNK_MIN + 2) * sizeof(uint32_t) + items; }
 static int staging_alloc(rtpbr_ctx* c, void** ptr, size_t* cap, size_t need) {
     if (need <= *cap) return RTPBR_OK;
@@ -794,21 +792,11 @@ static int next_event_of(std::vector<hipEvent_t>& pool, int& used, hipEvent_t* o
     if (int r_ = next_event_of(pool, used, &var)) return r_
 
 static int trace_grid(rtpbr_ctx* c, uint32_t total_items, bool selected = false) {
-    int per_cu = selected ? trace_selected_blocks_per_cu(c->kind, c->n_obj, c->P.scheduler)
+    const int per_cu = selected ? trace_selected_blocks_per_cu(c->kind, c->n_obj, c->P.scheduler)
                  : c->jit_mod ? c->jit_mod->trace_blocks_per_cu
                               : trace_blocks_per_cu(c->kind, c->n_obj, c->P.box_sig, c->scheduler < 0 ? 1 : c->scheduler);
-    if (per_cu <= 0) per_cu = 2;
-    if (c->waves_per_cu > 0) per_cu = (c->waves_per_cu + 3) / 4;
-    long long grid = (long long)per_cu * c->n_cu;
-    long long need = ((long long)total_items + 255) / 256;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    return (int)grid;
+    return (int)capped_grid(blocks_per_cu(per_cu, c->waves_per_cu), c->n_cu, total_items);
 }
-
-// Room kept free below 2^32 for the claims the last waves make past the end of the work (one failing claim per wave):
-// at most 32 waves per CU, at most 8192 items per claim (option "chunk" is clamped to that).
-static long long work_margin(const rtpbr_ctx* c) { return (long long)(c->n_cu > 0 ? c->n_cu : 256) * 32LL * 8192LL; }
 
 // Everything of a launch that is decided on the HOST from the context's state (configuration, scene, camera, tiles, options) and
 // that the run-time instance's key depends on: shared by rtpbr_sample() and rtpbr_jit_prebuild() (which has no device), so that
@@ -879,43 +867,6 @@ static void derive_launch(rtpbr_ctx* c, RtJitKey* key, bool* want, bool* strict_
 }
 
 static int launch_split_steps(rtpbr_ctx* c, int steps);
-// ------------------------------------------------------------------------------------------------------------------------
-// THE HOST SCHEDULER'S CONSTANTS, in one place.  Everything below that is a number was MEASURED on one MI355X (256 CUs, 4 SIMDs
-// per CU, 160 KB of LDS per CU); what follows from the device is read from hipDeviceProp (c->n_cu) or from the kernels'
-// occupancy (hipOccupancyMaxActiveBlocksPerMultiprocessor / the run-time module's own query).  Option defaults — the numbers a
-// caller can change — live in rt_ctx.hpp next to the option they belong to; rtpbr.h documents them.  On another SKU or a
-// partitioned device (CPX) these are the lines to re-measure (tools/gpu_src_grid.py, tools/gpu_src_1step.py sweep them).
-namespace tune {
-constexpr int WAVES_PER_BLOCK = 4;              // 256 threads: one wave per SIMD of a CU
-constexpr int CTX_PER_WAVE = 128;               // src/ pool kernel: 64 lanes + 64 LDS slots (rt_persistent.hpp)
-constexpr int MAX_FUSED_STEPS = 256;            // bounce-steps per fused src/ launch (G_META holds 9 bits)
-// --- src/ pool kernel (fused launches) -----------------------------------------------------------------------------------
-constexpr int POOL_MIN_PIX_PER_WAVE = 64;       // a wave never owns fewer pixels than it has lanes (grid <= np / 256)
-// beside the chain kernel a pool wave should own ~190 pixels, in whole blocks per CU, at least two (two waves of 162 contexts
-// march with 54-57 of 64 lanes, three of 108 with 34; a wave issues one instruction per ~6.5 cycles whatever it carries):
-// 1024x576 four -> three blocks per CU 30.8 -> 27.3 ms, 960x540 29.5 -> 24.2, 768x432 three -> two 22.7 -> 22.3 (round 5)
-constexpr int CHAIN_POOL_PIX_PER_BLOCK = 760;
-constexpr int CHAIN_POOL_MIN_BLOCKS_PER_CU = 2;
-constexpr int CHAIN_GRID_BLOCKS = 512;          // chain kernel: 2048 waves = the largest chain set a plan can make (waves without an entry leave at once)
-// --- src/ wavefront split (launches of <= src_split steps) -----------------------------------------------------------------
-// waves per SIMD of the march kernel: 2 / 3 / 4 / 5 / 8 = 0.53 / 0.51 / 0.51 / 0.55 / 0.59 ms per 1080p launch (the arbiter
-// serves the oldest wave first: with more the youngest starve and end last)
-constexpr int MARCH_MAX_BLOCKS_PER_CU = 4;
-// small frames are all tail: two waves per SIMD (640x360 0.230 / 0.236 / 0.240 ms at 2 / 3 / 4, 768x432 0.258 / 0.261 / 0.270,
-// no difference from 1024x576 on) and the list's heavy head interleaved over the groups (768x432 0.2375 -> 0.224; 1080p loses)
-constexpr long long MARCH_SMALL_FRAME_PIXELS = 600000;
-constexpr int MARCH_SMALL_BLOCKS_PER_CU = 2;
-constexpr int MARCH_MAX_TEAMS = 1024;           // team counters allocated (rtpbr_create)
-constexpr int SPARSE_LANES_DEFAULT = 24;        // option sparse_lanes as rt_ctx.hpp sets it (fused pool kernel: tracked march when <= 24 lanes march)
-constexpr int SPLIT_SPARSE_LANES = 8;           // ... the split march kernel with the object-parallel evaluation: from 8 lanes down
-// --- complete-path form ----------------------------------------------------------------------------------------------------
-constexpr long long PRIMARY_SPLIT_MIN_ITEMS = 1LL << 23;    // the separate primary kernel costs ~0.3 ms per launch: below ~8 M items the fused kernel wins
-// work items a wave claims per atomic: total / (waves x 64) clamped to [256, 1024]; 128 when a launch has fewer than 256 per wave
-// (1080p x 16 spp: 64 / 128 / 256 / 512 items = 10.6 / 9.6 / 9.2 / 9.3 ms; 4096 cost 2 % on the Cornell frame and 18 % on the
-// glass bunny — a wave that claims the last chunk works it off 128 paths at a time; C1: 1407 -> 1492 Msamples/s with 128)
-constexpr long long CHUNK_MIN = 256, CHUNK_MAX = 1024, CHUNK_TINY = 128;
-constexpr int PRIMARY_BLOCKS_PER_CU = 8;        // the primary kernel needs ~57 VGPRs: 32 waves per CU
-}  // namespace tune
 
 // What the LAST plan decided about the chain set, learned asynchronously (a 4-byte copy behind the plan kernels): the pool
 // grid makes room for the chain kernel only when a plan actually produced one (advisor, round 5: the grid used to shrink
@@ -954,54 +905,11 @@ static int sample_persistent(rtpbr_ctx* c, int n, bool* launched) {
         // 256x256 up (profiles/r03_src_*; round 2 switched at 2^20 pixels by a guess)
         const bool use_pool = c->scheduler != 0;
         if (use_pool) {
-            // Static ownership (persistent_pool_impl): every resident wave owns np / waves pixels.  A wave holds 128 contexts:
-            // when the frame fits (np <= 128 x resident waves) the grid is sized so that every wave owns <= 128 pixels and
-            // keeps them for the whole launch, in whole multiples of the CU count (every CU the same number of blocks), but
-            // never fewer than 64 pixels per wave; larger frames use every resident wave and walk their pixels in
-            // residencies of `residency` bounce-steps.
-            int per_cu = c->jit_mod ? c->jit_mod->persistent_blocks_per_cu : persistent_pool_blocks_per_cu(c->kind);
-            if (per_cu <= 0) per_cu = 2;
-            if (c->waves_per_cu > 0) per_cu = (c->waves_per_cu + 3) / 4;
-            const long long max_blocks = (long long)per_cu * c->n_cu;
-            const long long ctx_per_block = (long long)tune::CTX_PER_WAVE * tune::WAVES_PER_BLOCK;
-            long long grid = ((long long)P.np + ctx_per_block - 1) / ctx_per_block;
-            if (grid >= max_blocks) {
-                grid = max_blocks;
-            } else {
-                grid = (grid + c->n_cu - 1) / c->n_cu * c->n_cu;
-                if (grid > max_blocks) grid = max_blocks;
-                const long long dense = (long long)P.np / (tune::POOL_MIN_PIX_PER_WAVE * tune::WAVES_PER_BLOCK);
-                if (grid > dense) grid = dense;
-            }
-            // The chain kernel (rt_chain.hpp) runs BESIDE the pool kernel and needs wave slots of its own.  Frames up to about
-            // 1080p may be chain-bound (plan_scan decides, on the device, against the grid the pool kernel has beside the chain kernel);
-            // when the last plan made a chain set the pool grid makes room — whole multiples of the CU count: an uneven grid
-            // costs more than it gives (1024x576 42.8 -> 30 ms, 1280x720 46 -> 40, 1600x900 54.7 -> 50.4, 1080p 58.6 -> 57.3) —
-            // and is sized for ~190 pixels per wave.  Larger frames are throughput-bound and keep the whole device for the pool
-            // kernel (2560x1440: 97.2 against 100.3 ms).
+            const int per_cu = blocks_per_cu(c->jit_mod ? c->jit_mod->persistent_blocks_per_cu : persistent_pool_blocks_per_cu(c->kind), c->waves_per_cu);
             if (int r = poll_plan_readback(c)) return r;
-            const long long chain_blocks = (c->chain_waves + tune::WAVES_PER_BLOCK - 1) / tune::WAVES_PER_BLOCK;
             const bool chain_candidate = c->src_chain != 0 && c->grid_blocks == 0 && c->src_plan && (long long)P.np <= c->chain_np_max;
             const bool chain_room = chain_candidate && (c->plan_chain_waves > 0 || c->src_chain == 2);
-            // (the grid WITH room is computed whether or not room is made: it is what the plan decides "chain-bound" against, so that
-            // the decision is the same before and after — the host makes room only once a plan has said so)
-            // Two separate things (round 6 took them apart: `src_chain = 0 / 1 / 2` at 1080p = 56.3 / 56.5 / 53.4 ms showed that what
-            // helps there is the GRID, the plan never finds 1080p chain-bound): (a) a frame that may get a chain set leaves one block
-            // per CU free — four blocks per CU instead of five are faster at these sizes with or without a chain kernel beside them
-            // (1080p 56 -> 53.4 ms); (b) the ~190 pixels per wave of a small frame pay only BESIDE a chain kernel (without one the
-            // heaviest pixels need the larger grid: 768x432 26 against 36 ms) — applied once a plan has produced a chain set.
-            long long grid_room = grid;
-            if (chain_candidate) {
-                if (grid_room + chain_blocks > max_blocks && max_blocks - chain_blocks >= c->n_cu) grid_room = (max_blocks - chain_blocks) / c->n_cu * c->n_cu;
-                if (grid_room < 1) grid_room = 1;
-                grid = grid_room;                                                     // (a)
-                long long want = ((long long)P.np / tune::CHAIN_POOL_PIX_PER_BLOCK + c->n_cu / 2) / c->n_cu * c->n_cu;
-                if (want < (long long)tune::CHAIN_POOL_MIN_BLOCKS_PER_CU * c->n_cu) want = (long long)tune::CHAIN_POOL_MIN_BLOCKS_PER_CU * c->n_cu;
-                if (grid_room > want) grid_room = want;                               // (b): what the plan decides "chain-bound" against
-            }
-            if (chain_room) grid = grid_room;
-            if (c->grid_blocks > 0) grid = c->grid_blocks;
-            if (grid < 1) grid = 1;
+            const PoolPlan pool = pool_plan(P.np, per_cu, c->n_cu, c->chain_waves, chain_candidate, chain_room, c->grid_blocks);
             P.total_items = (uint32_t)P.np;
             P.chunk = (uint32_t)c->residency;                               // bounce-steps per residency (a power of two)
             // Cost-ordered ownership: the kernel records every pixel's march steps; once plan_interval bounce-steps
@@ -1021,10 +929,7 @@ static int sample_persistent(rtpbr_ctx* c, int n, bool* launched) {
             P.age_on = c->age_on;
             P.age_pack = 0;
             for (int k = 0; k < 8; k++) P.age_pack |= (uint32_t)(c->age_w[k] & 15) << (4 * k);
-            // the chain kernel is launched only when the device has room for both: more resident waves than it holds just queue
-            // the pool's last blocks behind the chain waves (measured -12 % at 720p)
-            const bool chain_fits = chain_candidate && grid + chain_blocks <= max_blocks;
-            const bool chain_eff = c->src_chain != 0 && (chain_fits || c->src_chain == 2);
+            const bool chain_eff = c->src_chain != 0 && (pool.chain_fits || c->src_chain == 2);
             if (c->src_plan) {
                 if (c->plan_np != (size_t)P.np) {
                     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1048,9 +953,9 @@ static int sample_persistent(rtpbr_ctx* c, int n, bool* launched) {
                 if (c->cost_steps >= c->plan_interval) {
                     // (the plan sizes its heavy waves for THIS launch's grid and decides "chain-bound" against the grid the pool
                     // kernel has beside the chain kernel: the decision does not depend on whether room has been made already)
-                    launch_plan(c->cost_buffer, c->order, c->plan, (uint32_t)P.np, (uint32_t)grid * 4u, c->heavy_own, c->heavy_mean_x16,
-                                c->heavy_bulk_x16, c->tiny_waves, c->n_cu, (int)((grid + c->n_cu - 1) / c->n_cu), chain_candidate || c->src_chain == 2 ? c->chain_waves : 0,
-                                (uint32_t)grid_room * 4u, c->stream);
+                    launch_plan(c->cost_buffer, c->order, c->plan, (uint32_t)P.np, (uint32_t)pool.grid * 4u, c->heavy_own, c->heavy_mean_x16,
+                                c->heavy_bulk_x16, c->tiny_waves, c->n_cu, pool.n_cls, chain_candidate || c->src_chain == 2 ? c->chain_waves : 0,
+                                (uint32_t)pool.grid_room * 4u, c->stream);
                     c->order_valid = true;
                     c->cost_steps = 0;
                     if (!c->plan_rb_host) {
@@ -1092,9 +997,9 @@ static int sample_persistent(rtpbr_ctx* c, int n, bool* launched) {
                 }
                 if (rc == RTPBR_OK) {
                     if (c->jit_mod)
-                        rc = rt_jit_launch_steps(c->jit_mod->persistent_pool, P, steps, (unsigned)grid, c->stream);
+                        rc = rt_jit_launch_steps(c->jit_mod->persistent_pool, P, steps, (unsigned)pool.grid, c->stream);
                     else
-                        launch_persistent_pool(P, c->kind, steps, (int)grid, c->stream);
+                        launch_persistent_pool(P, c->kind, steps, (int)pool.grid, c->stream);
                 }
                 // JOIN on every exit once the second stream has been forked (advisor, round 5): nothing that follows on the
                 // context's stream may overtake a chain kernel that is still running — if the event cannot be recorded, wait
@@ -1138,27 +1043,13 @@ static int launch_split_steps(rtpbr_ctx* c, int steps) {
     P.march_out = c->march_out;
     P.wait_lanes = c->split_wait;
     P.chain_on = 0;
-    // with the object-parallel evaluation the tracked forms pay from 8 marching lanes down; between 9 and 24 a wave's lanes rarely
-    // share an object and the three-smallest evaluation (2.7 kcycles per call in the tails) only replaces a plain step (1.1 k):
-    // 768x432 0.2125 -> 0.205 ms per launch, 1080p 0.454 -> 0.450.  (An explicit sparse_lanes — the tests force 64 — is respected.)
+    const MarchPlan march = march_plan(P.np, c->jit_mod ? c->jit_mod->march_blocks_per_cu : src_march_blocks_per_cu(c->kind), c->n_cu, c->waves_per_cu,
+                                       c->grid_blocks, c->split_head, c->sparse_lanes, c->src_op, c->n_obj);
     const int sparse_saved = P.sparse_lanes;
-    if (c->sparse_lanes == tune::SPARSE_LANES_DEFAULT && (c->src_op & 1) && c->n_obj <= 8) P.sparse_lanes = tune::SPLIT_SPARSE_LANES;
-    int mper = c->jit_mod ? c->jit_mod->march_blocks_per_cu : src_march_blocks_per_cu(c->kind);
-    if (mper <= 0) mper = 2;
-    if (mper > tune::MARCH_MAX_BLOCKS_PER_CU) mper = tune::MARCH_MAX_BLOCKS_PER_CU;
-    const bool small = (long long)P.np <= tune::MARCH_SMALL_FRAME_PIXELS;
-    if (small && mper > tune::MARCH_SMALL_BLOCKS_PER_CU) mper = tune::MARCH_SMALL_BLOCKS_PER_CU;
-    P.split_head = c->split_head >= 0 ? c->split_head : (small ? 1 : 0);
-    if (c->waves_per_cu > 0) mper = (c->waves_per_cu + 3) / 4;
-    long long mgrid = (long long)mper * c->n_cu;
-    const long long need = ((long long)P.np + 255) / 256;
-    if (mgrid > need) mgrid = need;
-    if (c->grid_blocks > 0) mgrid = c->grid_blocks;
-    if (mgrid < 1) mgrid = 1;
-    // teams of blocks that share a claim counter: the blocks resident on one CU (blocks are placed round-robin)
+    P.sparse_lanes = march.sparse_lanes;
+    P.split_head = march.split_head;
     P.team_counter = c->team_counter;
-    P.n_teams = (int)(mgrid < c->n_cu ? mgrid : c->n_cu);
-    if (P.n_teams > tune::MARCH_MAX_TEAMS) P.n_teams = tune::MARCH_MAX_TEAMS;
+    P.n_teams = march.n_teams;
     int rc = RTPBR_OK;
     // lazy shading: a step's shading rides with the next step's gen pass (src_shade_gen) — flush_shade() launches it when something
     // else wants to see ray_buffer or the counters first
@@ -1171,13 +1062,13 @@ static int launch_split_steps(rtpbr_ctx* c, int steps) {
             c->shade_pending = false;
         }
         if (c->jit_mod) {
-            rc = rt_jit_launch(!shade_first ? c->jit_mod->src_gen : count ? c->jit_mod->src_shade_gen_count : c->jit_mod->src_shade_gen, P, (unsigned)need, c->stream);
-            if (rc == RTPBR_OK) rc = rt_jit_launch(c->jit_mod->src_march, P, (unsigned)mgrid, c->stream);
-            if (rc == RTPBR_OK && !lazy) rc = rt_jit_launch(c->jit_mod->src_shade, P, (unsigned)need, c->stream);
+            rc = rt_jit_launch(!shade_first ? c->jit_mod->src_gen : count ? c->jit_mod->src_shade_gen_count : c->jit_mod->src_shade_gen, P, (unsigned)march.need, c->stream);
+            if (rc == RTPBR_OK) rc = rt_jit_launch(c->jit_mod->src_march, P, (unsigned)march.grid, c->stream);
+            if (rc == RTPBR_OK && !lazy) rc = rt_jit_launch(c->jit_mod->src_shade, P, (unsigned)march.need, c->stream);
         } else {
             if (shade_first) launch_src_shade_gen(P, c->kind, count, c->stream);
             else launch_src_gen(P, c->kind, c->stream);
-            launch_src_march(P, c->kind, (int)mgrid, c->stream);
+            launch_src_march(P, c->kind, (int)march.grid, c->stream);
             if (!lazy) launch_src_shade(P, c->kind, c->stream);
         }
         if (lazy && rc == RTPBR_OK) {
@@ -1209,21 +1100,14 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false, bool
         const bool split_ok = !selected && c->primary_split && P.scheduler == 1 && c->kind != KIND_BUNNY && c->kind != KIND_MIXED;
         // the tolerance flavour accumulates in LDS and adds to image_buffer directly: no staging, no accumulate kernel
         const bool unstaged = c->precision != 0 && c->jit_mod != nullptr && P.scheduler == 1;
-        long long per_spp = (long long)P.np * (long long)((unstaged ? 0 : STAGE_ITEM_BYTES) + (split_ok ? PRIMARY_REC_BYTES : 0));
-        if (per_spp < 1) per_spp = 1;
-        long long kmax = c->staging_bytes / per_spp;
-        if (kmax < 1) kmax = 1;
-        // keep total_items within 32 bits (minus the chunks the last waves claim past the end: the work counter must not wrap)
-        long long k32 = (0xFFFFFFFFLL - work_margin(c)) / (long long)P.np;
-        if (k32 < 1) k32 = 1;
-        if (kmax > k32) kmax = k32;
-        int K = (int)(left < kmax ? left : kmax);
-        const bool split = split_ok && (c->primary_split == 2 || (long long)P.np * K >= tune::PRIMARY_SPLIT_MIN_ITEMS);
+        const StagingPlan sp = staging_plan(P.np, left, c->staging_bytes, c->n_cu, split_ok, unstaged, c->primary_split);
+        const int K = (int)sp.K;
+        const bool split = sp.split;
         if (int r = ensure_staging(c, (size_t)P.np * (size_t)K, split, !unstaged)) {
             // no room for K samples per launch: halve the budget and go round again (1 spp per launch must fit)
             if (r != RTPBR_ENOMEM || K == 1)
                 return r == RTPBR_ENOMEM ? fail(RTPBR_ENOMEM, "no device memory for the staging of one sample per pixel") : r;
-            c->staging_bytes = (long long)((K + 1) / 2) * per_spp;
+            c->staging_bytes = (long long)((K + 1) / 2) * sp.per_spp;
             continue;
         }
         P.primary = c->primary;
@@ -1235,35 +1119,23 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false, bool
         P.K = K;
         P.k_shift = item_shift_of(K);       // (rt_item.hpp: a power-of-two K splits the work item by shift and mask)
         P.sample_base = c->sample_base;
-        P.total_items = (uint32_t)((long long)P.np * K);
-        int grid = trace_grid(c, P.total_items, selected);
-        long long waves = (long long)grid * tune::WAVES_PER_BLOCK;
-        long long chunk = (long long)P.total_items / (waves * 64);
-        if (chunk < tune::CHUNK_MIN) chunk = (long long)P.total_items < waves * tune::CHUNK_MIN ? tune::CHUNK_TINY : tune::CHUNK_MIN;
-        if (chunk > tune::CHUNK_MAX) chunk = tune::CHUNK_MAX;
-        if (c->chunk > 0) chunk = c->chunk;
+        P.total_items = sp.total_items;
+        const int grid = trace_grid(c, P.total_items, selected);
+        const long long chunk = claim_plan(P.total_items, grid, c->chunk);
         P.chunk = (uint32_t)chunk;
-        // dense staging (rt_trace.hpp stage_sample, accumulate_dense): the claim must be whole pixels or a whole fraction of one, and
-        // fit the record's one-byte offset; a launch that has no such claim size near the one wanted keeps the item-linear records
         P.stage_dense = 0;
         if (c->stage_dense && c->jit_mod != nullptr && !unstaged && P.scheduler == 1 && !tracked && !dealt) {      // (compiled into run-time instances only: RtJitKey::dense)
-            long long lo = DENSE_CHUNK_MIN, hi = chunk < 64 ? 64 : chunk > (long long)DENSE_CHUNK_MAX ? (long long)DENSE_CHUNK_MAX : chunk, cc = 0;
-            if (c->chunk > 0) lo = hi = c->chunk;       // a claim size that was asked for is kept as it is (or the records stay item-linear)
-            if (lo >= (long long)DENSE_CHUNK_MIN && hi <= (long long)DENSE_CHUNK_MAX)
-                for (long long t = hi; t >= lo; t--)
-                    if (t % K == 0 || K % t == 0) { cc = t; break; }
-            const long long unit = cc > K ? cc : K;      // one divides the other: their least common multiple
-            if (cc > 0 && unit <= (long long)DENSE_BATCH_MAX) {
-                P.chunk = (uint32_t)cc;
+            const DensePlan dense = dense_plan(P.total_items, K, chunk, c->chunk);
+            if (dense.on) {
+                P.chunk = dense.chunk;
                 P.stage_dense = 1;
                 c->dense_launches++;
-                P.acc_batch = (uint32_t)(unit * ((long long)DENSE_BATCH_MAX / unit));
-                P.acc_magic_k = K > 1 ? (uint32_t)(0x100000000ULL / (unsigned long long)K) + 1u : 0u;
-                P.acc_magic_chunk = (uint32_t)(0x100000000ULL / (unsigned long long)cc) + 1u;
-                const size_t n_fill = (size_t)P.total_items / (size_t)cc + 1;
+                P.acc_batch = dense.acc_batch;
+                P.acc_magic_k = dense.acc_magic_k;
+                P.acc_magic_chunk = dense.acc_magic_chunk;
                 P.stage_fill = reinterpret_cast<uint32_t*>(c->stage + (size_t)P.total_items * 3u);
-                P.stage_idx = reinterpret_cast<uint8_t*>(P.stage_fill + n_fill);
-                HIP_TRY(hipMemsetAsync(P.stage_fill, 0, n_fill * sizeof(uint32_t), c->stream));
+                P.stage_idx = reinterpret_cast<uint8_t*>(P.stage_fill + dense.n_fill);
+                HIP_TRY(hipMemsetAsync(P.stage_fill, 0, dense.n_fill * sizeof(uint32_t), c->stream));
             }
         }
         // [0] trace items, [1] primary groups: zeroed with the work counters by rtpbr_sample(); again before every further sub-launch
@@ -1273,8 +1145,7 @@ static int sample_complete_path(rtpbr_ctx* c, int n, bool selected = false, bool
             NEXT_EVENT(c->evp, c->evp_used, pb);
             if (c->timed) HIP_TRY(hipEventRecord(pa, c->stream));
             if (c->jit_mod) {
-                long long need = ((long long)P.total_items + 255) / 256, pg = (long long)c->n_cu * tune::PRIMARY_BLOCKS_PER_CU;
-                if (int r = rt_jit_launch(c->jit_mod->primary, P, (unsigned)(pg < need ? pg : need), c->stream)) return r;
+                if (int r = rt_jit_launch(c->jit_mod->primary, P, (unsigned)capped_grid(tune::PRIMARY_BLOCKS_PER_CU, c->n_cu, P.total_items), c->stream)) return r;
             } else
                 launch_primary(P, c->kind, c->n_cu, c->stream);
             if (c->timed) HIP_TRY(hipEventRecord(pb, c->stream));
@@ -1314,12 +1185,11 @@ static int sample_selected_tiered(rtpbr_ctx* c, int n) {
     c->dense_launches = 0;
     bool fresh = true;
     for (int t = T - 1; t >= 0 && n > 0; t--) {
-        const int hi = (n >> t) > 1 ? n >> t : 1;
-        const int lo = t + 1 == T ? 0 : (n >> (t + 1)) > 1 ? n >> (t + 1) : 1;
-        if (hi == lo || c->sel_cum[t] == 0) continue;
+        const TierStage st = tier_stage(n, t, T);
+        if (st.hi == st.lo || c->sel_cum[t] == 0) continue;
         c->P.np = (int32_t)c->sel_cum[t];
-        c->sample_base = base + (uint32_t)lo;
-        if (int r = sample_complete_path(c, hi - lo, true, fresh)) return r;
+        c->sample_base = base + (uint32_t)st.lo;
+        if (int r = sample_complete_path(c, st.hi - st.lo, true, fresh)) return r;
         fresh = false;
     }
     c->sample_base = base + (uint32_t)n;
@@ -3037,14 +2907,7 @@ extern "C" int rtpbr_set_option(rtpbr_ctx* c, const char* key, long long value) 
         if (int r = set_dev(c)) return r;
         const bool split_ok = c->primary_split && c->scheduler != 0 && !(c->have_scene && (c->kind == KIND_BUNNY || c->kind == KIND_MIXED));
         const bool unstaged = c->precision != 0 && c->scheduler != 0;      // the tolerance flavour has no staging (rtpbr_sample)
-        long long per_spp = (long long)c->P.np * (long long)((unstaged ? 0 : STAGE_ITEM_BYTES) + (split_ok ? PRIMARY_REC_BYTES : 0));
-        if (per_spp < 1) per_spp = 1;
-        long long kmax = c->staging_bytes / per_spp;
-        long long k32 = (0xFFFFFFFFLL - work_margin(c)) / (long long)c->P.np;
-        if (k32 < 1) k32 = 1;
-        if (kmax > k32) kmax = k32;
-        if (kmax < 1) kmax = 1;
-        const long long K = value < kmax ? value : kmax;
+        const long long K = staging_plan(c->P.np, value, c->staging_bytes, c->n_cu, split_ok, unstaged, c->primary_split).K;
         if (int r = ensure_staging(c, (size_t)c->P.np * (size_t)K, split_ok, !unstaged))
             return r == RTPBR_ENOMEM ? fail(RTPBR_ENOMEM, "reserve_spp: no device memory for the staging of that many samples per pixel") : r;
     } else if (!strcmp(key, "select_lattice")) {

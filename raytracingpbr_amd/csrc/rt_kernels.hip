@@ -25,6 +25,7 @@
 //   refresh, post_process, pack/unpack tiles, math_probe (test hook).
 #include <hip/hip_runtime.h>
 
+#include "rt_launch_plan.hpp"
 #include "rt_trace.hpp"
 
 namespace rt {
@@ -508,9 +509,7 @@ __global__ void __launch_bounds__(256) plan_scatter(uint32_t* __restrict__ cost,
 void launch_plan(uint32_t* cost, uint32_t* order, PlanBuf* plan, uint32_t np, uint32_t n_waves, int heavy_own, int mean_x16, int bulk_x16,
                  int tiny_waves, int n_cu, int n_cls, int chain_on, uint32_t chain_ref_waves, hipStream_t st) {
     (void)hipMemsetAsync(plan, 0, offsetof(PlanBuf, age_valid), st);      // (the self-tuned age weights and the lifetimes survive)
-    long long need = ((long long)np + 255) / 256, grid = (long long)n_cu * 8;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
+    const long long grid = capped_grid(tune::PRIMARY_BLOCKS_PER_CU, n_cu, np);
     hipLaunchKernelGGL(plan_hist, dim3((unsigned)grid), dim3(256), 0, st, cost, np, plan);
     hipLaunchKernelGGL(plan_scan, dim3(1), dim3(256), 0, st, plan, np, n_waves, (uint32_t)heavy_own, (uint32_t)mean_x16, (uint32_t)bulk_x16,
                        (uint32_t)tiny_waves, (uint32_t)n_cls, (uint32_t)chain_on, chain_ref_waves);
@@ -571,10 +570,7 @@ int trace_selected_blocks_per_cu(int kind, int n_obj, int scheduler) {
     return e == hipSuccess ? per_cu : 0;
 }
 void launch_primary(const Params& P, int kind, int n_cu, hipStream_t st) {
-    long long need = ((long long)P.total_items + 255) / 256;
-    long long grid = (long long)n_cu * 8;            // 32 waves per CU: the kernel needs only ~40 VGPRs
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
+    const long long grid = capped_grid(tune::PRIMARY_BLOCKS_PER_CU, n_cu, P.total_items);
     // scenes of up to 8 one-Lipschitz shapes use the culling instance (8-way unrolled, runtime object count)
     if (P.cull_ok && P.box_sig == 0 && kind == KIND_GENERIC) {
         hipLaunchKernelGGL((primary_rays<KIND_GENERIC, 8>), dim3((unsigned)grid), dim3(256), 0, st, P);
@@ -616,8 +612,8 @@ void launch_accumulate(const Params& P, int n_cu, hipStream_t st) {
         const uint32_t K = (uint32_t)P.K;
         const size_t lds = (size_t)(P.acc_batch / K) * (3u * K + ((3u * K) & 1u ? 0u : 1u)) * sizeof(float);
         const long long n_batch = ((long long)P.total_items + P.acc_batch - 1) / P.acc_batch;
-        const long long room = (long long)(n_cu > 0 ? n_cu : 256) * 8;
-        hipLaunchKernelGGL(accumulate_dense, dim3((unsigned)(n_batch < room ? n_batch : room)), dim3(256), lds, st, P);
+        const long long grid = capped_blocks(tune::PRIMARY_BLOCKS_PER_CU, cus_or_default(n_cu), n_batch);
+        hipLaunchKernelGGL(accumulate_dense, dim3((unsigned)grid), dim3(256), lds, st, P);
         return;
     }
     int grid = (P.np + 255) / 256;
